@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """ICP iterations/s on a synthetic uniform cloud (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--points P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step is ONE ICP iteration of the hot path on clouds already resident in HBM: three launches on the default path -- the fused
@@ -12,29 +12,39 @@ fixed ("scaling": "strong"): the moving cloud is sharded over the ranks for the 
 all-reduce per iteration), the fixed cloud for the every-pair search (plus a ncclMin all-reduce of the packed keys), all inside
 libmislam.so over xGMI; torch.distributed (gloo) is only the bootstrap / barrier / max.
 
-Rank 0 prints one JSON line.
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the --steps steps, writes its outputs (--dump-outputs) and reports:
+  value, ms_per_step   the timed steps: iterations/s and the milliseconds one step took
   roofline        the search kernel of the timed steps: algorithmic bytes (20*N + 12*M_local) over its HIP-event-timed
                   average launch; `issue` beside it is the vector pipe's share of that kernel, from the committed counter profile of
                   this command, CALIBRATED by the same counters read off a kernel of known instruction count (tools/valu_probe)
+  runtime         which libamdhip64 / librccl objects libmislam.so's calls bind to in this process, their versions, every copy mapped; a rank that
+                  finds two different RCCL (HIP) runtimes of different versions mapped refuses to start (exit 3, before any device call)
+  rccl            N > 1 only: what the communicator itself reports (ranks, bit mask of ranks seen in one all-reduce)
+  expected_scaling           N > 1: what the one-GPU emulation of a rank's share predicts, so that the first multi-GPU numbers are read against it
+  (wall budget)   N > 1 only: MISLAM_BENCH_WALL_BUDGET_S (default 420).  Every rank leaves a one-line stage file (start / gloo_init / comm_init /
+                  first_allreduce / load / warmup / timed / ...) and carries a watchdog thread; `--gpus N` without a launcher also watches its child
+                  tree from outside.  On expiry: ONE line with "error", "stages" (every rank's last stage) and "ranks_seen", exit code 124
+
+--dump-outputs DIR: what the timed steps computed, as a caller of mi_icp_run / mi_icp_result receives it after the last one --
+DIR/icp_R.npy (3 x 3) and icp_t.npy (3) in float32, icp_error.npy (the last iteration's mean squared error, float32) and
+icp_iterations.npy (float64).  The clouds come from a fixed seed: the same arguments give the same inputs on every run.
+
+--full adds the other measurements, each in runs of its own after the headline's (the --no-* options thin them out):
+  ms_per_step_without_events, library_default_batch   the headline's steps again without HIP events / with the library's own host-check interval
+  kernels_ms_per_step   ms per launch of every kernel, from a few more iterations with events around each
+  allreduce_f64_sum     N > 1: the headline path's collective in those iterations, event-timed
   whole_call      one registration as the reference times it (host buffers in, allocation / upload / index builds / 50 iterations /
                   result included: testrunner.cpp:54-56) at 1e5 and 1e6 points and on the bunny clouds (cfg 1), with the load split into its stages
   late_iterations the same number of steps LATE in the same registration (the headline's window is a transient: the search gets cheaper as the clouds close in)
   sizes           the same measurement at N = M = 1e4, 1e5, 1e7 (BASELINE.json: "N = 10^4 ... 10^7"), a few steps each
   bruteforce_nn   the every-pair kernel on the same clouds with `valu`, its launch against the fp32 vector-issue rate
   target_sharded  N > 1 only: cfg 3's split -- fixed cloud sharded, every-pair search, ncclAllReduce(u64, min) of the keys
-  rccl            N > 1 only: what the communicator itself reports (ranks, bit mask of ranks seen in one all-reduce)
   cpd_bunny       the CPD leg of the metric (cfg 4), with its own roofline object
   cpu_baseline    the REFERENCE's own GetCorrespondingPoints (oracle/_ref, all host threads) on a bounded sample of source rows,
                   scaled to a full iteration; sizes['10000'] / ['100000'] carry their own, timed DIRECTLY (one whole search each, SURVEY 8d);
                   cpd_bunny carries one too (one ComputePMatrix + one MStep of cpu-slam on the bunny clouds, single thread as the reference runs it)
   cpd_bunny.published_size   the size the reference publishes CPD times for (N = 49 000, doc/plots/ms-cpd-3.png): exact and hybrid, ms per EM iteration
-  runtime         which libamdhip64 / librccl objects libmislam.so's calls bind to in this process, their versions, every copy mapped; a rank that
-                  finds two different RCCL (HIP) runtimes of different versions mapped refuses to start (exit 3, before any device call)
   allreduce_f64_sum_floor    N = 1: the headline path's one collective (64 x 18 doubles) through a ONE-rank RCCL communicator, event-timed
-  expected_scaling           N > 1: what the one-GPU emulation of a rank's share predicts, so that the first multi-GPU numbers are read against it
-  (wall budget)   N > 1 only: MISLAM_BENCH_WALL_BUDGET_S (default 420).  Every rank leaves a one-line stage file (start / gloo_init / comm_init /
-                  first_allreduce / load / warmup / timed / ...) and carries a watchdog thread; `--gpus N` without a launcher also watches its child
-                  tree from outside.  On expiry: ONE line with "error", "stages" (every rank's last stage) and "ranks_seen", exit code 124
 """
 import argparse
 import glob
@@ -514,7 +524,7 @@ def start_rank_watchdog(rank, world, steps, warmup):
     return done
 
 
-def self_launch(n_ranks, steps, warmup):
+def self_launch(n_ranks, steps, warmup, dump_outputs=None):
     """`python bench.py --gpus N` (N > 1) without a launcher: start the N ranks as a fresh child process tree -- `python -m
     torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>`, the driver's own launch line -- relay rank 0's
     JSON line and return the child's exit code.  A child, not an exec; called before this process has imported the package or
@@ -529,6 +539,8 @@ def self_launch(n_ranks, steps, warmup):
     # and the launcher's bind -- ADVICE r04); --local-addr: the workers' MASTER_ADDR, an address that resolves everywhere
     cmd = [sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1", "--nnodes=1", "--nproc-per-node=%d" % n_ranks,
            os.path.abspath(__file__)] + sys.argv[1:]
+    if dump_outputs:            # (the ranks run in the repository root: hand them the directory as this process resolves it; the last one given counts)
+        cmd += ["--dump-outputs", os.path.abspath(dump_outputs)]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC: RCCL between processes needs it on this driver
     env.setdefault("OMP_NUM_THREADS", "1")
@@ -616,20 +628,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--points", type=int, default=1000000, help="N = M, BASELINE.json: 10^6")
     ap.add_argument("--dist-mode", type=int, default=0, help="0 = cpu-slam rounding (parity default), 1 = fma")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sizes", action="store_true", help="skip the N = 1e4 / 1e5 / 1e7 legs")
-    ap.add_argument("--no-whole-call", action="store_true", help="skip the whole-registration legs (host buffers in, 50 iterations)")
-    ap.add_argument("--no-cpd", action="store_true", help="skip the CPD leg (cfg 4 on the bunny clouds)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed steps' result (R, t, error, iterations) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also run every other leg: CPU baselines, sizes, CPD, whole calls, per-kernel figures")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-sizes", action="store_true", help="--full: skip the N = 1e4 / 1e5 / 1e7 legs and the late iterations")
+    ap.add_argument("--no-whole-call", action="store_true", help="--full: skip the whole-registration legs (host buffers in, 50 iterations)")
+    ap.add_argument("--no-cpd", action="store_true", help="--full: skip the CPD leg (cfg 4 on the bunny clouds)")
     ap.add_argument("--shard", choices=["auto", "target", "source"], default="auto",
                     help="what N > 1 GPUs split: auto = moving cloud for the indexed searches, fixed cloud for the every-pair search")
     ap.add_argument("--brute-ref-steps", type=int, default=2,
-                    help="untimed every-pair steps measured after the timed region when an indexed search was used (0 = skip)")
+                    help="--full: untimed every-pair steps measured after the timed region when an indexed search was used (0 = skip)")
     ap.add_argument("--nn", choices=["auto", "brute", "tree", "grid"], default="auto",
                     help="search strategy (identical results): auto = the library default (cell grid at this size)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        sys.exit(self_launch(args.gpus, args.steps, args.warmup))       # (nothing has touched the GPU or imported the package yet)
+        sys.exit(self_launch(args.gpus, args.steps, args.warmup, args.dump_outputs))       # (nothing has touched the GPU or imported the package yet)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -797,44 +813,56 @@ def main():
     params = capi.icp_params(eps=0.0, max_iterations=-1, dist_mode=args.dist_mode, nn_mode=nn_mode, shard_mode=shard_mode, sync_every=max(args.steps, 1))
     elapsed, nn_prof = timed_run(before, after, params, args.warmup, args.steps)
     R, t, iters, err, why = ctx.icp_result()
-    # the same steps with the library's OWN host-check interval (sync_every = 0 -> mi_icp_auto_batch: 16 at this size on one GPU): what a
-    # registration pays per iteration when the host looks at the state as often as mi_icp_run does by default (a flush + a read-back per batch)
-    params_default = capi.icp_params(eps=0.0, max_iterations=-1, dist_mode=args.dist_mode, nn_mode=nn_mode, shard_mode=shard_mode, sync_every=0)
-    elapsed_default, _ = timed_run(before, after, params_default, args.warmup, args.steps)
-    auto_batch = capi.icp_auto_batch(n, m, world, pl["source_sharded"], not pl["indexed"])
-    elapsed_plain, _ = timed_run(before, after, params, args.warmup, args.steps, events=False)
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("icp_R", np.asarray(R, np.float32)), ("icp_t", np.asarray(t, np.float32)),
+                        ("icp_error", np.array([err], np.float32)), ("icp_iterations", np.array([iters], np.float64))):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+    full = {}           # the --full legs' entries of the result line
+    if args.full:
+        # the same steps with the library's OWN host-check interval (sync_every = 0 -> mi_icp_auto_batch: 16 at this size on one GPU): what a
+        # registration pays per iteration when the host looks at the state as often as mi_icp_run does by default (a flush + a read-back per batch)
+        params_default = capi.icp_params(eps=0.0, max_iterations=-1, dist_mode=args.dist_mode, nn_mode=nn_mode, shard_mode=shard_mode, sync_every=0)
+        elapsed_default, _ = timed_run(before, after, params_default, args.warmup, args.steps)
+        auto_batch = capi.icp_auto_batch(n, m, world, pl["source_sharded"], not pl["indexed"])
+        elapsed_plain, _ = timed_run(before, after, params, args.warmup, args.steps, events=False)
+        full["ms_per_step_without_events"] = elapsed_plain / args.steps * 1e3    # the headline's timed region carries two HIP event records per step (the roofline's live kernel time)
+        full["library_default_batch"] = {"sync_every": auto_batch, "iterations_per_s": args.steps / elapsed_default, "ms_per_step": elapsed_default / args.steps * 1e3,
+                                         "note": "the same timed steps with mi_icp_run's default host-check interval (mi_icp_auto_batch) instead of ONE check "
+                                                 "behind all of them: every batch ends in a flush (transform + error of the last iteration) and a 256-byte read-back"}
     # The headline's window (iterations warmup .. warmup + steps of one registration) is a TRANSIENT: the search gets cheaper as the clouds close
     # in.  The same number of steps late in the same registration, for the record: what an iteration costs once a third of
     # the moving cloud no longer hangs out of the fixed one.
     steady = None
-    if not args.no_sizes:
+    if args.full and not args.no_sizes:
         late = max(40, 2 * (args.warmup + args.steps))
         el_late, nn_late = timed_run(before, after, params, late, args.steps)
         steady = {"warmup": late, "steps": args.steps, "iterations_per_s": args.steps / el_late, "ms_per_step": el_late / args.steps * 1e3,
                   "nn_avg_launch_ms": nn_late[0] / max(nn_late[1], 1), "error_after_steps": ctx.icp_result()[3],
                   "note": "iterations %d..%d of the same registration (the headline times iterations %d..%d)" % (late + 1, late + args.steps, args.warmup + 1, args.warmup + args.steps)}
-    # (the legs below continue from the headline's registration state: reload it)
-    timed_run(before, after, params, args.warmup, args.steps)
     headline_allreduce = None
-    # per-kernel breakdown of a step: a few more (untimed) iterations with events around every kernel
-    stage("breakdown")
-    ctx.profile_enable(True)
-    ctx.profile_select(None)
-    ctx.profile_reset()
-    extra = ctx.icp_run(min(args.steps, 5))
-    breakdown = {capi.KERNEL_NAMES[k]: ctx.profile_get(k) for k in range(len(capi.KERNEL_NAMES))}
-    if use_dist:
-        ar = breakdown.get("allreduce", (0.0, 0))
-        if ar[1] > 0:        # the headline path's own collective: one 64 x 18-double sum per iteration (+ a 2-double one per host batch), event-timed
-            headline_allreduce = {"launches": ar[1], "ms_per_launch": ar[0] / ar[1], "payload_bytes": 8 * 18 * 64,
-                                  "collective": "ncclAllReduce(ncclDouble, ncclSum) of the 64 reduced rows x (16 moments + 2 error sums) on the context's stream (mislam_api.hip allreduce_sum_f64)"
-                                                if rehearsal_transport != "gloo" else "caller's transport (gloo rehearsal)"}
-    breakdown = {k: v[0] / v[1] for k, v in breakdown.items() if v[1] > 0 and extra > 0}
+    if args.full:
+        # (the legs below continue from the headline's registration state: reload it)
+        timed_run(before, after, params, args.warmup, args.steps)
+        # per-kernel breakdown of a step: a few more (untimed) iterations with events around every kernel
+        stage("breakdown")
+        ctx.profile_enable(True)
+        ctx.profile_select(None)
+        ctx.profile_reset()
+        extra = ctx.icp_run(min(args.steps, 5))
+        breakdown = {capi.KERNEL_NAMES[k]: ctx.profile_get(k) for k in range(len(capi.KERNEL_NAMES))}
+        if use_dist:
+            ar = breakdown.get("allreduce", (0.0, 0))
+            if ar[1] > 0:        # the headline path's own collective: one 64 x 18-double sum per iteration (+ a 2-double one per host batch), event-timed
+                headline_allreduce = {"launches": ar[1], "ms_per_launch": ar[0] / ar[1], "payload_bytes": 8 * 18 * 64,
+                                      "collective": "ncclAllReduce(ncclDouble, ncclSum) of the 64 reduced rows x (16 moments + 2 error sums) on the context's stream (mislam_api.hip allreduce_sum_f64)"
+                                                    if rehearsal_transport != "gloo" else "caller's transport (gloo rehearsal)"}
+        full["kernels_ms_per_step"] = {k: v[0] / v[1] for k, v in breakdown.items() if v[1] > 0 and extra > 0}   # ms per launch, from the untimed follow-up iterations
 
     # Outside the timed region: the same steps with the every-pair search (K1), for the brute-force roofline figures the
     # north star asks for.  Same keys, same registration -- only the number of evaluated pairs differs.
     brute_fig = None
-    if pl["indexed"] and args.brute_ref_steps > 0:
+    if args.full and pl["indexed"] and args.brute_ref_steps > 0:
         bpl = plan(n, m, "brute", "source" if pl["source_sharded"] else "target")
         ctx.icp_load(before, after, capi.icp_params(eps=0.0, max_iterations=-1, dist_mode=args.dist_mode, nn_mode=capi.NN_BRUTEFORCE,
                                                     shard_mode=capi.SHARD_SOURCE if pl["source_sharded"] else capi.SHARD_TARGET))
@@ -855,7 +883,7 @@ def main():
     # ncclMin) of the N packed (min-dist, argmin) keys per iteration.  Event-timed, outside the headline (the indexed search with
     # a sharded MOVING cloud is what the headline measures, because it is two orders of magnitude faster).
     target_leg, rccl = None, None
-    if use_dist:
+    if use_dist and args.full:
         stage("target_sharded_leg")
         ctx.icp_load(before, after, capi.icp_params(eps=0.0, max_iterations=-1, dist_mode=args.dist_mode, nn_mode=capi.NN_BRUTEFORCE,
                                                     shard_mode=capi.SHARD_TARGET))
@@ -876,13 +904,14 @@ def main():
                       "allreduce_u64_min": {"launches": ar[1], "ms_per_launch": ar[0] / max(ar[1], 1), "payload_bytes": 8 * n,
                                             "collective": "ncclAllReduce(ncclUint64, ncclMin) on the context's stream (mislam_api.hip allreduce_min_u64)"
                                                           if rehearsal_transport != "gloo" else "caller's transport (gloo rehearsal)"}}
+    if use_dist:
         nr, rk, seen = ctx.dist_info()
         rccl = {"nranks": nr, "rank0_sees_rank": rk, "ranks_seen_mask": seen, "ranks_seen": bin(seen).count("1"),
                 "transport": "rccl" if rehearsal_transport != "gloo" else "gloo exchange context (rehearsal)"}
 
     # The other sizes BASELINE.json names, a few steps each (same recipe, same rules; 1e7 costs ~2 s of host-side generation)
     sizes = None
-    if not args.no_sizes:
+    if args.full and not args.no_sizes:
         sizes = {}
         for sn in SWEEP_SIZES:
             if sn == n:
@@ -902,7 +931,7 @@ def main():
     # bunny clouds from cpu-slam's own sigma^2_0 -- exact P and the parser's default hybrid mode.  One GPU by default; with
     # MISLAM_BENCH_CPD=1 also on N > 1 (fixed cloud sharded, one 24-double all-reduce per EM iteration).
     cpd = None
-    if not args.no_cpd and (world == 1 or os.environ.get("MISLAM_BENCH_CPD") == "1"):
+    if args.full and not args.no_cpd and (world == 1 or os.environ.get("MISLAM_BENCH_CPD") == "1"):
         stage("cpd_leg")
         cpd = cpd_bunny(np, capi, ctx, world)
         if world == 1 and rank == 0 and not args.no_cpu_baseline:
@@ -914,7 +943,7 @@ def main():
 
     # Outside the timed region too: whole registrations on host buffers, as the reference times a SlamFunc
     whole = None
-    if world == 1 and not args.no_whole_call:
+    if args.full and world == 1 and not args.no_whole_call:
         whole = {str(wn): whole_call(np, capi, ctx, wn) for wn in (100000, 1000000)}
         # cfg 1 the same way: the bunny clouds with config/default.json's rules (cpu-slam's 39 iterations), host buffers in, result out
         gold = os.path.join(ROOT, "tests", "golden")
@@ -926,7 +955,7 @@ def main():
     # The floor of the headline path's collective: the 64 x 18-double sum of one iteration through a ONE-rank RCCL communicator, event-timed
     # (what ncclAllReduce costs on this stream before a single byte crosses xGMI).  N = 1 only, outside the timed region, never fatal.
     allreduce_floor = None
-    if world == 1 and not use_dist and os.environ.get("MISLAM_BENCH_NO_RCCL_FLOOR") != "1":
+    if args.full and world == 1 and not use_dist and os.environ.get("MISLAM_BENCH_NO_RCCL_FLOOR") != "1":
         try:
             dctx = capi.Context(local_rank, 0, 1, capi.dist_unique_id())
             fb, fa = synth_cloud(np, 100000)
@@ -996,12 +1025,8 @@ def main():
                                        "fixed cloud sharded x%d, RCCL u64-min all-reduce of the packed keys + one 64 x 18-double sum per iteration" % world),
                        "error_after_steps": err},
             "roofline": roof,
-            "ms_per_step_without_events": elapsed_plain / args.steps * 1e3,     # the headline's timed region carries two HIP event records per step (the roofline's live kernel time)
-            "library_default_batch": {"sync_every": auto_batch, "iterations_per_s": args.steps / elapsed_default, "ms_per_step": elapsed_default / args.steps * 1e3,
-                                      "note": "the same timed steps with mi_icp_run's default host-check interval (mi_icp_auto_batch) instead of ONE check "
-                                              "behind all of them: every batch ends in a flush (transform + error of the last iteration) and a 256-byte read-back"},
-            "kernels_ms_per_step": breakdown,     # ms per launch, from the untimed follow-up iterations (every kernel event-timed)
         }
+        out.update(full)
         out["runtime"] = runtime
         if allreduce_floor is not None:
             out["allreduce_f64_sum_floor"] = allreduce_floor
@@ -1031,10 +1056,11 @@ def main():
             out["allreduce_f64_sum"] = headline_allreduce
         if target_leg is not None:
             out["target_sharded"] = target_leg
+        if rccl is not None:
             out["rccl"] = rccl
         if cpd is not None:
             out["cpd_bunny"] = cpd
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(np, before, after)
         print(json.dumps(out), flush=True)
 

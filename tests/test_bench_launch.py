@@ -42,7 +42,7 @@ def test_bench_launcher_passes_a_failing_rank_on():
 
 @pytest.mark.gpu
 def test_bench_two_ranks_on_one_gpu_without_a_launcher(capi):
-    out = run_bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--points", "60000", "--no-sizes", "--brute-ref-steps", "1"],
+    out = run_bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--points", "60000", "--full", "--no-sizes", "--brute-ref-steps", "1"],
                     {"MISLAM_BENCH_TRANSPORT": "gloo", "MISLAM_BENCH_DEVICE": "0"}, 900)
     assert out["n_gpus"] == 2 and out["rccl"]["ranks_seen"] == 2 and out["rccl"]["nranks"] == 2
     assert out["value"] > 0 and out["steps"] == 4 and "rehearsal" in out

@@ -151,7 +151,8 @@ def test_search_budget_is_recomputable_and_current(tmp_path):
     import sys
     if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc")
-    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "isa_dump.sh"), "nn_grid"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "isa_dump.sh"), "nn_grid"], capture_output=True, text=True, timeout=900,
+                       env=dict(os.environ, ISA_DIR=str(tmp_path)))
     assert r.returncode == 0, r.stderr[-2000:]
     isa = r.stdout.strip().splitlines()[-1]
     c, _, _ = _load()

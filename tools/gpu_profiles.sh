@@ -1,5 +1,5 @@
 #!/bin/bash
-# Profiles (round tag R, default r06) of the driver's default bench command (python bench.py --steps 20 --warmup 5): rocprofv3 kernel-trace stats + the
+# Profiles (round tag R, default r06) of the full bench command (python bench.py --full --steps 20 --warmup 5): rocprofv3 kernel-trace stats + the
 # rows of the TIMED dispatches, the --pmc passes (one per counter set, never mixed with tracing) for the search kernel, the every-pair
 # kernel and the CPD E-step kernels of the same run, and the same SQ counters on tools/valu_probe (kernels of a known instruction
 # count at 8 waves per SIMD) -- what bench.py's `issue` rooflines are calibrated by.
@@ -10,7 +10,7 @@ export MISLAM_BENCH_NO_RCCL_FLOOR=1   # (the one-rank RCCL communicator of the a
 # The shipped default is profiled (cooperative K-centre sweep ON).  ROCm 7.2's HIP runtime faults in its own static destructor when a process that made
 # ANY cooperative launch ends under rocprofv3 -- after the tool has written its files (profiles/r06_coop_exit_abort.md: reproduced by a 50-line program
 # without libmislam, frames symbolised) -- so a pass may end with exit code 139 if and only if its log shows the tool's finalisation before the abort.
-B="python3 bench.py --steps $S --warmup $W --no-cpu-baseline --no-sizes --no-whole-call"
+B="python3 bench.py --full --steps $S --warmup $W --no-cpu-baseline --no-sizes --no-whole-call"
 run() { d=gpurun_out/${R}_$1; shift; rm -rf $d; timeout -k 10 500 rocprofv3 "$@" -d $d --output-format csv -- $B > $d.log 2>&1; rc=$?
         if [ $rc -eq 139 ] && grep -q "tool finalization" $d.log && grep -q '"metric"' $d.log; then echo "pass $d done (exit 139 AFTER the tool's finalisation: the runtime's cooperative-queue teardown, r06_coop_exit_abort.md)"
         elif [ $rc -ne 0 ]; then tail -5 $d.log; exit 1; else echo "pass $d done"; fi; }
