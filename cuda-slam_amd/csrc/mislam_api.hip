@@ -1498,7 +1498,9 @@ extern "C" int mi_kabsch(mi_ctx* c, const float* src_xyz, int n, const float* tg
     {
         ProfScope ps(c, MI_KERNEL_SOLVE);
         MI_HIP(icp_rows_reduce(c->rows.p, nrows, c->rows_reduced.p, c->stream));
-        MI_HIP(icp_solve_deferred(c->d_state, c->rows_reduced.p, icp_reduced_count(nrows), MI_COMPOSE_EXACT, IcpRules{}, 0, c->stream));
+        IcpRules rules{};
+        rules.svd_ieee = c->tune.svd_ieee;     // (the context's MISLAM_SVD_IEEE switch holds here as in every other solve)
+        MI_HIP(icp_solve_deferred(c->d_state, c->rows_reduced.p, icp_reduced_count(nrows), MI_COMPOSE_EXACT, rules, 0, c->stream));
     }
     MI_TRY(icp_fetch_state(c));
     if (pairs_used) *pairs_used = c->h_state->pairs;

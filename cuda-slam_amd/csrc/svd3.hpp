@@ -261,11 +261,15 @@ static __attribute__((noinline, unused)) __device__ Svd3 svd3_ieee_out_of_line(c
 template <bool FAST = false>
 __host__ __device__ inline Kabsch3 kabsch_rotation(const Mat3& H, bool force_ieee = false)
 {
+    Kabsch3 k;
 #if defined(__HIP_DEVICE_COMPILE__)
     Svd3 s;
-    if (FAST && force_ieee) s = svd3_ieee_out_of_line(H);
-    else {
+    if (FAST && force_ieee) {
+        s = svd3_ieee_out_of_line(H);
+        k.det = det3(mul_abt(s.U, s.V));
+    } else {
         s = svd3<FAST>(H);
+        k.det = det3(mul_abt(s.U, s.V));
         if (FAST) {
             float chk = (fabsf(s.S[0]) + fabsf(s.S[1])) + fabsf(s.S[2]);
             for (int r = 0; r < 3; r++)
@@ -278,15 +282,22 @@ __host__ __device__ inline Kabsch3 kabsch_rotation(const Mat3& H, bool force_iee
             // iterations; with the IEEE forms 4e-6).  The fast forms differ from IEEE by rounding, which is harmless exactly as long as R
             // depends continuously on H: so when the decomposition says it does not -- S[2] below 1e-3 of S[0] -- the IEEE one decides.
             const bool ill = s.S[2] < 1e-3f * s.S[0];
-            if (__builtin_expect(!(chk <= FLT_MAX) || ill, 0)) s = svd3_ieee_out_of_line(H);
+            // The same discontinuity without a small singular value: a MIRROR TIE.  Where det(U V^T) < 0, R = U diag(1, 1, -1) V^T flips the
+            // direction of the smallest singular value, and when S[1] ~ S[2] which of the two directions that is -- and so R -- is again decided
+            // by the last bits (tests/test_gpu_kabsch3.py: exact and near reflections, det < 0 clouds with two equal spreads; one ulp of H moves R
+            // by up to 2 there, by 2.6e-4 at a gap of 1e-3 of S[0]).  Those go to the IEEE form too.
+            const bool mirror_tie = k.det < 0.f && s.S[1] - s.S[2] < 1e-3f * s.S[0];
+            if (__builtin_expect(!(chk <= FLT_MAX) || ill || mirror_tie, 0)) {
+                s = svd3_ieee_out_of_line(H);
+                k.det = det3(mul_abt(s.U, s.V));
+            }
         }
     }
 #else
     (void)force_ieee;
     Svd3 s = svd3<FAST>(H);
-#endif
-    Kabsch3 k;
     k.det = det3(mul_abt(s.U, s.V));
+#endif
     Mat3 Ud = s.U;
     for (int r = 0; r < 3; r++) Ud.a[r][2] = s.U.a[r][2] * k.det;
     k.R = mul_abt(Ud, s.V);

@@ -96,6 +96,19 @@ def jacobi_svd3(A):
     return u.reshape(3, 3), s, v.reshape(3, 3)
 
 
+def kabsch_from_h(H, cb=(0.0, 0.0, 0.0), ca=(0.0, 0.0, 0.0)):
+    """(R row-major, t, singular values, det(U V^T)) of the 3 x 3 cross-covariance H (common.cpp:531-551)."""
+    h = np.ascontiguousarray(H, np.float32).reshape(9)
+    cb = np.ascontiguousarray(cb, np.float32)
+    ca = np.ascontiguousarray(ca, np.float32)
+    r = np.empty(9, np.float32)
+    t = np.empty(3, np.float32)
+    s = np.empty(3, np.float32)
+    det = C.c_float(0)
+    lib().oracle_kabsch_from_h(_fp(h), _fp(cb), _fp(ca), _fp(r), _fp(t), _fp(s), C.byref(det))
+    return _from_col9(r), t, s, np.float32(det.value)
+
+
 def least_squares_svd(before_pts, after_pts):
     before_pts, after_pts = _cloud(before_pts), _cloud(after_pts)
     r = np.empty(9, np.float32)
