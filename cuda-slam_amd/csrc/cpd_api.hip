@@ -204,9 +204,11 @@ static int cpd_standalone_sum_blocks(int n) { return std::max(1, std::min(ICP_MA
 
 static int use_mfma_contraction(const mi_ctx* c) { return c->tune.cpd_mfma; }   // MISLAM_CPD_MFMA, read at context creation
 
-static int cpd_estep_enqueue(mi_ctx* c, CpdWorkspace* w, const CpdView& v)
+// estep_mode: MI_ESTEP_*, from the caller -- a registration passes its parameters' mode, the stand-alone E-step primitives MI_ESTEP_DEFAULT
+// (w->params belongs to the last registration on the context: a primitive must not inherit its summation order)
+static int cpd_estep_enqueue(mi_ctx* c, CpdWorkspace* w, const CpdView& v, int estep_mode)
 {
-    if (w->params.estep_mode == MI_ESTEP_CPU_SEQUENTIAL && !v.truncate) {
+    if (estep_mode == MI_ESTEP_CPU_SEQUENTIAL && !v.truncate) {
         // parity mode: cpu-slam's summation order (cpd_kernels.hip); the M-step's sums then come from the stand-alone kernels (sums_fresh = false)
         { ProfScope ps(c, MI_KERNEL_CPD_DENOM); MI_HIP(cpd_estep_sequential(v, c->stream)); }
         w->sums_fresh = false;
@@ -643,7 +645,7 @@ extern "C" int mi_cpd_register(mi_ctx* c, const float* before_xyz, int m_before,
     while (!w->h_state->done) {
         for (int b = ahead ? 1 : 0; b < batch; b++) {
             if (params->approximation == MI_CPD_APPROX_NONE) {
-                MI_TRY(cpd_estep_enqueue(c, w, v));
+                MI_TRY(cpd_estep_enqueue(c, w, v, params->estep_mode));
             } else {
                 // ComputePMatrixFast, coherentpointdrift.cpp:141-167 (the comparisons are double there: 0.05 and 0.015 are doubles)
                 float sigma2 = w->h_state->sigma2;
@@ -666,7 +668,7 @@ extern "C" int mi_cpd_register(mi_ctx* c, const float* before_xyz, int m_before,
                     vt.trunc_log = std::log(1e-3f);                // ComputePMatrix(..., true, 1e-3f), :166 / :182-183
                     // (MISLAM_CPD_TRUNC_CULL=0 -- round 4's every-pair truncated kernels -- has no sharded form: a sharded registration takes the culled ones)
                     if (c->tune.cpd_trunc_cull != 0 || w->queries_sharded) MI_TRY(cpd_estep_trunc_enqueue(c, w, vt));
-                    else MI_TRY(cpd_estep_enqueue(c, w, vt));
+                    else MI_TRY(cpd_estep_enqueue(c, w, vt, params->estep_mode));
                 }
             }
             MI_TRY(cpd_mstep_enqueue(c, w, v, rules, 1));
@@ -681,7 +683,7 @@ extern "C" int mi_cpd_register(mi_ctx* c, const float* before_xyz, int m_before,
         } else if (pipelined) {
             MI_HIP(hipMemcpyAsync(w->h_state, w->d_state, sizeof(CpdState), hipMemcpyDeviceToHost, c->stream));
             MI_HIP(hipEventRecord(c->peek_event, c->stream));
-            MI_TRY(cpd_estep_enqueue(c, w, v));                    // (returns at once on the device if the state copied above says "done")
+            MI_TRY(cpd_estep_enqueue(c, w, v, params->estep_mode));    // (returns at once on the device if the state copied above says "done")
             MI_TRY(cpd_mstep_enqueue(c, w, v, rules, 1));
             MI_HIP(cpd_transform(v, w->m_pad, c->stream));
             ahead = true;
@@ -763,7 +765,7 @@ static int estep_primitive(mi_ctx* c, const float* y_xyz, int m, const float* x_
             v.trunc_log = std::log(truncate);
         }
         if (mode == 1 && c->tune.cpd_trunc_cull != 0) MI_TRY(cpd_estep_trunc_enqueue(c, w, v));
-        else MI_TRY(cpd_estep_enqueue(c, w, v));
+        else MI_TRY(cpd_estep_enqueue(c, w, v, MI_ESTEP_DEFAULT));
     }
     w->sums_fresh = false;               // (a stand-alone E-step: nothing of it is carried into a later M-step call)
     const int nxb = cpd_standalone_sum_blocks(n);
