@@ -751,13 +751,18 @@ __global__ __launch_bounds__(FGT_TILE * FGT_MODEL_GROUPS) void fgt_model_kernel(
         const int cnt = max(0, min(FGT_TILE, j1 - mine));
         if (tid < cnt) {
             const int i = c.memb[mine + tid];
-            const float d[3] = {(c.x[i] - cx) * inv_sigma, (c.y[i] - cy) * inv_sigma, (c.z[i] - cz) * inv_sigma};
+            float d[3] = {(c.x[i] - cx) * inv_sigma, (c.y[i] - cy) * inv_sigma, (c.z[i] - cz) * inv_sigma};
+            const float s = expf(-len2(d[0], d[1], d[2]));
+            // the reference multiplies the coordinates onto the seed exp(-|d|^2) and gets exactly 0 when the seed is 0; the powers formed
+            // first overflow there once |d| > FLT_MAX^(1/(p-1)) (~379 at p = 16), and 0 * inf would be NaN -- such a member's powers are
+            // taken at d = 0 (every product is then +-0, which leaves a sum unchanged; a NaN mean still gives a NaN seed)
+            if (s == 0.f) d[0] = d[1] = d[2] = 0.f;
 #pragma unroll
             for (int a = 0; a < 3; a++) {
                 float pw = 1.0f;
                 for (int r = 0; r < t.p; r++) { sp[grp][a][r][tid] = pw; pw = d[a] * pw; }
             }
-            se[grp][tid] = expf(-len2(d[0], d[1], d[2]));
+            se[grp][tid] = s;
             if (W == 4) {
                 const float4 w = w4[i];
                 sw[grp][0][tid] = w.x; sw[grp][1 % W][tid] = w.y; sw[grp][2 % W][tid] = w.z; sw[grp][3 % W][tid] = w.w;
