@@ -192,6 +192,13 @@ struct mi_ctx {
     mislam::DevBuf<int> sinv;                            // its inverse (caller's index -> sorted slot), MI_SUM_CPU_SEQUENTIAL only
     mislam::DevBuf<float> resid;                         // per-slot squared residuals, same mode
 
+    // ---- mi_icp_register_batch: both concatenated arrays as uploaded (AoS), every problem's sorted moving cloud, the problem table,
+    // one state block per problem, the "still running" word (icp_batch.hip)
+    mislam::DevBuf<float> bat_before, bat_after, bat_sx, bat_sy, bat_sz;
+    mislam::DevBuf<mislam::IcpBatchProblem> bat_problems;
+    mislam::DevBuf<mislam::IcpState> bat_states;
+    mislam::DevBuf<int> bat_running;
+
     // ---- ICP problem currently loaded
     bool icp_loaded = false;
     int n = 0, n_pad = 0;

@@ -139,11 +139,39 @@ hipError_t invert_order(const int* order, int n, int* inv, hipStream_t s);
 hipError_t icp_seq_centroids(const IcpView& v, hipStream_t s);
 hipError_t icp_seq_error(const IcpView& v, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K-batch: many small registrations, one workgroup per problem, the iterations inside the kernel (icp_batch.hip)
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int ICP_BATCH_MAX_MOVING = 4096;    // moving points a workgroup carries in registers: 8 waves x 8 rows of 64 (mi_icp_batch_route)
+constexpr int ICP_BATCH_MAX_FIXED = 4096;     // fixed points: streamed through LDS in tiles, so a routing choice rather than a limit of the kernel
+struct IcpBatchProblem {
+    int b_off, n;                    // moving cloud: first point in `before`, count
+    int a_off, m;                    // fixed cloud: first point in `after`, count
+    int s_off;                       // first slot of the problem's sorted moving cloud in sx / sy / sz
+    int pad;
+};
+struct IcpBatchArgs {
+    const float* before;             // AoS xyz, as uploaded
+    const float* after;
+    const IcpBatchProblem* problems;
+    float *sx, *sy, *sz;             // every problem's moving cloud in its curve order, SoA
+    IcpState* states;                // one block per problem
+    int* running;                    // += 1 per problem still running when a launch ends (zeroed by the host before it)
+    int n_problems;
+    int iters;                       // loop bodies per problem and launch, at most
+    int compose_mode;
+    float max_distance_squared;
+    IcpRules rules;                  // m_total is the problem's own (set in the kernel)
+};
+hipError_t icp_batch_prepare(const IcpBatchArgs& a, hipStream_t s);            // sorted clouds + states at identity
+hipError_t icp_batch_iterate(const IcpBatchArgs& a, int fma, hipStream_t s);   // up to a.iters iterations of every running problem
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
 hipError_t preload_nn_grid();
 hipError_t preload_icp_kernels();
+hipError_t preload_icp_batch();
 hipError_t preload_cpd_kernels();
 hipError_t preload_cpd_fgt();
 hipError_t preload_nicp_api();

@@ -194,7 +194,7 @@ extern "C" int mi_ctx_preload(mi_ctx* c)
 {
     if (!c) { set_error("mi_ctx_preload: null context"); return MI_ERR_INVALID_ARG; }
     MI_ENTER(c);
-    MI_HIP(preload_nn_kernel()); MI_HIP(preload_nn_tree()); MI_HIP(preload_nn_grid()); MI_HIP(preload_icp_kernels()); MI_HIP(preload_cpd_kernels());
+    MI_HIP(preload_nn_kernel()); MI_HIP(preload_nn_tree()); MI_HIP(preload_nn_grid()); MI_HIP(preload_icp_kernels()); MI_HIP(preload_icp_batch()); MI_HIP(preload_cpd_kernels());
     MI_HIP(preload_cpd_fgt()); MI_HIP(preload_nicp_api()); MI_HIP(preload_prepare_api());
     return MI_OK;
 }
@@ -465,6 +465,8 @@ extern "C" void mi_ctx_destroy(mi_ctx* c)
     c->gpts.release(); c->gstart.release(); c->gfill.release(); c->gscan.release(); c->rows.release(); c->rows_reduced.release();
     c->sched_order.release(); c->sched_far.release(); c->sched_lanes.release(); c->sched_counters.release(); c->gslot_of.release(); c->match_slot.release();
     c->grow_occ.release(); c->gnear_tmp.release();
+    c->bat_before.release(); c->bat_after.release(); c->bat_sx.release(); c->bat_sy.release(); c->bat_sz.release();
+    c->bat_problems.release(); c->bat_states.release(); c->bat_running.release();
     for (auto& s : c->spans) { (void)hipEventDestroy(s.e0); (void)hipEventDestroy(s.e1); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     if (c->d_state) (void)hipFree(c->d_state);
@@ -1404,6 +1406,118 @@ extern "C" int mi_icp_register(mi_ctx* c, const float* before_xyz, int n_before,
     MI_TRY(mi_icp_load(c, before_xyz, n_before, after_xyz, n_after, params));
     MI_TRY(mi_icp_run(c, -1, nullptr));
     return mi_icp_result(c, out_T, iterations, error, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// batched ICP: many small registrations under one set of rules (icp_batch.hip)
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int mi_icp_batch_route(int n_before, int n_after, const mi_icp_params* params)
+{
+    if (!params || n_before < 1 || n_after < 1) return 0;
+    if (params->sum_mode != MI_SUM_EXACT || params->verbose != 0) return 0;     // the sequential sums and the per-iteration print are the single path's
+    return n_before <= ICP_BATCH_MAX_MOVING && n_after <= ICP_BATCH_MAX_FIXED ? 1 : 0;
+}
+
+static void state_to_outputs(const IcpState* s, float* out_T, int* iterations, float* error, int* stop_reason)
+{
+    for (int col = 0; col < 3; col++) {                 // (mi_icp_result's layout)
+        for (int row = 0; row < 3; row++) out_T[4 * col + row] = s->R[3 * col + row];
+        out_T[4 * col + 3] = 0.f;
+    }
+    out_T[12] = s->t[0]; out_T[13] = s->t[1]; out_T[14] = s->t[2]; out_T[15] = 1.f;
+    *iterations = s->iterations;
+    *error = s->error;
+    *stop_reason = s->done ? s->stop_reason : MI_STOP_RUNNING;
+}
+
+extern "C" int mi_icp_register_batch(mi_ctx* c, int n_problems, const float* before_xyz, const int* before_range, const float* after_xyz,
+                                     const int* after_range, const mi_icp_params* params, float* out_T, int* iterations, float* error,
+                                     int* stop_reason, mi_icp_batch_info* info)
+{
+    if (info) memset(info, 0, sizeof *info);
+    if (!c) { set_error("mi_icp_register_batch: null context"); return MI_ERR_INVALID_ARG; }
+    if (n_problems < 0) { set_error("mi_icp_register_batch: n_problems = %d", n_problems); return MI_ERR_INVALID_ARG; }
+    if (c->distributed()) { set_error("mi_icp_register_batch: single-GPU contexts only"); return MI_ERR_STATE; }
+    MI_TRY(icp_check_params(params));
+    if (n_problems == 0) return MI_OK;
+    if (!before_xyz || !after_xyz || !before_range || !after_range) { set_error("mi_icp_register_batch: null cloud or range array"); return MI_ERR_INVALID_ARG; }
+    if (!out_T || !iterations || !error || !stop_reason) { set_error("mi_icp_register_batch: out_T, iterations, error and stop_reason must be non-null"); return MI_ERR_INVALID_ARG; }
+    // the table of the problems the kernel carries; offsets relative to the first point any of them uses
+    std::vector<IcpBatchProblem> table;
+    std::vector<int> batched, fallback;
+    long long b_lo = -1, b_hi = 0, a_lo = -1, a_hi = 0, slots = 0, max_pairs = 0;
+    for (int k = 0; k < n_problems; k++) {
+        const long long bo = before_range[2 * k], bn = before_range[2 * k + 1], ao = after_range[2 * k], an = after_range[2 * k + 1];
+        if (bo < 0 || ao < 0 || bn < 1 || an < 1 || bo + bn > 0x7fffffffLL || ao + an > 0x7fffffffLL) {
+            set_error("mi_icp_register_batch: problem %d has an invalid range (before %lld + %lld, after %lld + %lld)", k, bo, bn, ao, an);
+            return MI_ERR_INVALID_ARG;
+        }
+        if (!mi_icp_batch_route((int)bn, (int)an, params)) { fallback.push_back(k); continue; }
+        batched.push_back(k);
+        b_lo = b_lo < 0 || bo < b_lo ? bo : b_lo; b_hi = std::max(b_hi, bo + bn);
+        a_lo = a_lo < 0 || ao < a_lo ? ao : a_lo; a_hi = std::max(a_hi, ao + an);
+        IcpBatchProblem p{};
+        p.b_off = (int)bo; p.n = (int)bn; p.a_off = (int)ao; p.m = (int)an; p.s_off = (int)slots;
+        table.push_back(p);
+        slots += bn;
+        max_pairs = std::max(max_pairs, bn * an);
+        if (slots > 0x7fffffffLL) { set_error("mi_icp_register_batch: more than 2^31 moving points in one call (problem %d)", k); return MI_ERR_INVALID_ARG; }
+    }
+    MI_ENTER(c);
+    c->icp_loaded = false;                               // whatever mi_icp_load left is gone, as after mi_icp_register of another pair
+    int launches = 0;
+    if (!batched.empty()) {
+        const int nb = (int)batched.size();
+        for (IcpBatchProblem& p : table) { p.b_off -= (int)b_lo; p.a_off -= (int)a_lo; }
+        const size_t nbefore = (size_t)(b_hi - b_lo), nafter = (size_t)(a_hi - a_lo);
+        MI_TRY(c->bat_before.reserve(3 * nbefore)); MI_TRY(c->bat_after.reserve(3 * nafter));
+        MI_TRY(c->bat_sx.reserve((size_t)slots)); MI_TRY(c->bat_sy.reserve((size_t)slots)); MI_TRY(c->bat_sz.reserve((size_t)slots));
+        MI_TRY(c->bat_problems.reserve((size_t)nb)); MI_TRY(c->bat_states.reserve((size_t)nb)); MI_TRY(c->bat_running.reserve(1));
+        MI_TRY(host_to_device(c, c->bat_before.p, before_xyz + 3 * (size_t)b_lo, sizeof(float) * 3 * nbefore));
+        MI_TRY(host_to_device(c, c->bat_after.p, after_xyz + 3 * (size_t)a_lo, sizeof(float) * 3 * nafter));
+        MI_HIP(hipMemcpyAsync(c->bat_problems.p, table.data(), sizeof(IcpBatchProblem) * (size_t)nb, hipMemcpyHostToDevice, c->stream));
+        MI_HIP(hipStreamSynchronize(c->stream));         // (the table is pageable host memory of this frame)
+        IcpBatchArgs a{};
+        a.before = c->bat_before.p; a.after = c->bat_after.p; a.problems = c->bat_problems.p;
+        a.sx = c->bat_sx.p; a.sy = c->bat_sy.p; a.sz = c->bat_sz.p;
+        a.states = c->bat_states.p; a.running = c->bat_running.p;
+        a.n_problems = nb;
+        // a launch ends after `iters` iterations of its longest problem: ~1e9 pair evaluations per workgroup and launch at the most (a few ms),
+        // never fewer than 8 iterations (a launch boundary is a host round trip)
+        a.iters = (int)std::max(8LL, std::min(64LL, (1LL << 30) / std::max(1LL, max_pairs)));
+        a.compose_mode = params->compose_mode;
+        a.max_distance_squared = params->max_distance_squared;
+        a.rules.eps = params->eps; a.rules.max_iterations = params->max_iterations; a.rules.filter_pairs = params->filter_pairs;
+        a.rules.abort_on_increase = params->abort_on_increase; a.rules.seq_sums = 0; a.rules.svd_ieee = c->tune.svd_ieee;
+        MI_HIP(icp_batch_prepare(a, c->stream));
+        int* h_running = reinterpret_cast<int*>(c->h_scratch);
+        *h_running = params->max_iterations == 0 ? 0 : 1;
+        while (*h_running != 0) {
+            MI_HIP(hipMemsetAsync(c->bat_running.p, 0, sizeof(int), c->stream));
+            MI_HIP(icp_batch_iterate(a, params->dist_mode == MI_DIST_FMA, c->stream));
+            launches++;
+            MI_HIP(hipMemcpyAsync(h_running, c->bat_running.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            MI_HIP(hipStreamSynchronize(c->stream));
+        }
+        std::vector<IcpState> states((size_t)nb);
+        MI_HIP(hipMemcpyAsync(states.data(), c->bat_states.p, sizeof(IcpState) * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+        MI_HIP(hipStreamSynchronize(c->stream));
+        retire_buffers(c);
+        for (int i = 0; i < nb; i++) {
+            const int k = batched[(size_t)i];
+            state_to_outputs(&states[(size_t)i], out_T + 16 * (size_t)k, iterations + k, error + k, stop_reason + k);
+        }
+    }
+    for (int k : fallback) {                             // the existing path, one after the other
+        const float* b = before_xyz + 3 * (size_t)before_range[2 * k];
+        const float* a = after_xyz + 3 * (size_t)after_range[2 * k];
+        MI_TRY(mi_icp_load(c, b, before_range[2 * k + 1], a, after_range[2 * k + 1], params));
+        MI_TRY(mi_icp_run(c, -1, nullptr));
+        MI_TRY(mi_icp_result(c, out_T + 16 * (size_t)k, iterations + k, error + k, stop_reason + k));
+    }
+    c->icp_loaded = false;                               // (also what a fallback problem loaded: the call leaves no problem behind, whatever its mix)
+    if (info) { info->problems_batched = (int)batched.size(); info->problems_fallback = (int)fallback.size(); info->launches = launches; }
+    return MI_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

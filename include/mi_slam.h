@@ -221,6 +221,45 @@ int mi_icp_auto_batch(long long n_moving_total, long long m_fixed_total, int wor
 int mi_icp_result(mi_ctx* ctx, float out_T[16], int* iterations, float* error, int* stop_reason);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * Batched ICP: many small registrations under ONE set of rules in one call (single-GPU contexts only).
+ * A registration of a few thousand points leaves most of the device idle and is bound by launches and host checks; here every
+ * problem gets a workgroup of its own and its iterations run inside one kernel, a few hundred problems side by side.  A caller
+ * with ONE pair keeps calling mi_icp_register: a single workgroup is slower than the whole device.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int problems_batched;    /* problems that ran on the batched kernel */
+    int problems_fallback;   /* problems that ran through the existing per-problem path inside this call */
+    int launches;            /* launches of the batched kernel */
+    int reserved[5];
+} mi_icp_batch_info;
+
+/* 1 if a problem of these sizes under these rules is carried by the batched kernel, 0 if the call routes it through the
+ * existing path.  Pure host function of its arguments (no context, no device), like mi_icp_auto_batch.  Routed: n_before <= 4096
+ * and n_after <= 4096 -- a function of the two sizes only -- under MI_SUM_EXACT with verbose = 0, whatever the other fields say
+ * (MI_SUM_CPU_SEQUENTIAL and verbose = 1 belong to the single path: its sequential sums, its per-iteration print). */
+int mi_icp_batch_route(int n_before, int n_after, const mi_icp_params* params);
+
+/* B independent registrations.  Problem k moves the points before_xyz[3*before_range[2k] ...] (before_range[2k+1] of them) onto
+ * after_xyz[3*after_range[2k] ...] (after_range[2k+1] of them); both arrays must reach as far as the ranges say.  Ranges may
+ * overlap or coincide (many scans against one map tile, one scan against many).  out_T: 16*B floats (column-major 4x4 each);
+ * iterations, error, stop_reason: B entries each, non-null.  info may be NULL.  Problem k's outputs are, BIT FOR BIT, what
+ *   mi_icp_register(ctx, before_k, n_k, after_k, m_k, params, ...) followed by mi_icp_result(...)
+ * returns on the same context (its developer switches included) -- whatever else is in the batch and in whatever position;
+ * nn_mode and sync_every are accepted and, as in the single call, move no bit.  Every problem mi_icp_register accepts is
+ * accepted: the ones mi_icp_batch_route does not route run through the existing path inside the call, one after the other.
+ * n_problems == 0 is MI_OK.  A range with a negative offset or a count < 1, or a NULL output: MI_ERR_INVALID_ARG, mi_last_error
+ * names the problem, nothing has touched the device.  A distributed context: MI_ERR_STATE.
+ * The call REPLACES whatever mi_icp_load had loaded: afterwards no problem is loaded (mi_icp_run / mi_icp_result return
+ * MI_ERR_STATE until the next mi_icp_load).  max_iterations = -1 on a problem that never meets a stop rule does not return,
+ * exactly like the single call -- but every launch of the kernel ends: it carries a bounded number of iterations. */
+int mi_icp_register_batch(mi_ctx* ctx, int n_problems,
+                          const float* before_xyz, const int* before_range,
+                          const float* after_xyz,  const int* after_range,
+                          const mi_icp_params* params,
+                          float* out_T, int* iterations, float* error, int* stop_reason,
+                          mi_icp_batch_info* info);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Test-grade primitives (one per reference primitive on the path; host in / host out).
  * -------------------------------------------------------------------------------------------------------------- */
 
