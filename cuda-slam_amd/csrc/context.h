@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
+#include <sys/resource.h>
 
 #include <cstdarg>
 #include <cstdio>
@@ -127,30 +128,33 @@ struct mi_ctx {
     } tune;
 
     // ---- a second lane for the loads (round 4): mi_icp_load uploads and indexes the FIXED cloud on `aux` (hierarchy) and `aux2` (cell grid)
-    // while the moving cloud is uploaded and ordered on `stream`; the helpers enqueue on work_stream() and take their scratch from the set
-    // `lane` names (0: the buffers below, 1: the *2 copies), so two lanes never share a scratch buffer.  Everything else runs on `stream`.
+    // while the moving cloud is uploaded and ordered on `stream`; the helpers enqueue on work_stream() and take their scratch from
+    // scratch[lane], so two lanes never share a scratch buffer.  Everything else runs on `stream`.
     hipStream_t aux = nullptr, aux2 = nullptr;
     hipEvent_t aux_event[3] = {nullptr, nullptr, nullptr};
     hipStream_t lane_stream = nullptr;                   // null: `stream`
     int lane = 0;
     hipStream_t work_stream() const { return lane_stream ? lane_stream : stream; }
-    mislam::DevBuf<float> staging2;
-    mislam::DevBuf<unsigned int> tcodes2_in, tcodes2_out;
-    mislam::DevBuf<int> torder2_in;
-    mislam::DevBuf<float> tbbox2, gbbox;
-    mislam::DevBuf<unsigned char> tsort_temp2;
+    struct LaneScratch {
+        mislam::DevBuf<float> staging;                   // AoS upload/download staging
+        mislam::DevBuf<unsigned int> codes_in, codes_out;   // Morton sort scratch (the fixed cloud's hierarchy and the moving cloud's ordering)
+        mislam::DevBuf<int> order_in;
+        mislam::DevBuf<float> bbox;
+        mislam::DevBuf<unsigned char> sort_temp;
+    } scratch[2];
 
     // ---- workspace shared by the drivers
-    mislam::DevBuf<float> staging;                       // AoS upload/download staging
     // pinned host staging of the cloud uploads (host_to_device): the runtime's own pageable-copy path stalls for 20-50 ms every
-    // few dozen calls on this machine (tools/alloc_probe.cpp: median 0.36 ms, max 27 ms for 12 MB).  A ring of PIN_SLOTS pieces of
+    // few dozen calls on this machine (tools/alloc_probe.cpp: median 0.36 ms, max 27 ms for 12 MB).  A ring of SLOTS pieces of
     // 1 MB, pinned once per context: a piece is copied in while the pieces before it are on their way -- 0.30 ms for 12 MB, every time
-    static constexpr int PIN_SLOTS = 16;
-    static constexpr size_t PIN_PIECE = 1u << 20;
-    char* pin = nullptr;
-    hipEvent_t pin_event[PIN_SLOTS] = {nullptr};         // recorded behind the last transfer out of slot k
-    unsigned int pin_busy = 0;                           // bit k: pin_event[k] has been recorded and not waited for since
-    unsigned int pin_next = 0;
+    struct PinnedRing {
+        static constexpr int SLOTS = 16;
+        static constexpr size_t PIECE = 1u << 20;
+        char* buf = nullptr;
+        hipEvent_t event[SLOTS] = {nullptr};             // recorded behind the last transfer out of slot k
+        unsigned int busy = 0;                           // bit k: event[k] has been recorded and not waited for since
+        unsigned int next = 0;
+    } pin;
     float* h_scratch = nullptr;                          // 64 pinned floats for small read-backs
     mislam::DevBuf<float> bx, by, bz;                    // original moving cloud, SoA
     mislam::DevBuf<float> cx, cy, cz;                    // current (transformed) moving cloud, SoA
@@ -159,9 +163,11 @@ struct mi_ctx {
     mislam::DevBuf<float4> tgt4;                         // same shard as float4 (gathers)
     mislam::DevBuf<unsigned long long> keys;
     mislam::DevBuf<double> part_mom, part_err;           // per-workgroup partial sums of the NICP / CPD drivers
-    mislam::DevBuf<int> sched_order, sched_counters;     // work order of the fused search (IcpSchedule)
-    mislam::DevBuf<unsigned char> sched_far;
-    mislam::DevBuf<unsigned long long> sched_lanes;      // per chunk: the lanes that walked (IcpSchedule::lanes)
+    struct WorkOrder {                                   // work order of the fused search (IcpSchedule)
+        mislam::DevBuf<int> order, counters;
+        mislam::DevBuf<unsigned char> far;
+        mislam::DevBuf<unsigned long long> lanes;        // per chunk: the lanes that walked (IcpSchedule::lanes)
+    } sched;
     mislam::DevBuf<double> rows, rows_reduced;           // ICP: one row of 18 sums per 64 moving points (icp_rows.hpp), and <= 64 reduced rows
     mislam::DevBuf<int> idx_tmp;
     mislam::DevBuf<unsigned char> keep_tmp;
@@ -170,45 +176,51 @@ struct mi_ctx {
     hipEvent_t peek_event = nullptr;                     // behind the state copy of an intermediate host check (mi_icp_run)
 
     // ---- exact-NN indexes over the fixed-cloud shard (built lazily, valid until the shard is replaced)
-    mislam::DevBuf<unsigned int> tcodes_in, tcodes_out;  // Morton sort scratch (also used for the moving cloud's ordering)
-    mislam::DevBuf<int> torder_in, torder_out;
-    mislam::DevBuf<float> tbbox;
-    mislam::DevBuf<unsigned char> tsort_temp;
-    mislam::DevBuf<float4> tpts, tboxes;                 // box hierarchy (nn_tree.h): sorted points and node boxes (build scratch)
-    mislam::DevBuf<float4> tleaf;                        // what the walk reads (NnTreeView): leaf coordinates, ...
-    mislam::DevBuf<int> tidx;                            // ... global indices ...
-    mislam::DevBuf<float> tboxes6;                       // ... and node boxes, six floats each
-    mislam::NnTreeView tree{};
-    bool tree_valid = false;
-    mislam::DevBuf<float4> gpts;                         // cell grid (nn_grid.h): points sorted by cell
-    mislam::DevBuf<unsigned int> gstart, gfill, gscan;   // cell offsets, build cursors, scan scratch
-    mislam::DevBuf<unsigned int> gslot_of;               // fixed point -> its slot in gpts
-    mislam::DevBuf<unsigned int> grow_occ;               // per cell: which of the 5 x 5 cell rows around it hold a point within reach (NnGridView::row_occ)
-    mislam::DevBuf<unsigned char> gnear_tmp;             // build scratch
-    mislam::DevBuf<unsigned int> match_slot;             // fused ICP: per moving point, the slot of its current match
-    mislam::NnGridView grid{};
-    bool grid_valid = false;
+    struct TreeIndex {                                   // box hierarchy (nn_tree.h)
+        mislam::DevBuf<int> order_out;                   // the hierarchy's own Morton order (a lane's scratch holds only what a sort consumes)
+        mislam::DevBuf<float4> pts, boxes;               // sorted points and node boxes (build scratch)
+        mislam::DevBuf<float4> leaf;                     // what the walk reads (NnTreeView): leaf coordinates, ...
+        mislam::DevBuf<int> idx;                         // ... global indices ...
+        mislam::DevBuf<float> boxes6;                    // ... and node boxes, six floats each
+        mislam::NnTreeView view{};
+        bool valid = false;
+    } tree;
+    struct GridIndex {                                   // cell grid (nn_grid.h)
+        mislam::DevBuf<float> bbox;                      // (its own: a Morton sort's bounding box may be in flight on another lane)
+        mislam::DevBuf<float4> pts;                      // points sorted by cell
+        mislam::DevBuf<unsigned int> start, fill, scan;  // cell offsets, build cursors, scan scratch
+        mislam::DevBuf<unsigned int> slot_of;            // fixed point -> its slot in pts
+        mislam::DevBuf<unsigned int> row_occ;            // per cell: which of the 5 x 5 cell rows around it hold a point within reach (NnGridView::row_occ)
+        mislam::DevBuf<unsigned char> near_tmp;          // build scratch
+        mislam::DevBuf<unsigned int> match_slot;         // fused ICP: per moving point, the slot of its current match
+        mislam::NnGridView view{};
+        bool valid = false;
+    } grid;
     mislam::DevBuf<int> sorder;                          // Morton order of the moving cloud (sorted slot -> caller's index)
     mislam::DevBuf<int> sinv;                            // its inverse (caller's index -> sorted slot), MI_SUM_CPU_SEQUENTIAL only
     mislam::DevBuf<float> resid;                         // per-slot squared residuals, same mode
 
     // ---- mi_icp_register_batch: both concatenated arrays as uploaded (AoS), every problem's sorted moving cloud, the problem table,
     // one state block per problem, the "still running" word (icp_batch.hip)
-    mislam::DevBuf<float> bat_before, bat_after, bat_sx, bat_sy, bat_sz;
-    mislam::DevBuf<mislam::IcpBatchProblem> bat_problems;
-    mislam::DevBuf<mislam::IcpState> bat_states;
-    mislam::DevBuf<int> bat_running;
+    struct BatchBuffers {
+        mislam::DevBuf<float> before, after, sx, sy, sz;
+        mislam::DevBuf<mislam::IcpBatchProblem> problems;
+        mislam::DevBuf<mislam::IcpState> states;
+        mislam::DevBuf<int> running;
+    } bat;
 
     // ---- ICP problem currently loaded
-    bool icp_loaded = false;
-    int n = 0, n_pad = 0;
-    int n_global = 0;                                    // moving points over ALL ranks (what rank-independent decisions are taken from)
-    int m_total = 0, shard_lo = 0, shard_hi = 0;
-    bool source_sharded = false;                         // MI_SHARD_SOURCE in effect: n = this rank's slice, fixed cloud replicated
-    bool fused = false;                                  // the grid search carries the O(N) part of the iteration (nn_grid.hip)
-    int enqueued_passes = 0;                             // fused iterations enqueued since the load / reset (GridSearchArgs::extend_reach)
-    mi_icp_params icp{};
-    double load_ms[MI_LOAD_STAGES] = {0};                // mi_icp_load_times
+    struct IcpProblem {
+        bool icp_loaded = false;
+        int n = 0, n_pad = 0;
+        int n_global = 0;                                // moving points over ALL ranks (what rank-independent decisions are taken from)
+        int m_total = 0, shard_lo = 0, shard_hi = 0;
+        bool source_sharded = false;                     // MI_SHARD_SOURCE in effect: n = this rank's slice, fixed cloud replicated
+        bool fused = false;                              // the grid search carries the O(N) part of the iteration (nn_grid.hip)
+        int enqueued_passes = 0;                         // fused iterations enqueued since the load / reset (GridSearchArgs::extend_reach)
+        mi_icp_params icp{};
+        double load_ms[MI_LOAD_STAGES] = {0};            // mi_icp_load_times
+    } prob;
 
     // ---- CPD workspace (allocated on first use)
     mislam::CpdWorkspace* cpd = nullptr;
@@ -217,17 +229,19 @@ struct mi_ctx {
     mislam::DevBuf<unsigned long long> nn_stats;         // mi_profile_search_stats counters
     bool nn_stats_on = false;
     int selftest_fail_loads = 0;                         // mi_selftest_fail_loads: the next N index builds fail on purpose (an explicit call of a test, never the environment: ADVICE r05)
-    bool profile = false;
-    unsigned int prof_mask = 0xffffffffu;                // kernels that get events while profiling (mi_profile_select)
-    std::vector<mislam::ProfileSpan> spans;
-    std::vector<hipEvent_t> event_pool;
-    double prof_ms[MI_KERNEL_COUNT] = {0};
-    long long prof_n[MI_KERNEL_COUNT] = {0};
-
-    int prof_begin(int kernel);
-    int prof_end();
-    int prof_span(int kernel, hipEvent_t* e0, hipEvent_t* e1);   // a span whose events the LAUNCH records (hipExtLaunchKernelGGL); null events if `kernel` is not being timed
-    int prof_collect();
+    struct Profiler {                                    // HIP events on the context's stream `s` around each kernel launch
+        bool on = false;
+        unsigned int mask = 0xffffffffu;                 // kernels that get events while profiling (mi_profile_select)
+        std::vector<mislam::ProfileSpan> spans;
+        std::vector<hipEvent_t> event_pool;
+        double ms[MI_KERNEL_COUNT] = {0};
+        long long n[MI_KERNEL_COUNT] = {0};
+        bool times(int kernel) const { return on && ((mask >> kernel) & 1u); }
+        int begin(int kernel, hipStream_t s);
+        int end(hipStream_t s);
+        int span(int kernel, hipEvent_t* e0, hipEvent_t* e1);   // a span whose events the LAUNCH records (hipExtLaunchKernelGGL); null events if `kernel` is not being timed
+        int collect(hipStream_t s);
+    } prof;
 };
 
 namespace mislam {
@@ -257,13 +271,30 @@ struct LaneScope {
 struct ProfScope {
     mi_ctx* c;
     bool on;
-    ProfScope(mi_ctx* ctx, int kernel) : c(ctx), on(ctx->profile && ((ctx->prof_mask >> kernel) & 1u)) { if (on) (void)c->prof_begin(kernel); }
-    ~ProfScope() { if (on) (void)c->prof_end(); }
+    ProfScope(mi_ctx* ctx, int kernel) : c(ctx), on(ctx->prof.times(kernel)) { if (on) (void)c->prof.begin(kernel, c->stream); }
+    ~ProfScope() { if (on) (void)c->prof.end(c->stream); }
 };
 
-struct NnPlan {
-    int R, n_chunks, chunk_len;
+// developer switch MISLAM_DEV_STALL_MS=<ms>: report any host-side section that takes longer, with the calling thread's context switches
+// over it -- an INVOLUNTARY one with no voluntary ones means the thread was taken off its core (a CPU quota of the container
+// running out: numpy's BLAS pool spinning on every host core did exactly that to the round-2 sweeps), not that the GPU or the
+// runtime made it wait.
+extern double g_stall_ms;
+struct StallProbe {
+    const char* label; double t0; struct rusage ru0;
+    explicit StallProbe(const char* l) : label(l), t0(0.0) { if (g_stall_ms > 0) { t0 = wall_ms(); getrusage(RUSAGE_THREAD, &ru0); } }
+    ~StallProbe()
+    {
+        if (g_stall_ms <= 0) return;
+        const double d = wall_ms() - t0;
+        if (d <= g_stall_ms) return;
+        struct rusage ru1; getrusage(RUSAGE_THREAD, &ru1);
+        fprintf(stderr, "mislam stall: %s %.2f ms (context switches: %ld voluntary, %ld involuntary)\n", label, d, ru1.ru_nvcsw - ru0.ru_nvcsw, ru1.ru_nivcsw - ru0.ru_nivcsw);
+    }
 };
+
+static inline int round_up(int v, int g) { return (v + g - 1) / g * g; }
+struct NnPlan { int R, n_chunks, chunk_len; };
 NnPlan plan_nn(const mi_ctx* ctx, int n, int m_local);
 size_t target_alloc_len(int m_local);
 
@@ -274,10 +305,17 @@ int host_to_device(mi_ctx* ctx, void* dst_dev, const void* src_host, size_t byte
 int upload_soa(mi_ctx* ctx, const float* host_aos, int n, int n_pad, float* x, float* y, float* z, float4* packed);
 // Uploads this rank's shard of the fixed cloud (SoA streams for K1 + float4 for gathers); invalidates the box hierarchy.
 int upload_target_shard(mi_ctx* ctx, const float* after_xyz, int m_total, bool replicate = false);
+int reserve_moving(mi_ctx* ctx, size_t n_pad, size_t c_pad);   // bx..bz and keys of n_pad entries, cx..cz of c_pad (>= n_pad where they double as load scratch)
+// Morton-sorts the moving cloud; the two index builds over the resident fixed-cloud shard, no-ops while it is valid (nn_api.hip)
+int sort_sources(mi_ctx* ctx, const float* sx, const float* sy, const float* sz, int n, int n_pad, float* dx, float* dy, float* dz);
+int ensure_tree(mi_ctx* ctx, int m_local, int index_base);
+int ensure_grid(mi_ctx* ctx, int m_local, int index_base);
 // Correspondence search of n moving points (SoA, padded) against the loaded fixed-cloud shard into ctx->keys (K1, K1t or K1g).
 int resolve_nn_mode(const mi_ctx* ctx, int nn_mode, int m_local);
+GridSearchArgs grid_search_args(const mi_ctx* ctx, int n);   // the fields of a grid search that depend on the context and n alone: n, keys, stats, deal_rows
 int launch_nn(mi_ctx* ctx, const float* sx, const float* sy, const float* sz, int n, int m_local, int index_base, int fma,
               const int* done_flag, int nn_mode);
+int allreduce_keys(mi_ctx* ctx, int n);                      // min over the ranks of ctx->keys[0, n), under MI_KERNEL_ALLREDUCE
 // In-place all-reduce of a device array over the ranks, on the context's stream: RCCL, or the caller's transport through pinned
 // host memory.  No-ops on a single-GPU context.
 int allreduce_min_u64(mi_ctx* ctx, unsigned long long* dev_ptr, size_t count);

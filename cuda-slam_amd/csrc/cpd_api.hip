@@ -130,7 +130,7 @@ static void plan_chunks(const mi_ctx* c, int owners, int owner_r, int stream_len
 // Uploads both clouds and sizes every buffer.  y starts as a copy of b (transformedCloud = cloudBefore, :104).
 static int cpd_load(mi_ctx* c, CpdWorkspace* w, const float* before_xyz, int m, const float* after_xyz, int n)
 {
-    c->icp_loaded = false;   // the moving-cloud buffers are shared with the ICP driver
+    c->prob.icp_loaded = false;   // the moving-cloud buffers are shared with the ICP driver
     w->fgt.a.swept_K = 0;    // a new fixed cloud: its clustering starts over
     w->fgt.y.guess_K = 0;    // a new moving cloud: nothing to guess its sweep from
     w->fgt.y.prelaunched = 0;
@@ -493,7 +493,7 @@ static int cpd_estep_fgt_enqueue(mi_ctx* c, CpdWorkspace* w, const CpdView& v, f
     // (a context created under MISLAM_FGT_RESUME=0 re-clusters from scratch every time; the results must not change by a bit -- tests/test_gpu_fgt.py)
     const bool resume = c->tune.fgt_resume != 0;
     const bool recluster = !resume || f->a.swept_K != K;
-    const bool beside = recluster && !c->profile && c->aux != nullptr && c->tune.fgt_two_streams != 0;
+    const bool beside = recluster && !c->prof.on && c->aux != nullptr && c->tune.fgt_two_streams != 0;
     struct AuxJoin {                       // every way out joins the auxiliary stream into `stream`
         mi_ctx* c; bool armed;
         ~AuxJoin() { if (armed && hipEventRecord(c->aux_event[1], c->aux) == hipSuccess) (void)hipStreamWaitEvent(c->stream, c->aux_event[1], 0); }
@@ -640,7 +640,7 @@ extern "C" int mi_cpd_register(mi_ctx* c, const float* before_xyz, int m_before,
     if (params->approximation != MI_CPD_APPROX_NONE) batch = 1;   // the E-step's shape depends on sigma^2: host-stepped
     // exact P in batches: a host check only peeks (state copy behind the batch, ONE iteration of the next batch behind the copy, the host
     // waits for the copy alone) -- the device does not idle for the ~26 us a drained stream and a fresh enqueue cost (mi_icp_run does the same)
-    const bool pipelined = batch > 1 && c->peek_event != nullptr && c->tune.icp_pipeline != 0 && !c->profile;
+    const bool pipelined = batch > 1 && c->peek_event != nullptr && c->tune.icp_pipeline != 0 && !c->prof.on;
     bool ahead = false;
     while (!w->h_state->done) {
         for (int b = ahead ? 1 : 0; b < batch; b++) {
@@ -812,7 +812,7 @@ extern "C" int mi_fgt_kcenter(mi_ctx* c, const float* cloud_xyz, int n, int K, f
     MI_ENTER(c);
     CpdWorkspace* w = nullptr;
     MI_TRY(cpd_workspace(c, &w));
-    c->icp_loaded = false;
+    c->prob.icp_loaded = false;
     const int n_pad = round_up_i(n, NN_SRC_PAD);
     MI_TRY(c->bx.reserve(n_pad)); MI_TRY(c->by.reserve(n_pad)); MI_TRY(c->bz.reserve(n_pad));
     MI_TRY(upload_soa(c, cloud_xyz, n, n_pad, c->bx.p, c->by.p, c->bz.p, nullptr));
@@ -837,7 +837,7 @@ extern "C" int mi_fgt_kcenter_guided(mi_ctx* c, const float* cloud_xyz, int n, i
     MI_ENTER(c);
     CpdWorkspace* w = nullptr;
     MI_TRY(cpd_workspace(c, &w));
-    c->icp_loaded = false;
+    c->prob.icp_loaded = false;
     w->fgt.y.guess_K = 0;
     const int n_pad = round_up_i(n, NN_SRC_PAD);
     MI_TRY(c->bx.reserve(n_pad)); MI_TRY(c->by.reserve(n_pad)); MI_TRY(c->bz.reserve(n_pad));

@@ -1,4 +1,4 @@
-// Internal launch interfaces between the C-ABI/driver layer (mislam_api.cpp) and the HIP kernels.
+// Internal launch interfaces between the C-ABI/driver layer (mislam_api.hip, nn_api.hip, icp_api.hip) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -311,7 +311,7 @@ extern "C" int mi_nicp_register(mi_ctx* c, const float* before_xyz, int m_before
         for (int i = 0; i < subcloud_n; i++)
             if (subcloud_idx[i] < 0 || subcloud_idx[i] >= m_before) { set_error("mi_nicp_register: subcloud_idx[%d] out of range", i); return MI_ERR_INVALID_ARG; }
     MI_ENTER(c);
-    c->icp_loaded = false;
+    c->prob.icp_loaded = false;
 
     // ---- one pass over both clouds: centroids, Gram matrices, pair sums
     const int m_pad = (m_before + NN_SRC_PAD - 1) / NN_SRC_PAD * NN_SRC_PAD;

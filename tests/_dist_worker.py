@@ -70,7 +70,7 @@ def main():
     assert abs(te[0].item() - (dfull ** 2).sum()) < 1e-9 * max(1.0, (dfull ** 2).sum())
     assert te[1].item() == kept.sum()
 
-    # MI_SHARD_SOURCE as the product splits it (mislam_api.hip mi_icp_load / deal_chunks_kernel): every rank orders the WHOLE moving
+    # MI_SHARD_SOURCE as the product splits it (icp_api.hip mi_icp_load / deal_chunks_kernel): every rank orders the WHOLE moving
     # cloud the same way (the product: along the Hilbert curve, on the device; here any order all ranks agree on) and keeps the
     # 64-point chunks rank, rank + W, rank + 2W ... of that order -- the last chunk may be ragged -- or, below 4 * 64 * W points, a
     # contiguous slice of the caller's order.  Nothing per-point is exchanged; the shares partition the cloud (mi_source_share
