@@ -36,7 +36,7 @@ EXPORTS = [
     "mi_abi_version", "mi_last_error", "mi_device_count", "mi_ctx_create", "mi_dist_unique_id", "mi_ctx_create_dist",
     "mi_ctx_create_exchange", "mi_runtime_info", "mi_ctx_preload", "mi_ctx_rank", "mi_dist_info", "mi_shard_range", "mi_source_share", "mi_pack_key", "mi_unpack_key", "mi_ctx_destroy", "mi_ctx_synchronize", "mi_icp_params_default", "mi_icp_params_cuda_slam",
     "mi_icp_register", "mi_icp_load", "mi_icp_reset", "mi_icp_run", "mi_icp_auto_batch", "mi_icp_result", "mi_icp_batch_route", "mi_icp_register_batch", "mi_nn_search", "mi_nn_search_ex", "mi_cross_moments", "mi_kabsch",
-    "mi_transform_mse", "mi_cpd_params_default", "mi_cpd_register", "mi_cpd_sigma_squared", "mi_cpd_sigma_squared_mode", "mi_cpd_estep",
+    "mi_transform_mse", "mi_cpd_params_default", "mi_cpd_register", "mi_cpd_batch_route", "mi_cpd_register_batch", "mi_cpd_sigma_squared", "mi_cpd_sigma_squared_mode", "mi_cpd_estep",
     "mi_cpd_estep_truncated", "mi_cpd_estep_fgt", "mi_fgt_kcenter", "mi_fgt_kcenter_guided", "mi_fgt_tables", "mi_nicp_params_default", "mi_nicp_register",
     "mi_prepare_params_default", "mi_prepare_cloud",
     "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_fail_loads", "mi_nn_kernel_name",
@@ -189,6 +189,51 @@ def icp_register_batch_raw(handle, n_problems, before, before_range, after, afte
     return f(handle, n_problems, before, before_range, after, after_range, params, out_T, iterations, error, stop_reason, info)
 
 
+class CpdBatchInfo(C.Structure):
+    _fields_ = [("problems_batched", C.c_int), ("problems_fallback", C.c_int), ("launches", C.c_int), ("reserved", C.c_int * 5)]
+
+
+def cpd_batch_route(m_before, n_after, params):
+    """1 if mi_cpd_register_batch carries a problem of these sizes under these rules on the batched kernel, 0 if it takes the existing path."""
+    f = lib().mi_cpd_batch_route
+    f.argtypes = [C.c_int, C.c_int, C.POINTER(CpdParams)]
+    f.restype = C.c_int
+    return f(int(m_before), int(n_after), C.byref(params))
+
+
+def cpd_register_batch_raw(handle, n_problems, before, before_range, after, after_range, params, out_sR_t, out_scale, iterations, error, stop_reason,
+                           info):
+    """mi_cpd_register_batch with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_cpd_register_batch
+    f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 11
+    f.restype = C.c_int
+    return f(handle, n_problems, before, before_range, after, after_range, params, out_sR_t, out_scale, iterations, error, stop_reason, info)
+
+
+def _batch_arrays(befores, afters, before_range, after_range):
+    """The two concatenated clouds and (B, 2) range tables of a batched call, from lists of clouds or from arrays plus ranges; checks
+    that no range runs past its array (the C interface trusts the arrays to reach as far as the ranges say)."""
+    if before_range is None:
+        counts = [len(b) for b in befores]
+        before_range = np.stack([np.cumsum([0] + counts[:-1]), counts], axis=1) if counts else np.zeros((0, 2))
+        befores = np.concatenate([_cloud(b) for b in befores]) if counts else np.zeros((0, 3), np.float32)
+    if after_range is None:
+        counts = [len(a) for a in afters]
+        after_range = np.stack([np.cumsum([0] + counts[:-1]), counts], axis=1) if counts else np.zeros((0, 2))
+        afters = np.concatenate([_cloud(a) for a in afters]) if counts else np.zeros((0, 3), np.float32)
+    before, after = _cloud(befores), _cloud(afters)
+    br = np.ascontiguousarray(before_range, np.int32).reshape(-1, 2)
+    ar = np.ascontiguousarray(after_range, np.int32).reshape(-1, 2)
+    if len(br) != len(ar):
+        raise ValueError("before_range and after_range must name the same number of problems")
+    for name, r, n in (("before", br, len(before)), ("after", ar, len(after))):
+        for k in range(len(br)):
+            if r[k, 0] >= 0 and r[k, 1] >= 0 and int(r[k, 0]) + int(r[k, 1]) > n:
+                raise MiSlamError("libmislam error %d: problem %d: %s range %d + %d runs past the array (%d points)"
+                                  % (MI_ERR_INVALID_ARG, k, name, r[k, 0], r[k, 1], n))
+    return before, br, after, ar
+
+
 def icp_auto_batch(n_moving_total, m_fixed_total, world, source_sharded, every_pair_search):
     """Iterations mi_icp_run enqueues between host checks with sync_every = 0: a function of global sizes only."""
     f = lib().mi_icp_auto_batch
@@ -307,26 +352,8 @@ class Context:
         """B registrations under one set of rules (mi_icp_register_batch).  befores / afters: two lists of (n, 3) arrays -- or two
         (N, 3) arrays plus before_range / after_range, (B, 2) integer arrays of (first point, count).  Returns (R [B,3,3], t [B,3],
         iterations [B], error [B], stop_reason [B], info)."""
-        if before_range is None:
-            counts = [len(b) for b in befores]
-            before_range = np.stack([np.cumsum([0] + counts[:-1]), counts], axis=1) if counts else np.zeros((0, 2))
-            befores = np.concatenate([_cloud(b) for b in befores]) if counts else np.zeros((0, 3), np.float32)
-        if after_range is None:
-            counts = [len(a) for a in afters]
-            after_range = np.stack([np.cumsum([0] + counts[:-1]), counts], axis=1) if counts else np.zeros((0, 2))
-            afters = np.concatenate([_cloud(a) for a in afters]) if counts else np.zeros((0, 3), np.float32)
-        before, after = _cloud(befores), _cloud(afters)
-        br = np.ascontiguousarray(before_range, np.int32).reshape(-1, 2)
-        ar = np.ascontiguousarray(after_range, np.int32).reshape(-1, 2)
-        if len(br) != len(ar):
-            raise ValueError("before_range and after_range must name the same number of problems")
+        before, br, after, ar = _batch_arrays(befores, afters, before_range, after_range)
         B = len(br)
-        # the C interface trusts the arrays to reach as far as the ranges say: the binding knows their lengths and checks
-        for name, r, n in (("before", br, len(before)), ("after", ar, len(after))):
-            for k in range(B):
-                if r[k, 0] >= 0 and r[k, 1] >= 0 and int(r[k, 0]) + int(r[k, 1]) > n:
-                    raise MiSlamError("libmislam error %d: problem %d: %s range %d + %d runs past the array (%d points)"
-                                      % (MI_ERR_INVALID_ARG, k, name, r[k, 0], r[k, 1], n))
         T = np.zeros((B, 16), np.float32)
         it, why = np.zeros(B, np.int32), np.zeros(B, np.int32)
         err = np.zeros(B, np.float32)
@@ -336,6 +363,22 @@ class Context:
                                       C.addressof(info)))
         M = T.reshape(B, 4, 4).transpose(0, 2, 1)        # column-major 4x4 -> [row, col]
         return M[:, :3, :3].copy(), M[:, :3, 3].copy(), it, err, why, info
+
+    def cpd_register_batch(self, befores, afters, params, before_range=None, after_range=None):
+        """B CPD registrations under one set of rules (mi_cpd_register_batch).  befores / afters: two lists of (n, 3) arrays -- or two
+        (N, 3) arrays plus before_range / after_range, (B, 2) integer arrays of (first point, count).  Returns (sR [B,3,3], t [B,3],
+        scale [B], iterations [B], error [B], stop_reason [B], info)."""
+        before, br, after, ar = _batch_arrays(befores, afters, before_range, after_range)
+        B = len(br)
+        T = np.zeros((B, 16), np.float32)
+        it, why = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        err, scale = np.zeros(B, np.float32), np.zeros(B, np.float32)
+        info = CpdBatchInfo()
+        _check(cpd_register_batch_raw(self._h, B, before.ctypes.data, br.ctypes.data, after.ctypes.data, ar.ctypes.data,
+                                      C.addressof(params), T.ctypes.data, scale.ctypes.data, it.ctypes.data, err.ctypes.data,
+                                      why.ctypes.data, C.addressof(info)))
+        M = T.reshape(B, 4, 4).transpose(0, 2, 1)        # column-major 4x4 -> [row, col]
+        return M[:, :3, :3].copy(), M[:, :3, 3].copy(), scale, it, err, why, info
 
     def icp_load(self, before, after, params):
         before, after = _cloud(before), _cloud(after)

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mi_slam.h"
+#include "cpd_kernels.h"
 #include "kernels.h"
 #include "nn_grid.h"
 #include "nn_tree.h"
@@ -200,12 +201,14 @@ struct mi_ctx {
     mislam::DevBuf<int> sinv;                            // its inverse (caller's index -> sorted slot), MI_SUM_CPU_SEQUENTIAL only
     mislam::DevBuf<float> resid;                         // per-slot squared residuals, same mode
 
-    // ---- mi_icp_register_batch: both concatenated arrays as uploaded (AoS), every problem's sorted moving cloud, the problem table,
-    // one state block per problem, the "still running" word (icp_batch.hip)
+    // ---- mi_icp_register_batch / mi_cpd_register_batch: both concatenated arrays as uploaded (AoS) and the "still running" word (shared);
+    // every ICP problem's sorted moving cloud; per method the problem table and one state block per problem (icp_batch.hip, cpd_batch.hip)
     struct BatchBuffers {
         mislam::DevBuf<float> before, after, sx, sy, sz;
         mislam::DevBuf<mislam::IcpBatchProblem> problems;
         mislam::DevBuf<mislam::IcpState> states;
+        mislam::DevBuf<mislam::CpdBatchProblem> cpd_problems;
+        mislam::DevBuf<mislam::CpdState> cpd_states;
         mislam::DevBuf<int> running;
     } bat;
 
@@ -320,5 +323,41 @@ int allreduce_keys(mi_ctx* ctx, int n);                      // min over the ran
 // host memory.  No-ops on a single-GPU context.
 int allreduce_min_u64(mi_ctx* ctx, unsigned long long* dev_ptr, size_t count);
 int allreduce_sum_f64(mi_ctx* ctx, double* dev_ptr, size_t count);
+
+// ---- host plumbing the batched calls share (mi_icp_register_batch, mi_cpd_register_batch)
+// The points any batched problem of a call uses: [b_lo, b_hi) of the caller's moving array, [a_lo, a_hi) of the fixed one.
+struct BatchSpan {
+    long long b_lo = -1, b_hi = 0, a_lo = -1, a_hi = 0;
+    void add(long long bo, long long bn, long long ao, long long an)
+    {
+        b_lo = b_lo < 0 || bo < b_lo ? bo : b_lo; b_hi = bo + bn > b_hi ? bo + bn : b_hi;
+        a_lo = a_lo < 0 || ao < a_lo ? ao : a_lo; a_hi = ao + an > a_hi ? ao + an : a_hi;
+    }
+};
+// One upload of each array (AoS, as it is, through the pinned ring) into ctx->bat.before / after; overlapping ranges travel once.
+static inline int batch_upload_clouds(mi_ctx* c, const float* before_xyz, const float* after_xyz, const BatchSpan& sp)
+{
+    const size_t nbefore = (size_t)(sp.b_hi - sp.b_lo), nafter = (size_t)(sp.a_hi - sp.a_lo);
+    MI_TRY(c->bat.before.reserve(3 * nbefore)); MI_TRY(c->bat.after.reserve(3 * nafter)); MI_TRY(c->bat.running.reserve(1));
+    MI_TRY(host_to_device(c, c->bat.before.p, before_xyz + 3 * (size_t)sp.b_lo, sizeof(float) * 3 * nbefore));
+    MI_TRY(host_to_device(c, c->bat.after.p, after_xyz + 3 * (size_t)sp.a_lo, sizeof(float) * 3 * nafter));
+    return MI_OK;
+}
+// Bounded launches until no problem is running: `launch` enqueues one launch of the iterate kernel, whose workgroups count the problems
+// they leave unfinished in ctx->bat.running; the host reads the word behind every launch.
+template <class Launch>
+static inline int batch_run_until_quiet(mi_ctx* c, bool anything_to_run, Launch&& launch, int* launches)
+{
+    int* h_running = reinterpret_cast<int*>(c->h_scratch);
+    *h_running = anything_to_run ? 1 : 0;
+    while (*h_running != 0) {
+        MI_HIP(hipMemsetAsync(c->bat.running.p, 0, sizeof(int), c->stream));
+        MI_HIP(launch());
+        (*launches)++;
+        MI_HIP(hipMemcpyAsync(h_running, c->bat.running.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        MI_HIP(hipStreamSynchronize(c->stream));
+    }
+    return MI_OK;
+}
 
 }  // namespace mislam

@@ -558,6 +558,19 @@ static int cpd_estep_fgt_enqueue(mi_ctx* c, CpdWorkspace* w, const CpdView& v, f
 
 }  // namespace mislam
 
+// return make_pair(scale * rotationMatrix, translationVector)   coherentpointdrift.cpp:123 / cpdcuda.cu:360
+static void cpd_state_to_outputs(const CpdState* s, float* out_sR_t, float* out_scale, int* iterations, float* error)
+{
+    for (int col = 0; col < 3; col++) {
+        for (int row = 0; row < 3; row++) out_sR_t[4 * col + row] = s->scale * s->R[3 * col + row];
+        out_sR_t[4 * col + 3] = 0.f;
+    }
+    out_sR_t[12] = s->t[0]; out_sR_t[13] = s->t[1]; out_sR_t[14] = s->t[2]; out_sR_t[15] = 1.f;
+    if (out_scale) *out_scale = s->scale;
+    *iterations = s->iterations;
+    *error = s->error;
+}
+
 extern "C" void mi_cpd_params_default(mi_cpd_params* p)
 {
     if (!p) return;
@@ -583,26 +596,44 @@ static int cpd_check(mi_ctx* c, const float* b, int m, const float* a, int n, bo
     return MI_OK;
 }
 
+// What a registration refuses in its parameters whatever the clouds are -- one place for mi_cpd_register and mi_cpd_register_batch, so that
+// the batched call refuses exactly what the single call refuses.  `who` names the entry point in the message.
+static int cpd_check_params(const mi_cpd_params* params, int world, const char* who)
+{
+    if (params->approximation < MI_CPD_APPROX_NONE || params->approximation > MI_CPD_APPROX_HYBRID) {
+        set_error("%s: unknown approximation %d", who, params->approximation);
+        return MI_ERR_INVALID_ARG;
+    }
+    if (params->approximation != MI_CPD_APPROX_NONE && (params->fgt_order_of_truncation < 1 || params->fgt_order_of_truncation > FGT_MAX_ORDER)) {
+        set_error("%s: the FGT modes need 1 <= order of truncation <= %d and >= 2 points per cloud", who, FGT_MAX_ORDER);
+        return MI_ERR_INVALID_ARG;
+    }
+    if (params->estep_mode != MI_ESTEP_DEFAULT && params->estep_mode != MI_ESTEP_CPU_SEQUENTIAL) { set_error("%s: bad estep_mode %d", who, params->estep_mode); return MI_ERR_INVALID_ARG; }
+    if (params->estep_mode == MI_ESTEP_CPU_SEQUENTIAL && (world > 1 || params->approximation != MI_CPD_APPROX_NONE)) {
+        set_error("%s: MI_ESTEP_CPU_SEQUENTIAL is a single-GPU parity mode of the exact E-step", who);
+        return MI_ERR_INVALID_ARG;
+    }
+    if (params->sigma2_mode != MI_SIGMA2_EXACT && params->sigma2_mode != MI_SIGMA2_CPU_SEQUENTIAL) { set_error("%s: bad sigma2_mode %d", who, params->sigma2_mode); return MI_ERR_INVALID_ARG; }
+    return MI_OK;
+}
+// ... and in the sizes of one pair under those parameters
+static int cpd_check_fgt_sizes(const mi_cpd_params* params, long long m, long long n, const char* who)
+{
+    if (params->approximation != MI_CPD_APPROX_NONE && (m < 2 || n < 2)) {
+        set_error("%s: the FGT modes need 1 <= order of truncation <= %d and >= 2 points per cloud (m=%lld, n=%lld)", who, FGT_MAX_ORDER, m, n);
+        return MI_ERR_INVALID_ARG;
+    }
+    return MI_OK;
+}
+
 extern "C" int mi_cpd_register(mi_ctx* c, const float* before_xyz, int m_before, const float* after_xyz, int n_after,
                                const mi_cpd_params* params, float out_sR_t[16], float* out_scale, int* iterations, float* error)
 {
     MI_TRY(cpd_check(c, before_xyz, m_before, after_xyz, n_after, true));
     if (!params || !out_sR_t || !iterations || !error) { set_error("mi_cpd_register: null argument"); return MI_ERR_INVALID_ARG; }
     if (n_after < c->world) { set_error("mi_cpd_register: %d fixed points cannot be split over %d ranks", n_after, c->world); return MI_ERR_INVALID_ARG; }
-    if (params->approximation < MI_CPD_APPROX_NONE || params->approximation > MI_CPD_APPROX_HYBRID) {
-        set_error("mi_cpd_register: unknown approximation %d", params->approximation);
-        return MI_ERR_INVALID_ARG;
-    }
-    if (params->approximation != MI_CPD_APPROX_NONE &&
-        (params->fgt_order_of_truncation < 1 || params->fgt_order_of_truncation > FGT_MAX_ORDER || m_before < 2 || n_after < 2)) {
-        set_error("mi_cpd_register: the FGT modes need 1 <= order of truncation <= %d and >= 2 points per cloud", FGT_MAX_ORDER);
-        return MI_ERR_INVALID_ARG;
-    }
-    if (params->estep_mode != MI_ESTEP_DEFAULT && params->estep_mode != MI_ESTEP_CPU_SEQUENTIAL) { set_error("mi_cpd_register: bad estep_mode %d", params->estep_mode); return MI_ERR_INVALID_ARG; }
-    if (params->estep_mode == MI_ESTEP_CPU_SEQUENTIAL && (c->world > 1 || params->approximation != MI_CPD_APPROX_NONE)) {
-        set_error("mi_cpd_register: MI_ESTEP_CPU_SEQUENTIAL is a single-GPU parity mode of the exact E-step");
-        return MI_ERR_INVALID_ARG;
-    }
+    MI_TRY(cpd_check_params(params, c->world, "mi_cpd_register"));
+    MI_TRY(cpd_check_fgt_sizes(params, m_before, n_after, "mi_cpd_register"));
     MI_ENTER(c);
     CpdWorkspace* w = nullptr;
     MI_TRY(cpd_workspace(c, &w));
@@ -624,7 +655,6 @@ extern "C" int mi_cpd_register(mi_ctx* c, const float* before_xyz, int m_before,
     w->n_total = n_after;
     const CpdView v = cpd_view(c, w);
     const CpdRules rules = cpd_rules(w, params);
-    if (params->sigma2_mode != MI_SIGMA2_EXACT && params->sigma2_mode != MI_SIGMA2_CPU_SEQUENTIAL) { set_error("mi_cpd_register: bad sigma2_mode %d", params->sigma2_mode); return MI_ERR_INVALID_ARG; }
     MI_TRY(cpd_init(c, w, v, rules, params->sigma2_init, params->sigma2_mode));
     MI_TRY(cpd_fetch(c, w));
     int batch = params->sync_every;
@@ -696,16 +726,109 @@ extern "C" int mi_cpd_register(mi_ctx* c, const float* before_xyz, int m_before,
     // that return at once) or the prelaunched K-centre replay.  Drained here, so that the call's wall time brackets all of its device work
     // (bench.py's timers around this call used to miss that tail) and the workspace is quiet when the caller gets it back.
     MI_HIP(hipStreamSynchronize(c->stream));
-    const CpdState* s = w->h_state;
-    // return make_pair(scale * rotationMatrix, translationVector)   coherentpointdrift.cpp:123 / cpdcuda.cu:360
-    for (int col = 0; col < 3; col++) {
-        for (int row = 0; row < 3; row++) out_sR_t[4 * col + row] = s->scale * s->R[3 * col + row];
-        out_sR_t[4 * col + 3] = 0.f;
+    cpd_state_to_outputs(w->h_state, out_sR_t, out_scale, iterations, error);
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// batched CPD: many small exact-P registrations under one set of rules (cpd_batch.hip)
+// ---------------------------------------------------------------------------------------------------------------
+// Sizes the batched kernel is routed: decided by measurement (DESIGN.md section 4, K-batch CPD): at 64 problems of 2 048 x 2 048 the
+// batch beats the loop of single calls, at 4 096 x 4 096 it lost; the kernel is sized to the routed edge
+constexpr int CPD_BATCH_ROUTE_MAX = CPD_BATCH_MAX_POINTS;
+
+extern "C" int mi_cpd_batch_route(int m_before, int n_after, const mi_cpd_params* params)
+{
+    if (!params || m_before < 1 || n_after < 1) return 0;
+    if (params->approximation != MI_CPD_APPROX_NONE) return 0;                  // the FGT / hybrid E-steps are host-stepped and cluster whole clouds
+    if (params->estep_mode != MI_ESTEP_DEFAULT || params->verbose != 0) return 0;   // the sequential parity sums and the per-iteration print are the single path's
+    if (params->sigma2_mode != MI_SIGMA2_EXACT && !(params->sigma2_init > 0.f)) return 0;
+    return m_before <= CPD_BATCH_ROUTE_MAX && n_after <= CPD_BATCH_ROUTE_MAX ? 1 : 0;
+}
+
+extern "C" int mi_cpd_register_batch(mi_ctx* c, int n_problems, const float* before_xyz, const int* before_range, const float* after_xyz,
+                                     const int* after_range, const mi_cpd_params* params, float* out_sR_t, float* out_scale, int* iterations,
+                                     float* error, int* stop_reason, mi_cpd_batch_info* info)
+{
+    if (info) memset(info, 0, sizeof *info);
+    if (!c) { set_error("CPD: null context"); return MI_ERR_INVALID_ARG; }       // (code and message of mi_cpd_register)
+    if (n_problems < 0) { set_error("mi_cpd_register_batch: n_problems = %d", n_problems); return MI_ERR_INVALID_ARG; }
+    if (c->distributed()) { set_error("mi_cpd_register_batch: single-GPU contexts only"); return MI_ERR_STATE; }
+    // what mi_cpd_register refuses whatever the sizes
+    if (!params) { set_error("mi_cpd_register_batch: null parameters"); return MI_ERR_INVALID_ARG; }
+    MI_TRY(cpd_check_params(params, c->world, "mi_cpd_register_batch"));
+    if (n_problems == 0) return MI_OK;
+    if (!before_xyz || !after_xyz || !before_range || !after_range) { set_error("mi_cpd_register_batch: null cloud or range array"); return MI_ERR_INVALID_ARG; }
+    if (!out_sR_t || !iterations || !error || !stop_reason) { set_error("mi_cpd_register_batch: out_sR_t, iterations, error and stop_reason must be non-null"); return MI_ERR_INVALID_ARG; }
+    // A context whose single path takes the VALU contraction (MISLAM_CPD_MFMA=0: two roundings per product) computes other bits than the
+    // matrix-pipe chain the batched kernel is built on: such a context sends every problem through the single path.
+    const bool kernel_follows = c->tune.cpd_mfma != 0;
+    std::vector<CpdBatchProblem> table;
+    std::vector<int> batched, fallback;
+    BatchSpan span;
+    long long max_pairs = 0;
+    int max_points = 0;
+    for (int k = 0; k < n_problems; k++) {
+        const long long bo = before_range[2 * k], bm = before_range[2 * k + 1], ao = after_range[2 * k], an = after_range[2 * k + 1];
+        if (bo < 0 || ao < 0 || bm < 1 || an < 1 || bo + bm > 0x7fffffffLL || ao + an > 0x7fffffffLL) {
+            set_error("mi_cpd_register_batch: problem %d has an invalid range (before %lld + %lld, after %lld + %lld)", k, bo, bm, ao, an);
+            return MI_ERR_INVALID_ARG;
+        }
+        { char who[64]; snprintf(who, sizeof who, "mi_cpd_register_batch: problem %d", k); MI_TRY(cpd_check_fgt_sizes(params, bm, an, who)); }
+        if (!kernel_follows || !mi_cpd_batch_route((int)bm, (int)an, params)) { fallback.push_back(k); continue; }
+        batched.push_back(k);
+        span.add(bo, bm, ao, an);
+        CpdBatchProblem p{};
+        p.b_off = (int)bo; p.m = (int)bm; p.a_off = (int)ao; p.n = (int)an;
+        // the single path's chunking of these sizes on this device (cpd_load)
+        plan_chunks(c, p.n, 4, p.m, &p.k_chunks, &p.k_chunk_len);
+        plan_chunks(c, p.m, 2, p.n, &p.x_chunks, &p.x_chunk_len);
+        table.push_back(p);
+        max_pairs = std::max(max_pairs, bm * an);
+        max_points = std::max(max_points, (int)std::max(bm, an));
     }
-    out_sR_t[12] = s->t[0]; out_sR_t[13] = s->t[1]; out_sR_t[14] = s->t[2]; out_sR_t[15] = 1.f;
-    if (out_scale) *out_scale = s->scale;
-    *iterations = s->iterations;
-    *error = s->error;
+    MI_ENTER(c);
+    c->prob.icp_loaded = false;                               // as cpd_load: no ICP problem stays loaded
+    int launches = 0;
+    if (!batched.empty()) {
+        const int nb = (int)batched.size();
+        for (CpdBatchProblem& p : table) { p.b_off -= (int)span.b_lo; p.a_off -= (int)span.a_lo; }
+        MI_TRY(c->bat.cpd_problems.reserve((size_t)nb)); MI_TRY(c->bat.cpd_states.reserve((size_t)nb));
+        MI_TRY(batch_upload_clouds(c, before_xyz, after_xyz, span));
+        MI_HIP(hipMemcpyAsync(c->bat.cpd_problems.p, table.data(), sizeof(CpdBatchProblem) * (size_t)nb, hipMemcpyHostToDevice, c->stream));
+        MI_HIP(hipStreamSynchronize(c->stream));         // (the table is pageable host memory of this frame)
+        CpdBatchArgs a{};
+        a.before = c->bat.before.p; a.after = c->bat.after.p; a.problems = c->bat.cpd_problems.p;
+        a.states = c->bat.cpd_states.p; a.running = c->bat.running.p;
+        a.n_problems = nb;
+        a.max_points = max_points;
+        // a launch ends after `iters` EM iterations of its longest problem: two passes over at most 2^26 pairs per workgroup and launch
+        // (~10 ms on one CU), never fewer than 4 iterations (a launch boundary is a host round trip)
+        a.iters = (int)std::max(4LL, std::min(64LL, (1LL << 26) / std::max(1LL, max_pairs)));
+        a.sigma2_override = params->sigma2_init;
+        CpdWorkspace shape{};                            // (cpd_rules reads the sizes and the SVD switch from a workspace; m, n are set per problem in the kernel)
+        shape.svd_ieee = c->tune.svd_ieee;
+        a.rules = cpd_rules(&shape, params);
+        MI_HIP(cpd_batch_init(a, c->stream));
+        MI_TRY(batch_run_until_quiet(c, params->max_iterations > 0, [&] { return cpd_batch_iterate(a, c->stream); }, &launches));
+        std::vector<CpdState> states((size_t)nb);
+        MI_HIP(hipMemcpyAsync(states.data(), c->bat.cpd_states.p, sizeof(CpdState) * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+        MI_HIP(hipStreamSynchronize(c->stream));
+        retire_buffers(c);
+        for (int i = 0; i < nb; i++) {
+            const int k = batched[(size_t)i];
+            cpd_state_to_outputs(&states[(size_t)i], out_sR_t + 16 * (size_t)k, out_scale ? out_scale + k : nullptr, iterations + k, error + k);
+            stop_reason[k] = states[(size_t)i].stop_reason;
+        }
+    }
+    for (int k : fallback) {                             // the existing path, one after the other
+        const float* b = before_xyz + 3 * (size_t)before_range[2 * k];
+        const float* a = after_xyz + 3 * (size_t)after_range[2 * k];
+        MI_TRY(mi_cpd_register(c, b, before_range[2 * k + 1], a, after_range[2 * k + 1], params, out_sR_t + 16 * (size_t)k,
+                               out_scale ? out_scale + k : nullptr, iterations + k, error + k));
+        stop_reason[k] = c->cpd->h_state->stop_reason;   // (the state block the single call's last host check read: the one that said "done")
+    }
+    if (info) { info->problems_batched = (int)batched.size(); info->problems_fallback = (int)fallback.size(); info->launches = launches; }
     return MI_OK;
 }
 

@@ -124,4 +124,30 @@ hipError_t cpd_solve(CpdState* state, const double* xpart, int nxb, const double
 hipError_t cpd_transform(const CpdView& v, int m_pad, hipStream_t s);                          // y = s*R*b + t
 hipError_t cpd_set_sigma2(CpdState* state, float sigma2, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K-batch CPD: many small exact-P registrations, one workgroup per problem, the EM iterations inside the kernel (cpd_batch.hip)
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int CPD_BATCH_MAX_POINTS = 2048;    // per cloud: the routed edge (mi_cpd_batch_route); both clouds' stream copies, the xw4 records and Pt1 of a problem sit in LDS whole
+struct CpdBatchProblem {
+    int b_off, m;                    // moving cloud: first point in `before`, count
+    int a_off, n;                    // fixed cloud: first point in `after`, count
+    int k_chunks, k_chunk_len;       // the single path's chunking of this problem (plan_chunks): the order the fp32 sums are added in
+    int x_chunks, x_chunk_len;
+};
+struct CpdBatchArgs {
+    const float* before;             // AoS xyz, as uploaded
+    const float* after;
+    const CpdBatchProblem* problems;
+    CpdState* states;                // one block per problem
+    int* running;                    // += 1 per problem still running when a launch ends (zeroed by the host before it)
+    int n_problems;
+    int iters;                       // EM iterations per problem and launch, at most
+    int max_points;                  // the largest cloud of the batch: sizes the workgroup's LDS
+    float sigma2_override;           // mi_cpd_params::sigma2_init
+    CpdRules rules;                  // m and n are the problem's own (set in the kernel)
+};
+size_t cpd_batch_lds_bytes(int max_points);
+hipError_t cpd_batch_init(const CpdBatchArgs& a, hipStream_t s);              // the state blocks at sigma^2_0
+hipError_t cpd_batch_iterate(const CpdBatchArgs& a, hipStream_t s);           // up to a.iters EM iterations of every running problem
+
 }  // namespace mislam

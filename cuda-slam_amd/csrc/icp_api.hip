@@ -525,7 +525,8 @@ extern "C" int mi_icp_register_batch(mi_ctx* c, int n_problems, const float* bef
     // the table of the problems the kernel carries; offsets relative to the first point any of them uses
     std::vector<IcpBatchProblem> table;
     std::vector<int> batched, fallback;
-    long long b_lo = -1, b_hi = 0, a_lo = -1, a_hi = 0, slots = 0, max_pairs = 0;
+    BatchSpan span;
+    long long slots = 0, max_pairs = 0;
     for (int k = 0; k < n_problems; k++) {
         const long long bo = before_range[2 * k], bn = before_range[2 * k + 1], ao = after_range[2 * k], an = after_range[2 * k + 1];
         if (bo < 0 || ao < 0 || bn < 1 || an < 1 || bo + bn > 0x7fffffffLL || ao + an > 0x7fffffffLL) {
@@ -534,8 +535,7 @@ extern "C" int mi_icp_register_batch(mi_ctx* c, int n_problems, const float* bef
         }
         if (!mi_icp_batch_route((int)bn, (int)an, params)) { fallback.push_back(k); continue; }
         batched.push_back(k);
-        b_lo = b_lo < 0 || bo < b_lo ? bo : b_lo; b_hi = std::max(b_hi, bo + bn);
-        a_lo = a_lo < 0 || ao < a_lo ? ao : a_lo; a_hi = std::max(a_hi, ao + an);
+        span.add(bo, bn, ao, an);
         IcpBatchProblem p{};
         p.b_off = (int)bo; p.n = (int)bn; p.a_off = (int)ao; p.m = (int)an; p.s_off = (int)slots;
         table.push_back(p);
@@ -548,13 +548,10 @@ extern "C" int mi_icp_register_batch(mi_ctx* c, int n_problems, const float* bef
     int launches = 0;
     if (!batched.empty()) {
         const int nb = (int)batched.size();
-        for (IcpBatchProblem& p : table) { p.b_off -= (int)b_lo; p.a_off -= (int)a_lo; }
-        const size_t nbefore = (size_t)(b_hi - b_lo), nafter = (size_t)(a_hi - a_lo);
-        MI_TRY(c->bat.before.reserve(3 * nbefore)); MI_TRY(c->bat.after.reserve(3 * nafter));
+        for (IcpBatchProblem& p : table) { p.b_off -= (int)span.b_lo; p.a_off -= (int)span.a_lo; }
         MI_TRY(c->bat.sx.reserve((size_t)slots)); MI_TRY(c->bat.sy.reserve((size_t)slots)); MI_TRY(c->bat.sz.reserve((size_t)slots));
-        MI_TRY(c->bat.problems.reserve((size_t)nb)); MI_TRY(c->bat.states.reserve((size_t)nb)); MI_TRY(c->bat.running.reserve(1));
-        MI_TRY(host_to_device(c, c->bat.before.p, before_xyz + 3 * (size_t)b_lo, sizeof(float) * 3 * nbefore));
-        MI_TRY(host_to_device(c, c->bat.after.p, after_xyz + 3 * (size_t)a_lo, sizeof(float) * 3 * nafter));
+        MI_TRY(c->bat.problems.reserve((size_t)nb)); MI_TRY(c->bat.states.reserve((size_t)nb));
+        MI_TRY(batch_upload_clouds(c, before_xyz, after_xyz, span));
         MI_HIP(hipMemcpyAsync(c->bat.problems.p, table.data(), sizeof(IcpBatchProblem) * (size_t)nb, hipMemcpyHostToDevice, c->stream));
         MI_HIP(hipStreamSynchronize(c->stream));         // (the table is pageable host memory of this frame)
         IcpBatchArgs a{};
@@ -569,15 +566,7 @@ extern "C" int mi_icp_register_batch(mi_ctx* c, int n_problems, const float* bef
         a.max_distance_squared = params->max_distance_squared;
         a.rules = icp_rules(*params, 0, c->tune.svd_ieee);   // (sum_mode is MI_SUM_EXACT for every batched problem: mi_icp_batch_route)
         MI_HIP(icp_batch_prepare(a, c->stream));
-        int* h_running = reinterpret_cast<int*>(c->h_scratch);
-        *h_running = params->max_iterations == 0 ? 0 : 1;
-        while (*h_running != 0) {
-            MI_HIP(hipMemsetAsync(c->bat.running.p, 0, sizeof(int), c->stream));
-            MI_HIP(icp_batch_iterate(a, params->dist_mode == MI_DIST_FMA, c->stream));
-            launches++;
-            MI_HIP(hipMemcpyAsync(h_running, c->bat.running.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            MI_HIP(hipStreamSynchronize(c->stream));
-        }
+        MI_TRY(batch_run_until_quiet(c, params->max_iterations != 0, [&] { return icp_batch_iterate(a, params->dist_mode == MI_DIST_FMA, c->stream); }, &launches));
         std::vector<IcpState> states((size_t)nb);
         MI_HIP(hipMemcpyAsync(states.data(), c->bat.states.p, sizeof(IcpState) * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
         MI_HIP(hipStreamSynchronize(c->stream));

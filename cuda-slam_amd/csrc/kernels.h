@@ -173,6 +173,7 @@ hipError_t preload_nn_grid();
 hipError_t preload_icp_kernels();
 hipError_t preload_icp_batch();
 hipError_t preload_cpd_kernels();
+hipError_t preload_cpd_batch();
 hipError_t preload_cpd_fgt();
 hipError_t preload_nicp_api();
 hipError_t preload_prepare_api();

@@ -358,6 +358,55 @@ void mi_cpd_params_default(mi_cpd_params* p);
 int mi_cpd_register(mi_ctx* ctx, const float* before_xyz, int m_before, const float* after_xyz, int n_after,
                     const mi_cpd_params* params, float out_sR_t[16], float* out_scale, int* iterations, float* error);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * Batched CPD: many small registrations under ONE set of rules in one call (single-GPU contexts only).
+ * An exact EM iteration of a cloud of a thousand points is six launches none of which fills more than a fraction of the device; here
+ * every problem gets a workgroup of its own and its EM iterations run inside one kernel, a few hundred problems side by side.  A
+ * caller with ONE pair keeps calling mi_cpd_register: a single workgroup is slower than the whole device.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int problems_batched;    /* problems that ran on the batched kernel */
+    int problems_fallback;   /* problems that ran through mi_cpd_register's path inside this call */
+    int launches;            /* launches of the batched kernel */
+    int reserved[5];
+} mi_cpd_batch_info;
+
+/* 1 if a problem of these sizes under these rules is carried by the batched kernel, 0 if the call routes it through the existing
+ * path.  Pure host function of its arguments (no context, no device).  Routed: 1 <= m_before <= 2048 and 1 <= n_after <= 2048
+ * under approximation == MI_CPD_APPROX_NONE, estep_mode == MI_ESTEP_DEFAULT, sigma2_mode == MI_SIGMA2_EXACT (or sigma2_init > 0,
+ * which leaves the mode nothing to compute) and verbose == 0 -- a function of the two sizes and those fields only, monotone in the
+ * sizes.  The FGT / hybrid E-steps are host-stepped and cluster whole clouds, the two CPU-sequential parity modes and the
+ * per-iteration print belong to the single path.  The edge was set by measurement (DESIGN.md section 4, K-batch CPD): at 64
+ * problems the batched call beats the loop of single calls 2.2 x at 2048 x 2048 and loses (0.8 x) at 4096 x 4096; sizes in between
+ * were not measured and are not routed.  Routed does not mean faster for every batch: one problem alone is slower batched at every
+ * size, and near the edge a batch needs several dozen problems to pay off (2048 points: 0.57 x at 16 problems, 2.2 x at 64; 1024
+ * points: 1.8 x at 16) -- the table in DESIGN.md has every measured (problems, size).
+ * Developer switch: a context created under MISLAM_CPD_MFMA=0 (the single path's contraction on the vector pipe: other roundings
+ * than the matrix-pipe chain the batched kernel is built on) sends every problem of a batched call through the existing path,
+ * whatever this function says; MISLAM_SVD_IEEE=1 is followed by the batched kernel. */
+int mi_cpd_batch_route(int m_before, int n_after, const mi_cpd_params* params);
+
+/* B independent registrations.  Problem k moves the points before_xyz[3*before_range[2k] ...] (before_range[2k+1] of them) onto
+ * after_xyz[3*after_range[2k] ...] (after_range[2k+1] of them); both arrays must reach as far as the ranges say.  Ranges may
+ * overlap or coincide.  out_sR_t: 16*B floats (column-major 4x4 each: scale*R and t, as mi_cpd_register writes them); out_scale,
+ * iterations, error, stop_reason: B entries each; out_scale and info may be NULL, the others not.  Problem k's out_sR_t, out_scale,
+ * iterations and error are, BIT FOR BIT, what
+ *   mi_cpd_register(ctx, before_k, m_k, after_k, n_k, params, ...)
+ * returns on the same context -- whatever else is in the batch and in whatever position; sync_every is accepted and, as in the
+ * single call, moves no bit.  stop_reason[k] is the MI_STOP_* of the problem's state block (MI_STOP_MAX_ITERATIONS, MI_STOP_TOLERANCE
+ * or MI_STOP_SIGMA, tested in that order after every iteration), which the single call does not return.  Every problem
+ * mi_cpd_register accepts is accepted: the ones mi_cpd_batch_route does not route run through the existing path inside the call,
+ * one after the other.  n_problems == 0 is MI_OK.  A range with a negative offset or a count < 1, a NULL output, or parameters
+ * mi_cpd_register would refuse: MI_ERR_INVALID_ARG, mi_last_error names the problem, nothing has touched the device.  A
+ * distributed context: MI_ERR_STATE.  Afterwards no ICP problem is loaded (as after mi_cpd_register).  Every launch of the kernel
+ * ends: it carries a bounded number of EM iterations. */
+int mi_cpd_register_batch(mi_ctx* ctx, int n_problems,
+                          const float* before_xyz, const int* before_range,
+                          const float* after_xyz,  const int* after_range,
+                          const mi_cpd_params* params,
+                          float* out_sR_t, float* out_scale, int* iterations, float* error, int* stop_reason,
+                          mi_cpd_batch_info* info);
+
 /* CalculateSigmaSquared (cpdcuda.cu:65-78 / coherentpointdrift.cpp:126-139): the exact value, or with an explicit MI_SIGMA2_* mode. */
 int mi_cpd_sigma_squared(mi_ctx* ctx, const float* before_xyz, int m, const float* after_xyz, int n, float* sigma2);
 int mi_cpd_sigma_squared_mode(mi_ctx* ctx, const float* before_xyz, int m, const float* after_xyz, int n, int sigma2_mode, float* sigma2);
