@@ -38,7 +38,7 @@ EXPORTS = [
     "mi_icp_register", "mi_icp_load", "mi_icp_reset", "mi_icp_run", "mi_icp_auto_batch", "mi_icp_result", "mi_icp_batch_route", "mi_icp_register_batch", "mi_nn_search", "mi_nn_search_ex", "mi_cross_moments", "mi_kabsch",
     "mi_transform_mse", "mi_cpd_params_default", "mi_cpd_register", "mi_cpd_batch_route", "mi_cpd_register_batch", "mi_cpd_sigma_squared", "mi_cpd_sigma_squared_mode", "mi_cpd_estep",
     "mi_cpd_estep_truncated", "mi_cpd_estep_fgt", "mi_fgt_kcenter", "mi_fgt_kcenter_guided", "mi_fgt_tables", "mi_nicp_params_default", "mi_nicp_register",
-    "mi_prepare_params_default", "mi_prepare_cloud",
+    "mi_prepare_params_default", "mi_prepare_cloud", "mi_voxel_index", "mi_voxel_downsample", "mi_voxel_downsample_times",
     "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_fail_loads", "mi_nn_kernel_name",
 ]
 
@@ -232,6 +232,31 @@ def _batch_arrays(befores, afters, before_range, after_range):
                 raise MiSlamError("libmislam error %d: problem %d: %s range %d + %d runs past the array (%d points)"
                                   % (MI_ERR_INVALID_ARG, k, name, r[k, 0], r[k, 1], n))
     return before, br, after, ar
+
+
+def voxel_index_raw(p, origin, voxel, out):
+    """mi_voxel_index with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_voxel_index
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+    f.restype = C.c_int
+    return f(p, origin, voxel, out)
+
+
+def voxel_index(p, origin, voxel):
+    """The voxel a point falls in (mi_voxel_index, host only): int32 [3] = floor((p - origin) / voxel) in fp32."""
+    p = np.ascontiguousarray(p, np.float32).reshape(3)
+    origin = np.ascontiguousarray(origin, np.float32).reshape(3)
+    out = np.zeros(3, np.int32)
+    _check(voxel_index_raw(p.ctypes.data, origin.ctypes.data, float(voxel), out.ctypes.data))
+    return out
+
+
+def voxel_downsample_raw(handle, xyz, n, voxel, origin, out_xyz, out_n, out_count, out_coord, voxel_of_point):
+    """mi_voxel_downsample with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_voxel_downsample
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 6
+    f.restype = C.c_int
+    return f(handle, xyz, n, voxel, origin, out_xyz, out_n, out_count, out_coord, voxel_of_point)
 
 
 def icp_auto_batch(n_moving_total, m_fixed_total, world, source_sharded, every_pair_search):
@@ -582,6 +607,40 @@ class Context:
                                       C.byref(p), _fp(out), C.byref(got)))
         assert got.value == n + n_out
         return out
+
+    # ---- voxel-grid downsampling
+    def voxel_downsample(self, xyz, voxel, origin=None, want_counts=False, want_coords=False, want_map=False):
+        """Voxel-grid centroids (mi_voxel_downsample): one row per occupied voxel, ascending by (cz, cy, cx).  Returns the centroids
+        [rows, 3], followed by whatever was asked for, in this order: counts [rows], voxel coordinates [rows, 3], and the output row
+        of every input point [n]."""
+        xyz = _cloud(xyz)
+        n = xyz.shape[0]
+        op = None
+        if origin is not None:
+            origin = np.ascontiguousarray(origin, np.float32).reshape(3)
+            op = origin.ctypes.data
+        out = np.empty((n, 3), np.float32)
+        counts = np.empty(n, np.int32) if want_counts else None
+        coords = np.empty((n, 3), np.int32) if want_coords else None
+        vmap = np.empty(n, np.int32) if want_map else None
+        rows = C.c_int(0)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _check(voxel_downsample_raw(self._h, xyz.ctypes.data, n, float(voxel), op, out.ctypes.data, C.addressof(rows), ptr(counts), ptr(coords),
+                                    ptr(vmap)))
+        res = [out[:rows.value].copy()]
+        if want_counts:
+            res.append(counts[:rows.value].copy())
+        if want_coords:
+            res.append(coords[:rows.value].copy())
+        if want_map:
+            res.append(vmap)
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def voxel_downsample_times(self):
+        """ms per stage of the last voxel_downsample: workspace, upload, range, sort, sums, download, total (mi_voxel_downsample_times)."""
+        out = (C.c_double * 8)()
+        _check(lib().mi_voxel_downsample_times(self._h, out))
+        return dict(zip(("workspace", "upload", "range", "sort", "sums", "download", "unused", "total"), list(out)))
 
     # ---- profiling
     def profile_enable(self, on=True):

@@ -212,6 +212,25 @@ struct mi_ctx {
         mislam::DevBuf<int> running;
     } bat;
 
+    // ---- mi_voxel_downsample: buffers of its own (a loaded ICP problem survives the call); what each one holds: VoxArgs, kernels.h
+    struct VoxelBuffers {
+        mislam::DevBuf<float> staging, x, y, z, range_lo_hi, out_xyz;
+        mislam::DevBuf<float4> pts;
+        mislam::DevBuf<unsigned int> keys_a, keys_b, axis_keys;
+        mislam::DevBuf<int> vals_a, vals_b, range_bad, block_heads, row_of, run_start, fix, out_count, out_coord, voxel_of_point;
+        mislam::DevBuf<double> front, back;
+        mislam::DevBuf<unsigned char> sort_temp;
+        mislam::DevBuf<mislam::VoxState> state;
+        double ms[MI_VOXEL_STAGES] = {0};                // mi_voxel_downsample_times
+        void release()
+        {
+            staging.release(); x.release(); y.release(); z.release(); range_lo_hi.release(); out_xyz.release(); pts.release();
+            keys_a.release(); keys_b.release(); axis_keys.release(); vals_a.release(); vals_b.release(); range_bad.release();
+            block_heads.release(); row_of.release(); run_start.release(); fix.release(); out_count.release(); out_coord.release();
+            voxel_of_point.release(); front.release(); back.release(); sort_temp.release(); state.release();
+        }
+    } vox;
+
     // ---- ICP problem currently loaded
     struct IcpProblem {
         bool icp_loaded = false;

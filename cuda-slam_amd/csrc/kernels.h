@@ -166,6 +166,61 @@ struct IcpBatchArgs {
 hipError_t icp_batch_prepare(const IcpBatchArgs& a, hipStream_t s);            // sorted clouds + states at identity
 hipError_t icp_batch_iterate(const IcpBatchArgs& a, int fma, hipStream_t s);   // up to a.iters iterations of every running problem
 
+// ---------------------------------------------------------------------------------------------------------------
+// Voxel-grid centroids of a cloud (voxel_kernels.hip; driver: voxel_api.hip)
+// ---------------------------------------------------------------------------------------------------------------
+// The voxel of a coordinate: floorf((p - o) / v) with one IEEE subtraction and one IEEE division, the same instructions' worth of
+// arithmetic on the host (mi_voxel_index) and in the kernels.  false: the quotient is not finite or outside [-2^30, 2^30).
+__host__ __device__ __forceinline__ bool voxel_axis(float p, float o, float v, int* out)
+{
+    const float q = floorf((p - o) / v);
+    if (!(q >= -1073741824.f && q < 1073741824.f)) return false;
+    *out = (int)q;
+    return true;
+}
+
+constexpr int VOX_RANGE_BLOCKS = 1024;       // blocks of the range pass at most (one partial row each)
+constexpr int VOX_SCAN_TILE = 1024;          // sorted positions per workgroup of the head-flag scan
+constexpr int VOX_SUM_TILE = 256;            // sorted positions per workgroup of the segmented sum: one per lane
+constexpr int VOX_NO_POINT = 0x7fffffff;     // VoxState::bad_index when every coordinate is finite
+
+// Device-resident facts of one call; the host reads it back once, behind the range pass, and `rows` behind the scan.
+struct VoxState {
+    float lo[3], hi[3];      // per-axis minimum and maximum over the finite coordinates
+    float origin[3];         // the caller's, or lo
+    int imin[3], imax[3];    // voxel coordinate of lo / hi: the occupied range (the voxel of a coordinate is monotone in it)
+    int bad_index;           // lowest index of a point with a non-finite coordinate, or VOX_NO_POINT
+    int range_bad;           // bit a / bit 3 + a: the voxel coordinate of lo[a] / hi[a] is outside [-2^30, 2^30)
+    int rows;                // occupied voxels
+};
+
+struct VoxArgs {
+    int n;
+    float voxel;
+    VoxState* state;
+    const float *x, *y, *z;          // the cloud, SoA, n entries
+    const float4* pts;               // the same points packed (gathers)
+    float* range_lo_hi;              // VOX_RANGE_BLOCKS x 6 partial minima / maxima
+    int* range_bad;                  // VOX_RANGE_BLOCKS partial lowest bad indices
+    unsigned int* keys;              // n sort keys (packed path: cx | cy << 10 | cz << 20, each minus the axis minimum; else cx)
+    unsigned int* axis_keys;         // 3 n: cx, cy, cz minus the axis minimum, by point (null on the packed path)
+    int* vals;                       // n: the identity, the sort's values
+    const unsigned int* sorted_keys; // packed path: the keys in sorted order
+    const int* sorted_idx;           // n: point of every sorted position
+    int* block_heads;                // per scan tile: heads in it, then (scanned) heads before it
+    int* row_of;                     // n: output row of every sorted position
+    int* run_start;                  // rows + 1: first sorted position of every row, then n
+    double *front, *back;            // per sum tile, 3 doubles: sum of the tile's points that belong to the run entering it / leaving it
+    int* fix;                        // per sum tile: the row whose run enters the tile and ends in it, or -1
+    float* out_xyz;                  // rows x 3
+    int *out_count, *out_coord, *voxel_of_point;
+};
+hipError_t vox_range(const VoxArgs& a, const float* origin3, hipStream_t s);         // -> state (origin3: 3 HOST floats, or null: the minimum)
+hipError_t vox_keys(const VoxArgs& a, hipStream_t s);                                 // -> keys (+ axis_keys), vals
+hipError_t vox_gather_keys(const unsigned int* axis_keys, const int* idx, int n, unsigned int* keys, hipStream_t s);   // keys[j] = axis_keys[idx[j]]
+hipError_t vox_rows(const VoxArgs& a, hipStream_t s);                                 // head flags + scan -> row_of, run_start, state->rows
+hipError_t vox_sums(const VoxArgs& a, hipStream_t s);                                 // segmented fp64 sums -> out_xyz, out_count, out_coord, voxel_of_point
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -177,5 +232,6 @@ hipError_t preload_cpd_batch();
 hipError_t preload_cpd_fgt();
 hipError_t preload_nicp_api();
 hipError_t preload_prepare_api();
+hipError_t preload_voxel_kernels();
 
 }  // namespace mislam

@@ -173,7 +173,7 @@ extern "C" int mi_ctx_preload(mi_ctx* c)
     if (!c) { set_error("mi_ctx_preload: null context"); return MI_ERR_INVALID_ARG; }
     MI_ENTER(c);
     MI_HIP(preload_nn_kernel()); MI_HIP(preload_nn_tree()); MI_HIP(preload_nn_grid()); MI_HIP(preload_icp_kernels()); MI_HIP(preload_icp_batch()); MI_HIP(preload_cpd_kernels()); MI_HIP(preload_cpd_batch());
-    MI_HIP(preload_cpd_fgt()); MI_HIP(preload_nicp_api()); MI_HIP(preload_prepare_api());
+    MI_HIP(preload_cpd_fgt()); MI_HIP(preload_nicp_api()); MI_HIP(preload_prepare_api()); MI_HIP(preload_voxel_kernels());
     return MI_OK;
 }
 
@@ -442,6 +442,7 @@ extern "C" void mi_ctx_destroy(mi_ctx* c)
     c->sched.order.release(); c->sched.far.release(); c->sched.lanes.release(); c->sched.counters.release();
     c->bat.before.release(); c->bat.after.release(); c->bat.sx.release(); c->bat.sy.release(); c->bat.sz.release();
     c->bat.problems.release(); c->bat.states.release(); c->bat.running.release();
+    c->vox.release();
     for (auto& s : c->prof.spans) { (void)hipEventDestroy(s.e0); (void)hipEventDestroy(s.e1); }
     for (auto e : c->prof.event_pool) (void)hipEventDestroy(e);
     if (c->d_state) (void)hipFree(c->d_state);

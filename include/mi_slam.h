@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MI_SLAM_ABI_VERSION 4   /* 4: mi_profile_search_phases, mi_selftest_fail_loads, mi_runtime_info (additive: no signature of version 3 changed); 3: mi_icp_load_times, mi_cross_moments, mi_icp_auto_batch; 2: mi_cpd_params gained sigma2_mode; mi_dist_info, mi_source_share, mi_cpd_sigma_squared_mode, mi_profile_search_stats, mi_selftest_sort_pairs */
+#define MI_SLAM_ABI_VERSION 4   /* 4: mi_profile_search_phases, mi_selftest_fail_loads, mi_runtime_info (additive: no signature of version 3 changed), later and additive again: mi_icp_register_batch, mi_cpd_register_batch, mi_voxel_index, mi_voxel_downsample, mi_voxel_downsample_times; 3: mi_icp_load_times, mi_cross_moments, mi_icp_auto_batch; 2: mi_cpd_params gained sigma2_mode; mi_dist_info, mi_source_share, mi_cpd_sigma_squared_mode, mi_profile_search_stats, mi_selftest_sort_pairs */
 
 enum {
     MI_OK = 0,
@@ -512,6 +512,56 @@ void mi_prepare_params_default(mi_prepare_params* p);
 int mi_prepare_cloud(mi_ctx* ctx, const float* raw_xyz, int n_raw, const int* subcloud_idx, int subcloud_n, const int* shuffle_idx,
                      const int* noise_rows, const float* noise_unit, int n_noise, const float* outlier_unit, int n_outliers,
                      const mi_prepare_params* params, float* out_xyz, int* out_n);
+
+/* ----------------------------------------------------------------------------------------------------------------
+ * Voxel-grid downsampling (no reference counterpart: the reference thins a cloud with the random GetSubcloud only): one output
+ * point per occupied voxel of a cubic lattice, the mean of the voxel's points -- what a pipeline runs on a raw scan or a map tile
+ * before it registers it (downsample, then mi_icp_register_batch).  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+
+/* Pure host function (no context, no device): the voxel a point falls in.
+ * out[a] = (int)floorf((p[a] - origin[a]) / voxel_size), a = x,y,z.
+ * Arithmetic: one IEEE fp32 subtraction and one IEEE fp32 division, each rounded to nearest.  No reciprocal, no contraction.  The
+ * kernels use the same arithmetic, bit for bit.
+ * Returns MI_ERR_INVALID_ARG for voxel_size <= 0 or non-finite, a non-finite operand, or a quotient outside [-2^30, 2^30); out is
+ * then left as it was. */
+int mi_voxel_index(const float p[3], const float origin[3], float voxel_size, int out[3]);
+
+/* Voxel-grid centroids of the n points of xyz, computed on the device.
+ *   Voxel of a point: mi_voxel_index with the given origin.  With origin3 == NULL the origin is the exact per-axis minimum of the
+ *     cloud, so every coordinate is >= 0; an explicit origin lets a scan and a map share one lattice, and coordinates may then be
+ *     negative.  Only the per-axis EXTENT (max - min + 1 over the occupied voxels) is limited, to <= 2^20.
+ *   Output order: one row per occupied voxel, ascending by (cz, cy, cx) as signed integers -- deterministic, and independent of the
+ *     order of the input points.
+ *   Output point: per coordinate, the fp64 sum of the voxel's points, divided in fp64 by their count, rounded once to fp32.  The
+ *     order of the sum is fixed by the implementation (a function of the sorted order): the same input gives the same bits on every
+ *     call, whatever ran on the context before.  There is no floating-point atomic anywhere on the path.
+ *   out_xyz (capacity n points) and *out_n receive the rows and their number.  Optional, each may be NULL: out_count (capacity n)
+ *     the points per voxel, summing to n; out_coord (capacity 3n) the voxel coordinate of each row; voxel_of_point (n entries) the
+ *     row whose out_coord equals the voxel of point i.
+ *   MI_ERR_INVALID_ARG -- mi_last_error names the cause and, for a bad point, its index; NO output array has been written -- for
+ *     n < 1; voxel_size non-finite or <= 0; a NULL xyz, out_xyz or out_n; a non-finite origin; a non-finite input coordinate; a
+ *     voxel coordinate outside [-2^30, 2^30); an axis extent above 2^20.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call: it works in buffers of its own in the context.
+ *   Synchronous, like the other host-in / host-out entry points. */
+int mi_voxel_downsample(mi_ctx* ctx, const float* xyz, int n, float voxel_size,
+                        const float* origin3,     /* NULL: per-axis minimum of the cloud */
+                        float* out_xyz,           /* capacity n points */
+                        int* out_n,
+                        int* out_count,           /* may be NULL; capacity n: points per voxel */
+                        int* out_coord,           /* may be NULL; capacity 3n: voxel coordinate of each output row */
+                        int* voxel_of_point);     /* may be NULL; n entries: output row of input point i */
+
+/* Where the last mi_voxel_downsample of this context spent its host wall time, in ms (measurement hook, tools/voxel_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA
+ *   out[2] range pass and its read-back             out[3] keys + sort
+ *   out[4] head flags, scan, segmented sums         out[5] row count read-back + download of the rows
+ *   out[6] unused (0)                               out[7] the whole call
+ * As with mi_icp_load_times, the parts are attributable only while profiling is enabled (the stream is then drained after every
+ * stage); otherwise the device work of a stage is waited for in the next stage that reads something back. */
+#define MI_VOXEL_STAGES 8
+int mi_voxel_downsample_times(mi_ctx* ctx, double out_ms[MI_VOXEL_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
