@@ -39,6 +39,7 @@ EXPORTS = [
     "mi_transform_mse", "mi_cpd_params_default", "mi_cpd_register", "mi_cpd_batch_route", "mi_cpd_register_batch", "mi_cpd_sigma_squared", "mi_cpd_sigma_squared_mode", "mi_cpd_estep",
     "mi_cpd_estep_truncated", "mi_cpd_estep_fgt", "mi_fgt_kcenter", "mi_fgt_kcenter_guided", "mi_fgt_tables", "mi_nicp_params_default", "mi_nicp_register",
     "mi_prepare_params_default", "mi_prepare_cloud", "mi_voxel_index", "mi_voxel_downsample", "mi_voxel_downsample_times",
+    "mi_knn_search", "mi_knn_search_times",
     "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_fail_loads", "mi_nn_kernel_name",
 ]
 
@@ -257,6 +258,17 @@ def voxel_downsample_raw(handle, xyz, n, voxel, origin, out_xyz, out_n, out_coun
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 6
     f.restype = C.c_int
     return f(handle, xyz, n, voxel, origin, out_xyz, out_n, out_count, out_coord, voxel_of_point)
+
+
+KNN_MAX_K = 32                      # MI_KNN_MAX_K
+
+
+def knn_search_raw(handle, query, n, cloud, m, k, dist_mode, max_d2, idx, d2, count):
+    """mi_knn_search with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_knn_search
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    return f(handle, query, n, cloud, m, k, dist_mode, max_d2, idx, d2, count)
 
 
 def icp_auto_batch(n_moving_total, m_fixed_total, world, source_sharded, every_pair_search):
@@ -641,6 +653,32 @@ class Context:
         out = (C.c_double * 8)()
         _check(lib().mi_voxel_downsample_times(self._h, out))
         return dict(zip(("workspace", "upload", "range", "sort", "sums", "download", "unused", "total"), list(out)))
+
+    # ---- k nearest neighbours
+    def knn_search(self, query, cloud, k, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_d2=True, want_count=False):
+        """Exact k nearest neighbours (mi_knn_search): idx [n, k] int32, ascending by (d2 bits, index), -1 in the slots no candidate
+        filled; then d2 [n, k] (+inf there) and count [n] if asked for.  query None: the cloud's own points, neighbour i of row i
+        skipped by index."""
+        cloud = _cloud(cloud)
+        m = cloud.shape[0]
+        if query is None:
+            n, qp = m, None
+        else:
+            query = _cloud(query)
+            n, qp = query.shape[0], query.ctypes.data
+        idx = np.empty((n, int(k)), np.int32)
+        d2 = np.empty((n, int(k)), np.float32) if want_d2 else None
+        count = np.empty(n, np.int32) if want_count else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _check(knn_search_raw(self._h, qp, n, cloud.ctypes.data, m, int(k), int(dist_mode), float(max_d2), idx.ctypes.data, ptr(d2), ptr(count)))
+        res = [idx] + ([d2] if want_d2 else []) + ([count] if want_count else [])
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def knn_search_times(self):
+        """ms per stage of the last knn_search: workspace, upload, check, grid, order, search, download, total (mi_knn_search_times)."""
+        out = (C.c_double * 8)()
+        _check(lib().mi_knn_search_times(self._h, out))
+        return dict(zip(("workspace", "upload", "check", "grid", "order", "search", "download", "total"), list(out)))
 
     # ---- profiling
     def profile_enable(self, on=True):

@@ -125,6 +125,7 @@ struct mi_ctx {
         int fgt_coop_sweep = 1;                          // MISLAM_FGT_COOP_SWEEP=0: K-centre sweeps of clouds beyond 16 384 points as in rounds 1-4 (one workgroup / two launches per centre); 2: the cooperative kernel for every sweep
         int fgt_shard_queries = 1;                       // MISLAM_FGT_SHARD_QUERIES=0: the FGT / hybrid CPD modes run replicated on a multi-rank context, no collective (rounds 4-5)
         int fgt_model_splits = 1;                        // MISLAM_FGT_MODEL_SPLITS=0: one workgroup per cell in the FGT model build whatever the cells' sizes (rounds 1-4)
+        float knn_points_per_cell = 0.f;                 // MISLAM_KNN_POINTS_PER_CELL: cell size of mi_knn_search's grid (0: the measured default for the call's k, knn_api.hip)
         int fgt_replay = 1;                              // MISLAM_FGT_REPLAY=0: sweep the moving cloud step by step every E-step (no guess replayed)
     } tune;
 
@@ -230,6 +231,28 @@ struct mi_ctx {
             voxel_of_point.release(); front.release(); back.release(); sort_temp.release(); state.release();
         }
     } vox;
+
+    // ---- mi_knn_search: buffers of its own, like the voxel call's (a loaded ICP problem survives the call)
+    struct KnnBuffers {
+        mislam::DevBuf<float> staging, cx, cy, cz, ux, uy, uz, qx, qy, qz;   // cloud SoA; queries SoA as uploaded (u) and along their curve (q)
+        mislam::DevBuf<float> range_lo_hi, bbox, out_d2;
+        mislam::DevBuf<int> range_bad, order_in, order, out_idx, out_count;
+        mislam::DevBuf<unsigned int> codes_in, codes_out;
+        mislam::DevBuf<unsigned char> sort_temp, near_tmp;
+        mislam::DevBuf<float4> pts;                      // the cell grid over the cloud (nn_grid.h), built by grid_build into these
+        mislam::DevBuf<unsigned int> start, fill, scan, slot_of, row_occ;
+        mislam::DevBuf<mislam::KnnState> state;
+        hipEvent_t ev[2] = {nullptr, nullptr};           // around the search launch while profiling (mi_knn_search_times)
+        double ms[MI_KNN_STAGES] = {0};
+        void release()
+        {
+            staging.release(); cx.release(); cy.release(); cz.release(); ux.release(); uy.release(); uz.release(); qx.release(); qy.release(); qz.release();
+            range_lo_hi.release(); bbox.release(); out_d2.release(); range_bad.release(); order_in.release(); order.release(); out_idx.release();
+            out_count.release(); codes_in.release(); codes_out.release(); sort_temp.release(); near_tmp.release(); pts.release(); start.release();
+            fill.release(); scan.release(); slot_of.release(); row_occ.release(); state.release();
+            for (hipEvent_t& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+        }
+    } knn;
 
     // ---- ICP problem currently loaded
     struct IcpProblem {

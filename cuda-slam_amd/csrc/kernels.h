@@ -221,6 +221,43 @@ hipError_t vox_gather_keys(const unsigned int* axis_keys, const int* idx, int n,
 hipError_t vox_rows(const VoxArgs& a, hipStream_t s);                                 // head flags + scan -> row_of, run_start, state->rows
 hipError_t vox_sums(const VoxArgs& a, hipStream_t s);                                 // segmented fp64 sums -> out_xyz, out_count, out_coord, voxel_of_point
 
+// ---------------------------------------------------------------------------------------------------------------
+// K13 exact k nearest neighbours (knn_kernels.hip; driver: knn_api.hip)
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int KNN_MAX_K = 32;                // = MI_KNN_MAX_K (knn_api.hip asserts it)
+constexpr int KNN_RANGE_BLOCKS = 512;        // blocks of the input check per array at most (one partial row each)
+constexpr int KNN_NO_POINT = 0x7fffffff;     // KnnState::bad_cloud / bad_query when every coordinate is usable
+constexpr float KNN_MAX_COORD = 1e18f;       // |coordinate| above this is refused: 3 (2e18)^2 < FLT_MAX keeps every d2 finite
+constexpr int KNN_BLOCK = 64;                // queries per workgroup of the search: one wave, no LDS
+// a slot no candidate filled: (+inf bits << 32) | 0xffffffff unpacks to d2 = +INFINITY, idx = -1, and every real key is below it
+constexpr unsigned long long KNN_KEY_EMPTY = 0x7f800000ffffffffull;
+
+// Device-resident facts of one call; the host reads it back once, behind the input check, before anything is written.
+struct KnnState {
+    float lo[3], hi[3];      // bounding box of the cloud's usable points
+    int bad_cloud;           // lowest index of a cloud point with a non-finite or too large coordinate, or KNN_NO_POINT
+    int bad_query;           // the same for the queries
+};
+
+struct NnGridView;           // nn_grid.h
+struct KnnSearchArgs {
+    const float *qx, *qy, *qz;       // the queries along their curve order, SoA, n entries
+    const int* order;                // sorted slot -> the caller's query index (the row the slot's answer goes to)
+    int n, k;
+    int self;                        // queries are the cloud's own points: candidate order[s] is skipped, by index
+    float max_d2;                    // candidates with d2 > this do not exist (+inf: no limit)
+    float hi[3];                     // upper corner of the cloud's bounding box (the lower one is the grid's origin)
+    int* idx;                        // n * k
+    float* d2;                       // n * k
+    int* count;                      // n
+};
+// partial minima / maxima and lowest bad index of one array (lo_hi: KNN_RANGE_BLOCKS x 6, bad: KNN_RANGE_BLOCKS), then both arrays
+// into the state (query partials may be null: self mode)
+hipError_t knn_check_inputs(const float* cx, const float* cy, const float* cz, int m, const float* qx, const float* qy, const float* qz, int n,
+                            float* lo_hi, int* bad, KnnState* st, hipStream_t s);
+hipError_t knn_search(const NnGridView& g, const KnnSearchArgs& a, int fma, hipStream_t s);
+int knn_list_size(int k);            // registers' worth of list the search of this k is instantiated with: 8, 16 or 32
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -233,5 +270,6 @@ hipError_t preload_cpd_fgt();
 hipError_t preload_nicp_api();
 hipError_t preload_prepare_api();
 hipError_t preload_voxel_kernels();
+hipError_t preload_knn_kernels();
 
 }  // namespace mislam

@@ -1,0 +1,237 @@
+// K13 -- EXACT k nearest neighbours through a uniform cell grid over the cloud (mi_knn_search; driver: knn_api.hip).
+//
+// Contract: row i of the answer = the k smallest keys (bits(d2) << 32) | j over the cloud points j, ascending, d2 in the arithmetic of
+// the 1-NN searches (sq3 of nn_walk.hpp on the fp32 differences cloud[j] - query[i]).  The key is a total order, so "the k smallest"
+// does not depend on the order in which candidates are met, and the kernel only has to make sure that it skips nothing that belongs.
+//
+//   check   one pass per array: bounding box of the cloud and the lowest index of a point the call refuses (non-finite, |c| > 1e18),
+//           two-stage block reduction (the voxel range pass's shape); read back once, before anything is written
+//   index   the cell grid of the 1-NN search, built by grid_build (nn_grid.h) into the call's own buffers: points sorted by cell, w =
+//           the caller's index, one offset per cell; a row of cells [x0, x1] is ONE contiguous run of pts
+//   search  one lane per query, queries along their curve order so that a wave's lanes visit the same cells.  The running list of
+//           K = 8 / 16 / 32 keys lives in REGISTERS, sorted; a candidate is offered only when its key is below the list's last one, and
+//           goes in through a fully unrolled chain of K selects (every index static: no scratch).  k < K: the K - k lowest slots hold
+//           key 0, which no offer moves (an offer is never below 0), so slots [K - k, K) are the k-list and its last slot the threshold.
+//           Candidates come in Chebyshev shells of cells around the query's (clamped) cell c: shell r = the cells with max |i - c| = r
+//           inside the grid; per (y, z) row of a shell either the whole x-run (rows on the shell's y / z faces) or its two end cells.
+//
+// Stop rule.  After shell r every unscanned point p sits in a cell whose index differs from c by >= r + 1 on some axis a.  Cell
+// coordinates are u = (p - o) * inv_h, the same fp32 expression at build and for the query, rounding <= 2^-23 * 1024 cells; with
+// i_p <= u_p (< i_p + 1 below the last cell) and the query's u in [c, c + 1) -- or beyond the grid on the far side of c when it was
+// clamped -- the two differ by more than r cells: |p_a - q_a| >= lb = (r - 1e-3) * h_lo in length (NnGridView::h_lo, the 1-NN scan's
+// idiom; 1e-3 cells and h_lo's 1e-5 cover every rounding on the way).  A query outside the box on axis b is at least e_b = max(lo_b -
+// q_b, q_b - hi_b) from every point on that axis, and when b = a the two add up (the point lies across the face): |p_a - q_a| >= e_a +
+// lb.  Hence, with g = e except g_a = (e_a + lb) shrunk by 1e-6, |fl(p - q)| >= g per axis (rounding is monotone), and the rounded
+// distance is >= sq3(g) evaluated like a distance.  The bound is the minimum of that over the three choices of a; the lane stops
+// when the bound is STRICTLY above its k-th distance (a point AT the k-th distance with a lower index still belongs in the answer),
+// or above the distance limit.  For a query inside the box this is (r h)^2; outside, |q - clamp(q)|^2 + 2 e_a r h + (r h)^2.
+// The shell loop ends at the grid's largest extent from c whatever the bound says: no lane can spin.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "kernels.h"
+#include "nn_grid.h"
+#include "nn_walk.hpp"
+
+namespace mislam {
+
+namespace {
+
+__device__ __forceinline__ bool usable3(float x, float y, float z)
+{
+    return fabsf(x) <= KNN_MAX_COORD && fabsf(y) <= KNN_MAX_COORD && fabsf(z) <= KNN_MAX_COORD;     // (false for NaN and the infinities)
+}
+
+__global__ __launch_bounds__(256) void knn_range_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+                                                        int n, float* __restrict__ lo_hi, int* __restrict__ bad)
+{
+    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    int first_bad = KNN_NO_POINT;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const float p[3] = {x[i], y[i], z[i]};
+        if (!usable3(p[0], p[1], p[2])) { first_bad = min(first_bad, i); continue; }
+#pragma unroll
+        for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], p[k]); hi[k] = fmaxf(hi[k], p[k]); }
+    }
+    __shared__ float s[6][256];
+    __shared__ int sb[256];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { s[k][threadIdx.x] = lo[k]; s[3 + k][threadIdx.x] = hi[k]; }
+    sb[threadIdx.x] = first_bad;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                s[k][threadIdx.x] = fminf(s[k][threadIdx.x], s[k][threadIdx.x + w]);
+                s[3 + k][threadIdx.x] = fmaxf(s[3 + k][threadIdx.x], s[3 + k][threadIdx.x + w]);
+            }
+            sb[threadIdx.x] = min(sb[threadIdx.x], sb[threadIdx.x + w]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) lo_hi[blockIdx.x * 6 + threadIdx.x] = s[threadIdx.x][0];
+    if (threadIdx.x == 0) bad[blockIdx.x] = sb[0];
+}
+
+// cloud partials [0, cloud_blocks), query partials [KNN_RANGE_BLOCKS, KNN_RANGE_BLOCKS + query_blocks) -> the state
+__global__ __launch_bounds__(256) void knn_range_finish_kernel(const float* __restrict__ lo_hi, const int* __restrict__ bad, int cloud_blocks,
+                                                               int query_blocks, KnnState* __restrict__ st)
+{
+    __shared__ float s[6][256];
+    __shared__ int sb[2][256];
+    float v[6];
+    int bad_c = KNN_NO_POINT, bad_q = KNN_NO_POINT;
+#pragma unroll
+    for (int k = 0; k < 6; k++) v[k] = k < 3 ? __builtin_inff() : -__builtin_inff();
+    for (int b = threadIdx.x; b < cloud_blocks; b += 256) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) v[k] = k < 3 ? fminf(v[k], lo_hi[b * 6 + k]) : fmaxf(v[k], lo_hi[b * 6 + k]);
+        bad_c = min(bad_c, bad[b]);
+    }
+    for (int b = threadIdx.x; b < query_blocks; b += 256) bad_q = min(bad_q, bad[KNN_RANGE_BLOCKS + b]);
+#pragma unroll
+    for (int k = 0; k < 6; k++) s[k][threadIdx.x] = v[k];
+    sb[0][threadIdx.x] = bad_c; sb[1][threadIdx.x] = bad_q;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < 6; k++)
+                s[k][threadIdx.x] = k < 3 ? fminf(s[k][threadIdx.x], s[k][threadIdx.x + w]) : fmaxf(s[k][threadIdx.x], s[k][threadIdx.x + w]);
+            sb[0][threadIdx.x] = min(sb[0][threadIdx.x], sb[0][threadIdx.x + w]);
+            sb[1][threadIdx.x] = min(sb[1][threadIdx.x], sb[1][threadIdx.x + w]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { st->lo[k] = s[k][0]; st->hi[k] = s[3 + k][0]; }
+    st->bad_cloud = sb[0][0];
+    st->bad_query = sb[1][0];
+}
+
+// (the build's expressions, nn_grid.hip: the SAME fp32 operations for the cloud's points and for the queries)
+__device__ __forceinline__ float knn_cell_u(float p, float o, float inv_h) { return (p - o) * inv_h; }
+__device__ __forceinline__ int knn_cell_index(float u, int n) { return (int)fminf(fmaxf(floorf(u), 0.f), (float)(n - 1)); }
+
+// the sorted list with `key` put in its place and the last entry dropped; the caller has checked key < l[K - 1]
+template <int K>
+__device__ __forceinline__ void knn_insert(unsigned long long (&l)[K], unsigned long long key)
+{
+#pragma unroll
+    for (int i = K - 1; i >= 1; i--) l[i] = key < l[i - 1] ? l[i - 1] : (key < l[i] ? key : l[i]);
+    l[0] = key < l[0] ? key : l[0];
+}
+
+template <int K, bool FMA>
+__global__ __launch_bounds__(KNN_BLOCK) void knn_search_kernel(NnGridView g, KnnSearchArgs a)
+{
+    const int s = blockIdx.x * KNN_BLOCK + (int)threadIdx.x;
+    if (s >= a.n) return;
+    const float q[3] = {a.qx[s], a.qy[s], a.qz[s]};
+    const int row_out = a.order[s];
+    const unsigned int skip = a.self ? (unsigned int)row_out : 0xffffffffu;      // (no cloud point has index 2^32 - 1)
+    const int k = a.k;
+
+    unsigned long long l[K];
+#pragma unroll
+    for (int i = 0; i < K; i++) l[i] = i < K - k ? 0ull : KNN_KEY_EMPTY;
+
+    const int c[3] = {knn_cell_index(knn_cell_u(q[0], g.ox, g.inv_h), g.nx), knn_cell_index(knn_cell_u(q[1], g.oy, g.inv_h), g.ny),
+                      knn_cell_index(knn_cell_u(q[2], g.oz, g.inv_h), g.nz)};
+    // how far outside the cloud's box the query is, per axis, rounded like a distance's difference (box_bound, nn_walk.hpp)
+    const float e[3] = {fmaxf(fmaxf(g.ox - q[0], q[0] - a.hi[0]), 0.f), fmaxf(fmaxf(g.oy - q[1], q[1] - a.hi[1]), 0.f),
+                        fmaxf(fmaxf(g.oz - q[2], q[2] - a.hi[2]), 0.f)};
+    const int r_end = max(max(max(c[0], g.nx - 1 - c[0]), max(c[1], g.ny - 1 - c[1])), max(c[2], g.nz - 1 - c[2]));   // the last shell that holds a cell
+
+    for (int r = 0; r <= r_end; r++) {
+        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.nz - 1), y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.ny - 1);
+        const int xa = c[0] - r, xb = c[0] + r, x0 = max(xa, 0), x1 = min(xb, g.nx - 1);
+        for (int iz = z0; iz <= z1; iz++) {
+            const bool z_face = iz == c[2] - r || iz == c[2] + r;
+            for (int iy = y0; iy <= y1; iy++) {
+                const unsigned int row = ((unsigned int)iz * (unsigned int)g.ny + (unsigned int)iy) * (unsigned int)g.nx;
+                const bool whole = z_face || iy == c[1] - r || iy == c[1] + r;       // (r = 0: the cell itself)
+                // the whole x-run of the row, or its two end cells where they exist
+                for (int seg = 0; seg < (whole ? 1 : 2); seg++) {
+                    const int sa = whole ? x0 : (seg == 0 ? xa : xb), sb = whole ? x1 : sa;
+                    if (sa < 0 || sb > g.nx - 1) continue;
+                    const unsigned int b = g.cell_start[row + (unsigned int)sa], end = g.cell_start[row + (unsigned int)sb + 1u];
+                    for (unsigned int j = b; j < end; j++) {
+                        const float4 p = g.pts[j];
+                        const float d2 = sq3<FMA>(p.x - q[0], p.y - q[1], p.z - q[2]);
+                        const unsigned int pj = __float_as_uint(p.w);
+                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | pj;
+                        if (key < l[K - 1] && pj != skip && d2 <= a.max_d2) knn_insert<K>(l, key);
+                    }
+                }
+            }
+        }
+        // everything not yet scanned is at least this far (see the head of the file)
+        const float lb = fmaxf((float)r - 1e-3f, 0.f) * g.h_lo;
+        const float gx = (e[0] + lb) * 0.999999f, gy = (e[1] + lb) * 0.999999f, gz = (e[2] + lb) * 0.999999f;
+        const float bound = fminf(fminf(sq3<FMA>(gx, e[1], e[2]), sq3<FMA>(e[0], gy, e[2])), sq3<FMA>(e[0], e[1], gz));
+        const float kth = __uint_as_float((unsigned int)(l[K - 1] >> 32));              // (+inf while the list is not full)
+        if (bound > kth || bound > a.max_d2) break;
+    }
+
+    int found = 0;
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        const int slot = i - (K - k);
+        if (slot >= 0) {
+            const unsigned int hi = (unsigned int)(l[i] >> 32);
+            a.idx[(size_t)row_out * (size_t)k + (size_t)slot] = (int)(unsigned int)(l[i] & 0xffffffffull);
+            if (a.d2) a.d2[(size_t)row_out * (size_t)k + (size_t)slot] = __uint_as_float(hi);
+            found += hi < 0x7f800000u ? 1 : 0;
+        }
+    }
+    if (a.count) a.count[row_out] = found;
+}
+
+template <int K>
+void knn_launch(const NnGridView& g, const KnnSearchArgs& a, int fma, hipStream_t s)
+{
+    const dim3 grid((a.n + KNN_BLOCK - 1) / KNN_BLOCK);
+    if (fma) hipLaunchKernelGGL((knn_search_kernel<K, true>), grid, dim3(KNN_BLOCK), 0, s, g, a);
+    else hipLaunchKernelGGL((knn_search_kernel<K, false>), grid, dim3(KNN_BLOCK), 0, s, g, a);
+}
+
+}  // namespace
+
+hipError_t knn_check_inputs(const float* cx, const float* cy, const float* cz, int m, const float* qx, const float* qy, const float* qz, int n,
+                            float* lo_hi, int* bad, KnnState* st, hipStream_t s)
+{
+    const int cb = std::max(1, std::min(KNN_RANGE_BLOCKS, (m + 255) / 256));
+    const int qb = qx ? std::max(1, std::min(KNN_RANGE_BLOCKS, (n + 255) / 256)) : 0;
+    hipLaunchKernelGGL(knn_range_kernel, dim3(cb), dim3(256), 0, s, cx, cy, cz, m, lo_hi, bad);
+    if (qb > 0) hipLaunchKernelGGL(knn_range_kernel, dim3(qb), dim3(256), 0, s, qx, qy, qz, n, lo_hi + 6 * KNN_RANGE_BLOCKS, bad + KNN_RANGE_BLOCKS);
+    hipLaunchKernelGGL(knn_range_finish_kernel, dim3(1), dim3(256), 0, s, lo_hi, bad, cb, qb, st);
+    return hipGetLastError();
+}
+
+int knn_list_size(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : 32); }
+
+hipError_t knn_search(const NnGridView& g, const KnnSearchArgs& a, int fma, hipStream_t s)
+{
+    if (a.n < 1 || a.k < 1 || a.k > KNN_MAX_K) return hipErrorInvalidValue;
+    switch (knn_list_size(a.k)) {
+        case 8: knn_launch<8>(g, a, fma, s); break;
+        case 16: knn_launch<16>(g, a, fma, s); break;
+        default: knn_launch<32>(g, a, fma, s); break;
+    }
+    return hipGetLastError();
+}
+
+// loads this translation unit's code object at mi_ctx_preload (kernels.h)
+__global__ void preload_knn_kernels_kernel() {}
+hipError_t preload_knn_kernels()
+{
+    hipFuncAttributes attr;
+    return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(preload_knn_kernels_kernel));
+}
+
+}  // namespace mislam

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MI_SLAM_ABI_VERSION 4   /* 4: mi_profile_search_phases, mi_selftest_fail_loads, mi_runtime_info (additive: no signature of version 3 changed), later and additive again: mi_icp_register_batch, mi_cpd_register_batch, mi_voxel_index, mi_voxel_downsample, mi_voxel_downsample_times; 3: mi_icp_load_times, mi_cross_moments, mi_icp_auto_batch; 2: mi_cpd_params gained sigma2_mode; mi_dist_info, mi_source_share, mi_cpd_sigma_squared_mode, mi_profile_search_stats, mi_selftest_sort_pairs */
+#define MI_SLAM_ABI_VERSION 4   /* 4: mi_profile_search_phases, mi_selftest_fail_loads, mi_runtime_info (additive: no signature of version 3 changed), later and additive again: mi_icp_register_batch, mi_cpd_register_batch, mi_voxel_index, mi_voxel_downsample, mi_voxel_downsample_times, mi_knn_search, mi_knn_search_times; 3: mi_icp_load_times, mi_cross_moments, mi_icp_auto_batch; 2: mi_cpd_params gained sigma2_mode; mi_dist_info, mi_source_share, mi_cpd_sigma_squared_mode, mi_profile_search_stats, mi_selftest_sort_pairs */
 
 enum {
     MI_OK = 0,
@@ -562,6 +562,54 @@ int mi_voxel_downsample(mi_ctx* ctx, const float* xyz, int n, float voxel_size,
  * stage); otherwise the device work of a stage is waited for in the next stage that reads something back. */
 #define MI_VOXEL_STAGES 8
 int mi_voxel_downsample_times(mi_ctx* ctx, double out_ms[MI_VOXEL_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
+ * Exact k nearest neighbours (no reference counterpart: the reference searches the single nearest neighbour only): what the stages
+ * between a downsample and a registration are built on -- normals, statistical and radius outlier removal, local descriptors,
+ * point-to-plane weights (neighbourhoods).  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+
+/* The k nearest cloud points of every query, computed on the device.
+ *   Order and arithmetic: for query i every cloud point j has the key (bits(d2) << 32) | j, d2 = |cloud[j] - query[i]|^2 evaluated
+ *     in the dist_mode arithmetic on the fp32 differences (cloud[j] - query[i]) -- exactly the arithmetic of mi_nn_search:
+ *     MI_DIST_CPU_ROUNDING (dx*dx + dy*dy) + dz*dz with every operation rounded, MI_DIST_FMA fma(dz, dz, fma(dy, dy, dx*dx)).  Row i
+ *     of the result holds the k SMALLEST keys in ascending order: the smaller distance first, equal distance bits to the lower
+ *     index.  For k = 1 and no limit this is mi_nn_search's answer bit for bit.
+ *   Self mode, query_xyz == NULL: the queries are the cloud's own points (n must equal m) and candidate j == i is skipped for query
+ *     i BY INDEX, not by distance -- a duplicate of point i stored elsewhere in the cloud is returned, at d2 = +0.
+ *   max_distance_squared: INFINITY for no limit; otherwise a candidate with d2 > max_distance_squared does not exist for the query.
+ *   Missing slots: a query with fewer than k candidates (m < k, m - 1 < k in self mode, or the limit) has its remaining slots set
+ *     to idx = -1, d2 = +INFINITY; count[i] is the number of filled slots (<= k).
+ *   idx (n*k) receives idx[i*k + r] = the r-th neighbour of query i; d2 (n*k, may be NULL) its distance; count (n, may be NULL).
+ *   Exact for every query position, far outside the cloud's bounding box included, and for every cloud shape (all points identical,
+ *     collinear, coplanar, a far outlier, m = 1); the speed is only claimed for queries in or near the cloud.  Deterministic: the
+ *     same input gives the same bits on every call, whatever ran on the context before.
+ *   MI_ERR_INVALID_ARG -- mi_last_error names the cause and, for a bad point, which array and which index; NO output array has been
+ *     written -- for a NULL ctx, cloud_xyz or idx; n < 1 or m < 1; k outside [1, MI_KNN_MAX_K]; a dist_mode other than the two
+ *     above; max_distance_squared NaN or negative; self mode with n != m; a non-finite coordinate in either array; a coordinate of
+ *     magnitude above 1e18 (which keeps every d2 finite: 3 (2e18)^2 < FLT_MAX).
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call: it works in buffers of its own in the context.
+ *   Synchronous, host in and host out. */
+#define MI_KNN_MAX_K 32
+int mi_knn_search(mi_ctx* ctx,
+                  const float* query_xyz, int n,   /* NULL: the queries are the cloud's own points (n must equal m); neighbour j == i is skipped */
+                  const float* cloud_xyz, int m,
+                  int k, int dist_mode,            /* 1 <= k <= MI_KNN_MAX_K; MI_DIST_CPU_ROUNDING or MI_DIST_FMA */
+                  float max_distance_squared,      /* INFINITY: no limit; else candidates with d2 > this do not exist for the query */
+                  int* idx,                        /* n*k: idx[i*k + r] = r-th neighbour of query i */
+                  float* d2,                       /* may be NULL; n*k */
+                  int* count);                     /* may be NULL; n: neighbours found for query i (<= k) */
+
+/* Where the last mi_knn_search of this context spent its host wall time, in ms (measurement hook, tools/knn_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA (cloud, queries)
+ *   out[2] input check, bounding box, its read-back out[3] cell grid over the cloud
+ *   out[4] curve order of the queries + permute     out[5] the search kernel
+ *   out[6] download of the results                  out[7] the whole call
+ * As with mi_voxel_downsample_times, the parts are attributable only while profiling is enabled (the stream is then drained after
+ * every stage, and out[5] is the search launch's own HIP-event time instead of host wall time). */
+#define MI_KNN_STAGES 8
+int mi_knn_search_times(mi_ctx* ctx, double out_ms[MI_KNN_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
