@@ -40,7 +40,7 @@ EXPORTS = [
     "mi_cpd_estep_truncated", "mi_cpd_estep_fgt", "mi_fgt_kcenter", "mi_fgt_kcenter_guided", "mi_fgt_tables", "mi_nicp_params_default", "mi_nicp_register",
     "mi_prepare_params_default", "mi_prepare_cloud", "mi_voxel_index", "mi_voxel_downsample", "mi_voxel_downsample_times",
     "mi_knn_search", "mi_knn_search_times",
-    "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_fail_loads", "mi_nn_kernel_name",
+    "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_nn_kernel_name",
 ]
 
 
@@ -293,6 +293,13 @@ def unpack_key(key):
     d2, idx = C.c_float(0), C.c_int(0)
     lib().mi_unpack_key(C.c_ulonglong(key), C.byref(d2), C.byref(idx))
     return d2.value, idx.value
+
+
+def selftest_live_buffers():
+    """Device buffers of the library alive in this process (mi_selftest_live_buffers)."""
+    n = C.c_longlong(0)
+    _check(lib().mi_selftest_live_buffers(C.byref(n)))
+    return n.value
 
 
 def dist_unique_id():

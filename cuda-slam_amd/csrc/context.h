@@ -12,22 +12,14 @@
 
 #include "../../include/mi_slam.h"
 #include "cpd_kernels.h"
+#include "devbuf.h"
 #include "kernels.h"
 #include "nn_grid.h"
 #include "nn_tree.h"
 
 namespace mislam {
 
-void set_error(const char* fmt, ...);
-
-#define MI_HIP(call)                                                                                       \
-    do {                                                                                                   \
-        hipError_t e_ = (call);                                                                            \
-        if (e_ != hipSuccess) {                                                                            \
-            mislam::set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);  \
-            return MI_ERR_HIP;                                                                             \
-        }                                                                                                  \
-    } while (0)
+void retire_buffers(struct ::mi_ctx* ctx);         // call right behind a synchronisation of ctx->stream, ctx->device current (devbuf.h: retire_later)
 
 #define MI_NCCL(call)                                                                                      \
     do {                                                                                                   \
@@ -44,47 +36,27 @@ void set_error(const char* fmt, ...);
         if (rc_ != MI_OK) return rc_; \
     } while (0)
 
-// Device buffers that were outgrown: work already enqueued may still read them, so they are released at the next point where the
-// host has drained the stream anyway (retire_buffers, called behind the loads' and runs' own synchronisations) -- not behind a
-// device-wide synchronisation per buffer, which is what a load of forty buffers used to pay when a size was new.
-// The list is the CONTEXT's (mi_ctx::retired): a buffer outgrown inside a call on context A is released only behind a drain of A's own
-// stream, with A's device current -- never by another host thread's context, never on another device (round 3 kept one process-wide list).
-void retire_later(void* p);                        // into the list of the context whose call is running on this thread (CtxScope)
-void retire_buffers(struct ::mi_ctx* ctx);         // call right behind a synchronisation of ctx->stream, ctx->device current
-// Device memory comes out of the runtime's stream-ordered pool, kept whole (release threshold: never): hipFree of a plain
-// allocation costs ~0.2 ms on this machine (tools/alloc_probe.cpp) -- forty buffers outgrown by a new size were 8 ms -- the pool's
-// free is ~1 us and its memory is handed out again.  MISLAM_POOL=0 (or a runtime without the pool) falls back to hipMalloc / hipFree.
-hipError_t device_alloc(void** p, size_t bytes);
-void device_free(void* p);
-double& alloc_ms_counter();        // host ms this thread has spent in hipMalloc through DevBuf::reserve (mi_icp_load_times)
-double wall_ms();
-
-// grow-only device buffer; grows by at least half (a sweep over slowly rising sizes reallocates a few times, not every call)
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t count)
-    {
-        if (count <= cap) return MI_OK;
-        if (p) retire_later(p);
-        p = nullptr;
-        const size_t grown = cap + cap / 2;
-        if (cap != 0 && count < grown) count = grown;
-        cap = 0;
-        const double t0 = wall_ms();
-        MI_HIP(device_alloc((void**)&p, count * sizeof(T)));
-        alloc_ms_counter() += wall_ms() - t0;
-        cap = count;
-        return MI_OK;
-    }
-    void release()
-    {
-        if (p) device_free(p);
-        p = nullptr;
-        cap = 0;
-    }
+// The buffers of one cell grid (nn_grid.h): the fixed cloud's of a context, the cloud's of a k-NN call.  grid_reserve plans the grid over a cloud of
+// m points with bounding box bbox (host), sizes the buffers and fills the view; grid_build_into enqueues the build of that view on `s`.  Two steps, so
+// that a caller can look at the plan, and book the reserves' time, before anything is enqueued (nn_api.hip).
+struct GridBuffers {
+    DevBuf<float4> pts;                              // points sorted by cell
+    DevBuf<unsigned int> start, fill, scan;          // cell offsets, build cursors, scan scratch
+    DevBuf<unsigned int> slot_of;                    // point -> its slot in pts
+    DevBuf<unsigned int> row_occ;                    // per cell: which of the 5 x 5 cell rows around it hold a point within reach (NnGridView::row_occ)
+    DevBuf<unsigned char> near_tmp;                  // build scratch
 };
+int grid_reserve(GridBuffers& b, const float bbox[6], int m, int index_base, float points_per_cell, NnGridView* view);
+int grid_build_into(GridBuffers& b, const NnGridView& view, const float* x, const float* y, const float* z, int m, hipStream_t s);
+
+// Scratch of one Morton sort (morton_order, nn_tree.h); morton_args sizes it for m points and fills the sort's arguments (nn_api.hip).
+struct MortonScratch {
+    DevBuf<unsigned int> codes_in, codes_out;
+    DevBuf<int> order_in;
+    DevBuf<float> bbox;
+    DevBuf<unsigned char> sort_temp;
+};
+int morton_args(MortonScratch& sc, const float* x, const float* y, const float* z, int m, int* order_out, MortonArgs* out);
 
 struct ProfileSpan {
     int kernel;
@@ -139,10 +111,7 @@ struct mi_ctx {
     hipStream_t work_stream() const { return lane_stream ? lane_stream : stream; }
     struct LaneScratch {
         mislam::DevBuf<float> staging;                   // AoS upload/download staging
-        mislam::DevBuf<unsigned int> codes_in, codes_out;   // Morton sort scratch (the fixed cloud's hierarchy and the moving cloud's ordering)
-        mislam::DevBuf<int> order_in;
-        mislam::DevBuf<float> bbox;
-        mislam::DevBuf<unsigned char> sort_temp;
+        mislam::MortonScratch morton;                    // (the fixed cloud's hierarchy and the moving cloud's ordering)
     } scratch[2];
 
     // ---- workspace shared by the drivers
@@ -188,12 +157,8 @@ struct mi_ctx {
         bool valid = false;
     } tree;
     struct GridIndex {                                   // cell grid (nn_grid.h)
+        mislam::GridBuffers cells;
         mislam::DevBuf<float> bbox;                      // (its own: a Morton sort's bounding box may be in flight on another lane)
-        mislam::DevBuf<float4> pts;                      // points sorted by cell
-        mislam::DevBuf<unsigned int> start, fill, scan;  // cell offsets, build cursors, scan scratch
-        mislam::DevBuf<unsigned int> slot_of;            // fixed point -> its slot in pts
-        mislam::DevBuf<unsigned int> row_occ;            // per cell: which of the 5 x 5 cell rows around it hold a point within reach (NnGridView::row_occ)
-        mislam::DevBuf<unsigned char> near_tmp;          // build scratch
         mislam::DevBuf<unsigned int> match_slot;         // fused ICP: per moving point, the slot of its current match
         mislam::NnGridView view{};
         bool valid = false;
@@ -223,35 +188,18 @@ struct mi_ctx {
         mislam::DevBuf<unsigned char> sort_temp;
         mislam::DevBuf<mislam::VoxState> state;
         double ms[MI_VOXEL_STAGES] = {0};                // mi_voxel_downsample_times
-        void release()
-        {
-            staging.release(); x.release(); y.release(); z.release(); range_lo_hi.release(); out_xyz.release(); pts.release();
-            keys_a.release(); keys_b.release(); axis_keys.release(); vals_a.release(); vals_b.release(); range_bad.release();
-            block_heads.release(); row_of.release(); run_start.release(); fix.release(); out_count.release(); out_coord.release();
-            voxel_of_point.release(); front.release(); back.release(); sort_temp.release(); state.release();
-        }
     } vox;
 
     // ---- mi_knn_search: buffers of its own, like the voxel call's (a loaded ICP problem survives the call)
     struct KnnBuffers {
         mislam::DevBuf<float> staging, cx, cy, cz, ux, uy, uz, qx, qy, qz;   // cloud SoA; queries SoA as uploaded (u) and along their curve (q)
-        mislam::DevBuf<float> range_lo_hi, bbox, out_d2;
-        mislam::DevBuf<int> range_bad, order_in, order, out_idx, out_count;
-        mislam::DevBuf<unsigned int> codes_in, codes_out;
-        mislam::DevBuf<unsigned char> sort_temp, near_tmp;
-        mislam::DevBuf<float4> pts;                      // the cell grid over the cloud (nn_grid.h), built by grid_build into these
-        mislam::DevBuf<unsigned int> start, fill, scan, slot_of, row_occ;
+        mislam::DevBuf<float> range_lo_hi, out_d2;
+        mislam::DevBuf<int> range_bad, order, out_idx, out_count;
+        mislam::MortonScratch morton;                    // the queries' curve order
+        mislam::GridBuffers cells;                       // the cell grid over the cloud
         mislam::DevBuf<mislam::KnnState> state;
-        hipEvent_t ev[2] = {nullptr, nullptr};           // around the search launch while profiling (mi_knn_search_times)
+        hipEvent_t ev[2] = {nullptr, nullptr};           // around the search launch while profiling (mi_knn_search_times); destroyed by mi_ctx_destroy
         double ms[MI_KNN_STAGES] = {0};
-        void release()
-        {
-            staging.release(); cx.release(); cy.release(); cz.release(); ux.release(); uy.release(); uz.release(); qx.release(); qy.release(); qz.release();
-            range_lo_hi.release(); bbox.release(); out_d2.release(); range_bad.release(); order_in.release(); order.release(); out_idx.release();
-            out_count.release(); codes_in.release(); codes_out.release(); sort_temp.release(); near_tmp.release(); pts.release(); start.release();
-            fill.release(); scan.release(); slot_of.release(); row_occ.release(); state.release();
-            for (hipEvent_t& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-        }
     } knn;
 
     // ---- ICP problem currently loaded
@@ -319,6 +267,29 @@ struct ProfScope {
     ProfScope(mi_ctx* ctx, int kernel) : c(ctx), on(ctx->prof.times(kernel)) { if (on) (void)c->prof.begin(kernel, c->stream); }
     ~ProfScope() { if (on) (void)c->prof.end(c->stream); }
 };
+
+// Host wall time per stage of a call, into the eight slots of ms (mi_icp_load_times, mi_voxel_downsample_times, mi_knn_search_times): mark(stage) books
+// the time since the last mark to `stage` and the device allocations in it to slot 0; with profiling on, the stream is drained at every mark.
+struct StageClock {
+    mi_ctx* c;
+    double* ms;
+    double t_begin, t_mark, a_mark;
+    StageClock(mi_ctx* ctx, double* stage_ms) : c(ctx), ms(stage_ms), t_begin(wall_ms()), t_mark(t_begin), a_mark(alloc_ms_counter())
+    {
+        for (int i = 0; i < 8; i++) ms[i] = 0.0;
+    }
+    int mark(int stage)
+    {
+        if (c->prof.on) MI_HIP(hipStreamSynchronize(c->stream));
+        const double now = wall_ms(), a_now = alloc_ms_counter();
+        ms[0] += a_now - a_mark;
+        ms[stage] += (now - t_mark) - (a_now - a_mark);
+        t_mark = now; a_mark = a_now;
+        return MI_OK;
+    }
+    void finish() { ms[7] = wall_ms() - t_begin; }
+};
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 
 // developer switch MISLAM_DEV_STALL_MS=<ms>: report any host-side section that takes longer, with the calling thread's context switches
 // over it -- an INVOLUNTARY one with no voluntary ones means the thread was taken off its core (a CPU quota of the container

@@ -27,11 +27,6 @@ struct FgtSide {
     int swept_K = 0;            // the fixed cloud only: centres of the sweep dist/indx currently hold (0 = none); see fgt_kcenter_kernel
     int guess_K = 0;            // the moving cloud only: leading entries of `picked` the last E-step's sweep left -- the next one's guess
     int prelaunched = 0;        // > 0: a replay of that guess (this many centres) is on the stream already, behind the last transform
-    void release()
-    {
-        dist.release(); xc.release(); indx.release(); memb.release(); off.release(); sweep.release(); picked.release(); replay_state.release();
-        replay_partial.release(); swept_K = 0; guess_K = 0; prelaunched = 0;
-    }
 };
 
 // Fast-Gauss-Transform E-step workspace ("approximation-type" full / hybrid)
@@ -46,11 +41,6 @@ struct FgtWork {
     DevBuf<float> ck;
     DevBuf<int> hpos;
     int p = 0, pd = 0;
-    void release()
-    {
-        y.release(); a.release(); By.release(); Ba.release(); By_part.release(); Ba_part.release(); kt1.release(); v4.release(); sort_temp.release(); sort_temp_a.release();
-        mono.release(); ck.release(); hpos.release(); p = pd = 0;
-    }
 };
 
 struct CpdWorkspace {
@@ -62,10 +52,9 @@ struct CpdWorkspace {
     DevBuf<unsigned char> sig_scratch;   // cpd_sigma2_sequential
     // K7t (cpd_trunc.hip): both clouds along a space-filling curve -- the orders (once per load), the fixed cloud's sorted copy and boxes (once),
     // the moving cloud's current positions in curve order and their boxes (every truncated E-step)
-    DevBuf<float> t_ax, t_ay, t_az, t_yx, t_yy, t_yz, t_abox, t_ybox, t_bbox;
-    DevBuf<int> t_aorder, t_border, t_order_tmp;
-    DevBuf<unsigned int> t_codes_in, t_codes_out;
-    DevBuf<unsigned char> t_sort;
+    DevBuf<float> t_ax, t_ay, t_az, t_yx, t_yy, t_yz, t_abox, t_ybox;
+    DevBuf<int> t_aorder, t_border;
+    MortonScratch t_morton;                   // of both orders, one after the other
     DevBuf<float4> t_xw4;
     bool trunc_ready = false;                 // the orders and the fixed cloud's sorted copy belong to the clouds now loaded
     CpdState* d_state = nullptr;
@@ -89,13 +78,6 @@ void cpd_workspace_destroy(mi_ctx* c)
 {
     CpdWorkspace* w = c->cpd;
     if (!w) return;
-    w->ax.release(); w->ay.release(); w->az.release();
-    w->den_part.release(); w->pt1.release(); w->p1_part.release(); w->px_part.release(); w->p1.release(); w->px.release();
-    w->xw4.release(); w->part_x.release(); w->part_k.release(); w->part_init.release();
-    w->t_ax.release(); w->t_ay.release(); w->t_az.release(); w->t_yx.release(); w->t_yy.release(); w->t_yz.release();
-    w->t_abox.release(); w->t_ybox.release(); w->t_bbox.release(); w->t_aorder.release(); w->t_border.release(); w->t_order_tmp.release();
-    w->t_codes_in.release(); w->t_codes_out.release(); w->t_sort.release(); w->t_xw4.release();
-    w->fgt.release();
     if (w->d_state) (void)hipFree(w->d_state);
     if (w->h_state) (void)hipHostFree(w->h_state);
     delete w;
@@ -231,10 +213,6 @@ static int cpd_trunc_tiles(int n) { return (n + CPD_TRUNC_TILE - 1) / CPD_TRUNC_
 static int cpd_trunc_prepare(mi_ctx* c, CpdWorkspace* w, const CpdView& v)
 {
     if (w->trunc_ready) return MI_OK;
-    const int big = std::max(w->m, w->n);
-    MI_TRY(w->t_bbox.reserve(256 * 6 + 6));
-    MI_TRY(w->t_codes_in.reserve(big)); MI_TRY(w->t_codes_out.reserve(big)); MI_TRY(w->t_order_tmp.reserve(big));
-    MI_TRY(w->t_sort.reserve(std::max<size_t>(tree_sort_temp_bytes(big), 16)));
     MI_TRY(w->t_aorder.reserve(w->n)); MI_TRY(w->t_border.reserve(w->m));
     const size_t na = (size_t)cpd_trunc_tiles(w->n) * CPD_TRUNC_TILE, ny = (size_t)cpd_trunc_tiles(w->m) * CPD_TRUNC_TILE;
     MI_TRY(w->t_ax.reserve(na)); MI_TRY(w->t_ay.reserve(na)); MI_TRY(w->t_az.reserve(na)); MI_TRY(w->t_xw4.reserve(na));
@@ -243,11 +221,10 @@ static int cpd_trunc_prepare(mi_ctx* c, CpdWorkspace* w, const CpdView& v)
     MI_TRY(w->t_abox.reserve(6 * (size_t)per_tile * cpd_trunc_tiles(w->n)));
     MI_TRY(w->t_ybox.reserve(6 * (size_t)per_tile * cpd_trunc_tiles(w->m)));
     // the fixed cloud along its curve; the moving cloud along the curve of its ORIGINAL points (a similarity transform keeps neighbours together)
+    // (both sorts out of one scratch, sized for the larger cloud)
     MortonArgs ma{};
-    ma.bbox_partials = w->t_bbox.p; ma.bbox = w->t_bbox.p + 256 * 6;
-    ma.codes_in = w->t_codes_in.p; ma.codes_out = w->t_codes_out.p; ma.order_in = w->t_order_tmp.p;
-    ma.sort_temp = w->t_sort.p; ma.sort_temp_bytes = w->t_sort.cap;
-    ma.x = v.ax; ma.y = v.ay; ma.z = v.az; ma.m = w->n; ma.order_out = w->t_aorder.p;
+    MI_TRY(morton_args(w->t_morton, v.ax, v.ay, v.az, std::max(w->m, w->n), w->t_aorder.p, &ma));
+    ma.m = w->n;
     MI_HIP(morton_order(ma, c->stream));
     ma.x = v.bx; ma.y = v.by; ma.z = v.bz; ma.m = w->m; ma.order_out = w->t_border.p;
     MI_HIP(morton_order(ma, c->stream));

@@ -151,18 +151,7 @@ extern "C" int mi_icp_load(mi_ctx* c, const float* before_xyz, int n_before, con
     MI_TRY(icp_check_params(params));
     if (params->sum_mode == MI_SUM_CPU_SEQUENTIAL && c->distributed()) { set_error("mi_icp_load: MI_SUM_CPU_SEQUENTIAL needs a single-GPU context (the running sums follow one global point order)"); return MI_ERR_INVALID_ARG; }
     MI_ENTER(c);
-    // mi_icp_load_times: host wall time per stage; with profiling on, the stream is drained at every mark
-    const double t_begin = wall_ms();
-    double t_mark = t_begin, a_mark = alloc_ms_counter();
-    for (double& v : c->prob.load_ms) v = 0.0;
-    auto mark = [&](int stage) -> int {             // time since the last mark -> `stage`, its device allocations -> stage 0
-        if (c->prof.on) MI_HIP(hipStreamSynchronize(c->stream));
-        const double now = wall_ms(), a_now = alloc_ms_counter();
-        c->prob.load_ms[0] += a_now - a_mark;
-        c->prob.load_ms[stage] += (now - t_mark) - (a_now - a_mark);
-        t_mark = now; a_mark = a_now;
-        return MI_OK;
-    };
+    StageClock clock(c, c->prob.load_ms);      // mi_icp_load_times: time since the last mark -> `stage`, its device allocations -> stage 0
     c->prob.icp_loaded = false;
     c->prob.icp = *params;
     // what the ranks split (mi_slam.h MI_SHARD_*): decided from GLOBAL sizes, so every rank decides alike
@@ -192,27 +181,27 @@ extern "C" int mi_icp_load(mi_ctx* c, const float* before_xyz, int n_before, con
     const int all_pad = round_up(n_all, NN_SRC_PAD);
     MI_TRY(reserve_moving(c, np, deal_chunks ? (size_t)all_pad : np));      // (cx.. hold the whole cloud while it is dealt out)
     MI_TRY(reserve_rows(c));
-    MI_TRY(mark(0));
+    MI_TRY(clock.mark(0));
     if (deal_chunks) {
         MI_TRY(c->ax.reserve((size_t)all_pad)); MI_TRY(c->ay.reserve((size_t)all_pad)); MI_TRY(c->az.reserve((size_t)all_pad));
         MI_TRY(upload_soa(c, before_xyz, n_all, all_pad, c->cx.p, c->cy.p, c->cz.p, nullptr));
-        MI_TRY(mark(1));
+        MI_TRY(clock.mark(1));
         MI_TRY(sort_sources(c, c->cx.p, c->cy.p, c->cz.p, n_all, all_pad, c->ax.p, c->ay.p, c->az.p));
         MI_HIP(deal_chunks_soa(c->ax.p, c->ay.p, c->az.p, n_all, c->rank, c->world, c->prob.n, c->prob.n_pad, c->bx.p, c->by.p, c->bz.p, c->stream));
-        MI_TRY(mark(2));
+        MI_TRY(clock.mark(2));
     } else {
         // moving cloud: upload in the caller's order (cx.. as scratch), keep it Hilbert-sorted in bx..
         MI_TRY(upload_soa(c, before_xyz, n_before, c->prob.n_pad, c->cx.p, c->cy.p, c->cz.p, nullptr));
-        MI_TRY(mark(1));
+        MI_TRY(clock.mark(1));
         MI_TRY(sort_sources(c, c->cx.p, c->cy.p, c->cz.p, n_before, c->prob.n_pad, c->bx.p, c->by.p, c->bz.p));
-        MI_TRY(mark(2));
+        MI_TRY(clock.mark(2));
     }
     if (params->sum_mode == MI_SUM_CPU_SEQUENTIAL) {   // the sequential sums run in the CALLER's point order
         MI_TRY(c->sinv.reserve((size_t)n_before));
         MI_TRY(c->resid.reserve(np));
         MI_HIP(invert_order(c->sorder.p, n_before, c->sinv.p, c->stream));
     }
-    MI_TRY(mark(2));
+    MI_TRY(clock.mark(2));
     // The FIXED cloud's share of the load -- upload, box hierarchy, cell grid -- depends on nothing the moving cloud's does, so it runs
     // on its own lanes (round 4): the upload and the hierarchy on `aux`, the grid (behind the upload) on `aux2`, their own scratch sets,
     // while `stream` is still ordering the moving cloud.  The host only copies into the pinned ring and enqueues; its one wait -- the grid's
@@ -240,7 +229,7 @@ extern "C" int mi_icp_load(mi_ctx* c, const float* before_xyz, int n_before, con
         MI_TRY(upload_target_shard(c, after_xyz, n_after, c->prob.source_sharded));
         if (lanes) MI_HIP(hipEventRecord(c->aux_event[0], c->aux));           // the fixed cloud is on the device
     }
-    MI_TRY(mark(3));
+    MI_TRY(clock.mark(3));
     const int m_local = c->prob.shard_hi - c->prob.shard_lo;
     c->prob.fused = mode == MI_NN_GRID && (!c->distributed() || c->prob.source_sharded) && params->sum_mode == MI_SUM_EXACT;
     if (mode != MI_NN_BRUTEFORCE) {          // build the indexes now, not inside the first timed iteration
@@ -248,13 +237,13 @@ extern "C" int mi_icp_load(mi_ctx* c, const float* before_xyz, int n_before, con
             LaneScope ls(c, lanes ? c->aux : nullptr, lanes ? 1 : 0);
             MI_TRY(ensure_tree(c, m_local, c->prob.shard_lo));
         }
-        MI_TRY(mark(4));
+        MI_TRY(clock.mark(4));
         if (mode == MI_NN_GRID) {
             if (lanes) MI_HIP(hipStreamWaitEvent(c->aux2, c->aux_event[0], 0));
             LaneScope ls(c, lanes ? c->aux2 : nullptr, 0);                    // (the grid build has its own scratch; lane 0's sort scratch is not touched)
             MI_TRY(ensure_grid(c, m_local, c->prob.shard_lo));
         }
-        MI_TRY(mark(5));
+        MI_TRY(clock.mark(5));
     }
     if (lanes) {                             // everything after the load runs on `stream`: it waits for both lanes here, once
         MI_HIP(hipEventRecord(c->aux_event[1], c->aux));
@@ -265,8 +254,8 @@ extern "C" int mi_icp_load(mi_ctx* c, const float* before_xyz, int n_before, con
     }
     c->prob.icp_loaded = true;
     MI_TRY(mi_icp_reset(c));
-    MI_TRY(mark(6));
-    c->prob.load_ms[7] = wall_ms() - t_begin;
+    MI_TRY(clock.mark(6));
+    clock.finish();
     return MI_OK;
 }
 

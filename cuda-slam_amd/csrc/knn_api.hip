@@ -35,18 +35,7 @@ extern "C" int mi_knn_search(mi_ctx* c, const float* query_xyz, int n, const flo
     if (c->distributed()) { set_error("mi_knn_search: single-GPU contexts only"); return MI_ERR_STATE; }
     MI_ENTER(c);
     mi_ctx::KnnBuffers& b = c->knn;
-    // mi_knn_search_times: host wall time per stage, as mi_voxel_downsample keeps it; with profiling on, the stream is drained at every mark
-    const double t_begin = wall_ms();
-    double t_mark = t_begin, a_mark = alloc_ms_counter();
-    for (double& v : b.ms) v = 0.0;
-    auto mark = [&](int stage) -> int {
-        if (c->prof.on) MI_HIP(hipStreamSynchronize(c->stream));
-        const double now = wall_ms(), a_now = alloc_ms_counter();
-        b.ms[0] += a_now - a_mark;
-        b.ms[stage] += (now - t_mark) - (a_now - a_mark);
-        t_mark = now; a_mark = a_now;
-        return MI_OK;
-    };
+    StageClock clock(c, b.ms);         // mi_knn_search_times
 
     const size_t np = (size_t)n, mp = (size_t)m, rows = np * (size_t)k;
     MI_TRY(b.staging.reserve(3 * std::max(np, mp)));
@@ -54,15 +43,11 @@ extern "C" int mi_knn_search(mi_ctx* c, const float* query_xyz, int n, const flo
     if (!self) { MI_TRY(b.ux.reserve(np)); MI_TRY(b.uy.reserve(np)); MI_TRY(b.uz.reserve(np)); }
     MI_TRY(b.qx.reserve(np)); MI_TRY(b.qy.reserve(np)); MI_TRY(b.qz.reserve(np));
     MI_TRY(b.range_lo_hi.reserve(2 * 6 * KNN_RANGE_BLOCKS)); MI_TRY(b.range_bad.reserve(2 * KNN_RANGE_BLOCKS)); MI_TRY(b.state.reserve(1));
-    MI_TRY(b.bbox.reserve(256 * 6 + 8));
-    MI_TRY(b.codes_in.reserve(np)); MI_TRY(b.codes_out.reserve(np)); MI_TRY(b.order_in.reserve(np)); MI_TRY(b.order.reserve(np));
-    const size_t sort_bytes = tree_sort_temp_bytes(n);
-    MI_TRY(b.sort_temp.reserve(sort_bytes + 16));
-    MI_TRY(b.pts.reserve(mp + GRID_PTS_PAD)); MI_TRY(b.slot_of.reserve(mp));
+    MI_TRY(b.order.reserve(np));
     MI_TRY(b.out_idx.reserve(rows));
     if (d2) MI_TRY(b.out_d2.reserve(rows));
     if (count) MI_TRY(b.out_count.reserve(np));
-    MI_TRY(mark(0));
+    MI_TRY(clock.mark(0));
 
     MI_TRY(host_to_device(c, b.staging.p, cloud_xyz, sizeof(float) * 3 * mp));
     MI_HIP(aos_to_soa(b.staging.p, m, m, b.cx.p, b.cy.p, b.cz.p, nullptr, c->stream));
@@ -71,14 +56,14 @@ extern "C" int mi_knn_search(mi_ctx* c, const float* query_xyz, int n, const flo
         MI_HIP(aos_to_soa(b.staging.p, n, n, b.ux.p, b.uy.p, b.uz.p, nullptr, c->stream));
     }
     const float *ux = self ? b.cx.p : b.ux.p, *uy = self ? b.cy.p : b.uy.p, *uz = self ? b.cz.p : b.uz.p;
-    MI_TRY(mark(1));
+    MI_TRY(clock.mark(1));
 
     MI_HIP(knn_check_inputs(b.cx.p, b.cy.p, b.cz.p, m, self ? nullptr : ux, uy, uz, n, b.range_lo_hi.p, b.range_bad.p, b.state.p, c->stream));
     KnnState* st = reinterpret_cast<KnnState*>(c->h_scratch);     // (pinned, 256 bytes)
     static_assert(sizeof(KnnState) <= 64 * sizeof(float), "KnnState must fit the context's pinned scratch");
     MI_HIP(hipMemcpyAsync(st, b.state.p, sizeof(KnnState), hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
-    MI_TRY(mark(2));
+    MI_TRY(clock.mark(2));
     // everything that can refuse the input is known here, before any output array has been touched
     if (st->bad_cloud != KNN_NO_POINT) {
         set_error("mi_knn_search: cloud_xyz point %d has a non-finite coordinate or one above 1e18 in magnitude", st->bad_cloud);
@@ -93,32 +78,23 @@ extern "C" int mi_knn_search(mi_ctx* c, const float* query_xyz, int n, const flo
     const float bbox[6] = {st->lo[0], st->lo[1], st->lo[2], st->hi[0], st->hi[1], st->hi[2]};
     const float ppc = c->tune.knn_points_per_cell > 0.f ? c->tune.knn_points_per_cell : knn_default_points_per_cell(k);
     NnGridView g{};
-    grid_plan(bbox, m, ppc, &g);
+    MI_TRY(grid_reserve(b.cells, bbox, m, 0, ppc, &g));
+    MI_TRY(clock.mark(0));
+    // (grid_plan clamps the counts to [1, GRID_MAX_DIM], so the reserves above were sane whatever the box; a cell size that left fp32 can still show here)
     if (g.nx < 1 || g.ny < 1 || g.nz < 1 || g.nx > GRID_MAX_DIM || g.ny > GRID_MAX_DIM || g.nz > GRID_MAX_DIM || !(g.inv_h > 0.f) || !(g.h_lo > 0.f)) {
         set_error("internal: mi_knn_search planned a %d x %d x %d grid", g.nx, g.ny, g.nz);
         return MI_ERR_STATE;
     }
     const size_t n_cells = (size_t)g.nx * g.ny * g.nz;
-    MI_TRY(b.row_occ.reserve(n_cells)); MI_TRY(b.near_tmp.reserve(n_cells));
-    MI_TRY(b.start.reserve(n_cells + 1 + 3)); MI_TRY(b.fill.reserve(n_cells + 1)); MI_TRY(b.scan.reserve((n_cells + 1) / 1024 + 2));
-    MI_TRY(mark(0));
-    g.pts = b.pts.p; g.cell_start = b.start.p; g.slot_of = b.slot_of.p; g.row_occ = b.row_occ.p; g.index_base = 0;
-    GridBuildArgs ga{};
-    ga.x = b.cx.p; ga.y = b.cy.p; ga.z = b.cz.p; ga.m = m; ga.index_base = 0;
-    ga.view = g; ga.cell_fill = b.fill.p; ga.scan_tmp = b.scan.p; ga.pts_out = b.pts.p; ga.cell_start_out = b.start.p; ga.slot_of_out = b.slot_of.p;
-    ga.row_occ_out = b.row_occ.p; ga.near_tmp = b.near_tmp.p;
-    MI_HIP(grid_build(ga, c->stream));
-    MI_TRY(mark(3));
+    MI_TRY(grid_build_into(b.cells, g, b.cx.p, b.cy.p, b.cz.p, m, c->stream));
+    MI_TRY(clock.mark(3));
 
     // the queries along their curve: order[s] = the caller's index of sorted slot s
     MortonArgs ma{};
-    ma.x = ux; ma.y = uy; ma.z = uz; ma.m = n;
-    ma.bbox_partials = b.bbox.p; ma.bbox = b.bbox.p + 256 * 6;
-    ma.codes_in = b.codes_in.p; ma.codes_out = b.codes_out.p; ma.order_in = b.order_in.p; ma.order_out = b.order.p;
-    ma.sort_temp = b.sort_temp.p; ma.sort_temp_bytes = sort_bytes;
+    MI_TRY(morton_args(b.morton, ux, uy, uz, n, b.order.p, &ma));
     MI_HIP(morton_order(ma, c->stream));
     MI_HIP(permute_soa(ux, uy, uz, b.order.p, n, n, b.qx.p, b.qy.p, b.qz.p, c->stream));
-    MI_TRY(mark(4));
+    MI_TRY(clock.mark(4));
 
     KnnSearchArgs a{};
     a.qx = b.qx.p; a.qy = b.qy.p; a.qz = b.qz.p; a.order = b.order.p;
@@ -127,7 +103,7 @@ extern "C" int mi_knn_search(mi_ctx* c, const float* query_xyz, int n, const flo
     a.idx = b.out_idx.p; a.d2 = d2 ? b.out_d2.p : nullptr; a.count = count ? b.out_count.p : nullptr;
     // host-side shape checks before the hand-written kernel runs: every array it indexes is as long as the launch assumes
     if (b.qx.cap < np || b.order.cap < np || b.out_idx.cap < rows || (d2 && b.out_d2.cap < rows) || (count && b.out_count.cap < np) ||
-        b.start.cap < n_cells + 1 || b.pts.cap < mp) {
+        b.cells.start.cap < n_cells + 1 || b.cells.pts.cap < mp) {
         set_error("internal: mi_knn_search buffers shorter than the launch");
         return MI_ERR_STATE;
     }
@@ -139,7 +115,7 @@ extern "C" int mi_knn_search(mi_ctx* c, const float* query_xyz, int n, const flo
     }
     MI_HIP(knn_search(g, a, dist_mode == MI_DIST_FMA, c->stream));
     if (timed) MI_HIP(hipEventRecord(b.ev[1], c->stream));
-    MI_TRY(mark(5));
+    MI_TRY(clock.mark(5));
     if (timed) {
         float ms = 0.f;
         MI_HIP(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
@@ -150,8 +126,8 @@ extern "C" int mi_knn_search(mi_ctx* c, const float* query_xyz, int n, const flo
     if (d2) MI_HIP(hipMemcpyAsync(d2, b.out_d2.p, sizeof(float) * rows, hipMemcpyDeviceToHost, c->stream));
     if (count) MI_HIP(hipMemcpyAsync(count, b.out_count.p, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
-    MI_TRY(mark(6));
-    b.ms[7] = wall_ms() - t_begin;
+    MI_TRY(clock.mark(6));
+    clock.finish();
     return MI_OK;
 }
 

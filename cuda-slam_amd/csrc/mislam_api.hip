@@ -5,6 +5,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -97,6 +98,7 @@ static hipStream_t alloc_stream(hipMemPool_t* pool_out = nullptr)
     return g_alloc_stream[dev];
 }
 static bool g_pool_proven = false;               // a pool allocation has succeeded: the mode never changes after that
+static std::atomic<long long> g_live_buffers{0}; // successful device_alloc calls minus device_free calls (mi_selftest_live_buffers)
 hipError_t device_alloc(void** p, size_t bytes)
 {
     hipMemPool_t pool = nullptr;
@@ -104,16 +106,19 @@ hipError_t device_alloc(void** p, size_t bytes)
         hipError_t e = hipMallocFromPoolAsync(p, bytes, pool, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);          // (nothing else is ever on this stream: the memory is usable on any stream from here)
         std::lock_guard<std::mutex> lock(g_pool_mutex);
-        if (e == hipSuccess) { g_pool_proven = true; return e; }
+        if (e == hipSuccess) { g_pool_proven = true; g_live_buffers += 1; return e; }
         (void)hipGetLastError();
         if (g_pool_proven || e == hipErrorOutOfMemory) return e;
         g_use_pool = 0;                          // this runtime has no working pool: plain allocations throughout
     }
-    return hipMalloc(p, bytes);
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) g_live_buffers += 1;
+    return e;
 }
 void device_free(void* p)
 {
     if (p == nullptr) return;
+    g_live_buffers -= 1;
     if (hipStream_t s = alloc_stream()) { (void)hipFreeAsync(p, s); return; }
     (void)hipFree(p);
 }
@@ -431,20 +436,7 @@ extern "C" void mi_ctx_destroy(mi_ctx* c)
     if (c->pin.buf) (void)hipHostFree(c->pin.buf);
     if (c->h_scratch) (void)hipHostFree(c->h_scratch);
     cpd_workspace_destroy(c);
-    for (mi_ctx::LaneScratch& l : c->scratch) { l.staging.release(); l.codes_in.release(); l.codes_out.release(); l.order_in.release(); l.bbox.release(); l.sort_temp.release(); }
-    c->bx.release(); c->by.release(); c->bz.release();
-    c->cx.release(); c->cy.release(); c->cz.release(); c->ax.release(); c->ay.release(); c->az.release();
-    c->tx.release(); c->ty.release(); c->tz.release();
-    c->tgt4.release(); c->keys.release(); c->part_mom.release(); c->part_err.release();
-    c->idx_tmp.release(); c->keep_tmp.release(); c->sorder.release(); c->sinv.release(); c->resid.release(); c->nn_stats.release(); c->rows.release(); c->rows_reduced.release();
-    c->tree.order_out.release(); c->tree.pts.release(); c->tree.boxes.release(); c->tree.leaf.release(); c->tree.idx.release(); c->tree.boxes6.release();
-    c->grid.bbox.release(); c->grid.pts.release(); c->grid.start.release(); c->grid.fill.release(); c->grid.scan.release(); c->grid.slot_of.release();
-    c->grid.row_occ.release(); c->grid.near_tmp.release(); c->grid.match_slot.release();
-    c->sched.order.release(); c->sched.far.release(); c->sched.lanes.release(); c->sched.counters.release();
-    c->bat.before.release(); c->bat.after.release(); c->bat.sx.release(); c->bat.sy.release(); c->bat.sz.release();
-    c->bat.problems.release(); c->bat.states.release(); c->bat.running.release();
-    c->vox.release();
-    c->knn.release();
+    for (hipEvent_t e : c->knn.ev) if (e) (void)hipEventDestroy(e);
     for (auto& s : c->prof.spans) { (void)hipEventDestroy(s.e0); (void)hipEventDestroy(s.e1); }
     for (auto e : c->prof.event_pool) (void)hipEventDestroy(e);
     if (c->d_state) (void)hipFree(c->d_state);
@@ -454,8 +446,9 @@ extern "C" void mi_ctx_destroy(mi_ctx* c)
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->aux2) (void)hipStreamDestroy(c->aux2);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    pool_context_gone(c->device);
-    delete c;
+    const int device = c->device;
+    delete c;                                   // every DevBuf of the context frees itself here (device_free: on the allocation stream) ...
+    pool_context_gone(device);                  // ... and the last context of a device trims the pool behind those frees
 }
 
 extern "C" int mi_ctx_synchronize(mi_ctx* c)
@@ -612,6 +605,13 @@ extern "C" int mi_selftest_fail_loads(mi_ctx* c, int n)
     return MI_OK;
 }
 
+extern "C" int mi_selftest_live_buffers(long long* count)
+{
+    if (!count) { set_error("mi_selftest_live_buffers: null argument"); return MI_ERR_INVALID_ARG; }
+    *count = g_live_buffers.load();
+    return MI_OK;
+}
+
 extern "C" int mi_selftest_sort_pairs(mi_ctx* c, unsigned int* keys, int* values, int n, int bits)
 {
     if (!c || n < 0 || (n > 0 && (!keys || !values)) || (bits != 10 && bits != 20 && bits != 30)) {
@@ -631,7 +631,6 @@ extern "C" int mi_selftest_sort_pairs(mi_ctx* c, unsigned int* keys, int* values
     MI_HIP(hipMemcpyAsync(keys, k1.p, sizeof(unsigned int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipMemcpyAsync(values, v1.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
-    k0.release(); k1.release(); v0.release(); v1.release(); temp.release();      // (DevBuf has no destructor: the call's own scratch goes back to the pool here)
     return MI_OK;
 }
 

@@ -76,21 +76,50 @@ int upload_soa(mi_ctx* c, const float* host_aos, int n, int n_pad, float* x, flo
     return MI_OK;
 }
 
-// Scratch for one Morton sort of m points (shared by the fixed-cloud hierarchy and the moving-cloud ordering).
-static int morton_args(mi_ctx* c, const float* x, const float* y, const float* z, int m, int* order_out, MortonArgs* out)
+// Scratch for one Morton sort of m points.  (sort_temp_bytes is a bound nothing reads: the radix sort's scratch has one size whatever m is.)
+int morton_args(MortonScratch& sc, const float* x, const float* y, const float* z, int m, int* order_out, MortonArgs* out)
 {
     const size_t sort_bytes = tree_sort_temp_bytes(m);
-    mi_ctx::LaneScratch& l = c->scratch[c->lane];       // (the lane's own scratch set: two sorts may be in flight, one per lane)
-    MI_TRY(l.codes_in.reserve((size_t)m)); MI_TRY(l.codes_out.reserve((size_t)m));
-    MI_TRY(l.order_in.reserve((size_t)m));
-    MI_TRY(l.bbox.reserve(256 * 6 + 8));
-    MI_TRY(l.sort_temp.reserve(sort_bytes + 16));
+    MI_TRY(sc.codes_in.reserve((size_t)m)); MI_TRY(sc.codes_out.reserve((size_t)m));
+    MI_TRY(sc.order_in.reserve((size_t)m));
+    MI_TRY(sc.bbox.reserve(256 * 6 + 8));
+    MI_TRY(sc.sort_temp.reserve(sort_bytes + 16));
     MortonArgs a{};
     a.x = x; a.y = y; a.z = z; a.m = m;
-    a.bbox_partials = l.bbox.p; a.bbox = l.bbox.p + 256 * 6;
-    a.codes_in = l.codes_in.p; a.codes_out = l.codes_out.p; a.order_in = l.order_in.p; a.order_out = order_out;
-    a.sort_temp = l.sort_temp.p; a.sort_temp_bytes = sort_bytes;
+    a.bbox_partials = sc.bbox.p; a.bbox = sc.bbox.p + 256 * 6;
+    a.codes_in = sc.codes_in.p; a.codes_out = sc.codes_out.p; a.order_in = sc.order_in.p; a.order_out = order_out;
+    a.sort_temp = sc.sort_temp.p; a.sort_temp_bytes = sort_bytes;
     *out = a;
+    return MI_OK;
+}
+
+int grid_reserve(GridBuffers& b, const float bbox[6], int m, int index_base, float points_per_cell, NnGridView* view)
+{
+    NnGridView g{};
+    grid_plan(bbox, m, points_per_cell, &g);
+    const size_t n_cells = (size_t)g.nx * g.ny * g.nz;
+    MI_TRY(b.pts.reserve((size_t)m + GRID_PTS_PAD));
+    MI_TRY(b.row_occ.reserve(n_cells)); MI_TRY(b.near_tmp.reserve(n_cells));
+    MI_TRY(b.start.reserve(n_cells + 1 + 3));           // (+3: a row's offsets are fetched four words at a time)
+    MI_TRY(b.fill.reserve(n_cells + 1));
+    MI_TRY(b.scan.reserve((n_cells + 1) / 1024 + 2));
+    MI_TRY(b.slot_of.reserve((size_t)m));
+    g.pts = b.pts.p;
+    g.cell_start = b.start.p;
+    g.slot_of = b.slot_of.p;
+    g.row_occ = b.row_occ.p;
+    g.index_base = index_base;
+    *view = g;
+    return MI_OK;
+}
+
+int grid_build_into(GridBuffers& b, const NnGridView& view, const float* x, const float* y, const float* z, int m, hipStream_t s)
+{
+    GridBuildArgs a{};
+    a.x = x; a.y = y; a.z = z; a.m = m; a.index_base = view.index_base;
+    a.view = view; a.cell_fill = b.fill.p; a.scan_tmp = b.scan.p; a.pts_out = b.pts.p; a.cell_start_out = b.start.p; a.slot_of_out = b.slot_of.p;
+    a.row_occ_out = b.row_occ.p; a.near_tmp = b.near_tmp.p;
+    MI_HIP(grid_build(a, s));
     return MI_OK;
 }
 
@@ -114,7 +143,7 @@ int ensure_tree(mi_ctx* c, int m_local, int index_base)
     MI_TRY(c->tree.idx.reserve((size_t)n_leaves * TREE_LEAF));
     MI_TRY(c->tree.boxes6.reserve((size_t)12 * ((size_t)n_pad + 6)));        // pairs of nodes (nn_tree.h), incl. the padding a step may read
     TreeBuildArgs a{};
-    MI_TRY(morton_args(c, c->tx.p, c->ty.p, c->tz.p, m_local, c->tree.order_out.p, &a.morton));
+    MI_TRY(morton_args(c->scratch[c->lane].morton, c->tx.p, c->ty.p, c->tz.p, m_local, c->tree.order_out.p, &a.morton));   // (the lane's own scratch: two sorts may be in flight, one per lane)
     a.index_base = index_base; a.n_leaves = n_leaves; a.n_pad = n_pad;
     a.pts = c->tree.pts.p; a.boxes = c->tree.boxes.p;
     a.leaf_soa = c->tree.leaf.p; a.leaf_idx = c->tree.idx.p; a.boxes6 = c->tree.boxes6.p;
@@ -140,24 +169,8 @@ int ensure_grid(mi_ctx* c, int m_local, int index_base)
     { StallProbe sp("grid: bounding-box synchronize"); MI_HIP(hipStreamSynchronize(ws)); }
     StallProbe sp_rest("grid: reserve + enqueue build");
     NnGridView g{};
-    grid_plan(bbox, m_local, c->tune.grid_points_per_cell, &g);
-    const size_t n_cells = (size_t)g.nx * g.ny * g.nz;
-    MI_TRY(c->grid.pts.reserve((size_t)m_local + GRID_PTS_PAD));
-    MI_TRY(c->grid.row_occ.reserve(n_cells)); MI_TRY(c->grid.near_tmp.reserve(n_cells));
-    MI_TRY(c->grid.start.reserve(n_cells + 1 + 3));           // (+3: a row's offsets are fetched four words at a time)
-    MI_TRY(c->grid.fill.reserve(n_cells + 1));
-    MI_TRY(c->grid.scan.reserve((n_cells + 1) / 1024 + 2));
-    MI_TRY(c->grid.slot_of.reserve((size_t)m_local));
-    g.pts = c->grid.pts.p;
-    g.cell_start = c->grid.start.p;
-    g.slot_of = c->grid.slot_of.p;
-    g.row_occ = c->grid.row_occ.p;
-    g.index_base = index_base;
-    GridBuildArgs a{};
-    a.x = c->tx.p; a.y = c->ty.p; a.z = c->tz.p; a.m = m_local; a.index_base = index_base;
-    a.view = g; a.cell_fill = c->grid.fill.p; a.scan_tmp = c->grid.scan.p; a.pts_out = c->grid.pts.p; a.cell_start_out = c->grid.start.p; a.slot_of_out = c->grid.slot_of.p;
-    a.row_occ_out = c->grid.row_occ.p; a.near_tmp = c->grid.near_tmp.p;
-    MI_HIP(grid_build(a, ws));
+    MI_TRY(grid_reserve(c->grid.cells, bbox, m_local, index_base, c->tune.grid_points_per_cell, &g));
+    MI_TRY(grid_build_into(c->grid.cells, g, c->tx.p, c->ty.p, c->tz.p, m_local, ws));
     c->grid.view = g;
     c->grid.valid = true;
     return MI_OK;
@@ -177,7 +190,7 @@ int sort_sources(mi_ctx* c, const float* sx, const float* sy, const float* sz, i
 {
     MI_TRY(c->sorder.reserve((size_t)n));
     MortonArgs ma{};
-    MI_TRY(morton_args(c, sx, sy, sz, n, c->sorder.p, &ma));
+    MI_TRY(morton_args(c->scratch[c->lane].morton, sx, sy, sz, n, c->sorder.p, &ma));
     MI_HIP(morton_order(ma, c->work_stream()));
     MI_HIP(permute_soa(sx, sy, sz, c->sorder.p, n, n_pad, dx, dy, dz, c->work_stream()));
     return MI_OK;

@@ -45,18 +45,7 @@ extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float vox
     if (c->distributed()) { set_error("mi_voxel_downsample: single-GPU contexts only"); return MI_ERR_STATE; }
     MI_ENTER(c);
     mi_ctx::VoxelBuffers& b = c->vox;
-    // mi_voxel_downsample_times: host wall time per stage, as mi_icp_load keeps it; with profiling on, the stream is drained at every mark
-    const double t_begin = wall_ms();
-    double t_mark = t_begin, a_mark = alloc_ms_counter();
-    for (double& v : b.ms) v = 0.0;
-    auto mark = [&](int stage) -> int {
-        if (c->prof.on) MI_HIP(hipStreamSynchronize(c->stream));
-        const double now = wall_ms(), a_now = alloc_ms_counter();
-        b.ms[0] += a_now - a_mark;
-        b.ms[stage] += (now - t_mark) - (a_now - a_mark);
-        t_mark = now; a_mark = a_now;
-        return MI_OK;
-    };
+    StageClock clock(c, b.ms);         // mi_voxel_downsample_times
 
     const size_t np = (size_t)n;
     const int scan_tiles = (n + VOX_SCAN_TILE - 1) / VOX_SCAN_TILE, sum_tiles = (n + VOX_SUM_TILE - 1) / VOX_SUM_TILE;
@@ -67,11 +56,11 @@ extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float vox
     MI_TRY(b.block_heads.reserve((size_t)scan_tiles)); MI_TRY(b.row_of.reserve(np)); MI_TRY(b.run_start.reserve(np + 1));
     MI_TRY(b.front.reserve(3 * (size_t)sum_tiles)); MI_TRY(b.back.reserve(3 * (size_t)sum_tiles)); MI_TRY(b.fix.reserve((size_t)sum_tiles));
     MI_TRY(b.out_xyz.reserve(3 * np)); MI_TRY(b.out_count.reserve(np)); MI_TRY(b.out_coord.reserve(3 * np)); MI_TRY(b.voxel_of_point.reserve(np));
-    MI_TRY(mark(0));
+    MI_TRY(clock.mark(0));
 
     MI_TRY(host_to_device(c, b.staging.p, xyz, sizeof(float) * 3 * np));
     MI_HIP(aos_to_soa(b.staging.p, n, n, b.x.p, b.y.p, b.z.p, b.pts.p, c->stream));
-    MI_TRY(mark(1));
+    MI_TRY(clock.mark(1));
 
     VoxArgs a{};
     a.n = n; a.voxel = voxel_size; a.state = b.state.p;
@@ -82,7 +71,7 @@ extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float vox
     static_assert(sizeof(VoxState) <= 64 * sizeof(float), "VoxState must fit the context's pinned scratch");
     MI_HIP(hipMemcpyAsync(st, b.state.p, sizeof(VoxState), hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
-    MI_TRY(mark(2));
+    MI_TRY(clock.mark(2));
     // everything that can refuse the cloud is known here, before any output array has been touched
     if (st->bad_index != VOX_NO_POINT) {
         set_error("mi_voxel_downsample: point %d has a non-finite coordinate", st->bad_index);
@@ -105,7 +94,7 @@ extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float vox
         }
     }
     const bool packed = extent[0] <= VOX_PACKED_EXTENT && extent[1] <= VOX_PACKED_EXTENT && extent[2] <= VOX_PACKED_EXTENT;
-    if (!packed) { MI_TRY(b.axis_keys.reserve(3 * np)); MI_TRY(mark(0)); }
+    if (!packed) { MI_TRY(b.axis_keys.reserve(3 * np)); MI_TRY(clock.mark(0)); }
 
     a.keys = b.keys_a.p; a.vals = b.vals_a.p; a.axis_keys = packed ? nullptr : b.axis_keys.p;
     MI_HIP(vox_keys(a, c->stream));
@@ -122,14 +111,14 @@ extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float vox
         MI_HIP(radix_sort_pairs_u32(b.sort_temp.p, b.keys_a.p, b.keys_b.p, b.vals_a.p, b.vals_b.p, n, bits(2), c->stream));
     }
     a.sorted_idx = b.vals_b.p;
-    MI_TRY(mark(3));
+    MI_TRY(clock.mark(3));
 
     a.block_heads = b.block_heads.p; a.row_of = b.row_of.p; a.run_start = b.run_start.p;
     a.front = b.front.p; a.back = b.back.p; a.fix = b.fix.p;
     a.out_xyz = b.out_xyz.p; a.out_count = b.out_count.p; a.out_coord = b.out_coord.p; a.voxel_of_point = b.voxel_of_point.p;
     MI_HIP(vox_rows(a, c->stream));
     MI_HIP(vox_sums(a, c->stream));
-    MI_TRY(mark(4));
+    MI_TRY(clock.mark(4));
 
     MI_HIP(hipMemcpyAsync(&st->rows, &b.state.p->rows, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
@@ -141,8 +130,8 @@ extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float vox
     if (voxel_of_point) MI_HIP(hipMemcpyAsync(voxel_of_point, b.voxel_of_point.p, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
     *out_n = rows;
-    MI_TRY(mark(5));
-    b.ms[7] = wall_ms() - t_begin;
+    MI_TRY(clock.mark(5));
+    clock.finish();
     return MI_OK;
 }
 

@@ -666,6 +666,10 @@ int mi_selftest_sort_pairs(mi_ctx* ctx, unsigned int* keys, int* values, int n, 
  * early-return path of mi_icp_load).  Only ever by this explicit call -- round 5 read it from the environment, where a stray variable could have failed
  * loads in production.  n = 0 disarms. */
 int mi_selftest_fail_loads(mi_ctx* ctx, int n);
+/* Device buffers of the library now alive in this process, over all contexts: successful allocations minus frees.  A buffer that was outgrown counts
+ * until it is really freed (behind the next drain of its context's stream).  Creating a context, using it and destroying it leaves the count where
+ * it was: what the library's own tests check.  Needs no context. */
+int mi_selftest_live_buffers(long long* count);
 /* Name of the correspondence-search kernel (MI_KERNEL_NN) a search of n_moving points against m_fixed_local fixed points runs
  * with this nn_mode and the current settings -- the name a rocprofv3 kernel trace shows (static string). */
 const char* mi_nn_kernel_name(const mi_ctx* ctx, int n_moving, int m_fixed_local, int nn_mode);

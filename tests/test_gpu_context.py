@@ -83,3 +83,64 @@ def test_a_failed_load_leaves_the_context_usable(capi, monkeypatch):
             for b, a in ((b2, a2), (b1, a1)):
                 x, y = bad.icp_register(b, a, p), fresh.icp_register(b, a, p)
                 assert x[2] == y[2] == 6 and np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1]) and x[3] == y[3]
+
+
+def _use_every_buffer_owner(capi, c):
+    """One call of everything that owns device buffers in a context, at the smallest sizes that reach it."""
+    rng = np.random.default_rng(7)
+    cloud = lambda n: rng.uniform(-5.0, 5.0, (n, 3)).astype(np.float32)
+    b, a = cloud(300), cloud(300)
+    c.nn_search(b, a, capi.DIST_CPU_ROUNDING, capi.NN_GRID)              # hierarchy, grid, both lanes' scratch, work order
+    for sum_mode in (capi.SUM_EXACT, capi.SUM_CPU_SEQUENTIAL):           # (the sequential sums: sinv, resid)
+        c.icp_load(b, a, capi.icp_params(eps=0.0, max_iterations=3, nn_mode=capi.NN_GRID, sum_mode=sum_mode))
+        c.icp_run(3)
+    y, x = cloud(200), cloud(200)
+    for approx in (capi.CPD_APPROX_NONE, capi.CPD_APPROX_HYBRID, capi.CPD_APPROX_FULL):   # FGT sides, the truncated E-step's Morton scratch
+        c.cpd_register(y, x, capi.cpd_params(max_iterations=4, tolerance=0.0, approximation=approx))
+    c.cpd_estep_truncated(y, x, 1.0, 2.0)
+    c.cpd_register(y, x, capi.cpd_params(max_iterations=2, sigma2_mode=capi.SIGMA2_CPU_SEQUENTIAL))   # sig_scratch
+    pairs = [cloud(64), cloud(64)], [cloud(64), cloud(64)]
+    c.icp_register_batch(*pairs, capi.icp_params(eps=0.0, max_iterations=3))
+    c.cpd_register_batch(*pairs, capi.cpd_params(max_iterations=3))
+    v = cloud(100)
+    c.voxel_downsample(v, 1.0)                                           # packed keys
+    c.voxel_downsample(v, 1e-3, want_counts=True, want_coords=True, want_map=True)   # 10 000 voxels per axis: the per-axis sorts (axis_keys)
+    q = cloud(200)
+    c.knn_search(q, q, 8, want_d2=True, want_count=True)
+    c.profile_enable(True)                                               # (profiled once: the call's two events exist)
+    c.knn_search(q, q, 8, want_d2=True, want_count=True)
+    c.profile_enable(False)
+    c.selftest_sort_pairs(rng.integers(0, 2 ** 30, 1000), np.arange(1000))
+
+
+def test_a_destroyed_context_leaves_no_device_buffer_behind(capi, ctx):
+    # Every device buffer belongs to a DevBuf, and a DevBuf frees itself: whatever a context allocated, through whichever entry point, is back in the
+    # pool once the context is gone.  (The hand-written release lists this replaced had lost cpd_problems, cpd_states and sig_scratch.)
+    start = capi.selftest_live_buffers()
+    with capi.Context(0) as c:
+        _use_every_buffer_owner(capi, c)
+        assert capi.selftest_live_buffers() > start
+    assert capi.selftest_live_buffers() == start
+
+
+def test_a_failed_load_leaves_no_device_buffer_behind(capi, ctx):
+    from conftest import synth_cloud
+    b, a = synth_cloud(12000, seed=5)[:2]          # the smallest size at which a load builds the indexes by default (MI_NN_INDEX_MIN_POINTS)
+    p = capi.icp_params(eps=0.0, max_iterations=2)
+    start = capi.selftest_live_buffers()
+    with capi.Context(0) as c:
+        c.selftest_fail_loads(1)
+        with pytest.raises(capi.MiSlamError):
+            c.icp_load(b, a, p)
+        c.icp_load(b, a, p)
+    assert capi.selftest_live_buffers() == start
+
+
+def test_the_sort_selftest_hands_its_scratch_back(capi, ctx):
+    rng = np.random.default_rng(11)
+    keys, vals = rng.integers(0, 2 ** 30, 1000), np.arange(1000)
+    live = []
+    for _ in range(50):
+        ctx.selftest_sort_pairs(keys, vals)
+        live.append(capi.selftest_live_buffers())
+    assert live[49] == live[0]
