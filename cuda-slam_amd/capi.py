@@ -40,7 +40,7 @@ EXPORTS = [
     "mi_cpd_estep_truncated", "mi_cpd_estep_fgt", "mi_fgt_kcenter", "mi_fgt_kcenter_guided", "mi_fgt_tables", "mi_nicp_params_default", "mi_nicp_register",
     "mi_prepare_params_default", "mi_prepare_cloud", "mi_voxel_index", "mi_voxel_downsample", "mi_voxel_downsample_times",
     "mi_knn_search", "mi_knn_search_times",
-    "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_nn_kernel_name",
+    "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_nn_kernel_name",
 ]
 
 
@@ -293,6 +293,14 @@ def unpack_key(key):
     d2, idx = C.c_float(0), C.c_int(0)
     lib().mi_unpack_key(C.c_ulonglong(key), C.byref(d2), C.byref(idx))
     return d2.value, idx.value
+
+
+def selftest_cloud_range_raw(ctx, xyz, n, check, out_lo_hi, out_first_bad):
+    """mi_selftest_cloud_range with raw pointers -> its return code."""
+    f = lib().mi_selftest_cloud_range
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    return f(ctx, xyz, n, check, out_lo_hi, out_first_bad)
 
 
 def selftest_live_buffers():
@@ -719,6 +727,16 @@ class Context:
         assert k.shape == v.shape and k.ndim == 1
         _check(lib().mi_selftest_sort_pairs(self._h, k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), int(k.size), int(bits)))
         return k, v
+
+    def selftest_cloud_range(self, xyz, check=0):
+        """The range pass of csrc/cloud_range.hpp over an (n, 3) host cloud: (lo_hi float32[6], lowest refused index or 0x7fffffff).
+        check 0: refuse nothing; 1: non-finite points; 2: those and |coordinate| > 1e18 (mi_selftest_cloud_range)."""
+        p = np.ascontiguousarray(xyz, dtype=np.float32)
+        assert p.ndim == 2 and p.shape[1] == 3
+        lo_hi = np.zeros(6, np.float32)
+        bad = C.c_int(-1)
+        _check(selftest_cloud_range_raw(self._h, p.ctypes.data, int(p.shape[0]), int(check), lo_hi.ctypes.data, C.byref(bad)))
+        return lo_hi, int(bad.value)
 
     def nn_kernel_name(self, n_moving, m_fixed_local, nn_mode=NN_AUTO):
         lib().mi_nn_kernel_name.restype = C.c_char_p

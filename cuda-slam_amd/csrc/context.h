@@ -64,6 +64,7 @@ struct ProfileSpan {
 };
 
 struct CpdWorkspace;   // cpd_api.hip
+struct PrepState;      // prepare_api.hip
 
 }  // namespace mislam
 
@@ -201,6 +202,13 @@ struct mi_ctx {
         hipEvent_t ev[2] = {nullptr, nullptr};           // around the search launch while profiling (mi_knn_search_times); destroyed by mi_ctx_destroy
         double ms[MI_KNN_STAGES] = {0};
     } knn;
+
+    // ---- mi_prepare_cloud: buffers of its own, like the voxel call's: the raw cloud, the prepared one, the caller's index vectors and draws
+    struct PrepareBuffers {
+        mislam::DevBuf<float> raw, out, partials, noise_unit, outlier_unit;
+        mislam::DevBuf<int> sub, shuffle, rows;
+        mislam::DevBuf<mislam::PrepState> state;
+    } prep;
 
     // ---- ICP problem currently loaded
     struct IcpProblem {

@@ -84,7 +84,6 @@ void cpd_workspace_destroy(mi_ctx* c)
     c->cpd = nullptr;
 }
 
-static inline int round_up_i(int v, int g) { return (v + g - 1) / g * g; }
 
 static int cpd_workspace(mi_ctx* c, CpdWorkspace** out)
 {
@@ -105,7 +104,7 @@ static void plan_chunks(const mi_ctx* c, int owners, int owner_r, int stream_len
     const int owner_blocks = std::max(1, (owners + 256 * owner_r - 1) / (256 * owner_r));
     int ch = (c->cu_count * 8 + owner_blocks - 1) / owner_blocks;
     ch = std::max(1, std::min(ch, std::min(CPD_MAX_CHUNKS, std::max(1, stream_len / (CPD_T * 8)))));
-    *chunk_len = round_up_i((stream_len + ch - 1) / ch, CPD_T);
+    *chunk_len = round_up((stream_len + ch - 1) / ch, CPD_T);
     *chunks = (stream_len + *chunk_len - 1) / *chunk_len;
 }
 
@@ -118,8 +117,8 @@ static int cpd_load(mi_ctx* c, CpdWorkspace* w, const float* before_xyz, int m, 
     w->fgt.y.prelaunched = 0;
     w->m = m; w->n = n; w->n_total = n;
     w->trunc_ready = false;
-    w->m_pad = round_up_i(m, NN_SRC_PAD);
-    w->n_pad = round_up_i(n, NN_SRC_PAD);
+    w->m_pad = round_up(m, NN_SRC_PAD);
+    w->n_pad = round_up(n, NN_SRC_PAD);
     const size_t mp = (size_t)w->m_pad, np = (size_t)w->n_pad;
     MI_TRY(c->bx.reserve(mp)); MI_TRY(c->by.reserve(mp)); MI_TRY(c->bz.reserve(mp));
     MI_TRY(c->cx.reserve(mp)); MI_TRY(c->cy.reserve(mp)); MI_TRY(c->cz.reserve(mp));
@@ -913,7 +912,7 @@ extern "C" int mi_fgt_kcenter(mi_ctx* c, const float* cloud_xyz, int n, int K, f
     CpdWorkspace* w = nullptr;
     MI_TRY(cpd_workspace(c, &w));
     c->prob.icp_loaded = false;
-    const int n_pad = round_up_i(n, NN_SRC_PAD);
+    const int n_pad = round_up(n, NN_SRC_PAD);
     MI_TRY(c->bx.reserve(n_pad)); MI_TRY(c->by.reserve(n_pad)); MI_TRY(c->bz.reserve(n_pad));
     MI_TRY(upload_soa(c, cloud_xyz, n, n_pad, c->bx.p, c->by.p, c->bz.p, nullptr));
     FgtClusters cl{};
@@ -939,7 +938,7 @@ extern "C" int mi_fgt_kcenter_guided(mi_ctx* c, const float* cloud_xyz, int n, i
     MI_TRY(cpd_workspace(c, &w));
     c->prob.icp_loaded = false;
     w->fgt.y.guess_K = 0;
-    const int n_pad = round_up_i(n, NN_SRC_PAD);
+    const int n_pad = round_up(n, NN_SRC_PAD);
     MI_TRY(c->bx.reserve(n_pad)); MI_TRY(c->by.reserve(n_pad)); MI_TRY(c->bz.reserve(n_pad));
     MI_TRY(upload_soa(c, cloud_xyz, n, n_pad, c->bx.p, c->by.p, c->bz.p, nullptr));
     FgtClusters cl{};

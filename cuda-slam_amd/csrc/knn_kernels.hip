@@ -5,7 +5,7 @@
 // does not depend on the order in which candidates are met, and the kernel only has to make sure that it skips nothing that belongs.
 //
 //   check   one pass per array: bounding box of the cloud and the lowest index of a point the call refuses (non-finite, |c| > 1e18),
-//           two-stage block reduction (the voxel range pass's shape); read back once, before anything is written
+//           the range pass of cloud_range.hpp under the predicate UsablePoint; read back once, before anything is written
 //   index   the cell grid of the 1-NN search, built by grid_build (nn_grid.h) into the call's own buffers: points sorted by cell, w =
 //           the caller's index, one offset per cell; a row of cells [x0, x1] is ONE contiguous run of pts
 //   search  one lane per query, queries along their curve order so that a wave's lanes visit the same cells.  The running list of
@@ -28,8 +28,7 @@
 // The shell loop ends at the grid's largest extent from c whatever the bound says: no lane can spin.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
+#include "cloud_range.hpp"
 #include "kernels.h"
 #include "nn_grid.h"
 #include "nn_walk.hpp"
@@ -38,79 +37,22 @@ namespace mislam {
 
 namespace {
 
-__device__ __forceinline__ bool usable3(float x, float y, float z)
-{
-    return fabsf(x) <= KNN_MAX_COORD && fabsf(y) <= KNN_MAX_COORD && fabsf(z) <= KNN_MAX_COORD;     // (false for NaN and the infinities)
-}
-
 __global__ __launch_bounds__(256) void knn_range_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
                                                         int n, float* __restrict__ lo_hi, int* __restrict__ bad)
 {
-    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    int first_bad = KNN_NO_POINT;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float p[3] = {x[i], y[i], z[i]};
-        if (!usable3(p[0], p[1], p[2])) { first_bad = min(first_bad, i); continue; }
-#pragma unroll
-        for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], p[k]); hi[k] = fmaxf(hi[k], p[k]); }
-    }
-    __shared__ float s[6][256];
-    __shared__ int sb[256];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { s[k][threadIdx.x] = lo[k]; s[3 + k][threadIdx.x] = hi[k]; }
-    sb[threadIdx.x] = first_bad;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                s[k][threadIdx.x] = fminf(s[k][threadIdx.x], s[k][threadIdx.x + w]);
-                s[3 + k][threadIdx.x] = fmaxf(s[3 + k][threadIdx.x], s[3 + k][threadIdx.x + w]);
-            }
-            sb[threadIdx.x] = min(sb[threadIdx.x], sb[threadIdx.x + w]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 6) lo_hi[blockIdx.x * 6 + threadIdx.x] = s[threadIdx.x][0];
-    if (threadIdx.x == 0) bad[blockIdx.x] = sb[0];
+    range_block(SoaPoints{x, y, z}, UsablePoint{}, n, lo_hi, bad);
 }
 
 // cloud partials [0, cloud_blocks), query partials [KNN_RANGE_BLOCKS, KNN_RANGE_BLOCKS + query_blocks) -> the state
 __global__ __launch_bounds__(256) void knn_range_finish_kernel(const float* __restrict__ lo_hi, const int* __restrict__ bad, int cloud_blocks,
                                                                int query_blocks, KnnState* __restrict__ st)
 {
-    __shared__ float s[6][256];
-    __shared__ int sb[2][256];
-    float v[6];
-    int bad_c = KNN_NO_POINT, bad_q = KNN_NO_POINT;
+    RangeAcc a;
+    if (!range_finish<2>(a, lo_hi, cloud_blocks, bad, bad + KNN_RANGE_BLOCKS, query_blocks)) return;
 #pragma unroll
-    for (int k = 0; k < 6; k++) v[k] = k < 3 ? __builtin_inff() : -__builtin_inff();
-    for (int b = threadIdx.x; b < cloud_blocks; b += 256) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) v[k] = k < 3 ? fminf(v[k], lo_hi[b * 6 + k]) : fmaxf(v[k], lo_hi[b * 6 + k]);
-        bad_c = min(bad_c, bad[b]);
-    }
-    for (int b = threadIdx.x; b < query_blocks; b += 256) bad_q = min(bad_q, bad[KNN_RANGE_BLOCKS + b]);
-#pragma unroll
-    for (int k = 0; k < 6; k++) s[k][threadIdx.x] = v[k];
-    sb[0][threadIdx.x] = bad_c; sb[1][threadIdx.x] = bad_q;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int k = 0; k < 6; k++)
-                s[k][threadIdx.x] = k < 3 ? fminf(s[k][threadIdx.x], s[k][threadIdx.x + w]) : fmaxf(s[k][threadIdx.x], s[k][threadIdx.x + w]);
-            sb[0][threadIdx.x] = min(sb[0][threadIdx.x], sb[0][threadIdx.x + w]);
-            sb[1][threadIdx.x] = min(sb[1][threadIdx.x], sb[1][threadIdx.x + w]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { st->lo[k] = s[k][0]; st->hi[k] = s[3 + k][0]; }
-    st->bad_cloud = sb[0][0];
-    st->bad_query = sb[1][0];
+    for (int k = 0; k < 3; k++) { st->lo[k] = a.v[k]; st->hi[k] = a.v[3 + k]; }
+    st->bad_cloud = a.bad[0];
+    st->bad_query = a.bad[1];
 }
 
 // (the build's expressions, nn_grid.hip: the SAME fp32 operations for the cloud's points and for the queries)
@@ -205,8 +147,8 @@ void knn_launch(const NnGridView& g, const KnnSearchArgs& a, int fma, hipStream_
 hipError_t knn_check_inputs(const float* cx, const float* cy, const float* cz, int m, const float* qx, const float* qy, const float* qz, int n,
                             float* lo_hi, int* bad, KnnState* st, hipStream_t s)
 {
-    const int cb = std::max(1, std::min(KNN_RANGE_BLOCKS, (m + 255) / 256));
-    const int qb = qx ? std::max(1, std::min(KNN_RANGE_BLOCKS, (n + 255) / 256)) : 0;
+    const int cb = range_blocks(m, KNN_RANGE_BLOCKS);
+    const int qb = qx ? range_blocks(n, KNN_RANGE_BLOCKS) : 0;
     hipLaunchKernelGGL(knn_range_kernel, dim3(cb), dim3(256), 0, s, cx, cy, cz, m, lo_hi, bad);
     if (qb > 0) hipLaunchKernelGGL(knn_range_kernel, dim3(qb), dim3(256), 0, s, qx, qy, qz, n, lo_hi + 6 * KNN_RANGE_BLOCKS, bad + KNN_RANGE_BLOCKS);
     hipLaunchKernelGGL(knn_range_finish_kernel, dim3(1), dim3(256), 0, s, lo_hi, bad, cb, qb, st);

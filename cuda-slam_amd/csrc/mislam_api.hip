@@ -14,6 +14,7 @@
 #include <mutex>
 #include <vector>
 
+#include "cloud_range.hpp"
 #include "context.h"
 
 using namespace mislam;
@@ -631,6 +632,57 @@ extern "C" int mi_selftest_sort_pairs(mi_ctx* c, unsigned int* keys, int* values
     MI_HIP(hipMemcpyAsync(keys, k1.p, sizeof(unsigned int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipMemcpyAsync(values, v1.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
+    return MI_OK;
+}
+
+// the range pass of cloud_range.hpp and nothing else: SoA loader, block cap 256, the result as six floats and one index
+template <class Pred>
+__global__ __launch_bounds__(256) void selftest_range_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+                                                             int n, float* __restrict__ lo_hi, int* __restrict__ bad)
+{
+    range_block(SoaPoints{x, y, z}, Pred{}, n, lo_hi, bad);
+}
+template <int NBAD>
+__global__ __launch_bounds__(256) void selftest_range_finish_kernel(const float* __restrict__ lo_hi, const int* __restrict__ bad, int nblocks,
+                                                                    float* __restrict__ out)
+{
+    RangeAcc a;
+    if (!range_finish<NBAD>(a, lo_hi, nblocks, bad)) return;
+#pragma unroll
+    for (int k = 0; k < 6; k++) out[k] = a.v[k];
+    out[6] = __int_as_float(a.bad[0]);       // (RANGE_NO_POINT where nothing can be refused)
+}
+
+extern "C" int mi_selftest_cloud_range(mi_ctx* c, const float* xyz, int n, int check, float out_lo_hi[6], int* out_first_bad)
+{
+    if (!c || !xyz || !out_lo_hi || !out_first_bad || n < 1 || check < 0 || check > 2) {
+        set_error("mi_selftest_cloud_range: bad argument");
+        return MI_ERR_INVALID_ARG;
+    }
+    MI_ENTER(c);
+    std::vector<float> soa((size_t)3 * n);
+    for (int i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) soa[(size_t)k * n + i] = xyz[3 * (size_t)i + k];
+    const int nb = range_blocks(n, 256);
+    DevBuf<float> pts, lo_hi, out;
+    DevBuf<int> bad;
+    MI_TRY(pts.reserve((size_t)3 * n)); MI_TRY(lo_hi.reserve((size_t)6 * 256)); MI_TRY(bad.reserve(256)); MI_TRY(out.reserve(7));
+    MI_HIP(hipMemcpyAsync(pts.p, soa.data(), sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    const float *x = pts.p, *y = pts.p + n, *z = pts.p + 2 * (size_t)n;
+    if (check == 0) {
+        hipLaunchKernelGGL(selftest_range_kernel<AnyPoint>, dim3(nb), dim3(256), 0, c->stream, x, y, z, n, lo_hi.p, bad.p);
+        hipLaunchKernelGGL(selftest_range_finish_kernel<0>, dim3(1), dim3(256), 0, c->stream, lo_hi.p, bad.p, nb, out.p);
+    } else {
+        if (check == 1) hipLaunchKernelGGL(selftest_range_kernel<FinitePoint>, dim3(nb), dim3(256), 0, c->stream, x, y, z, n, lo_hi.p, bad.p);
+        else hipLaunchKernelGGL(selftest_range_kernel<UsablePoint>, dim3(nb), dim3(256), 0, c->stream, x, y, z, n, lo_hi.p, bad.p);
+        hipLaunchKernelGGL(selftest_range_finish_kernel<1>, dim3(1), dim3(256), 0, c->stream, lo_hi.p, bad.p, nb, out.p);
+    }
+    MI_HIP(hipGetLastError());
+    float h[7];
+    MI_HIP(hipMemcpyAsync(h, out.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    memcpy(out_lo_hi, h, 6 * sizeof(float));
+    memcpy(out_first_bad, &h[6], sizeof(int));
     return MI_OK;
 }
 

@@ -17,6 +17,7 @@
 // in DESIGN.md.
 #include <hip/hip_runtime.h>
 
+#include "cloud_range.hpp"
 #include "kernels.h"
 #include "nn_tree.h"
 #include "nn_walk.hpp"
@@ -29,33 +30,15 @@ namespace mislam {
 __global__ __launch_bounds__(256) void tree_bbox_partial_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                 const float* __restrict__ z, int m, float* __restrict__ partials)
 {
-    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < m; j += gridDim.x * 256) {
-        const float p[3] = {x[j], y[j], z[j]};
-        for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], p[a]); hi[a] = fmaxf(hi[a], p[a]); }
-    }
-    __shared__ float s[6][256];
-    for (int a = 0; a < 3; a++) { s[a][threadIdx.x] = lo[a]; s[3 + a][threadIdx.x] = hi[a]; }
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w)
-            for (int a = 0; a < 3; a++) {
-                s[a][threadIdx.x] = fminf(s[a][threadIdx.x], s[a][threadIdx.x + w]);
-                s[3 + a][threadIdx.x] = fmaxf(s[3 + a][threadIdx.x], s[3 + a][threadIdx.x + w]);
-            }
-        __syncthreads();
-    }
-    if (threadIdx.x < 6) partials[blockIdx.x * 6 + threadIdx.x] = s[threadIdx.x][0];
+    range_block(SoaPoints{x, y, z}, AnyPoint{}, m, partials, nullptr);
 }
 
-__global__ void tree_bbox_final_kernel(const float* __restrict__ partials, int nblocks, float* __restrict__ bbox)
+__global__ __launch_bounds__(256) void tree_bbox_final_kernel(const float* __restrict__ partials, int nblocks, float* __restrict__ bbox)
 {
-    const int a = threadIdx.x;
-    if (a >= 6) return;
-    float v = partials[a];
-    for (int b = 1; b < nblocks; b++) v = a < 3 ? fminf(v, partials[b * 6 + a]) : fmaxf(v, partials[b * 6 + a]);
-    bbox[a] = v;
+    RangeAcc a;
+    if (!range_finish<0>(a, partials, nblocks)) return;
+#pragma unroll
+    for (int k = 0; k < 6; k++) bbox[k] = a.v[k];
 }
 
 __global__ __launch_bounds__(256) void tree_morton_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -73,10 +56,9 @@ size_t tree_sort_temp_bytes(int m) { return radix_sort_temp_bytes(m); }
 
 hipError_t cloud_bbox(const float* x, const float* y, const float* z, int m, float* partials, float* bbox, hipStream_t s)
 {
-    const int blocks = (m + 255) / 256;
-    const int rb = blocks < 256 ? blocks : 256;
+    const int rb = range_blocks(m, 256);
     hipLaunchKernelGGL(tree_bbox_partial_kernel, dim3(rb), dim3(256), 0, s, x, y, z, m, partials);
-    hipLaunchKernelGGL(tree_bbox_final_kernel, dim3(1), dim3(64), 0, s, partials, rb, bbox);
+    hipLaunchKernelGGL(tree_bbox_final_kernel, dim3(1), dim3(256), 0, s, partials, rb, bbox);
     return hipGetLastError();
 }
 

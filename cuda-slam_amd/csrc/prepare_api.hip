@@ -18,30 +18,26 @@
 // costs ~3.3 ms per million points (8 cycles per term) and is what makes the normalisation bit-exact.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 
+#include "cloud_range.hpp"
 #include "context.h"
+#include "reduce.hpp"
 
 using namespace mislam;
 
-namespace {
-
-constexpr int PREP_BLOCKS = 1024;
-
+namespace mislam {
 struct PrepState {
     float centre[3];
     float scale;
     int degenerate;       // |largest span| < 1e-15: NormalizeCloud returns the cloud unchanged (common.cpp:89-90)
     float lo[3], hi[3];   // result of the last bounds pass
 };
+}  // namespace mislam
 
-__device__ __forceinline__ float seq_add64(float acc, float term)
-{
-#pragma unroll
-    for (int j = 0; j < 64; j++) acc = acc + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(term), j));
-    return acc;
-}
+namespace {
+
+constexpr int PREP_BLOCKS = 1024;
 
 // centre of mass of raw[sub[i]], i = 0 .. n-1, in that order: 3 waves, wave w sums component w (common.cpp:281-284)
 __global__ __launch_bounds__(192) void prep_centre_kernel(const float* __restrict__ raw, const int* __restrict__ sub, int n, PrepState* __restrict__ st)
@@ -57,68 +53,39 @@ __global__ __launch_bounds__(192) void prep_centre_kernel(const float* __restric
     if (lane == 0) st->centre[wave] = acc / (float)n;
 }
 
+// point i of a bounds pass: pts (through `idx` when given) minus the centre, or as it is
+template <bool SHIFT>
+struct PrepPoints {
+    const float* __restrict__ pts;
+    const int* __restrict__ idx;
+    float c[3];
+    __device__ __forceinline__ void operator()(int i, float (&p)[3]) const
+    {
+        const float* q = pts + 3 * (size_t)(idx ? idx[i] : i);
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = SHIFT ? q[k] - c[k] : q[k];
+    }
+};
+
 // per-block min / max of (p - shift) over n points of `pts` (through `idx` when given); shift = st->centre or nothing
 template <bool SHIFT>
 __global__ __launch_bounds__(256) void prep_bounds_kernel(const float* __restrict__ pts, const int* __restrict__ idx, int n,
                                                           const PrepState* __restrict__ st, float* __restrict__ partials)
 {
-    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    const float c[3] = {SHIFT ? st->centre[0] : 0.f, SHIFT ? st->centre[1] : 0.f, SHIFT ? st->centre[2] : 0.f};
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float* p = pts + 3 * (size_t)(idx ? idx[i] : i);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float v = SHIFT ? p[k] - c[k] : p[k];
-            lo[k] = fminf(lo[k], v);
-            hi[k] = fmaxf(hi[k], v);
-        }
-    }
-    __shared__ float s[6][256];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { s[k][threadIdx.x] = lo[k]; s[3 + k][threadIdx.x] = hi[k]; }
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                s[k][threadIdx.x] = fminf(s[k][threadIdx.x], s[k][threadIdx.x + w]);
-                s[3 + k][threadIdx.x] = fmaxf(s[3 + k][threadIdx.x], s[3 + k][threadIdx.x + w]);
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 6) partials[blockIdx.x * 6 + threadIdx.x] = s[threadIdx.x][0];
+    const PrepPoints<SHIFT> load{pts, idx, {SHIFT ? st->centre[0] : 0.f, SHIFT ? st->centre[1] : 0.f, SHIFT ? st->centre[2] : 0.f}};
+    range_block(load, AnyPoint{}, n, partials, nullptr);
 }
 
 // finish a bounds pass; what = 0: keep lo/hi; what = 1: also derive the normalisation scale (common.cpp:86-92)
 __global__ __launch_bounds__(256) void prep_bounds_finish_kernel(const float* __restrict__ partials, int nblocks, PrepState* __restrict__ st,
                                                                  int what, float size)
 {
-    __shared__ float s[6][256];
-    float v[6];
+    RangeAcc a;
+    if (!range_finish<0>(a, partials, nblocks)) return;
 #pragma unroll
-    for (int k = 0; k < 6; k++) v[k] = k < 3 ? __builtin_inff() : -__builtin_inff();
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) v[k] = k < 3 ? fminf(v[k], partials[b * 6 + k]) : fmaxf(v[k], partials[b * 6 + k]);
-    }
-#pragma unroll
-    for (int k = 0; k < 6; k++) s[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int k = 0; k < 6; k++)
-                s[k][threadIdx.x] = k < 3 ? fminf(s[k][threadIdx.x], s[k][threadIdx.x + w]) : fmaxf(s[k][threadIdx.x], s[k][threadIdx.x + w]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { st->lo[k] = s[k][0]; st->hi[k] = s[3 + k][0]; }
+    for (int k = 0; k < 3; k++) { st->lo[k] = a.v[k]; st->hi[k] = a.v[3 + k]; }
     if (what == 1) {
-        const float span = fmaxf(fmaxf(s[3][0] - s[0][0], s[4][0] - s[1][0]), s[5][0] - s[2][0]);   // CalculateCloudSpread, common.cpp:72-79
+        const float span = fmaxf(fmaxf(a.v[3] - a.v[0], a.v[4] - a.v[1]), a.v[5] - a.v[2]);   // CalculateCloudSpread, common.cpp:72-79
         st->degenerate = fabsf(span) < 1e-15f ? 1 : 0;
         st->scale = size / span;
     }
@@ -185,31 +152,9 @@ __global__ __launch_bounds__(256) void prep_move_kernel(float* __restrict__ pts,
     for (int k = 0; k < 3; k++) p[k] = (g.r[k] * x + g.r[3 + k] * y + g.r[6 + k] * z) + g.t[k];
 }
 
-struct Scratch {     // per-call device scratch, freed on every exit path
-    static constexpr int SLOTS = 12;      // mi_prepare_cloud takes 9
-    void* p[SLOTS] = {nullptr};
-    int used = 0;
-    ~Scratch() { for (int i = 0; i < used; i++) (void)hipFree(p[i]); }
-    template <typename T> int get(T** out, size_t count)
-    {
-        *out = nullptr;
-        if (used >= SLOTS) { set_error("mi_prepare_cloud: scratch slots exhausted"); return MI_ERR_STATE; }
-        MI_HIP(hipMalloc((void**)out, std::max<size_t>(count, 1) * sizeof(T)));
-        p[used++] = *out;
-        return MI_OK;
-    }
-};
-
-template <typename T> int upload(mi_ctx* c, Scratch& s, const T* host, size_t count, T** dev)
-{
-    MI_TRY(s.get(dev, count));
-    if (count) MI_HIP(hipMemcpyAsync(*dev, host, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    return MI_OK;
-}
-
 int bounds_pass(mi_ctx* c, const float* pts, const int* idx, int n, bool shift, PrepState* st, float* partials, int what, float size)
 {
-    const int nb = std::max(1, std::min(PREP_BLOCKS, (n + 255) / 256));
+    const int nb = range_blocks(n, PREP_BLOCKS);
     if (shift) hipLaunchKernelGGL(prep_bounds_kernel<true>, dim3(nb), dim3(256), 0, c->stream, pts, idx, n, st, partials);
     else hipLaunchKernelGGL(prep_bounds_kernel<false>, dim3(nb), dim3(256), 0, c->stream, pts, idx, n, st, partials);
     hipLaunchKernelGGL(prep_bounds_finish_kernel, dim3(1), dim3(256), 0, c->stream, partials, nb, st, what, size);
@@ -256,17 +201,23 @@ extern "C" int mi_prepare_cloud(mi_ctx* c, const float* raw_xyz, int n_raw, cons
         }
     MI_ENTER(c);
 
-    Scratch s;
-    float *d_raw, *d_out, *d_partials, *d_noise_unit = nullptr, *d_outlier_unit = nullptr;
-    int *d_sub = nullptr, *d_shuffle = nullptr, *d_rows = nullptr;
-    PrepState* d_st;
+    // the call's buffers live in the context (grow-only, like the voxel call's): reserved here, before anything is enqueued
+    mi_ctx::PrepareBuffers& b = c->prep;
     const int n_total = n + n_outliers;
-    MI_TRY(upload(c, s, raw_xyz, (size_t)3 * n_raw, &d_raw));
-    if (subcloud_idx) MI_TRY(upload(c, s, subcloud_idx, (size_t)n, &d_sub));
-    if (shuffle_idx) MI_TRY(upload(c, s, shuffle_idx, (size_t)n, &d_shuffle));
-    MI_TRY(s.get(&d_out, (size_t)3 * n_total));
-    MI_TRY(s.get(&d_partials, (size_t)6 * PREP_BLOCKS));
-    MI_TRY(s.get(&d_st, 1));
+    MI_TRY(b.raw.reserve((size_t)3 * n_raw));
+    MI_TRY(b.out.reserve((size_t)3 * n_total));
+    MI_TRY(b.partials.reserve((size_t)6 * PREP_BLOCKS));
+    MI_TRY(b.state.reserve(1));
+    if (subcloud_idx) MI_TRY(b.sub.reserve((size_t)n));
+    if (shuffle_idx) MI_TRY(b.shuffle.reserve((size_t)n));
+    if (n_noise > 0) { MI_TRY(b.rows.reserve((size_t)n_noise)); MI_TRY(b.noise_unit.reserve((size_t)3 * n_noise)); }
+    if (n_outliers > 0) MI_TRY(b.outlier_unit.reserve((size_t)3 * n_outliers));
+    float *d_raw = b.raw.p, *d_out = b.out.p, *d_partials = b.partials.p;
+    const int *d_sub = subcloud_idx ? b.sub.p : nullptr, *d_shuffle = shuffle_idx ? b.shuffle.p : nullptr;
+    PrepState* d_st = b.state.p;
+    MI_HIP(hipMemcpyAsync(b.raw.p, raw_xyz, sizeof(float) * 3 * (size_t)n_raw, hipMemcpyHostToDevice, c->stream));
+    if (subcloud_idx) MI_HIP(hipMemcpyAsync(b.sub.p, subcloud_idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if (shuffle_idx) MI_HIP(hipMemcpyAsync(b.shuffle.p, shuffle_idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     MI_HIP(hipMemsetAsync(d_st, 0, sizeof(PrepState), c->stream));
 
     if (params->has_spread) {
@@ -277,17 +228,17 @@ extern "C" int mi_prepare_cloud(mi_ctx* c, const float* raw_xyz, int n_raw, cons
     hipLaunchKernelGGL(prep_place_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_raw, d_sub, d_shuffle, n, d_st, params->has_spread, d_out);
     MI_HIP(hipGetLastError());
     if (n_noise > 0) {
-        MI_TRY(upload(c, s, noise_rows, (size_t)n_noise, &d_rows));
-        MI_TRY(upload(c, s, noise_unit, (size_t)3 * n_noise, &d_noise_unit));
+        MI_HIP(hipMemcpyAsync(b.rows.p, noise_rows, sizeof(int) * (size_t)n_noise, hipMemcpyHostToDevice, c->stream));
+        MI_HIP(hipMemcpyAsync(b.noise_unit.p, noise_unit, sizeof(float) * 3 * (size_t)n_noise, hipMemcpyHostToDevice, c->stream));
         MI_TRY(bounds_pass(c, d_out, nullptr, n, false, d_st, d_partials, 0, 0.f));
-        hipLaunchKernelGGL(prep_noise_kernel, dim3((n_noise + 255) / 256), dim3(256), 0, c->stream, d_out, d_rows, d_noise_unit, n_noise, d_st,
+        hipLaunchKernelGGL(prep_noise_kernel, dim3((n_noise + 255) / 256), dim3(256), 0, c->stream, d_out, b.rows.p, b.noise_unit.p, n_noise, d_st,
                            params->noise_intensity);
         MI_HIP(hipGetLastError());
     }
     if (n_outliers > 0) {
-        MI_TRY(upload(c, s, outlier_unit, (size_t)3 * n_outliers, &d_outlier_unit));
+        MI_HIP(hipMemcpyAsync(b.outlier_unit.p, outlier_unit, sizeof(float) * 3 * (size_t)n_outliers, hipMemcpyHostToDevice, c->stream));
         MI_TRY(bounds_pass(c, d_out, nullptr, n, false, d_st, d_partials, 0, 0.f));
-        hipLaunchKernelGGL(prep_outliers_kernel, dim3((n_outliers + 255) / 256), dim3(256), 0, c->stream, d_out, n, d_outlier_unit, n_outliers, d_st);
+        hipLaunchKernelGGL(prep_outliers_kernel, dim3((n_outliers + 255) / 256), dim3(256), 0, c->stream, d_out, n, b.outlier_unit.p, n_outliers, d_st);
         MI_HIP(hipGetLastError());
     }
     if (params->has_transform) {

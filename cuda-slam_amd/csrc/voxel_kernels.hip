@@ -1,8 +1,9 @@
 // Voxel-grid centroids of a cloud: one output point per occupied voxel, the fp64 mean of the voxel's points (mi_voxel_downsample).
 //
-//   range   per-axis minimum and maximum of the coordinates and the lowest index of a non-finite point: two-stage block reduction
-//           (reduce.hpp's shape).  The voxel of a coordinate, floorf((p - o) / v), is monotone in p, so the voxels of the minimum and the
-//           maximum ARE the occupied range -- the same pass serves a given origin and the origin it finds itself (the minimum).
+//   range   per-axis minimum and maximum of the coordinates and the lowest index of a non-finite point: the range pass of
+//           cloud_range.hpp under the predicate FinitePoint.  The voxel of a coordinate, floorf((p - o) / v), is monotone in p, so the
+//           voxels of the minimum and the maximum ARE the occupied range -- the same pass serves a given origin and the origin it finds
+//           itself (the minimum).
 //   keys    voxel coordinate minus the axis minimum, per point: packed cx | cy << 10 | cz << 20 when every extent fits ten bits, else
 //           one key array per axis (the driver sorts by x, y, z in turn: radix_sort.hip is stable)
 //   rows    head flag of a sorted position = its voxel differs from its predecessor's; exclusive scan of the flags, block scan + carry
@@ -14,8 +15,7 @@
 // Every sum has a fixed order (a function of the sorted order alone) and there is no floating-point atomic: same input, same bits.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
+#include "cloud_range.hpp"
 #include "kernels.h"
 #include "reduce.hpp"
 
@@ -23,84 +23,29 @@ namespace mislam {
 
 namespace {
 
-__device__ __forceinline__ bool finite3(float x, float y, float z)
-{
-    return fabsf(x) < __builtin_inff() && fabsf(y) < __builtin_inff() && fabsf(z) < __builtin_inff();     // (false for NaN)
-}
-
 __global__ __launch_bounds__(256) void vox_range_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
                                                         int n, float* __restrict__ lo_hi, int* __restrict__ bad)
 {
-    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    int first_bad = VOX_NO_POINT;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float p[3] = {x[i], y[i], z[i]};
-        if (!finite3(p[0], p[1], p[2])) { first_bad = min(first_bad, i); continue; }
-#pragma unroll
-        for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], p[k]); hi[k] = fmaxf(hi[k], p[k]); }
-    }
-    __shared__ float s[6][256];
-    __shared__ int sb[256];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { s[k][threadIdx.x] = lo[k]; s[3 + k][threadIdx.x] = hi[k]; }
-    sb[threadIdx.x] = first_bad;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                s[k][threadIdx.x] = fminf(s[k][threadIdx.x], s[k][threadIdx.x + w]);
-                s[3 + k][threadIdx.x] = fmaxf(s[3 + k][threadIdx.x], s[3 + k][threadIdx.x + w]);
-            }
-            sb[threadIdx.x] = min(sb[threadIdx.x], sb[threadIdx.x + w]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 6) lo_hi[blockIdx.x * 6 + threadIdx.x] = s[threadIdx.x][0];
-    if (threadIdx.x == 0) bad[blockIdx.x] = sb[0];
+    range_block(SoaPoints{x, y, z}, FinitePoint{}, n, lo_hi, bad);
 }
 
 __global__ __launch_bounds__(256) void vox_range_finish_kernel(const float* __restrict__ lo_hi, const int* __restrict__ bad, int nblocks,
                                                                int has_origin, float ox, float oy, float oz, float voxel, VoxState* __restrict__ st)
 {
-    __shared__ float s[6][256];
-    __shared__ int sb[256];
-    float v[6];
-    int first_bad = VOX_NO_POINT;
-#pragma unroll
-    for (int k = 0; k < 6; k++) v[k] = k < 3 ? __builtin_inff() : -__builtin_inff();
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) v[k] = k < 3 ? fminf(v[k], lo_hi[b * 6 + k]) : fmaxf(v[k], lo_hi[b * 6 + k]);
-        first_bad = min(first_bad, bad[b]);
-    }
-#pragma unroll
-    for (int k = 0; k < 6; k++) s[k][threadIdx.x] = v[k];
-    sb[threadIdx.x] = first_bad;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int k = 0; k < 6; k++)
-                s[k][threadIdx.x] = k < 3 ? fminf(s[k][threadIdx.x], s[k][threadIdx.x + w]) : fmaxf(s[k][threadIdx.x], s[k][threadIdx.x + w]);
-            sb[threadIdx.x] = min(sb[threadIdx.x], sb[threadIdx.x + w]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
+    RangeAcc a;
+    if (!range_finish<1>(a, lo_hi, nblocks, bad)) return;
     int range_bad = 0;
     const float given[3] = {ox, oy, oz};
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        const float o = has_origin ? given[k] : s[k][0];
-        st->lo[k] = s[k][0]; st->hi[k] = s[3 + k][0]; st->origin[k] = o;
+        const float o = has_origin ? given[k] : a.v[k];
+        st->lo[k] = a.v[k]; st->hi[k] = a.v[3 + k]; st->origin[k] = o;
         int c0 = 0, c1 = 0;
-        if (!voxel_axis(s[k][0], o, voxel, &c0)) range_bad |= 1 << k;
-        if (!voxel_axis(s[3 + k][0], o, voxel, &c1)) range_bad |= 8 << k;
+        if (!voxel_axis(a.v[k], o, voxel, &c0)) range_bad |= 1 << k;
+        if (!voxel_axis(a.v[3 + k], o, voxel, &c1)) range_bad |= 8 << k;
         st->imin[k] = c0; st->imax[k] = c1;
     }
-    st->bad_index = sb[0];
+    st->bad_index = a.bad[0];
     st->range_bad = range_bad;
     st->rows = 0;
 }
@@ -330,7 +275,7 @@ __global__ __launch_bounds__(256) void vox_fixup_kernel(VoxArgs a, int tiles)
 
 hipError_t vox_range(const VoxArgs& a, const float* origin3, hipStream_t s)
 {
-    const int nb = std::max(1, std::min(VOX_RANGE_BLOCKS, (a.n + 255) / 256));
+    const int nb = range_blocks(a.n, VOX_RANGE_BLOCKS);
     hipLaunchKernelGGL(vox_range_kernel, dim3(nb), dim3(256), 0, s, a.x, a.y, a.z, a.n, a.range_lo_hi, a.range_bad);
     hipLaunchKernelGGL(vox_range_finish_kernel, dim3(1), dim3(256), 0, s, a.range_lo_hi, a.range_bad, nb, origin3 ? 1 : 0,
                        origin3 ? origin3[0] : 0.f, origin3 ? origin3[1] : 0.f, origin3 ? origin3[2] : 0.f, a.voxel, a.state);

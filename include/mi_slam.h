@@ -662,6 +662,11 @@ int mi_profile_search_phases(mi_ctx* ctx, unsigned long long out[20]);
 /* Self-test of the library's own device radix sort (the Hilbert ordering of the index build): sorts the n (key, value) pairs in
  * place, stable, ascending by the low `bits` (10, 20 or 30) of the keys.  Host arrays; test use only. */
 int mi_selftest_sort_pairs(mi_ctx* ctx, unsigned int* keys, int* values, int n, int bits);
+/* Self-test of the range pass every cloud-taking call opens with (csrc/cloud_range.hpp): per-axis minimum and maximum over the usable points of
+ * the n points of xyz (host, AoS) into out_lo_hi (lo xyz, hi xyz; +inf / -inf where no point is usable) and the lowest index of a refused point, or
+ * 0x7fffffff, into out_first_bad.  check = 0 refuses nothing (NaN coordinates are ignored), 1 refuses points with a non-finite coordinate (the voxel
+ * call's rule), 2 those and coordinates above 1e18 in magnitude (the k-NN call's).  Test use only. */
+int mi_selftest_cloud_range(mi_ctx* ctx, const float* xyz, int n, int check, float out_lo_hi[6], int* out_first_bad);
 /* Fault injection for the library's own tests: the next n index builds of this context fail with MI_ERR_INVALID_ARG behind the fixed cloud's upload (the
  * early-return path of mi_icp_load).  Only ever by this explicit call -- round 5 read it from the environment, where a stray variable could have failed
  * loads in production.  n = 0 disarms. */
