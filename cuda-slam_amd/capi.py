@@ -39,7 +39,7 @@ EXPORTS = [
     "mi_transform_mse", "mi_cpd_params_default", "mi_cpd_register", "mi_cpd_batch_route", "mi_cpd_register_batch", "mi_cpd_sigma_squared", "mi_cpd_sigma_squared_mode", "mi_cpd_estep",
     "mi_cpd_estep_truncated", "mi_cpd_estep_fgt", "mi_fgt_kcenter", "mi_fgt_kcenter_guided", "mi_fgt_tables", "mi_nicp_params_default", "mi_nicp_register",
     "mi_prepare_params_default", "mi_prepare_cloud", "mi_voxel_index", "mi_voxel_downsample", "mi_voxel_downsample_times",
-    "mi_knn_search", "mi_knn_search_times",
+    "mi_knn_search", "mi_knn_search_times", "mi_estimate_normals", "mi_estimate_normals_times",
     "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_nn_kernel_name",
 ]
 
@@ -269,6 +269,14 @@ def knn_search_raw(handle, query, n, cloud, m, k, dist_mode, max_d2, idx, d2, co
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     f.restype = C.c_int
     return f(handle, query, n, cloud, m, k, dist_mode, max_d2, idx, d2, count)
+
+
+def estimate_normals_raw(handle, cloud, n, k, dist_mode, max_d2, viewpoint, normals, curvature, count):
+    """mi_estimate_normals with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_estimate_normals
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    return f(handle, cloud, n, k, dist_mode, max_d2, viewpoint, normals, curvature, count)
 
 
 def icp_auto_batch(n_moving_total, m_fixed_total, world, source_sharded, every_pair_search):
@@ -694,6 +702,28 @@ class Context:
         out = (C.c_double * 8)()
         _check(lib().mi_knn_search_times(self._h, out))
         return dict(zip(("workspace", "upload", "check", "grid", "order", "search", "download", "total"), list(out)))
+
+    # ---- surface normals
+    def estimate_normals(self, cloud, k, viewpoint=None, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_curvature=False, want_count=False):
+        """Surface normals from every point's k nearest neighbours (mi_estimate_normals): normals [n, 3] float32, unit length, or (0, 0, 0)
+        where a point has fewer than two neighbours; then curvature [n] and count [n] if asked for.  viewpoint: normals are turned
+        towards it; None leaves the sign to the solve (deterministic)."""
+        cloud = _cloud(cloud)
+        n = cloud.shape[0]
+        view = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float32).reshape(3)
+        normals = np.empty((n, 3), np.float32)
+        curvature = np.empty(n, np.float32) if want_curvature else None
+        count = np.empty(n, np.int32) if want_count else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _check(estimate_normals_raw(self._h, cloud.ctypes.data, n, int(k), int(dist_mode), float(max_d2), ptr(view), normals.ctypes.data, ptr(curvature), ptr(count)))
+        res = [normals] + ([curvature] if want_curvature else []) + ([count] if want_count else [])
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def estimate_normals_times(self):
+        """ms per stage of the last estimate_normals: workspace, upload, check, grid, order, fused, download, total (mi_estimate_normals_times)."""
+        out = (C.c_double * 8)()
+        _check(lib().mi_estimate_normals_times(self._h, out))
+        return dict(zip(("workspace", "upload", "check", "grid", "order", "fused", "download", "total"), list(out)))
 
     # ---- profiling
     def profile_enable(self, on=True):

@@ -203,6 +203,18 @@ struct mi_ctx {
         double ms[MI_KNN_STAGES] = {0};
     } knn;
 
+    // ---- mi_estimate_normals: buffers of its own again, so that neither call leaves anything in the other's (a loaded ICP problem survives the call)
+    struct NormalsBuffers {
+        mislam::DevBuf<float> staging, cx, cy, cz, qx, qy, qz;   // the cloud SoA in the caller's order (c) and along its curve (q)
+        mislam::DevBuf<float> range_lo_hi, out_normals, out_curvature;
+        mislam::DevBuf<int> range_bad, order, out_count;
+        mislam::MortonScratch morton;                    // the cloud's curve order
+        mislam::GridBuffers cells;                       // the cell grid over the cloud
+        mislam::DevBuf<mislam::KnnState> state;
+        hipEvent_t ev[2] = {nullptr, nullptr};           // around the fused launch while profiling (mi_estimate_normals_times); destroyed by mi_ctx_destroy
+        double ms[MI_NORMALS_STAGES] = {0};
+    } normals;
+
     // ---- mi_prepare_cloud: buffers of its own, like the voxel call's: the raw cloud, the prepared one, the caller's index vectors and draws
     struct PrepareBuffers {
         mislam::DevBuf<float> raw, out, partials, noise_unit, outlier_unit;
@@ -276,7 +288,7 @@ struct ProfScope {
     ~ProfScope() { if (on) (void)c->prof.end(c->stream); }
 };
 
-// Host wall time per stage of a call, into the eight slots of ms (mi_icp_load_times, mi_voxel_downsample_times, mi_knn_search_times): mark(stage) books
+// Host wall time per stage of a call, into the eight slots of ms (mi_icp_load_times, mi_voxel_downsample_times, mi_knn_search_times, mi_estimate_normals_times): mark(stage) books
 // the time since the last mark to `stage` and the device allocations in it to slot 0; with profiling on, the stream is drained at every mark.
 struct StageClock {
     mi_ctx* c;
@@ -297,7 +309,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 
 // developer switch MISLAM_DEV_STALL_MS=<ms>: report any host-side section that takes longer, with the calling thread's context switches
 // over it -- an INVOLUNTARY one with no voluntary ones means the thread was taken off its core (a CPU quota of the container

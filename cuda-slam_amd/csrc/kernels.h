@@ -257,6 +257,26 @@ hipError_t knn_check_inputs(const float* cx, const float* cy, const float* cz, i
                             float* lo_hi, int* bad, KnnState* st, hipStream_t s);
 hipError_t knn_search(const NnGridView& g, const KnnSearchArgs& a, int fma, hipStream_t s);
 int knn_list_size(int k);            // registers' worth of list the search of this k is instantiated with: 8, 16 or 32
+float knn_default_points_per_cell(int k);    // cell size of the k-NN grid unless MISLAM_KNN_POINTS_PER_CELL says otherwise (knn_api.hip)
+
+// ---------------------------------------------------------------------------------------------------------------
+// K14 surface normals and curvature (normals_kernels.hip; driver: normals_api.hip): K13's search in self mode and, with the keys
+// still in registers, the neighbourhood's fp64 covariance and its smallest eigenvector (eig3.hpp)
+// ---------------------------------------------------------------------------------------------------------------
+struct KnnNormalsArgs {
+    const float *qx, *qy, *qz;       // the cloud along its curve order, SoA, n entries
+    const int* order;                // sorted slot -> the caller's index (the row the slot's answer goes to, and the candidate it skips)
+    const float *cx, *cy, *cz;       // the cloud in the caller's order, SoA: what the neighbours' indices point into
+    int n, k;
+    float max_d2;                    // candidates with d2 > this do not exist (+inf: no limit)
+    float hi[3];                     // upper corner of the cloud's bounding box (the lower one is the grid's origin)
+    int oriented;                    // view holds a viewpoint: normals are turned towards it
+    double view[3];
+    float* normals;                  // n * 3, AoS, the caller's order
+    float* curvature;                // n, may be null
+    int* count;                      // n, may be null
+};
+hipError_t knn_normals(const NnGridView& g, const KnnNormalsArgs& a, int fma, hipStream_t s);
 
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
@@ -271,5 +291,6 @@ hipError_t preload_nicp_api();
 hipError_t preload_prepare_api();
 hipError_t preload_voxel_kernels();
 hipError_t preload_knn_kernels();
+hipError_t preload_normals_kernels();
 
 }  // namespace mislam

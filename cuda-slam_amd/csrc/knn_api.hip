@@ -12,14 +12,10 @@ using namespace mislam;
 
 static_assert(KNN_MAX_K == MI_KNN_MAX_K, "the kernels' list sizes cover MI_KNN_MAX_K");
 
-namespace {
-
-// Points per cell of the grid for a search of k neighbours, unless MISLAM_KNN_POINTS_PER_CELL says otherwise.  A lane stops behind
-// shell r once r cells are longer than its k-th distance, so the cell size trades candidates tested (27 cells of k / 2 points) against
+// Points per cell of the grid for a search of k neighbours, unless MISLAM_KNN_POINTS_PER_CELL says otherwise (mi_estimate_normals uses the same rule).
+// A lane stops behind shell r once r cells are longer than its k-th distance, so the cell size trades candidates tested (27 cells of k / 2 points) against
 // shells walked.  An estimate: the sweep of tools/knn_bench.py --sweep has not been run yet.
-float knn_default_points_per_cell(int k) { return std::max(1.0f, 0.5f * (float)k); }
-
-}  // namespace
+float mislam::knn_default_points_per_cell(int k) { return std::max(1.0f, 0.5f * (float)k); }
 
 extern "C" int mi_knn_search(mi_ctx* c, const float* query_xyz, int n, const float* cloud_xyz, int m, int k, int dist_mode,
                              float max_distance_squared, int* idx, float* d2, int* count)

@@ -8,7 +8,8 @@
 //           the range pass of cloud_range.hpp under the predicate UsablePoint; read back once, before anything is written
 //   index   the cell grid of the 1-NN search, built by grid_build (nn_grid.h) into the call's own buffers: points sorted by cell, w =
 //           the caller's index, one offset per cell; a row of cells [x0, x1] is ONE contiguous run of pts
-//   search  one lane per query, queries along their curve order so that a wave's lanes visit the same cells.  The running list of
+//   search  (its body: knn_scan.hpp, shared with K14's normals_kernels.hip)  one lane per query, queries along their curve order so that a
+//           wave's lanes visit the same cells.  The running list of
 //           K = 8 / 16 / 32 keys lives in REGISTERS, sorted; a candidate is offered only when its key is below the list's last one, and
 //           goes in through a fully unrolled chain of K selects (every index static: no scratch).  k < K: the K - k lowest slots hold
 //           key 0, which no offer moves (an offer is never below 0), so slots [K - k, K) are the k-list and its last slot the threshold.
@@ -30,8 +31,8 @@
 
 #include "cloud_range.hpp"
 #include "kernels.h"
+#include "knn_scan.hpp"
 #include "nn_grid.h"
-#include "nn_walk.hpp"
 
 namespace mislam {
 
@@ -55,19 +56,6 @@ __global__ __launch_bounds__(256) void knn_range_finish_kernel(const float* __re
     st->bad_query = a.bad[1];
 }
 
-// (the build's expressions, nn_grid.hip: the SAME fp32 operations for the cloud's points and for the queries)
-__device__ __forceinline__ float knn_cell_u(float p, float o, float inv_h) { return (p - o) * inv_h; }
-__device__ __forceinline__ int knn_cell_index(float u, int n) { return (int)fminf(fmaxf(floorf(u), 0.f), (float)(n - 1)); }
-
-// the sorted list with `key` put in its place and the last entry dropped; the caller has checked key < l[K - 1]
-template <int K>
-__device__ __forceinline__ void knn_insert(unsigned long long (&l)[K], unsigned long long key)
-{
-#pragma unroll
-    for (int i = K - 1; i >= 1; i--) l[i] = key < l[i - 1] ? l[i - 1] : (key < l[i] ? key : l[i]);
-    l[0] = key < l[0] ? key : l[0];
-}
-
 template <int K, bool FMA>
 __global__ __launch_bounds__(KNN_BLOCK) void knn_search_kernel(NnGridView g, KnnSearchArgs a)
 {
@@ -81,44 +69,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_search_kernel(NnGridView g, Knn
     unsigned long long l[K];
 #pragma unroll
     for (int i = 0; i < K; i++) l[i] = i < K - k ? 0ull : KNN_KEY_EMPTY;
-
-    const int c[3] = {knn_cell_index(knn_cell_u(q[0], g.ox, g.inv_h), g.nx), knn_cell_index(knn_cell_u(q[1], g.oy, g.inv_h), g.ny),
-                      knn_cell_index(knn_cell_u(q[2], g.oz, g.inv_h), g.nz)};
-    // how far outside the cloud's box the query is, per axis, rounded like a distance's difference (box_bound, nn_walk.hpp)
-    const float e[3] = {fmaxf(fmaxf(g.ox - q[0], q[0] - a.hi[0]), 0.f), fmaxf(fmaxf(g.oy - q[1], q[1] - a.hi[1]), 0.f),
-                        fmaxf(fmaxf(g.oz - q[2], q[2] - a.hi[2]), 0.f)};
-    const int r_end = max(max(max(c[0], g.nx - 1 - c[0]), max(c[1], g.ny - 1 - c[1])), max(c[2], g.nz - 1 - c[2]));   // the last shell that holds a cell
-
-    for (int r = 0; r <= r_end; r++) {
-        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.nz - 1), y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.ny - 1);
-        const int xa = c[0] - r, xb = c[0] + r, x0 = max(xa, 0), x1 = min(xb, g.nx - 1);
-        for (int iz = z0; iz <= z1; iz++) {
-            const bool z_face = iz == c[2] - r || iz == c[2] + r;
-            for (int iy = y0; iy <= y1; iy++) {
-                const unsigned int row = ((unsigned int)iz * (unsigned int)g.ny + (unsigned int)iy) * (unsigned int)g.nx;
-                const bool whole = z_face || iy == c[1] - r || iy == c[1] + r;       // (r = 0: the cell itself)
-                // the whole x-run of the row, or its two end cells where they exist
-                for (int seg = 0; seg < (whole ? 1 : 2); seg++) {
-                    const int sa = whole ? x0 : (seg == 0 ? xa : xb), sb = whole ? x1 : sa;
-                    if (sa < 0 || sb > g.nx - 1) continue;
-                    const unsigned int b = g.cell_start[row + (unsigned int)sa], end = g.cell_start[row + (unsigned int)sb + 1u];
-                    for (unsigned int j = b; j < end; j++) {
-                        const float4 p = g.pts[j];
-                        const float d2 = sq3<FMA>(p.x - q[0], p.y - q[1], p.z - q[2]);
-                        const unsigned int pj = __float_as_uint(p.w);
-                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | pj;
-                        if (key < l[K - 1] && pj != skip && d2 <= a.max_d2) knn_insert<K>(l, key);
-                    }
-                }
-            }
-        }
-        // everything not yet scanned is at least this far (see the head of the file)
-        const float lb = fmaxf((float)r - 1e-3f, 0.f) * g.h_lo;
-        const float gx = (e[0] + lb) * 0.999999f, gy = (e[1] + lb) * 0.999999f, gz = (e[2] + lb) * 0.999999f;
-        const float bound = fminf(fminf(sq3<FMA>(gx, e[1], e[2]), sq3<FMA>(e[0], gy, e[2])), sq3<FMA>(e[0], e[1], gz));
-        const float kth = __uint_as_float((unsigned int)(l[K - 1] >> 32));              // (+inf while the list is not full)
-        if (bound > kth || bound > a.max_d2) break;
-    }
+    knn_scan<K, FMA>(g, q, a.hi, skip, k, a.max_d2, l);      // (knn_scan.hpp: the list and the shell walk, shared with K14)
 
     int found = 0;
 #pragma unroll

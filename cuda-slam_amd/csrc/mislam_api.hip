@@ -179,7 +179,7 @@ extern "C" int mi_ctx_preload(mi_ctx* c)
     if (!c) { set_error("mi_ctx_preload: null context"); return MI_ERR_INVALID_ARG; }
     MI_ENTER(c);
     MI_HIP(preload_nn_kernel()); MI_HIP(preload_nn_tree()); MI_HIP(preload_nn_grid()); MI_HIP(preload_icp_kernels()); MI_HIP(preload_icp_batch()); MI_HIP(preload_cpd_kernels()); MI_HIP(preload_cpd_batch());
-    MI_HIP(preload_cpd_fgt()); MI_HIP(preload_nicp_api()); MI_HIP(preload_prepare_api()); MI_HIP(preload_voxel_kernels()); MI_HIP(preload_knn_kernels());
+    MI_HIP(preload_cpd_fgt()); MI_HIP(preload_nicp_api()); MI_HIP(preload_prepare_api()); MI_HIP(preload_voxel_kernels()); MI_HIP(preload_knn_kernels()); MI_HIP(preload_normals_kernels());
     return MI_OK;
 }
 
@@ -438,6 +438,7 @@ extern "C" void mi_ctx_destroy(mi_ctx* c)
     if (c->h_scratch) (void)hipHostFree(c->h_scratch);
     cpd_workspace_destroy(c);
     for (hipEvent_t e : c->knn.ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->normals.ev) if (e) (void)hipEventDestroy(e);
     for (auto& s : c->prof.spans) { (void)hipEventDestroy(s.e0); (void)hipEventDestroy(s.e1); }
     for (auto e : c->prof.event_pool) (void)hipEventDestroy(e);
     if (c->d_state) (void)hipFree(c->d_state);

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MI_SLAM_ABI_VERSION 4   /* 4: mi_profile_search_phases, mi_selftest_fail_loads, mi_runtime_info (additive: no signature of version 3 changed), later and additive again: mi_icp_register_batch, mi_cpd_register_batch, mi_voxel_index, mi_voxel_downsample, mi_voxel_downsample_times, mi_knn_search, mi_knn_search_times; 3: mi_icp_load_times, mi_cross_moments, mi_icp_auto_batch; 2: mi_cpd_params gained sigma2_mode; mi_dist_info, mi_source_share, mi_cpd_sigma_squared_mode, mi_profile_search_stats, mi_selftest_sort_pairs */
+#define MI_SLAM_ABI_VERSION 4   /* 4: mi_profile_search_phases, mi_selftest_fail_loads, mi_runtime_info (additive: no signature of version 3 changed), later and additive again: mi_icp_register_batch, mi_cpd_register_batch, mi_voxel_index, mi_voxel_downsample, mi_voxel_downsample_times, mi_knn_search, mi_knn_search_times, mi_estimate_normals, mi_estimate_normals_times; 3: mi_icp_load_times, mi_cross_moments, mi_icp_auto_batch; 2: mi_cpd_params gained sigma2_mode; mi_dist_info, mi_source_share, mi_cpd_sigma_squared_mode, mi_profile_search_stats, mi_selftest_sort_pairs */
 
 enum {
     MI_OK = 0,
@@ -610,6 +610,56 @@ int mi_knn_search(mi_ctx* ctx,
  * every stage, and out[5] is the search launch's own HIP-event time instead of host wall time). */
 #define MI_KNN_STAGES 8
 int mi_knn_search_times(mi_ctx* ctx, double out_ms[MI_KNN_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
+ * Surface normals and curvature (no reference counterpart: the reference has no normals anywhere): the first consumer of the k-NN
+ * lists, which here never leave the device (normals).  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+
+/* Normal, curvature and neighbour count of every point of a cloud, computed on the device.
+ *   Neighbourhood of point i: point i itself plus the neighbours that
+ *     mi_knn_search(ctx, NULL, n, cloud_xyz, n, k, dist_mode, max_distance_squared, ...) returns for row i -- the same set, bit for
+ *     bit: self mode skips by index, and a duplicate of point i stored elsewhere is a neighbour.  count[i] is that call's count[i].
+ *     A finite max_distance_squared makes it the "hybrid" k-and-radius neighbourhood; INFINITY is no limit.
+ *   Covariance: that of the neighbourhood's count + 1 points about their mean, divided by the number of points, in fp64.  It is formed
+ *     in one pass from the differences d = p_j - p_i, taken in fp64 (exact, or rounded at 2^-53): with c = count + 1, m = sum d / c and
+ *     C = sum d d^T / c - m m^T; the point itself contributes d = 0.  Every magnitude is bounded by the neighbourhood's radius, not by
+ *     the cloud's offset from the origin, so the one pass agrees with the two-pass form to a few 2^-53 of the trace.
+ *   Normal: the unit eigenvector of C's smallest eigenvalue from an fp64 cyclic Jacobi iteration, normalised in fp64, rounded once to
+ *     fp32.  With viewpoint3 it is flipped so that n . (v - p_i) >= 0, the sign test done in fp64 on the unrounded vector.  Without
+ *     viewpoint3 the sign is unspecified but deterministic: the same input gives the same bits on every call, whatever ran on the
+ *     context before.
+ *   Curvature: lambda0 / (lambda0 + lambda1 + lambda2), lambda0 the smallest eigenvalue clamped below at 0; 0 when the trace is 0.
+ *   Too few points: with count[i] < 2 (fewer than three points) the normal is (0, 0, 0) and the curvature 0; count[i] tells the caller.
+ *   Degenerate neighbourhoods (collinear, all points identical): the normal is finite and of unit length, or exactly zero under the
+ *     rule above; nothing else is promised for them.
+ *   normals_xyz (n*3, AoS like the clouds) receives the normals; curvature (n, may be NULL) and count (n, may be NULL; the neighbours
+ *     used, the point itself not counted) what their names say.
+ *   MI_ERR_INVALID_ARG -- mi_last_error names the cause and, for a bad point, its index; NO output array has been written -- for a
+ *     NULL ctx, cloud_xyz or normals_xyz; n < 1; k outside [2, MI_KNN_MAX_K]; a dist_mode other than the two of mi_knn_search;
+ *     max_distance_squared NaN or negative; a non-finite viewpoint; a non-finite coordinate or one above 1e18 in magnitude.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything mi_knn_search keeps: it works in buffers of its own.
+ *   Synchronous, host in and host out. */
+int mi_estimate_normals(mi_ctx* ctx,
+                        const float* cloud_xyz, int n,
+                        int k, int dist_mode,            /* 2 <= k <= MI_KNN_MAX_K; MI_DIST_CPU_ROUNDING or MI_DIST_FMA */
+                        float max_distance_squared,      /* INFINITY: no limit; else neighbours with d2 > this do not exist */
+                        const float* viewpoint3,         /* may be NULL; else normals are turned towards this point */
+                        float* normals_xyz,              /* n*3 */
+                        float* curvature,                /* may be NULL; n */
+                        int* count);                     /* may be NULL; n: neighbours used for point i (<= k) */
+
+/* Where the last mi_estimate_normals of this context spent its host wall time, in ms (measurement hook, tools/normals_bench.py).  The
+ * stages are those of mi_knn_search_times:
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA
+ *   out[2] input check, bounding box, its read-back out[3] cell grid over the cloud
+ *   out[4] curve order of the cloud + permute       out[5] the fused search-and-solve kernel
+ *   out[6] download of the results                  out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage, and out[5] is the
+ * launch's own HIP-event time instead of host wall time). */
+#define MI_NORMALS_STAGES 8
+int mi_estimate_normals_times(mi_ctx* ctx, double out_ms[MI_NORMALS_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
