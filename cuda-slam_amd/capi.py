@@ -40,6 +40,7 @@ EXPORTS = [
     "mi_cpd_estep_truncated", "mi_cpd_estep_fgt", "mi_fgt_kcenter", "mi_fgt_kcenter_guided", "mi_fgt_tables", "mi_nicp_params_default", "mi_nicp_register",
     "mi_prepare_params_default", "mi_prepare_cloud", "mi_voxel_index", "mi_voxel_downsample", "mi_voxel_downsample_times",
     "mi_knn_search", "mi_knn_search_times", "mi_estimate_normals", "mi_estimate_normals_times",
+    "mi_outlier_params_default", "mi_remove_outliers", "mi_remove_outliers_times",
     "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_nn_kernel_name",
 ]
 
@@ -66,6 +67,15 @@ class NicpParams(C.Structure):
 class PrepareParams(C.Structure):
     _fields_ = [("has_spread", C.c_int), ("spread", C.c_float), ("noise_intensity", C.c_float), ("has_transform", C.c_int),
                 ("rotation", C.c_float * 9), ("translation", C.c_float * 3), ("reserved", C.c_int * 4)]
+
+
+class OutlierParams(C.Structure):
+    _fields_ = [("method", C.c_int), ("dist_mode", C.c_int), ("k", C.c_int), ("std_ratio", C.c_float), ("radius", C.c_float),
+                ("min_neighbours", C.c_int), ("reserved", C.c_int * 6)]
+
+
+class OutlierStats(C.Structure):
+    _fields_ = [("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double), ("kept", C.c_longlong), ("reserved", C.c_int * 4)]
 
 
 class MiSlamError(RuntimeError):
@@ -277,6 +287,29 @@ def estimate_normals_raw(handle, cloud, n, k, dist_mode, max_d2, viewpoint, norm
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     f.restype = C.c_int
     return f(handle, cloud, n, k, dist_mode, max_d2, viewpoint, normals, curvature, count)
+
+
+OUTLIER_STATISTICAL, OUTLIER_RADIUS = 0, 1     # MI_OUTLIER_*
+
+
+def outlier_params(**kw):
+    """mi_outlier_params at its defaults (statistical, k = 16, std_ratio = 2, CPU rounding) with the given fields set."""
+    p = OutlierParams()
+    lib().mi_outlier_params_default.restype = None
+    lib().mi_outlier_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def remove_outliers_raw(handle, cloud, n, params, out_xyz, out_index, out_n, keep, mean_distance, neighbours, stats):
+    """mi_remove_outliers with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_remove_outliers
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+    f.restype = C.c_int
+    return f(handle, cloud, n, params, out_xyz, out_index, out_n, keep, mean_distance, neighbours, stats)
 
 
 def icp_auto_batch(n_moving_total, m_fixed_total, world, source_sharded, every_pair_search):
@@ -724,6 +757,33 @@ class Context:
         out = (C.c_double * 8)()
         _check(lib().mi_estimate_normals_times(self._h, out))
         return dict(zip(("workspace", "upload", "check", "grid", "order", "fused", "download", "total"), list(out)))
+
+    # ---- outlier removal
+    def remove_outliers(self, cloud, params, want_keep=False, want_mean_distance=False, want_neighbours=False, want_stats=False):
+        """Statistical or radius outlier removal (mi_remove_outliers; params: outlier_params(...)): the kept points [kept, 3] with the
+        input's bits and their indices [kept] int32, ascending; then, as asked for and in this order: keep [n] uint8, mean_distance [n]
+        float32 (statistical only), neighbours [n] int32 and the OutlierStats (mean, stddev, threshold, kept)."""
+        cloud = _cloud(cloud)
+        n = cloud.shape[0]
+        if want_mean_distance and params.method != OUTLIER_STATISTICAL:
+            raise ValueError("mean_distance exists for the statistical method only")
+        out_xyz, out_index, out_n = np.empty((n, 3), np.float32), np.empty(n, np.int32), C.c_int(0)
+        keep = np.empty(n, np.uint8) if want_keep else None
+        mean_distance = np.empty(n, np.float32) if want_mean_distance else None
+        neighbours = np.empty(n, np.int32) if want_neighbours else None
+        stats = OutlierStats() if want_stats else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _check(remove_outliers_raw(self._h, cloud.ctypes.data, n, C.addressof(params), out_xyz.ctypes.data, out_index.ctypes.data, C.addressof(out_n),
+                                   ptr(keep), ptr(mean_distance), ptr(neighbours), None if stats is None else C.addressof(stats)))
+        res = [out_xyz[:out_n.value].copy(), out_index[:out_n.value].copy()]
+        res += [a for a in (keep, mean_distance, neighbours, stats) if a is not None]
+        return tuple(res)
+
+    def remove_outliers_times(self):
+        """ms per stage of the last remove_outliers: workspace, upload, check, grid, order, kernel, finish, total (mi_remove_outliers_times)."""
+        out = (C.c_double * 8)()
+        _check(lib().mi_remove_outliers_times(self._h, out))
+        return dict(zip(("workspace", "upload", "check", "grid", "order", "kernel", "finish", "total"), list(out)))
 
     # ---- profiling
     def profile_enable(self, on=True):

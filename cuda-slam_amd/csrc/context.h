@@ -99,6 +99,7 @@ struct mi_ctx {
         int fgt_shard_queries = 1;                       // MISLAM_FGT_SHARD_QUERIES=0: the FGT / hybrid CPD modes run replicated on a multi-rank context, no collective (rounds 4-5)
         int fgt_model_splits = 1;                        // MISLAM_FGT_MODEL_SPLITS=0: one workgroup per cell in the FGT model build whatever the cells' sizes (rounds 1-4)
         float knn_points_per_cell = 0.f;                 // MISLAM_KNN_POINTS_PER_CELL: cell size of mi_knn_search's grid (0: the measured default for the call's k, knn_api.hip)
+        float outlier_radius_cell = 1.f;                 // MISLAM_OUTLIER_RADIUS_CELL: cell edge of mi_remove_outliers' radius grid in radii (outlier_api.hip)
         int fgt_replay = 1;                              // MISLAM_FGT_REPLAY=0: sweep the moving cloud step by step every E-step (no guess replayed)
     } tune;
 
@@ -215,6 +216,21 @@ struct mi_ctx {
         double ms[MI_NORMALS_STAGES] = {0};
     } normals;
 
+    // ---- mi_remove_outliers: buffers of its own once more (a loaded ICP problem, the k-NN call's and the normals call's buffers survive the call)
+    struct OutlierBuffers {
+        mislam::DevBuf<float> staging, cx, cy, cz, qx, qy, qz;   // the cloud as uploaded (AoS: what the compaction gathers from), SoA in the caller's order (c) and along its curve (q)
+        mislam::DevBuf<float> range_lo_hi, out_xyz, out_mean;
+        mislam::DevBuf<int> range_bad, order, count, tile_counts, out_index;
+        mislam::DevBuf<double> score, partials;          // the unrounded scores; one partial sum per workgroup of a statistics pass
+        mislam::DevBuf<unsigned char> keep;              // the flags, the caller's order
+        mislam::MortonScratch morton;                    // the cloud's curve order
+        mislam::GridBuffers cells;                       // the cell grid over the cloud
+        mislam::DevBuf<mislam::KnnState> state;
+        mislam::DevBuf<mislam::OutlierState> ostate;
+        hipEvent_t ev[2] = {nullptr, nullptr};           // around the score / count launch while profiling (mi_remove_outliers_times); destroyed by mi_ctx_destroy
+        double ms[MI_OUTLIER_STAGES] = {0};
+    } outlier;
+
     // ---- mi_prepare_cloud: buffers of its own, like the voxel call's: the raw cloud, the prepared one, the caller's index vectors and draws
     struct PrepareBuffers {
         mislam::DevBuf<float> raw, out, partials, noise_unit, outlier_unit;
@@ -288,7 +304,7 @@ struct ProfScope {
     ~ProfScope() { if (on) (void)c->prof.end(c->stream); }
 };
 
-// Host wall time per stage of a call, into the eight slots of ms (mi_icp_load_times, mi_voxel_downsample_times, mi_knn_search_times, mi_estimate_normals_times): mark(stage) books
+// Host wall time per stage of a call, into the eight slots of ms (mi_icp_load_times, mi_voxel_downsample_times, mi_knn_search_times, mi_estimate_normals_times, mi_remove_outliers_times): mark(stage) books
 // the time since the last mark to `stage` and the device allocations in it to slot 0; with profiling on, the stream is drained at every mark.
 struct StageClock {
     mi_ctx* c;
@@ -309,7 +325,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 
 // developer switch MISLAM_DEV_STALL_MS=<ms>: report any host-side section that takes longer, with the calling thread's context switches
 // over it -- an INVOLUNTARY one with no voluntary ones means the thread was taken off its core (a CPU quota of the container

@@ -278,6 +278,61 @@ struct KnnNormalsArgs {
 };
 hipError_t knn_normals(const NnGridView& g, const KnnNormalsArgs& a, int fma, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K15 statistical and radius outlier removal (outlier_kernels.hip; driver: outlier_api.hip): K13's search in self mode with the
+// keys' fp64 mean root as the point's score, or a fixed-radius count over the same shells (radius_scan.hpp); fp64 mean / deviation
+// of the scores in a fixed order (reduce.hpp); flags in the caller's order and their stable compaction
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int OUTLIER_STAT_BLOCK = 256;      // scores per workgroup and trip of the two statistics passes (reduce.hpp's block)
+constexpr int OUTLIER_STAT_BLOCKS = 512;     // workgroups of a statistics pass at most (one partial sum each)
+constexpr int OUTLIER_SCAN_TILE = 1024;      // flags per workgroup of the compaction: 256 lanes x 4 consecutive flags
+
+// Device-resident facts of one call; the host reads it back once, with the results.
+struct OutlierState {
+    double mean, stddev, threshold;  // statistical: of the unrounded scores; the flags pass reads threshold from here
+    long long kept;                  // the last element of the flags' scan
+};
+
+struct KnnOutlierArgs {
+    const float *qx, *qy, *qz;       // the cloud along its curve order, SoA, n entries
+    const int* order;                // sorted slot -> the caller's index (the row the slot's answer goes to, and the candidate it skips)
+    int n, k;
+    float hi[3];                     // upper corner of the cloud's bounding box (the lower one is the grid's origin)
+    double* score;                   // n: (sum of sqrt((double)d2) over the filled slots, nearest first) / count, 0 where count is 0
+    int* count;                      // n, may be null
+};
+hipError_t knn_outlier_score(const NnGridView& g, const KnnOutlierArgs& a, int fma, hipStream_t s);
+
+struct RadiusCountArgs {
+    const float *qx, *qy, *qz;       // as above
+    const int* order;
+    int n;
+    float r2;                        // a point j != row (by index) with d2 <= r2 counts
+    int min_neighbours;              // early: a lane leaves its loops once it has counted this many
+    float hi[3];
+    int* count;                      // n: the number of neighbours, or (early) min(that, some value >= min_neighbours)
+};
+hipError_t radius_count(const NnGridView& g, const RadiusCountArgs& a, int fma, int early, hipStream_t s);
+
+int outlier_stat_blocks(int n);      // partial sums of a statistics pass over n scores (<= OUTLIER_STAT_BLOCKS)
+int outlier_scan_tiles(int n);       // tiles of the compaction of n flags
+// mean, stddev (population, two passes) and threshold = mean + (double)std_ratio * stddev of n scores -> state; partials: outlier_stat_blocks(n) doubles
+hipError_t outlier_statistics(const double* score, int n, float std_ratio, double* partials, OutlierState* state, hipStream_t s);
+// keep[i] = score[i] <= state->threshold; mean_distance[i] = (float)score[i] where asked
+hipError_t outlier_flags_statistical(const double* score, int n, const OutlierState* state, unsigned char* keep, float* mean_distance, hipStream_t s);
+// keep[i] = count[i] >= min_neighbours
+hipError_t outlier_flags_radius(const int* count, int n, int min_neighbours, unsigned char* keep, hipStream_t s);
+struct OutlierCompactArgs {
+    const unsigned char* keep;       // n flags, the caller's order
+    const float* xyz;                // n * 3, AoS, as uploaded
+    int n;
+    int* tile_counts;                // outlier_scan_tiles(n): ones per tile, then (scanned) ones before the tile
+    int* out_index;                  // n: indices of the ones, ascending (may be null)
+    float* out_xyz;                  // n * 3: their points (may be null)
+    OutlierState* state;             // kept
+};
+hipError_t outlier_compact(const OutlierCompactArgs& a, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -292,5 +347,6 @@ hipError_t preload_prepare_api();
 hipError_t preload_voxel_kernels();
 hipError_t preload_knn_kernels();
 hipError_t preload_normals_kernels();
+hipError_t preload_outlier_kernels();
 
 }  // namespace mislam

@@ -179,7 +179,7 @@ extern "C" int mi_ctx_preload(mi_ctx* c)
     if (!c) { set_error("mi_ctx_preload: null context"); return MI_ERR_INVALID_ARG; }
     MI_ENTER(c);
     MI_HIP(preload_nn_kernel()); MI_HIP(preload_nn_tree()); MI_HIP(preload_nn_grid()); MI_HIP(preload_icp_kernels()); MI_HIP(preload_icp_batch()); MI_HIP(preload_cpd_kernels()); MI_HIP(preload_cpd_batch());
-    MI_HIP(preload_cpd_fgt()); MI_HIP(preload_nicp_api()); MI_HIP(preload_prepare_api()); MI_HIP(preload_voxel_kernels()); MI_HIP(preload_knn_kernels()); MI_HIP(preload_normals_kernels());
+    MI_HIP(preload_cpd_fgt()); MI_HIP(preload_nicp_api()); MI_HIP(preload_prepare_api()); MI_HIP(preload_voxel_kernels()); MI_HIP(preload_knn_kernels()); MI_HIP(preload_normals_kernels()); MI_HIP(preload_outlier_kernels());
     return MI_OK;
 }
 
@@ -230,6 +230,7 @@ static int ctx_create_common(int device, mi_ctx** out)
         c->tune.svd_ieee = env_i("MISLAM_SVD_IEEE", 0);
         if (const char* ppc = getenv("MISLAM_GRID_PPC")) { const float f = (float)atof(ppc); if (f >= 0.25f && f <= 64.f) c->tune.grid_points_per_cell = f; }
         if (const char* ppc = getenv("MISLAM_KNN_POINTS_PER_CELL")) { const float f = (float)atof(ppc); if (f >= 0.125f && f <= 1e30f) c->tune.knn_points_per_cell = f; }
+        if (const char* rc = getenv("MISLAM_OUTLIER_RADIUS_CELL")) { const float f = (float)atof(rc); if (f >= 0.125f && f <= 1024.f) c->tune.outlier_radius_cell = f; }
         if (env_i("MISLAM_PRELOAD", 0) == 1) MI_TRY(mi_ctx_preload(c));       // =1: mi_ctx_preload as part of every context creation
         // Host clouds go up through the runtime's own pageable-copy path (round 6).  Rounds 3-5 staged them through an own pinned ring of 16 x 1 MB, built
         // against 20-50 ms stalls that round 3 pinned on the runtime's path -- and that were the process's CPU quota being throttled by idle BLAS pools
@@ -439,6 +440,7 @@ extern "C" void mi_ctx_destroy(mi_ctx* c)
     cpd_workspace_destroy(c);
     for (hipEvent_t e : c->knn.ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->normals.ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->outlier.ev) if (e) (void)hipEventDestroy(e);
     for (auto& s : c->prof.spans) { (void)hipEventDestroy(s.e0); (void)hipEventDestroy(s.e1); }
     for (auto e : c->prof.event_pool) (void)hipEventDestroy(e);
     if (c->d_state) (void)hipFree(c->d_state);

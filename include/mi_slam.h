@@ -662,6 +662,72 @@ int mi_estimate_normals(mi_ctx* ctx,
 int mi_estimate_normals_times(mi_ctx* ctx, double out_ms[MI_NORMALS_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * Statistical and radius outlier removal (no reference counterpart): the second consumer of the k-NN search, whose lists never leave
+ * the device here either (outlier removal).  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+#define MI_OUTLIER_STATISTICAL 0
+#define MI_OUTLIER_RADIUS      1
+typedef struct {
+    int   method;          /* MI_OUTLIER_* */
+    int   dist_mode;       /* MI_DIST_CPU_ROUNDING or MI_DIST_FMA: the d2 arithmetic of mi_knn_search */
+    int   k;               /* statistical: neighbours per point, 1 .. MI_KNN_MAX_K */
+    float std_ratio;       /* statistical: finite, >= 0 */
+    float radius;          /* radius: finite, > 0 */
+    int   min_neighbours;  /* radius: >= 1 */
+    int   reserved[6];
+} mi_outlier_params;
+void mi_outlier_params_default(mi_outlier_params* p);   /* statistical, k = 16, std_ratio = 2, CPU rounding (radius = 0, min_neighbours = 1: set both for the radius method) */
+
+typedef struct { double mean, stddev, threshold; long long kept; int reserved[4]; } mi_outlier_stats;
+
+/* The points of a cloud that pass one of the two usual outlier filters, computed on the device.
+ *   Statistical (MI_OUTLIER_STATISTICAL): the neighbours of point i are exactly row i of
+ *     mi_knn_search(ctx, NULL, n, cloud_xyz, n, k, dist_mode, INFINITY, ...) -- self is skipped by index, a duplicate of point i stored
+ *     elsewhere is a neighbour at d2 = +0 -- and neighbours[i] is that call's count[i] (= min(k, n - 1)).  The point's score is
+ *     mu_i = (sum over the row of sqrt((double)d2)) / count[i] in fp64, the roots added nearest first; mu_i = 0 when count[i] = 0.
+ *     mean_distance[i] is mu_i rounded once to fp32.  The statistics are taken over the UNROUNDED mu_i: mean = sum mu_i / n,
+ *     stddev = sqrt(sum (mu_i - mean)^2 / n) -- the population form, two passes, fp64, in a summation order that depends on n alone --
+ *     and threshold = mean + (double)std_ratio * stddev.  Point i is kept iff mu_i <= threshold ("<=": a cloud of identical points
+ *     keeps every point).
+ *   Radius (MI_OUTLIER_RADIUS): r2 = radius * radius, one IEEE fp32 multiplication (it may underflow to +0: only duplicates count
+ *     then).  neighbours[i] is the number of j != i (by index) with d2(i, j) <= r2 in the dist_mode arithmetic, and point i is kept iff
+ *     that number >= min_neighbours.  min_neighbours may exceed n - 1: nothing is kept, *out_n = 0, MI_OK.  stats->mean, stddev and
+ *     threshold are 0, 0 and (double)min_neighbours; mean_distance is not written.  With neighbours == NULL a point's count stops at
+ *     min_neighbours; the mask is the same either way.  Cost: a point's work is proportional to the number of points inside its ball
+ *     (and its cell's neighbourhood), so a radius that holds a large share of the cloud makes the call quadratic.
+ *   Outputs: the kept points in ascending caller index -- out_xyz (capacity n points, may be NULL) their coordinates, the input's bits;
+ *     out_index (capacity n, may be NULL) their indices; rows beyond *out_n are not written.  keep (n, may be NULL) is 1 for a kept point
+ *     and 0 for a removed one.  *out_n == stats->kept == the number of ones in keep.
+ *   Deterministic: the same input gives the same bits on every call, whatever ran on the context before.  No floating-point atomics.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with "mi_remove_outliers" and names the cause and, for a bad point, its index (the
+ *     lowest); NO output has been written -- for a NULL ctx, cloud_xyz, params or out_n; n < 1; an unknown method or dist_mode;
+ *     statistical: k outside [1, MI_KNN_MAX_K], std_ratio NaN, infinite or negative; radius: radius NaN, infinite or <= 0, radius^2 not
+ *     finite, min_neighbours < 1; a non-finite coordinate or one above 1e18 in magnitude.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything mi_knn_search and mi_estimate_normals keep: it works in
+ *     buffers of its own.
+ *   Synchronous, host in and host out. */
+int mi_remove_outliers(mi_ctx* ctx, const float* cloud_xyz, int n, const mi_outlier_params* params,
+                       float* out_xyz,          /* may be NULL; capacity n points: the kept points, in the caller's order */
+                       int* out_index,          /* may be NULL; capacity n: their indices, ascending */
+                       int* out_n,              /* non-NULL */
+                       unsigned char* keep,     /* may be NULL; n: 1 kept, 0 removed */
+                       float* mean_distance,    /* may be NULL; n; statistical only (radius: not written) */
+                       int* neighbours,         /* may be NULL; n */
+                       mi_outlier_stats* stats);/* may be NULL */
+
+/* Where the last mi_remove_outliers of this context spent its host wall time, in ms (measurement hook, tools/outlier_bench.py).  The
+ * first six stages are those of mi_estimate_normals_times:
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA
+ *   out[2] input check, bounding box, its read-back out[3] cell grid over the cloud
+ *   out[4] curve order of the cloud + permute       out[5] the score (statistical) or count (radius) kernel
+ *   out[6] statistics + flags + compaction + download   out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage, and out[5] is the
+ * launch's own HIP-event time instead of host wall time). */
+#define MI_OUTLIER_STAGES 8
+int mi_remove_outliers_times(mi_ctx* ctx, double out_ms[MI_OUTLIER_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
  * -------------------------------------------------------------------------------------------------------------- */
 enum {
