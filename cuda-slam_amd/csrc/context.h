@@ -58,6 +58,22 @@ struct MortonScratch {
 };
 int morton_args(MortonScratch& sc, const float* x, const float* y, const float* z, int m, int* order_out, MortonArgs* out);
 
+// What every search over a cloud's cell grid needs before its own kernel runs (search_front.hip): the uploads, the input check, the cell grid
+// over the cloud and the queries along their curve.  One instance per call that searches (mi_ctx::knn, normals, outlier).
+struct SearchFrontBuffers {
+    DevBuf<float> staging;                           // the cloud as uploaded (AoS); separate queries pass through it behind the cloud
+    DevBuf<float> cx, cy, cz;                        // the cloud, SoA, the caller's order
+    DevBuf<float> ux, uy, uz;                        // separate queries, SoA as uploaded (mi_knn_search alone)
+    DevBuf<float> qx, qy, qz;                        // the queries along their curve (self mode: the cloud)
+    DevBuf<float> range_lo_hi;                       // the input check's partials ...
+    DevBuf<int> range_bad;
+    DevBuf<KnnState> state;                          // ... and what the host reads back from it
+    DevBuf<int> order;                               // sorted slot -> the caller's query index
+    MortonScratch morton;                            // the queries' curve order
+    GridBuffers cells;                               // the cell grid over the cloud
+    hipEvent_t ev[2] = {nullptr, nullptr};           // around the call's search launch while profiling; destroyed by mi_ctx_destroy (search_front_destroy_events)
+};
+
 struct ProfileSpan {
     int kernel;
     hipEvent_t e0, e1;
@@ -98,7 +114,7 @@ struct mi_ctx {
         int fgt_coop_sweep = 1;                          // MISLAM_FGT_COOP_SWEEP=0: K-centre sweeps of clouds beyond 16 384 points as in rounds 1-4 (one workgroup / two launches per centre); 2: the cooperative kernel for every sweep
         int fgt_shard_queries = 1;                       // MISLAM_FGT_SHARD_QUERIES=0: the FGT / hybrid CPD modes run replicated on a multi-rank context, no collective (rounds 4-5)
         int fgt_model_splits = 1;                        // MISLAM_FGT_MODEL_SPLITS=0: one workgroup per cell in the FGT model build whatever the cells' sizes (rounds 1-4)
-        float knn_points_per_cell = 0.f;                 // MISLAM_KNN_POINTS_PER_CELL: cell size of mi_knn_search's grid (0: the measured default for the call's k, knn_api.hip)
+        float knn_points_per_cell = 0.f;                 // MISLAM_KNN_POINTS_PER_CELL: cell size of mi_knn_search's grid (0: the default for the call's k, knn_default_points_per_cell of search_front.hip)
         float outlier_radius_cell = 1.f;                 // MISLAM_OUTLIER_RADIUS_CELL: cell edge of mi_remove_outliers' radius grid in radii (outlier_api.hip)
         int fgt_replay = 1;                              // MISLAM_FGT_REPLAY=0: sweep the moving cloud step by step every E-step (no guess replayed)
     } tune;
@@ -192,43 +208,28 @@ struct mi_ctx {
         double ms[MI_VOXEL_STAGES] = {0};                // mi_voxel_downsample_times
     } vox;
 
-    // ---- mi_knn_search: buffers of its own, like the voxel call's (a loaded ICP problem survives the call)
+    // ---- mi_knn_search, mi_estimate_normals, mi_remove_outliers: each call has a search front end (SearchFrontBuffers) and results of its own,
+    // so that none leaves anything in another's buffers, and a loaded ICP problem survives all three
     struct KnnBuffers {
-        mislam::DevBuf<float> staging, cx, cy, cz, ux, uy, uz, qx, qy, qz;   // cloud SoA; queries SoA as uploaded (u) and along their curve (q)
-        mislam::DevBuf<float> range_lo_hi, out_d2;
-        mislam::DevBuf<int> range_bad, order, out_idx, out_count;
-        mislam::MortonScratch morton;                    // the queries' curve order
-        mislam::GridBuffers cells;                       // the cell grid over the cloud
-        mislam::DevBuf<mislam::KnnState> state;
-        hipEvent_t ev[2] = {nullptr, nullptr};           // around the search launch while profiling (mi_knn_search_times); destroyed by mi_ctx_destroy
-        double ms[MI_KNN_STAGES] = {0};
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<float> out_d2;
+        mislam::DevBuf<int> out_idx, out_count;
+        double ms[MI_KNN_STAGES] = {0};                  // mi_knn_search_times
     } knn;
-
-    // ---- mi_estimate_normals: buffers of its own again, so that neither call leaves anything in the other's (a loaded ICP problem survives the call)
     struct NormalsBuffers {
-        mislam::DevBuf<float> staging, cx, cy, cz, qx, qy, qz;   // the cloud SoA in the caller's order (c) and along its curve (q)
-        mislam::DevBuf<float> range_lo_hi, out_normals, out_curvature;
-        mislam::DevBuf<int> range_bad, order, out_count;
-        mislam::MortonScratch morton;                    // the cloud's curve order
-        mislam::GridBuffers cells;                       // the cell grid over the cloud
-        mislam::DevBuf<mislam::KnnState> state;
-        hipEvent_t ev[2] = {nullptr, nullptr};           // around the fused launch while profiling (mi_estimate_normals_times); destroyed by mi_ctx_destroy
-        double ms[MI_NORMALS_STAGES] = {0};
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<float> out_normals, out_curvature;
+        mislam::DevBuf<int> out_count;
+        double ms[MI_NORMALS_STAGES] = {0};              // mi_estimate_normals_times
     } normals;
-
-    // ---- mi_remove_outliers: buffers of its own once more (a loaded ICP problem, the k-NN call's and the normals call's buffers survive the call)
     struct OutlierBuffers {
-        mislam::DevBuf<float> staging, cx, cy, cz, qx, qy, qz;   // the cloud as uploaded (AoS: what the compaction gathers from), SoA in the caller's order (c) and along its curve (q)
-        mislam::DevBuf<float> range_lo_hi, out_xyz, out_mean;
-        mislam::DevBuf<int> range_bad, order, count, tile_counts, out_index;
+        mislam::SearchFrontBuffers front;                // (front.staging, the cloud as uploaded, is what the compaction gathers from)
+        mislam::DevBuf<float> out_xyz, out_mean;
+        mislam::DevBuf<int> count, tile_counts, out_index;
         mislam::DevBuf<double> score, partials;          // the unrounded scores; one partial sum per workgroup of a statistics pass
         mislam::DevBuf<unsigned char> keep;              // the flags, the caller's order
-        mislam::MortonScratch morton;                    // the cloud's curve order
-        mislam::GridBuffers cells;                       // the cell grid over the cloud
-        mislam::DevBuf<mislam::KnnState> state;
         mislam::DevBuf<mislam::OutlierState> ostate;
-        hipEvent_t ev[2] = {nullptr, nullptr};           // around the score / count launch while profiling (mi_remove_outliers_times); destroyed by mi_ctx_destroy
-        double ms[MI_OUTLIER_STAGES] = {0};
+        double ms[MI_OUTLIER_STAGES] = {0};              // mi_remove_outliers_times
     } outlier;
 
     // ---- mi_prepare_cloud: buffers of its own, like the voxel call's: the raw cloud, the prepared one, the caller's index vectors and draws
@@ -326,6 +327,46 @@ struct StageClock {
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
 static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+
+// ---- the front end of a search over a cloud's cell grid (search_front.hip).  A driver calls, in this order: search_front_reserve and its own
+// reserves (every reserve comes before the first upload), clock.mark(0), search_front_upload_and_check (stages 1 and 2: nothing has been written
+// to a caller's array when it refuses), search_front_index_and_order with the points per cell it chose (stages 3 and 4; the plan's reserves to
+// slot 0), search_front_fits beside the check of its own buffers, search_front_timed_launch (stage 5).  who: the entry point's name, for messages.
+struct SearchFront {
+    int n = 0, m = 0;                                // queries, cloud points
+    const float *ux = nullptr, *uy = nullptr, *uz = nullptr;   // the queries as uploaded, SoA: the cloud's arrays in self mode
+    float bbox[6] = {0};                             // of the cloud: lower corner, upper corner
+    NnGridView g{};
+    size_t n_cells = 0;
+};
+int search_front_reserve(SearchFrontBuffers& b, size_t n, size_t m, bool self);
+// query_xyz null: self mode, the cloud is its own query set (n == m)
+int search_front_upload_and_check(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, const char* who, const float* cloud_xyz, int m,
+                                  const float* query_xyz, int n, SearchFront* f);
+int search_front_index_and_order(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, const char* who, float points_per_cell, SearchFront* f);
+// the host-side shape check of what every search kernel indexes: q*, order, c*, the grid's offsets and points
+bool search_front_fits(const SearchFrontBuffers& b, const SearchFront& f);
+void search_front_destroy_events(mi_ctx* c);         // of all three calls' front ends (mi_ctx_destroy)
+// Stage 5: `launch` enqueues the call's search kernel.  With profiling on, the slot holds the launch's own HIP-event time instead of the host's.
+template <class Launch>
+static inline int search_front_timed_launch(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, Launch&& launch)
+{
+    const bool timed = c->prof.on;
+    if (timed) {
+        for (hipEvent_t& e : b.ev)
+            if (!e) MI_HIP(hipEventCreate(&e));
+        MI_HIP(hipEventRecord(b.ev[0], c->stream));
+    }
+    MI_HIP(launch());
+    if (timed) MI_HIP(hipEventRecord(b.ev[1], c->stream));
+    MI_TRY(clock.mark(5));
+    if (timed) {
+        float ms = 0.f;
+        MI_HIP(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
+        clock.ms[5] = (double)ms;
+    }
+    return MI_OK;
+}
 
 // developer switch MISLAM_DEV_STALL_MS=<ms>: report any host-side section that takes longer, with the calling thread's context switches
 // over it -- an INVOLUNTARY one with no voluntary ones means the thread was taken off its core (a CPU quota of the container

@@ -257,7 +257,7 @@ hipError_t knn_check_inputs(const float* cx, const float* cy, const float* cz, i
                             float* lo_hi, int* bad, KnnState* st, hipStream_t s);
 hipError_t knn_search(const NnGridView& g, const KnnSearchArgs& a, int fma, hipStream_t s);
 int knn_list_size(int k);            // registers' worth of list the search of this k is instantiated with: 8, 16 or 32
-float knn_default_points_per_cell(int k);    // cell size of the k-NN grid unless MISLAM_KNN_POINTS_PER_CELL says otherwise (knn_api.hip)
+float knn_default_points_per_cell(int k);    // cell size of the k-NN grid unless MISLAM_KNN_POINTS_PER_CELL says otherwise (search_front.hip)
 
 // ---------------------------------------------------------------------------------------------------------------
 // K14 surface normals and curvature (normals_kernels.hip; driver: normals_api.hip): K13's search in self mode and, with the keys
@@ -280,7 +280,7 @@ hipError_t knn_normals(const NnGridView& g, const KnnNormalsArgs& a, int fma, hi
 
 // ---------------------------------------------------------------------------------------------------------------
 // K15 statistical and radius outlier removal (outlier_kernels.hip; driver: outlier_api.hip): K13's search in self mode with the
-// keys' fp64 mean root as the point's score, or a fixed-radius count over the same shells (radius_scan.hpp); fp64 mean / deviation
+// keys' fp64 mean root as the point's score, or a fixed-radius count over the same shells (knn_scan.hpp); fp64 mean / deviation
 // of the scores in a fixed order (reduce.hpp); flags in the caller's order and their stable compaction
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int OUTLIER_STAT_BLOCK = 256;      // scores per workgroup and trip of the two statistics passes (reduce.hpp's block)

@@ -8,7 +8,7 @@
 //           the range pass of cloud_range.hpp under the predicate UsablePoint; read back once, before anything is written
 //   index   the cell grid of the 1-NN search, built by grid_build (nn_grid.h) into the call's own buffers: points sorted by cell, w =
 //           the caller's index, one offset per cell; a row of cells [x0, x1] is ONE contiguous run of pts
-//   search  (its body: knn_scan.hpp, shared with K14's normals_kernels.hip)  one lane per query, queries along their curve order so that a
+//   search  (its body: knn_scan.hpp, shared with K14's normals_kernels.hip and K15's outlier_kernels.hip)  one lane per query, queries along their curve order so that a
 //           wave's lanes visit the same cells.  The running list of
 //           K = 8 / 16 / 32 keys lives in REGISTERS, sorted; a candidate is offered only when its key is below the list's last one, and
 //           goes in through a fully unrolled chain of K selects (every index static: no scratch).  k < K: the K - k lowest slots hold
@@ -59,10 +59,9 @@ __global__ __launch_bounds__(256) void knn_range_finish_kernel(const float* __re
 template <int K, bool FMA>
 __global__ __launch_bounds__(KNN_BLOCK) void knn_search_kernel(NnGridView g, KnnSearchArgs a)
 {
-    const int s = blockIdx.x * KNN_BLOCK + (int)threadIdx.x;
-    if (s >= a.n) return;
-    const float q[3] = {a.qx[s], a.qy[s], a.qz[s]};
-    const int row_out = a.order[s];
+    float q[3];
+    int row_out;
+    if (!knn_lane(a.qx, a.qy, a.qz, a.order, a.n, q, row_out)) return;
     const unsigned int skip = a.self ? (unsigned int)row_out : 0xffffffffu;      // (no cloud point has index 2^32 - 1)
     const int k = a.k;
 
@@ -85,14 +84,6 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_search_kernel(NnGridView g, Knn
     if (a.count) a.count[row_out] = found;
 }
 
-template <int K>
-void knn_launch(const NnGridView& g, const KnnSearchArgs& a, int fma, hipStream_t s)
-{
-    const dim3 grid((a.n + KNN_BLOCK - 1) / KNN_BLOCK);
-    if (fma) hipLaunchKernelGGL((knn_search_kernel<K, true>), grid, dim3(KNN_BLOCK), 0, s, g, a);
-    else hipLaunchKernelGGL((knn_search_kernel<K, false>), grid, dim3(KNN_BLOCK), 0, s, g, a);
-}
-
 }  // namespace
 
 hipError_t knn_check_inputs(const float* cx, const float* cy, const float* cz, int m, const float* qx, const float* qy, const float* qz, int n,
@@ -111,11 +102,9 @@ int knn_list_size(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : 32); }
 hipError_t knn_search(const NnGridView& g, const KnnSearchArgs& a, int fma, hipStream_t s)
 {
     if (a.n < 1 || a.k < 1 || a.k > KNN_MAX_K) return hipErrorInvalidValue;
-    switch (knn_list_size(a.k)) {
-        case 8: knn_launch<8>(g, a, fma, s); break;
-        case 16: knn_launch<16>(g, a, fma, s); break;
-        default: knn_launch<32>(g, a, fma, s); break;
-    }
+    knn_dispatch(a.n, a.k, fma, [&](auto list, auto fused, dim3 grid) {
+        hipLaunchKernelGGL((knn_search_kernel<decltype(list)::value, decltype(fused)::value>), grid, dim3(KNN_BLOCK), 0, s, g, a);
+    });
     return hipGetLastError();
 }
 

@@ -1,9 +1,13 @@
-// K13 / K14 -- the search body of the exact k-NN kernels, stated once: the sorted list of K keys in registers and the walk over
-// Chebyshev shells of cells with its stop rule (the contract and the proof of the stop rule: the head of knn_kernels.hip).
-// knn_search_kernel (knn_kernels.hip) writes the list out; knn_normals_kernel (normals_kernels.hip) goes on to the neighbourhood's
-// covariance with the keys still in registers.  One lane per query; no LDS, no scratch: every index into the list is static.
+// K13 / K14 / K15 -- the search body of the kernels that walk a cloud's cell grid, stated once: the walk over Chebyshev shells of cells with
+// its stop rule (shell_walk; the contract and the proof of the stop rule: the head of knn_kernels.hip), the sorted list of K keys in
+// registers that the exact k-NN kernels feed from it (knn_scan) and the counter of the fixed-radius kernel (radius_scan), and what the
+// kernels share around them: the lane's query (knn_lane) and the host's choice of an instantiation (knn_dispatch).
+// knn_search_kernel (knn_kernels.hip) writes the list out; knn_normals_kernel (normals_kernels.hip) and knn_outlier_score_kernel
+// (outlier_kernels.hip) go on with the keys still in registers.  One lane per query; no LDS, no scratch: every index into the list is static.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "kernels.h"
 #include "nn_grid.h"
@@ -24,14 +28,26 @@ __device__ __forceinline__ void knn_insert(unsigned long long (&l)[K], unsigned 
     l[0] = key < l[0] ? key : l[0];
 }
 
-// The k smallest keys (bits(d2) << 32) | j of query q over the grid's points, ascending in l[K - k, K).  The CALLER initialises the
-// list, l[i] = i < K - k ? 0 : KNN_KEY_EMPTY (slots below K - k hold key 0, which no offer moves; unfilled ones stay KNN_KEY_EMPTY): with
-// that loop in here hipcc keeps a second copy of the list alive across the shell loop (K = 8: 90 VGPRs instead of 60).
-// skip: the one point index that is no candidate (self mode), 0xffffffff for none (no cloud point has index 2^32 - 1).  hi: the upper
-// corner of the cloud's bounding box (the lower one is the grid's origin).
-template <int K, bool FMA>
-__device__ __forceinline__ void knn_scan(const NnGridView& g, const float (&q)[3], const float (&hi)[3], unsigned int skip, int k, float max_d2,
-                                         unsigned long long (&l)[K])
+// The lane of a search kernel: its sorted slot's query into q and the caller's row that slot answers for (in self mode also the one candidate
+// it skips) into row_out; false for a lane beyond the n queries.  (knn_normals_kernel keeps these lines of its own: see there.)
+__device__ __forceinline__ bool knn_lane(const float* qx, const float* qy, const float* qz, const int* order, int n, float (&q)[3], int& row_out)
+{
+    const int s = blockIdx.x * KNN_BLOCK + (int)threadIdx.x;
+    if (s >= n) return false;
+    q[0] = qx[s]; q[1] = qy[s]; q[2] = qz[s];
+    row_out = order[s];
+    return true;
+}
+
+// Every point of the grid to `sink`, in Chebyshev shells of cells around the cell of query q, until the sink says that no point behind the
+// shells walked can matter.  hi: the upper corner of the cloud's bounding box (the lower one is the grid's origin).  The sink, by reference:
+//   bool take(float d2, unsigned int j)   candidate j at rounded squared distance d2; true: the lane leaves the walk at once
+//   static constexpr bool LEAVES          whether take can say so.  Where it cannot, the walk has no way out of its loops but the shell loop's:
+//                                         with the dead exit in the source hipcc lays the row loops out differently and does not unroll the counter's
+//   bool stop(float bound) const          behind a shell: every point not yet offered is at least `bound` away (rounded like a distance);
+//                                         true once none of them can matter.  STRICTLY above the sink's reach: a point AT the reach belongs.
+template <bool FMA, class Sink>
+__device__ __forceinline__ void shell_walk(const NnGridView& g, const float (&q)[3], const float (&hi)[3], Sink& sink)
 {
     const int c[3] = {knn_cell_index(knn_cell_u(q[0], g.ox, g.inv_h), g.nx), knn_cell_index(knn_cell_u(q[1], g.oy, g.inv_h), g.ny),
                       knn_cell_index(knn_cell_u(q[2], g.oz, g.inv_h), g.nz)};
@@ -56,9 +72,11 @@ __device__ __forceinline__ void knn_scan(const NnGridView& g, const float (&q)[3
                     for (unsigned int j = b; j < end; j++) {
                         const float4 p = g.pts[j];
                         const float d2 = sq3<FMA>(p.x - q[0], p.y - q[1], p.z - q[2]);
-                        const unsigned int pj = __float_as_uint(p.w);
-                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | pj;
-                        if (key < l[K - 1] && pj != skip && d2 <= max_d2) knn_insert<K>(l, key);
+                        if constexpr (Sink::LEAVES) {
+                            if (sink.take(d2, __float_as_uint(p.w))) return;
+                        } else {
+                            sink.take(d2, __float_as_uint(p.w));
+                        }
                     }
                 }
             }
@@ -67,8 +85,87 @@ __device__ __forceinline__ void knn_scan(const NnGridView& g, const float (&q)[3
         const float lb = fmaxf((float)r - 1e-3f, 0.f) * g.h_lo;
         const float gx = (e[0] + lb) * 0.999999f, gy = (e[1] + lb) * 0.999999f, gz = (e[2] + lb) * 0.999999f;
         const float bound = fminf(fminf(sq3<FMA>(gx, e[1], e[2]), sq3<FMA>(e[0], gy, e[2])), sq3<FMA>(e[0], e[1], gz));
+        if (sink.stop(bound)) break;
+    }
+}
+
+// the sorted list as a sink: a candidate is offered when its key is below the list's last one; the reach is the k-th distance and the limit
+template <int K>
+struct KnnListSink {
+    static constexpr bool LEAVES = false;
+    unsigned long long (&l)[K];
+    unsigned int skip;
+    float max_d2;
+    __device__ __forceinline__ bool take(float d2, unsigned int pj)
+    {
+        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | pj;
+        if (key < l[K - 1] && pj != skip && d2 <= max_d2) knn_insert<K>(l, key);
+        return false;
+    }
+    __device__ __forceinline__ bool stop(float bound) const
+    {
         const float kth = __uint_as_float((unsigned int)(l[K - 1] >> 32));              // (+inf while the list is not full)
-        if (bound > kth || bound > max_d2) break;
+        return bound > kth || bound > max_d2;
+    }
+};
+
+// The k smallest keys (bits(d2) << 32) | j of query q over the grid's points, ascending in l[K - k, K).  The CALLER initialises the
+// list, l[i] = i < K - k ? 0 : KNN_KEY_EMPTY (slots below K - k hold key 0, which no offer moves; unfilled ones stay KNN_KEY_EMPTY): with
+// that loop in here hipcc keeps a second copy of the list alive across the shell loop (K = 8: 90 VGPRs instead of 60).
+// skip: the one point index that is no candidate (self mode), 0xffffffff for none (no cloud point has index 2^32 - 1).  hi: the upper
+// corner of the cloud's bounding box (the lower one is the grid's origin).
+template <int K, bool FMA>
+__device__ __forceinline__ void knn_scan(const NnGridView& g, const float (&q)[3], const float (&hi)[3], unsigned int skip, int k, float max_d2,
+                                         unsigned long long (&l)[K])
+{
+    KnnListSink<K> sink{l, skip, max_d2};
+    shell_walk<FMA>(g, q, hi, sink);
+}
+
+// a counter as a sink (K15's radius method): the reach is r2, and a point AT r2 counts
+template <bool EARLY>
+struct RadiusCountSink {
+    static constexpr bool LEAVES = EARLY;
+    unsigned int skip;
+    float r2;
+    int enough;
+    int& found;
+    __device__ __forceinline__ bool take(float d2, unsigned int pj)
+    {
+        if (pj != skip && d2 <= r2) {
+            found++;
+            if (EARLY && found >= enough) return true;
+        }
+        return false;
+    }
+    __device__ __forceinline__ bool stop(float bound) const { return bound > r2; }
+};
+
+// The number of grid points j != skip with d2(q, j) <= r2, d2 in the arithmetic of knn_scan.  EARLY: returns as soon as the counter
+// reaches `enough` (>= 1), so the answer is min(the number, enough).  hi: the upper corner of the cloud's bounding box.
+template <bool FMA, bool EARLY>
+__device__ __forceinline__ int radius_scan(const NnGridView& g, const float (&q)[3], const float (&hi)[3], unsigned int skip, float r2, int enough)
+{
+    int found = 0;
+    RadiusCountSink<EARLY> sink{skip, r2, enough, found};
+    shell_walk<FMA>(g, q, hi, sink);
+    return found;
+}
+
+// Host: launch(K, FMA, grid) with the list size of k (knn_list_size) and the distance arithmetic as integral constants, and the grid of one
+// lane per query in workgroups of KNN_BLOCK -- the one place that maps (k, fma) to an instantiation of a kernel template.
+template <class Launch>
+void knn_dispatch(int n, int k, int fma, Launch&& launch)
+{
+    const dim3 grid((n + KNN_BLOCK - 1) / KNN_BLOCK);
+    auto with_list = [&](auto list) {
+        if (fma) launch(list, std::true_type{}, grid);
+        else launch(list, std::false_type{}, grid);
+    };
+    switch (knn_list_size(k)) {
+        case 8: with_list(std::integral_constant<int, 8>{}); break;
+        case 16: with_list(std::integral_constant<int, 16>{}); break;
+        default: with_list(std::integral_constant<int, 32>{}); break;
     }
 }
 

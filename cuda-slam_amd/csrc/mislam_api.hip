@@ -438,9 +438,7 @@ extern "C" void mi_ctx_destroy(mi_ctx* c)
     if (c->pin.buf) (void)hipHostFree(c->pin.buf);
     if (c->h_scratch) (void)hipHostFree(c->h_scratch);
     cpd_workspace_destroy(c);
-    for (hipEvent_t e : c->knn.ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->normals.ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->outlier.ev) if (e) (void)hipEventDestroy(e);
+    search_front_destroy_events(c);
     for (auto& s : c->prof.spans) { (void)hipEventDestroy(s.e0); (void)hipEventDestroy(s.e1); }
     for (auto e : c->prof.event_pool) (void)hipEventDestroy(e);
     if (c->d_state) (void)hipFree(c->d_state);

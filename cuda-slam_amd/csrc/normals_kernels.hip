@@ -32,7 +32,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_normals_kernel(NnGridView g, Kn
 {
     const int s = blockIdx.x * KNN_BLOCK + (int)threadIdx.x;
     if (s >= a.n) return;
-    const float q[3] = {a.qx[s], a.qy[s], a.qz[s]};
+    const float q[3] = {a.qx[s], a.qy[s], a.qz[s]};     // (not knn_lane: through it this kernel takes one more SGPR at K = 8)
     const int row_out = a.order[s];
     const int k = a.k;
 
@@ -76,24 +76,14 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_normals_kernel(NnGridView g, Kn
     if (a.count) a.count[row_out] = found;
 }
 
-template <int K>
-void normals_launch(const NnGridView& g, const KnnNormalsArgs& a, int fma, hipStream_t s)
-{
-    const dim3 grid((a.n + KNN_BLOCK - 1) / KNN_BLOCK);
-    if (fma) hipLaunchKernelGGL((knn_normals_kernel<K, true>), grid, dim3(KNN_BLOCK), 0, s, g, a);
-    else hipLaunchKernelGGL((knn_normals_kernel<K, false>), grid, dim3(KNN_BLOCK), 0, s, g, a);
-}
-
 }  // namespace
 
 hipError_t knn_normals(const NnGridView& g, const KnnNormalsArgs& a, int fma, hipStream_t s)
 {
     if (a.n < 1 || a.k < 2 || a.k > KNN_MAX_K) return hipErrorInvalidValue;
-    switch (knn_list_size(a.k)) {
-        case 8: normals_launch<8>(g, a, fma, s); break;
-        case 16: normals_launch<16>(g, a, fma, s); break;
-        default: normals_launch<32>(g, a, fma, s); break;
-    }
+    knn_dispatch(a.n, a.k, fma, [&](auto list, auto fused, dim3 grid) {
+        hipLaunchKernelGGL((knn_normals_kernel<decltype(list)::value, decltype(fused)::value>), grid, dim3(KNN_BLOCK), 0, s, g, a);
+    });
     return hipGetLastError();
 }
 

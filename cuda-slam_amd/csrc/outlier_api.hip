@@ -1,7 +1,7 @@
-// mi_remove_outliers behind the C ABI: argument checks, the call's own buffers in the context, the upload, then mi_estimate_normals'
-// stages through the same helpers -- the input check and its one read-back (knn_check_inputs), the cell grid over the cloud
-// (grid_reserve / grid_build_into), the curve order (morton_order / permute_soa) -- the method's launch of outlier_kernels.hip (the fused
-// search-and-score, or the fixed-radius count), the statistics, the flags, their compaction and the download of what was asked for.
+// mi_remove_outliers behind the C ABI: argument checks, the reserves of the call's own buffers in the context, the search front end in
+// self mode (search_front.hip: upload, input check and its one read-back, the cell grid over the cloud, the curve order), the method's
+// launch of outlier_kernels.hip (the fused search-and-score, or the fixed-radius count), the statistics, the flags, their compaction and the
+// download of what was asked for.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -66,11 +66,8 @@ extern "C" int mi_remove_outliers(mi_ctx* c, const float* cloud_xyz, int n, cons
 
     const size_t np = (size_t)n;
     const int tiles = outlier_scan_tiles(n), stat_blocks = outlier_stat_blocks(n);
-    MI_TRY(b.staging.reserve(3 * np));
-    MI_TRY(b.cx.reserve(np)); MI_TRY(b.cy.reserve(np)); MI_TRY(b.cz.reserve(np));
-    MI_TRY(b.qx.reserve(np)); MI_TRY(b.qy.reserve(np)); MI_TRY(b.qz.reserve(np));
-    MI_TRY(b.range_lo_hi.reserve(2 * 6 * KNN_RANGE_BLOCKS)); MI_TRY(b.range_bad.reserve(2 * KNN_RANGE_BLOCKS)); MI_TRY(b.state.reserve(1)); MI_TRY(b.ostate.reserve(1));
-    MI_TRY(b.order.reserve(np));
+    MI_TRY(search_front_reserve(b.front, np, np, true));
+    MI_TRY(b.ostate.reserve(1));
     MI_TRY(b.keep.reserve(np)); MI_TRY(b.tile_counts.reserve((size_t)tiles));
     if (statistical) { MI_TRY(b.score.reserve(np)); MI_TRY(b.partials.reserve((size_t)stat_blocks)); }
     if (!statistical || neighbours) MI_TRY(b.count.reserve(np));
@@ -79,81 +76,37 @@ extern "C" int mi_remove_outliers(mi_ctx* c, const float* cloud_xyz, int n, cons
     if (out_index) MI_TRY(b.out_index.reserve(np));
     MI_TRY(clock.mark(0));
 
-    MI_TRY(host_to_device(c, b.staging.p, cloud_xyz, sizeof(float) * 3 * np));
-    MI_HIP(aos_to_soa(b.staging.p, n, n, b.cx.p, b.cy.p, b.cz.p, nullptr, c->stream));
-    MI_TRY(clock.mark(1));
-
-    MI_HIP(knn_check_inputs(b.cx.p, b.cy.p, b.cz.p, n, nullptr, nullptr, nullptr, n, b.range_lo_hi.p, b.range_bad.p, b.state.p, c->stream));
-    KnnState* st = reinterpret_cast<KnnState*>(c->h_scratch);     // (pinned, 256 bytes)
-    static_assert(sizeof(KnnState) <= 64 * sizeof(float), "KnnState must fit the context's pinned scratch");
-    MI_HIP(hipMemcpyAsync(st, b.state.p, sizeof(KnnState), hipMemcpyDeviceToHost, c->stream));
-    MI_HIP(hipStreamSynchronize(c->stream));
-    MI_TRY(clock.mark(2));
-    // everything that can refuse the input is known here, before any output has been touched
-    if (st->bad_cloud != KNN_NO_POINT) {
-        set_error("mi_remove_outliers: cloud_xyz point %d has a non-finite coordinate or one above 1e18 in magnitude", st->bad_cloud);
-        return MI_ERR_INVALID_ARG;
-    }
-
+    SearchFront f;
+    MI_TRY(search_front_upload_and_check(c, b.front, clock, "mi_remove_outliers", cloud_xyz, n, nullptr, n, &f));
     // the cell grid over the cloud: mi_knn_search's for the statistical method, cell size included; a cell about a radius long for the other
-    const float bbox[6] = {st->lo[0], st->lo[1], st->lo[2], st->hi[0], st->hi[1], st->hi[2]};
     const float ppc = c->tune.knn_points_per_cell > 0.f ? c->tune.knn_points_per_cell
-                      : (statistical ? knn_default_points_per_cell(k) : radius_points_per_cell(bbox, n, p->radius, c->tune.outlier_radius_cell));
-    NnGridView g{};
-    MI_TRY(grid_reserve(b.cells, bbox, n, 0, ppc, &g));
-    MI_TRY(clock.mark(0));
-    if (g.nx < 1 || g.ny < 1 || g.nz < 1 || g.nx > GRID_MAX_DIM || g.ny > GRID_MAX_DIM || g.nz > GRID_MAX_DIM || !(g.inv_h > 0.f) || !(g.h_lo > 0.f)) {
-        set_error("internal: mi_remove_outliers planned a %d x %d x %d grid", g.nx, g.ny, g.nz);
-        return MI_ERR_STATE;
-    }
-    const size_t n_cells = (size_t)g.nx * g.ny * g.nz;
-    MI_TRY(grid_build_into(b.cells, g, b.cx.p, b.cy.p, b.cz.p, n, c->stream));
-    MI_TRY(clock.mark(3));
-
-    // the cloud along its curve: order[s] = the caller's index of sorted slot s
-    MortonArgs ma{};
-    MI_TRY(morton_args(b.morton, b.cx.p, b.cy.p, b.cz.p, n, b.order.p, &ma));
-    MI_HIP(morton_order(ma, c->stream));
-    MI_HIP(permute_soa(b.cx.p, b.cy.p, b.cz.p, b.order.p, n, n, b.qx.p, b.qy.p, b.qz.p, c->stream));
-    MI_TRY(clock.mark(4));
+                      : (statistical ? knn_default_points_per_cell(k) : radius_points_per_cell(f.bbox, n, p->radius, c->tune.outlier_radius_cell));
+    MI_TRY(search_front_index_and_order(c, b.front, clock, "mi_remove_outliers", ppc, &f));
 
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (b.qx.cap < np || b.qy.cap < np || b.qz.cap < np || b.order.cap < np || b.staging.cap < 3 * np || b.keep.cap < np || b.tile_counts.cap < (size_t)tiles ||
+    if (!search_front_fits(b.front, f) || b.front.staging.cap < 3 * np || b.keep.cap < np || b.tile_counts.cap < (size_t)tiles ||
         (statistical && (b.score.cap < np || b.partials.cap < (size_t)stat_blocks)) || ((!statistical || neighbours) && b.count.cap < np) ||
-        (statistical && mean_distance && b.out_mean.cap < np) || (out_xyz && b.out_xyz.cap < 3 * np) || (out_index && b.out_index.cap < np) ||
-        b.cells.start.cap < n_cells + 1 || b.cells.pts.cap < np) {
+        (statistical && mean_distance && b.out_mean.cap < np) || (out_xyz && b.out_xyz.cap < 3 * np) || (out_index && b.out_index.cap < np)) {
         set_error("internal: mi_remove_outliers buffers shorter than the launch");
         return MI_ERR_STATE;
     }
-    const bool timed = c->prof.on;
-    if (timed) {
-        for (hipEvent_t& e : b.ev)
-            if (!e) MI_HIP(hipEventCreate(&e));
-        MI_HIP(hipEventRecord(b.ev[0], c->stream));
-    }
     const int fma = p->dist_mode == MI_DIST_FMA;
-    if (statistical) {
-        KnnOutlierArgs a{};
-        a.qx = b.qx.p; a.qy = b.qy.p; a.qz = b.qz.p; a.order = b.order.p;
-        a.n = n; a.k = k;
-        for (int i = 0; i < 3; i++) a.hi[i] = bbox[3 + i];
-        a.score = b.score.p; a.count = neighbours ? b.count.p : nullptr;
-        MI_HIP(knn_outlier_score(g, a, fma, c->stream));
-    } else {
+    MI_TRY(search_front_timed_launch(c, b.front, clock, [&] {
+        if (statistical) {
+            KnnOutlierArgs a{};
+            a.qx = b.front.qx.p; a.qy = b.front.qy.p; a.qz = b.front.qz.p; a.order = b.front.order.p;
+            a.n = n; a.k = k;
+            for (int i = 0; i < 3; i++) a.hi[i] = f.bbox[3 + i];
+            a.score = b.score.p; a.count = neighbours ? b.count.p : nullptr;
+            return knn_outlier_score(f.g, a, fma, c->stream);
+        }
         RadiusCountArgs a{};
-        a.qx = b.qx.p; a.qy = b.qy.p; a.qz = b.qz.p; a.order = b.order.p;
+        a.qx = b.front.qx.p; a.qy = b.front.qy.p; a.qz = b.front.qz.p; a.order = b.front.order.p;
         a.n = n; a.r2 = r2; a.min_neighbours = min_nb;
-        for (int i = 0; i < 3; i++) a.hi[i] = bbox[3 + i];
+        for (int i = 0; i < 3; i++) a.hi[i] = f.bbox[3 + i];
         a.count = b.count.p;
-        MI_HIP(radius_count(g, a, fma, neighbours ? 0 : 1, c->stream));
-    }
-    if (timed) MI_HIP(hipEventRecord(b.ev[1], c->stream));
-    MI_TRY(clock.mark(5));
-    if (timed) {
-        float ms = 0.f;
-        MI_HIP(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
-        b.ms[5] = (double)ms;
-    }
+        return radius_count(f.g, a, fma, neighbours ? 0 : 1, c->stream);
+    }));
 
     if (statistical) {
         MI_HIP(outlier_statistics(b.score.p, n, p->std_ratio, b.partials.p, b.ostate.p, c->stream));
@@ -163,7 +116,7 @@ extern "C" int mi_remove_outliers(mi_ctx* c, const float* cloud_xyz, int n, cons
         MI_HIP(outlier_flags_radius(b.count.p, n, min_nb, b.keep.p, c->stream));
     }
     OutlierCompactArgs ca{};
-    ca.keep = b.keep.p; ca.xyz = b.staging.p; ca.n = n; ca.tile_counts = b.tile_counts.p;
+    ca.keep = b.keep.p; ca.xyz = b.front.staging.p; ca.n = n; ca.tile_counts = b.tile_counts.p;
     ca.out_index = out_index ? b.out_index.p : nullptr; ca.out_xyz = out_xyz ? b.out_xyz.p : nullptr; ca.state = b.ostate.p;
     MI_HIP(outlier_compact(ca, c->stream));
 

@@ -4,7 +4,7 @@
 //            knn_scan.hpp, and behind it the lane holds its point's neighbours as K sorted keys in registers -- the keys mi_knn_search would
 //            have written out.  They are walked with static indices, predicated on "slot filled": sum += sqrt((double)d2), nearest first, a
 //            fixed order; the score is sum / count in fp64 (0 where count is 0), written unrounded to row order[s].  No LDS, no scratch.
-//   count    radius.  radius_scan.hpp: the same shells with a counter in the place of the list, stopped by the same bound against r2.
+//   count    radius.  radius_scan (knn_scan.hpp): the same walk with a counter in the place of the list, stopped by the same bound against r2.
 //            EARLY leaves the loops at min_neighbours: the flag is the same, the count is not the whole one.
 //   stats    two passes over the n scores, each a grid-stride sum into one partial per workgroup (block_sum_store) and one workgroup
 //            over the partials in a fixed order (reduce_partials): the sum -> mean; the squared deviations about it -> stddev, threshold.
@@ -17,7 +17,6 @@
 #include "kernels.h"
 #include "knn_scan.hpp"
 #include "nn_grid.h"
-#include "radius_scan.hpp"
 #include "reduce.hpp"
 
 namespace mislam {
@@ -27,10 +26,9 @@ namespace {
 template <int K, bool FMA>
 __global__ __launch_bounds__(KNN_BLOCK) void knn_outlier_score_kernel(NnGridView g, KnnOutlierArgs a)
 {
-    const int s = blockIdx.x * KNN_BLOCK + (int)threadIdx.x;
-    if (s >= a.n) return;
-    const float q[3] = {a.qx[s], a.qy[s], a.qz[s]};
-    const int row_out = a.order[s];
+    float q[3];
+    int row_out;
+    if (!knn_lane(a.qx, a.qy, a.qz, a.order, a.n, q, row_out)) return;
     const int k = a.k;
 
     unsigned long long l[K];
@@ -52,21 +50,12 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_outlier_score_kernel(NnGridView
     if (a.count) a.count[row_out] = found;
 }
 
-template <int K>
-void score_launch(const NnGridView& g, const KnnOutlierArgs& a, int fma, hipStream_t s)
-{
-    const dim3 grid((a.n + KNN_BLOCK - 1) / KNN_BLOCK);
-    if (fma) hipLaunchKernelGGL((knn_outlier_score_kernel<K, true>), grid, dim3(KNN_BLOCK), 0, s, g, a);
-    else hipLaunchKernelGGL((knn_outlier_score_kernel<K, false>), grid, dim3(KNN_BLOCK), 0, s, g, a);
-}
-
 template <bool FMA, bool EARLY>
 __global__ __launch_bounds__(KNN_BLOCK) void radius_count_kernel(NnGridView g, RadiusCountArgs a)
 {
-    const int s = blockIdx.x * KNN_BLOCK + (int)threadIdx.x;
-    if (s >= a.n) return;
-    const float q[3] = {a.qx[s], a.qy[s], a.qz[s]};
-    const int row_out = a.order[s];
+    float q[3];
+    int row_out;
+    if (!knn_lane(a.qx, a.qy, a.qz, a.order, a.n, q, row_out)) return;
     a.count[row_out] = radius_scan<FMA, EARLY>(g, q, a.hi, (unsigned int)row_out, a.r2, a.min_neighbours);
 }
 
@@ -205,11 +194,9 @@ __global__ __launch_bounds__(256) void outlier_scatter_kernel(OutlierCompactArgs
 hipError_t knn_outlier_score(const NnGridView& g, const KnnOutlierArgs& a, int fma, hipStream_t s)
 {
     if (a.n < 1 || a.k < 1 || a.k > KNN_MAX_K || !a.score) return hipErrorInvalidValue;
-    switch (knn_list_size(a.k)) {
-        case 8: score_launch<8>(g, a, fma, s); break;
-        case 16: score_launch<16>(g, a, fma, s); break;
-        default: score_launch<32>(g, a, fma, s); break;
-    }
+    knn_dispatch(a.n, a.k, fma, [&](auto list, auto fused, dim3 grid) {
+        hipLaunchKernelGGL((knn_outlier_score_kernel<decltype(list)::value, decltype(fused)::value>), grid, dim3(KNN_BLOCK), 0, s, g, a);
+    });
     return hipGetLastError();
 }
 
