@@ -41,7 +41,7 @@ EXPORTS = [
     "mi_prepare_params_default", "mi_prepare_cloud", "mi_voxel_index", "mi_voxel_downsample", "mi_voxel_downsample_times",
     "mi_knn_search", "mi_knn_search_times", "mi_estimate_normals", "mi_estimate_normals_times",
     "mi_outlier_params_default", "mi_remove_outliers", "mi_remove_outliers_times",
-    "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_nn_kernel_name",
+    "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_selftest_icp_schedule", "mi_nn_kernel_name",
 ]
 
 
@@ -827,6 +827,19 @@ class Context:
         bad = C.c_int(-1)
         _check(selftest_cloud_range_raw(self._h, p.ctypes.data, int(p.shape[0]), int(check), lo_hi.ctypes.data, C.byref(bad)))
         return lo_hi, int(bad.value)
+
+    def selftest_icp_schedule(self):
+        """What the last ICP step left on the device: dict(order int32[rows], far uint8[rows], cursors int32[4], ticket, sums float64[18]
+        = the 16 moments and 2 error sums the last solve read) (mi_selftest_icp_schedule)."""
+        f = lib().mi_selftest_icp_schedule
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        rows, ticket = C.c_int(0), C.c_int(-1)
+        cursors, sums = np.zeros(4, np.int32), np.zeros(18, np.float64)
+        _check(f(self._h, 0, None, None, C.byref(rows), cursors.ctypes.data, C.byref(ticket), sums.ctypes.data))
+        order, far = np.zeros(rows.value, np.int32), np.zeros(rows.value, np.uint8)
+        _check(f(self._h, rows.value, order.ctypes.data, far.ctypes.data, C.byref(rows), cursors.ctypes.data, C.byref(ticket), sums.ctypes.data))
+        return dict(order=order, far=far, cursors=cursors, ticket=int(ticket.value), sums=sums)
 
     def nn_kernel_name(self, n_moving, m_fixed_local, nn_mode=NN_AUTO):
         lib().mi_nn_kernel_name.restype = C.c_char_p

@@ -108,6 +108,7 @@ struct mi_ctx {
         int grid_deal_rows = -1;                         // MISLAM_GRID_DEAL_ROWS=0 / 1: K1g's leftover rows never / always dealt out one per lane (default: by size)
         int svd_ieee = 0;                                // MISLAM_SVD_IEEE=1: the 3 x 3 SVD of every solve in IEEE divisions and roots (svd3.hpp)
         int icp_fused_solve = 1;                         // MISLAM_ICP_FUSED_SOLVE=0: rows reduce and solve as two launches at every size
+        int icp_ticket_solve = 1;                        // MISLAM_ICP_TICKET_SOLVE=0: above the one-workgroup size, rows reduce and solve as two launches
         int icp_pipeline = 1;                            // MISLAM_ICP_PIPELINE=0: every host check of mi_icp_run settles the pending iteration and drains the stream
         int fgt_two_streams = 1;                         // MISLAM_FGT_TWO_STREAMS=0: the fixed cloud's clustering of an FGT E-step on the main stream, behind the moving side's
         int fgt_lists_in_model = 1;                      // MISLAM_FGT_LISTS_IN_MODEL=0: the member lists of an FGT E-step by the three-launch counting sort (round 4) instead of inside the model kernel
@@ -154,6 +155,7 @@ struct mi_ctx {
     mislam::DevBuf<double> part_mom, part_err;           // per-workgroup partial sums of the NICP / CPD drivers
     struct WorkOrder {                                   // work order of the fused search (IcpSchedule)
         mislam::DevBuf<int> order, counters;
+        mislam::DevBuf<int> ticket;                      // icp_rows_reduce_solve: summing workgroups that have arrived (a line of its own; 0 between launches)
         mislam::DevBuf<unsigned char> far;
         mislam::DevBuf<unsigned long long> lanes;        // per chunk: the lanes that walked (IcpSchedule::lanes)
     } sched;

@@ -29,7 +29,8 @@ static int reserve_rows(mi_ctx* c)
     MI_TRY(c->sched.order.reserve((size_t)icp_row_count(c->prob.n_pad)));
     MI_TRY(c->sched.far.reserve((size_t)icp_row_count(c->prob.n_pad)));
     MI_TRY(c->sched.lanes.reserve((size_t)icp_row_count(c->prob.n_pad)));
-    MI_TRY(c->sched.counters.reserve(2));
+    MI_TRY(c->sched.counters.reserve(ICP_SCHED_CURSORS));
+    MI_TRY(c->sched.ticket.reserve(32));                   // (one word in use: a cache line away from the cursors' atomics)
     return MI_OK;
 }
 
@@ -37,6 +38,7 @@ static IcpSchedule make_schedule(mi_ctx* c)
 {
     IcpSchedule s{};
     s.order = c->sched.order.p; s.far = c->sched.far.p; s.counters = c->sched.counters.p; s.lanes = c->sched.lanes.p;
+    s.ticket = c->sched.ticket.p;
     return s;
 }
 
@@ -302,9 +304,9 @@ static int icp_flush_pending(mi_ctx* c)
     return MI_OK;
 }
 
-// One loop body of basicicp.cpp:32-57 / icpcuda.cu:31-54, enqueued without host synchronisation.  Three launches on the
-// default path: fused search (transform, previous error, search, moments) -> rows reduce -> solve (previous stop rule, Kabsch,
-// compose).
+// One loop body of basicicp.cpp:32-57 / icpcuda.cu:31-54, enqueued without host synchronisation.  Two launches on the
+// default path: fused search (transform, previous error, search, moments) -> rows reduce whose last workgroup solves (previous
+// stop rule, Kabsch, compose).
 static int icp_enqueue_iteration(mi_ctx* c)
 {
     const IcpView v = make_view(c);
@@ -313,6 +315,7 @@ static int icp_enqueue_iteration(mi_ctx* c)
     const int nrows = icp_row_count(c->prob.n);
     const int reduced = icp_reduced_count(nrows);
     const int seq = c->prob.icp.sum_mode == MI_SUM_CPU_SEQUENTIAL;
+    const int parity = c->prob.enqueued_passes & 1;      // which pair of the work order's cursors this step deals on (IcpSchedule)
     if (c->prob.fused) {
         GridSearchArgs a = grid_search_args(c, c->prob.n);
         a.state = c->d_state;
@@ -346,7 +349,7 @@ static int icp_enqueue_iteration(mi_ctx* c)
             // rank sends the same length whatever its share), so that the solve kernel adds them up exactly as on one GPU and no kernel sits between
             // the reduction and the collective (a 9 KB all-reduce is as latency-bound as a 144-byte one)
             (void)reduced;
-            { ProfScope ps(c, MI_KERNEL_SOLVE); MI_HIP(icp_rows_reduce(c->rows.p, nrows, c->rows_reduced.p, c->stream, c->prob.fused ? &sched : nullptr, true)); }
+            { ProfScope ps(c, MI_KERNEL_SOLVE); MI_HIP(icp_rows_reduce(c->rows.p, nrows, c->rows_reduced.p, c->stream, c->prob.fused ? &sched : nullptr, true, parity)); }
             { ProfScope ps(c, MI_KERNEL_ALLREDUCE); MI_TRY(allreduce_sum_f64(c, c->rows_reduced.p, ICP_REDUCED_ROWS * (ICP_MOMENTS + ICP_ERRSUMS))); }
             ProfScope ps(c, MI_KERNEL_SOLVE);
             MI_HIP(icp_solve_deferred(c->d_state, c->rows_reduced.p, ICP_REDUCED_ROWS, c->prob.icp.compose_mode, rules, 1, c->stream, cursors));
@@ -354,9 +357,14 @@ static int icp_enqueue_iteration(mi_ctx* c)
             // small clouds: one launch of one workgroup for both (and no work order: every wave of such a search is resident from the start)
             ProfScope ps(c, MI_KERNEL_SOLVE);
             MI_HIP(icp_reduce_solve(c->d_state, c->rows.p, nrows, c->prob.icp.compose_mode, rules, 1, c->stream));
+        } else if (c->tune.icp_ticket_solve != 0 && !seq) {
+            // larger clouds: still one launch -- the summing workgroup that arrives last solves (icp_rows_reduce_solve_kernel)
+            ProfScope ps(c, MI_KERNEL_SOLVE);
+            MI_HIP(icp_rows_reduce_solve(c->d_state, c->rows.p, nrows, c->rows_reduced.p, c->prob.fused ? &sched : nullptr, parity, sched.ticket,
+                                         c->prob.icp.compose_mode, rules, 1, c->stream));
         } else {
             ProfScope ps(c, MI_KERNEL_SOLVE);
-            MI_HIP(icp_rows_reduce(c->rows.p, nrows, c->rows_reduced.p, c->stream, c->prob.fused ? &sched : nullptr));
+            MI_HIP(icp_rows_reduce(c->rows.p, nrows, c->rows_reduced.p, c->stream, c->prob.fused ? &sched : nullptr, false, parity));
             MI_HIP(icp_solve_deferred(c->d_state, c->rows_reduced.p, reduced, c->prob.icp.compose_mode, rules, 1, c->stream, cursors));
         }
     }
@@ -477,6 +485,30 @@ extern "C" int mi_icp_result(mi_ctx* c, float out_T[16], int* iterations, float*
     MI_ENTER(c);
     MI_TRY(icp_fetch_state(c));
     state_to_outputs(c->h_state, out_T, iterations, error, stop_reason);
+    return MI_OK;
+}
+
+// Test hook: what a step leaves behind besides the result -- the work order dealt for the next search with its flags and cursors, the ticket of
+// icp_rows_reduce_solve and the sums the last solve read (state->mom, state->err).
+extern "C" int mi_selftest_icp_schedule(mi_ctx* c, int cap_rows, int* order, unsigned char* far, int* rows, int cursors[4], int* ticket, double sums[18])
+{
+    if (!c || !c->prob.icp_loaded) { set_error("mi_selftest_icp_schedule: no problem loaded"); return MI_ERR_STATE; }
+    if (!rows || !cursors || !ticket || !sums || cap_rows < 0 || (cap_rows > 0 && (!order || !far))) { set_error("mi_selftest_icp_schedule: bad argument"); return MI_ERR_INVALID_ARG; }
+    MI_ENTER(c);
+    static_assert(ICP_SCHED_CURSORS == 4 && ICP_MOMENTS + ICP_ERRSUMS == 18, "the sizes mi_slam.h states");
+    const int nrows = icp_row_count(c->prob.n);
+    *rows = nrows;
+    const size_t take = (size_t)std::min(cap_rows, nrows);
+    MI_TRY(icp_fetch_state(c));
+    if (take > 0) {
+        MI_HIP(hipMemcpyAsync(order, c->sched.order.p, sizeof(int) * take, hipMemcpyDeviceToHost, c->stream));
+        MI_HIP(hipMemcpyAsync(far, c->sched.far.p, take, hipMemcpyDeviceToHost, c->stream));
+    }
+    MI_HIP(hipMemcpyAsync(cursors, c->sched.counters.p, sizeof(int) * ICP_SCHED_CURSORS, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipMemcpyAsync(ticket, c->sched.ticket.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < ICP_MOMENTS; i++) sums[i] = c->h_state->mom[i];
+    for (int i = 0; i < ICP_ERRSUMS; i++) sums[ICP_MOMENTS + i] = c->h_state->err[i];
     return MI_OK;
 }
 

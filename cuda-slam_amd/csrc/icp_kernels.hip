@@ -22,7 +22,7 @@
 // sum the rows in index order.  No float atomics: results are bitwise reproducible run to run.
 // The stop rule of iteration i is evaluated at the START of the solve kernel of iteration i+1 (its error sums ride in the same
 // rows as that iteration's moments), or by icp_finalize_pending when the host stops enqueuing: one all-reduce per iteration on
-// several GPUs, three launches per iteration on one.
+// several GPUs, two launches per iteration on one (the search, then the rows reduction whose last workgroup solves).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -121,57 +121,100 @@ __global__ __launch_bounds__(ICP_ROW_POINTS) void icp_moments_rows_kernel(IcpVie
 // and the short grid-only chunks fill in behind them instead of the other way round (a wave that walks lives ~5x longer).  Scheduling
 // only: which workgroup handles which chunk never changes a result.
 constexpr int ROWS_REDUCE_THREADS = 1024;
-// The two jobs are independent, so with a schedule the launch is twice as wide: workgroups [0, n_sum) add their slices up, workgroups
-// [n_sum, 2 n_sum) deal the next search its order for theirs -- the launch lasts as long as the longer of the two, not as their sum.
-__global__ __launch_bounds__(ROWS_REDUCE_THREADS) void icp_rows_reduce_kernel(const double* __restrict__ rows, int nrows, int rows_per_block,
-                                                                             double* __restrict__ out, IcpSchedule sched, int n_sum)
+constexpr int ROWS_REDUCE_STRIPS = ROWS_REDUCE_THREADS / ICP_ROW;      // 56 strips of rows, 18 columns each
+
+// a dealing workgroup: the chunks of rows [lo, hi) into the next search's order, walking ones from the front, the others from the back
+__device__ __forceinline__ void deal_work_order(const IcpSchedule& sched, int* cursors, int lo, int hi, int nrows)
 {
-    constexpr int STRIPS = ROWS_REDUCE_THREADS / ICP_ROW;      // 56 strips of rows, 18 columns each
-    __shared__ double lds[STRIPS * ICP_ROW];
-    if ((int)blockIdx.x >= n_sum) {
-        __shared__ int s_far, s_near, s_base_far, s_base_near;
-        const int lo = ((int)blockIdx.x - n_sum) * rows_per_block;
-        const int hi = lo + rows_per_block < nrows ? lo + rows_per_block : nrows;
-        if (threadIdx.x == 0) { s_far = 0; s_near = 0; }
-        __syncthreads();
-        // two passes over the slice: count, reserve a range at each end of the order, place
-        int my_far = 0, my_near = 0;
-        for (int r = lo + (int)threadIdx.x; r < hi; r += ROWS_REDUCE_THREADS) { if (sched.far[r]) my_far++; else my_near++; }
-        if (my_far) atomicAdd(&s_far, my_far);
-        if (my_near) atomicAdd(&s_near, my_near);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            s_base_far = atomicAdd(&sched.counters[0], s_far);
-            s_base_near = atomicAdd(&sched.counters[1], s_near);
-            s_far = 0; s_near = 0;
-        }
-        __syncthreads();
-        for (int r0 = lo; r0 < hi; r0 += ROWS_REDUCE_THREADS) {    // one LDS cursor per class
-            const int r = r0 + (int)threadIdx.x;
-            if (r < hi) {
-                if (sched.far[r]) sched.order[s_base_far + atomicAdd(&s_far, 1)] = r;
-                else sched.order[nrows - 1 - (s_base_near + atomicAdd(&s_near, 1))] = r;
-            }
-        }
-        return;
+    __shared__ int s_far, s_near, s_base_far, s_base_near;
+    if (threadIdx.x == 0) { s_far = 0; s_near = 0; }
+    __syncthreads();
+    // two passes over the slice: count, reserve a range at each end of the order, place
+    int my_far = 0, my_near = 0;
+    for (int r = lo + (int)threadIdx.x; r < hi; r += ROWS_REDUCE_THREADS) { if (sched.far[r]) my_far++; else my_near++; }
+    if (my_far) atomicAdd(&s_far, my_far);
+    if (my_near) atomicAdd(&s_near, my_near);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        s_base_far = atomicAdd(&cursors[0], s_far);
+        s_base_near = atomicAdd(&cursors[1], s_near);
+        s_far = 0; s_near = 0;
     }
+    __syncthreads();
+    for (int r0 = lo; r0 < hi; r0 += ROWS_REDUCE_THREADS) {    // one LDS cursor per class
+        const int r = r0 + (int)threadIdx.x;
+        if (r < hi) {
+            if (sched.far[r]) sched.order[s_base_far + atomicAdd(&s_far, 1)] = r;
+            else sched.order[nrows - 1 - (s_base_near + atomicAdd(&s_near, 1))] = r;
+        }
+    }
+}
+
+// a summing workgroup: rows [lo, hi) -> out_row[0..18), 56 strips of rows first, then the strips in order (lds: ROWS_REDUCE_STRIPS * ICP_ROW doubles)
+__device__ __forceinline__ void sum_row_slice(const double* __restrict__ rows, int lo, int hi, double* lds, double* out_row)
+{
     const int k = threadIdx.x % ICP_ROW, strip = threadIdx.x / ICP_ROW;
-    const int lo = blockIdx.x * rows_per_block;
-    const int hi = lo + rows_per_block < nrows ? lo + rows_per_block : nrows;
-    if (strip < STRIPS) {
+    if (strip < ROWS_REDUCE_STRIPS) {
         double s = 0.0;
 #pragma unroll 4
-        for (int r = lo + strip; r < hi; r += STRIPS) s += rows[(size_t)r * ICP_ROW + k];
+        for (int r = lo + strip; r < hi; r += ROWS_REDUCE_STRIPS) s += rows[(size_t)r * ICP_ROW + k];
         lds[strip * ICP_ROW + k] = s;
     }
     __syncthreads();
     if (threadIdx.x < ICP_ROW) {
         double tot = lds[threadIdx.x];
-        for (int g = 1; g < STRIPS; g++) tot += lds[g * ICP_ROW + threadIdx.x];
-        out[(size_t)blockIdx.x * ICP_ROW + threadIdx.x] = tot;
+        for (int g = 1; g < ROWS_REDUCE_STRIPS; g++) tot += lds[g * ICP_ROW + threadIdx.x];
+        out_row[threadIdx.x] = tot;
     }
 }
 
+// The two jobs are independent, so with a schedule the launch is twice as wide: workgroups [0, n_sum) add their slices up, workgroups
+// [n_sum, 2 n_sum) deal the next search its order for theirs -- the launch lasts as long as the longer of the two, not as their sum.
+__global__ __launch_bounds__(ROWS_REDUCE_THREADS) void icp_rows_reduce_kernel(const double* __restrict__ rows, int nrows, int rows_per_block,
+                                                                             double* __restrict__ out, IcpSchedule sched, int n_sum)
+{
+    __shared__ double lds[ROWS_REDUCE_STRIPS * ICP_ROW];
+    const int slice = (int)blockIdx.x >= n_sum ? (int)blockIdx.x - n_sum : (int)blockIdx.x;
+    const int lo = slice * rows_per_block;
+    const int hi = lo + rows_per_block < nrows ? lo + rows_per_block : nrows;
+    if ((int)blockIdx.x >= n_sum) deal_work_order(sched, sched.counters, lo, hi, nrows);
+    else sum_row_slice(rows, lo, hi, lds, out + (size_t)blockIdx.x * ICP_ROW);
+}
+
+// The same launch with the deferred solve behind it (one rank, above ICP_FUSED_SOLVE_MAX_ROWS): the summing workgroup that finishes LAST goes
+// on as icp_solve_deferred_kernel would.  Every summing workgroup writes its row exactly as above, releases it at agent scope and draws a ticket;
+// whoever draws n_sum - 1 knows all n_sum rows are out, acquires, and its first wave reads them back FROM MEMORY (its own row too) and runs
+// solve_deferred_wave: the same rows in the same butterfly, so the same bits as the two-launch form.  Nobody waits for anybody -- a workgroup that
+// is not last returns -- so the launch needs no co-residency and cannot hang.  The last arrival leaves the ticket at 0 for the next launch.
+// The dealing workgroups take no ticket.  Their two cursors come in two pairs: this launch deals on pair `parity` (the step's parity, from the host),
+// and the solving wave zeroes the OTHER pair, which no workgroup of this launch touches and the next launch deals on; the pair in use is zeroed by
+// the next launch's solving wave, a launch boundary behind the last dealer.  (icp_solve_deferred_kernel zeroes both: no dealer runs beside it.)
+__global__ __launch_bounds__(ROWS_REDUCE_THREADS) void icp_rows_reduce_solve_kernel(IcpState* __restrict__ state, const double* __restrict__ rows, int nrows,
+                                                                                   int rows_per_block, double* out, IcpSchedule sched, int n_sum, int parity,
+                                                                                   int* ticket, int compose_mode, IcpRules rules, int mark_pending)
+{
+    __shared__ double lds[ROWS_REDUCE_STRIPS * ICP_ROW];
+    __shared__ double sums[ICP_ROW];
+    __shared__ int s_ticket;
+    const int slice = (int)blockIdx.x >= n_sum ? (int)blockIdx.x - n_sum : (int)blockIdx.x;
+    const int lo = slice * rows_per_block;
+    const int hi = lo + rows_per_block < nrows ? lo + rows_per_block : nrows;
+    if ((int)blockIdx.x >= n_sum) { deal_work_order(sched, sched.counters + 2 * parity, lo, hi, nrows); return; }
+    sum_row_slice(rows, lo, hi, lds, out + (size_t)blockIdx.x * ICP_ROW);
+    if (threadIdx.x == 0) {              // (the row's 18 stores are this wave's: its wait covers them)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        s_ticket = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (s_ticket != n_sum - 1 || threadIdx.x >= 64) return;      // not the last arrival; of the last one, the first wave goes on alone
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (sched.counters != nullptr && threadIdx.x < 2) sched.counters[2 * (1 - parity) + threadIdx.x] = 0;
+    if (state->done != 0) return;
+    solve_deferred_wave(state, out, n_sum, sums, compose_mode, rules, mark_pending);
+}
 
 // reduced rows -> state->mom[16], state->err[2] (contiguous in the state block); which = 1 moments, 2 error sums, 3 both
 __global__ __launch_bounds__(64) void icp_rows_to_state_kernel(IcpState* __restrict__ state, const double* __restrict__ part, int count, int which)
@@ -315,26 +358,11 @@ __global__ __launch_bounds__(256) void invert_order_kernel(const int* __restrict
 __global__ __launch_bounds__(64) void icp_solve_deferred_kernel(IcpState* __restrict__ state, const double* __restrict__ part, int count,
                                                                 int compose_mode, IcpRules rules, int mark_pending, int* __restrict__ sched_counters)
 {
-    if (sched_counters != nullptr && threadIdx.x < 2) sched_counters[threadIdx.x] = 0;   // the reduce kernel's range cursors (IcpSchedule)
+    // the reduce kernel's range cursors (IcpSchedule), both pairs: no dealing workgroup runs beside this launch
+    if (sched_counters != nullptr && threadIdx.x < ICP_SCHED_CURSORS) sched_counters[threadIdx.x] = 0;
     if (state->done != 0) return;
     __shared__ double sums[ICP_ROW];
-    if (part != nullptr) reduce_rows_wave(part, count, sums);
-    else {
-        if (threadIdx.x < ICP_ROW) sums[threadIdx.x] = threadIdx.x < ICP_MOMENTS ? state->mom[threadIdx.x] : state->err[threadIdx.x - ICP_MOMENTS];
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-    if (state->err_pending) {            // the previous iteration's error sums have arrived with these moments
-        state->err_pending = 0;
-        state->err[0] = sums[ICP_MOMENTS];
-        state->err[1] = sums[ICP_MOMENTS + 1];
-        finalize_iteration(state, sums[ICP_MOMENTS], sums[ICP_MOMENTS + 1], rules);
-        if (state->done != 0) return;    // its stop rule fired: nothing of this iteration is applied
-    }
-    double mom[ICP_MOMENTS];
-    for (int i = 0; i < ICP_MOMENTS; i++) { mom[i] = sums[i]; state->mom[i] = sums[i]; }
-    apply_solve(state, mom, compose_mode, rules.seq_sums, rules.svd_ieee);
-    if (mark_pending && state->done == 0) state->err_pending = 1;
+    solve_deferred_wave(state, part, count, sums, compose_mode, rules, mark_pending);
 }
 
 // the same evaluation alone, when the host stops enqueuing and wants the state
@@ -375,14 +403,28 @@ int icp_reduced_count(int nrows)
 // all_rows: write every one of the ICP_REDUCED_ROWS output rows, the ones past this cloud's own count as zeros (their workgroups find an
 // empty slice).  The multi-GPU path all-reduces the 64 rows IN PLACE: a rank whose share yields fewer rows than a neighbour's would
 // otherwise keep the neighbour's summed rows from the previous iteration and add them into the next collective.
-hipError_t icp_rows_reduce(const double* rows, int nrows, double* part, hipStream_t s, const IcpSchedule* sched, bool all_rows)
+hipError_t icp_rows_reduce(const double* rows, int nrows, double* part, hipStream_t s, const IcpSchedule* sched, bool all_rows, int parity)
 {
     const int g = icp_reduced_count(nrows);
     const int per = (nrows + g - 1) / g;
     const int n_sum = all_rows ? ICP_REDUCED_ROWS : g;
     IcpSchedule sc{};
     if (sched != nullptr) sc = *sched;
+    if (sc.counters != nullptr) sc.counters += 2 * (parity & 1);     // (the pair of cursors this step deals on)
     hipLaunchKernelGGL(icp_rows_reduce_kernel, dim3(sched != nullptr && sc.order != nullptr ? 2 * n_sum : n_sum), dim3(ROWS_REDUCE_THREADS), 0, s, rows, nrows, per, part, sc, n_sum);
+    return hipGetLastError();
+}
+
+hipError_t icp_rows_reduce_solve(IcpState* state, const double* rows, int nrows, double* part, const IcpSchedule* sched, int parity, int* ticket,
+                                 int compose_mode, const IcpRules& rules, int mark_pending, hipStream_t s)
+{
+    if (ticket == nullptr) return hipErrorInvalidValue;
+    const int g = icp_reduced_count(nrows);
+    const int per = (nrows + g - 1) / g;
+    IcpSchedule sc{};
+    if (sched != nullptr && sched->order != nullptr) sc = *sched;
+    hipLaunchKernelGGL(icp_rows_reduce_solve_kernel, dim3(sc.order != nullptr ? 2 * g : g), dim3(ROWS_REDUCE_THREADS), 0, s, state, rows, nrows, per, part, sc, g,
+                       parity & 1, ticket, compose_mode, rules, mark_pending);
     return hipGetLastError();
 }
 
@@ -390,7 +432,8 @@ __global__ __launch_bounds__(256) void icp_schedule_reset_kernel(IcpSchedule sch
 {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r < nrows) { sched.order[r] = r; sched.far[r] = 0; if (sched.lanes != nullptr) sched.lanes[r] = 0ull; }
-    if (r < 2) sched.counters[r] = 0;
+    if (r < ICP_SCHED_CURSORS) sched.counters[r] = 0;
+    if (r == 0 && sched.ticket != nullptr) *sched.ticket = 0;
 }
 
 hipError_t icp_schedule_reset(const IcpSchedule& sched, int nrows, hipStream_t s)
@@ -437,19 +480,7 @@ __global__ __launch_bounds__(ROWS_REDUCE_THREADS) void icp_reduce_solve_kernel(I
     }
     __syncthreads();
     if (threadIdx.x >= 64) return;                   // the first wave goes on alone (the barrier inside reduce_rows_wave then counts one wave)
-    reduce_rows_wave(part, count, sums);
-    if (threadIdx.x != 0) return;
-    if (state->err_pending) {
-        state->err_pending = 0;
-        state->err[0] = sums[ICP_MOMENTS];
-        state->err[1] = sums[ICP_MOMENTS + 1];
-        finalize_iteration(state, sums[ICP_MOMENTS], sums[ICP_MOMENTS + 1], rules);
-        if (state->done != 0) return;
-    }
-    double mom[ICP_MOMENTS];
-    for (int i = 0; i < ICP_MOMENTS; i++) { mom[i] = sums[i]; state->mom[i] = sums[i]; }
-    apply_solve(state, mom, compose_mode, rules.seq_sums, rules.svd_ieee);
-    if (mark_pending && state->done == 0) state->err_pending = 1;
+    solve_deferred_wave(state, part, count, sums, compose_mode, rules, mark_pending);
 }
 hipError_t icp_reduce_solve(IcpState* state, const double* rows, int nrows, int compose_mode, const IcpRules& rules, int mark_pending, hipStream_t s)
 {

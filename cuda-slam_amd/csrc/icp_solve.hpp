@@ -144,4 +144,30 @@ __device__ void finalize_iteration(IcpState* __restrict__ state, double e0, doub
     }
 }
 
+// K3 + K6, deferred, as one wave runs it: the sums of the `count` reduced rows (part == null: they are already in state->mom / state->err), the
+// PREVIOUS iteration's stop rule if its error sums were pending, then -- unless it fired -- the solve and the composition.  The one body behind
+// icp_solve_deferred_kernel, icp_reduce_solve_kernel and icp_rows_reduce_solve_kernel (icp_kernels.hip): the same instructions in the same order
+// whichever launch carries them.  Call with the 64 threads of the workgroup's first wave and state->done == 0; sums is LDS (ICP_ROW doubles).
+__device__ __forceinline__ void solve_deferred_wave(IcpState* __restrict__ state, const double* part, int count, double* sums, int compose_mode,
+                                                    const IcpRules& rules, int mark_pending)
+{
+    if (part != nullptr) reduce_rows_wave(part, count, sums);
+    else {
+        if (threadIdx.x < ICP_ROW) sums[threadIdx.x] = threadIdx.x < ICP_MOMENTS ? state->mom[threadIdx.x] : state->err[threadIdx.x - ICP_MOMENTS];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    if (state->err_pending) {            // the previous iteration's error sums have arrived with these moments
+        state->err_pending = 0;
+        state->err[0] = sums[ICP_MOMENTS];
+        state->err[1] = sums[ICP_MOMENTS + 1];
+        finalize_iteration(state, sums[ICP_MOMENTS], sums[ICP_MOMENTS + 1], rules);
+        if (state->done != 0) return;    // its stop rule fired: nothing of this iteration is applied
+    }
+    double mom[ICP_MOMENTS];
+    for (int i = 0; i < ICP_MOMENTS; i++) { mom[i] = sums[i]; state->mom[i] = sums[i]; }
+    apply_solve(state, mom, compose_mode, rules.seq_sums, rules.svd_ieee);
+    if (mark_pending && state->done == 0) state->err_pending = 1;
+}
+
 }  // namespace mislam

@@ -119,10 +119,16 @@ struct IcpSchedule {
     int* order;                            // nrows entries, always a permutation of the chunks
     unsigned char* far;                    // nrows flags
     unsigned long long* lanes;             // nrows lane masks (GridSearchArgs::far_lanes)
-    int* counters;                         // 2 cursors, zeroed by the solve kernel
+    int* counters;                         // ICP_SCHED_CURSORS cursors: two pairs, a step deals on the pair of its parity; zeroed by the solve
+    int* ticket;                           // arrivals of icp_rows_reduce_solve's summing workgroups; 0 between launches
 };
+constexpr int ICP_SCHED_CURSORS = 4;
 hipError_t icp_schedule_reset(const IcpSchedule& sched, int nrows, hipStream_t s);             // identity order, no flags
-hipError_t icp_rows_reduce(const double* rows, int nrows, double* part, hipStream_t s, const IcpSchedule* sched = nullptr, bool all_rows = false);   // -> part[icp_reduced_count(nrows)][18]
+hipError_t icp_rows_reduce(const double* rows, int nrows, double* part, hipStream_t s, const IcpSchedule* sched = nullptr, bool all_rows = false,
+                           int parity = 0);   // -> part[icp_reduced_count(nrows)][18]
+// the same launch with icp_solve_deferred behind it: the summing workgroup that arrives last (by `ticket`) solves.  One rank, part != null.
+hipError_t icp_rows_reduce_solve(IcpState* state, const double* rows, int nrows, double* part, const IcpSchedule* sched, int parity, int* ticket,
+                                 int compose_mode, const IcpRules& rules, int mark_pending, hipStream_t s);
 constexpr int ICP_FUSED_SOLVE_MAX_ROWS = 2048;      // up to this many rows (131 072 moving points) rows reduce + solve are one launch of one workgroup
 hipError_t icp_reduce_solve(IcpState* state, const double* rows, int nrows, int compose_mode, const IcpRules& rules, int mark_pending, hipStream_t s);
 // reduced rows -> state->mom / state->err (which: 1 moments, 2 error sums, 3 both); the multi-GPU paths all-reduce them there

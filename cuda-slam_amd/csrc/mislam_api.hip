@@ -227,6 +227,7 @@ static int ctx_create_common(int device, mi_ctx** out)
         c->tune.grid_split_walks = env_i("MISLAM_GRID_SPLIT_WALKS", -1);
         c->tune.icp_pipeline = env_i("MISLAM_ICP_PIPELINE", 1);
         c->tune.icp_fused_solve = env_i("MISLAM_ICP_FUSED_SOLVE", 1);
+        c->tune.icp_ticket_solve = env_i("MISLAM_ICP_TICKET_SOLVE", 1);
         c->tune.svd_ieee = env_i("MISLAM_SVD_IEEE", 0);
         if (const char* ppc = getenv("MISLAM_GRID_PPC")) { const float f = (float)atof(ppc); if (f >= 0.25f && f <= 64.f) c->tune.grid_points_per_cell = f; }
         if (const char* ppc = getenv("MISLAM_KNN_POINTS_PER_CELL")) { const float f = (float)atof(ppc); if (f >= 0.125f && f <= 1e30f) c->tune.knn_points_per_cell = f; }

@@ -791,6 +791,12 @@ int mi_selftest_fail_loads(mi_ctx* ctx, int n);
  * until it is really freed (behind the next drain of its context's stream).  Creating a context, using it and destroying it leaves the count where
  * it was: what the library's own tests check.  Needs no context. */
 int mi_selftest_live_buffers(long long* count);
+/* What the last ICP step of the loaded problem left on the device besides its result: rows = the moving cloud's 64-point chunks; the first
+ * min(cap_rows, rows) entries of the work order dealt for the next search (a permutation of the chunks, walking ones first) and of the chunks' flags
+ * (non-zero: its wave walked the box hierarchy); the four range cursors of the dealing (two pairs: a step deals on the pair of its parity and leaves the
+ * other pair zero); the arrival ticket of the rows reduction whose last workgroup solves (zero between launches); and the 16 moments and 2 error sums the
+ * last solve read.  order / far may be NULL when cap_rows is 0.  Test use only. */
+int mi_selftest_icp_schedule(mi_ctx* ctx, int cap_rows, int* order, unsigned char* far, int* rows, int cursors[4], int* ticket, double sums[18]);
 /* Name of the correspondence-search kernel (MI_KERNEL_NN) a search of n_moving points against m_fixed_local fixed points runs
  * with this nn_mode and the current settings -- the name a rocprofv3 kernel trace shows (static string). */
 const char* mi_nn_kernel_name(const mi_ctx* ctx, int n_moving, int m_fixed_local, int nn_mode);
