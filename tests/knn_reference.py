@@ -37,12 +37,15 @@ def d2_matrix(query, cloud, dist_mode):
     return fma_sq_f32(dz, fma_sq_f32(dy, dx * dx))
 
 
-def sorted_keys(query, cloud, dist_mode, max_d2=np.inf, keep=32, block=256):
+def sorted_keys(query, cloud, dist_mode, max_d2=np.inf, keep=32, block=256, only=None):
     """uint64 [n, keep]: every row's `keep` smallest keys, ascending, KEY_EMPTY where the candidates run out.  query None: self mode,
-    the key of candidate i is void in row i (by index).  (Rows are worked `block` at a time: the matrix itself is never held whole.)"""
+    the key of candidate i is void in row i (by index).  (Rows are worked `block` at a time: the matrix itself is never held whole.)
+    only: the answer's rows `only` alone, [len(only), keep] -- what a large case can afford; in self mode its row r voids candidate only[r]."""
     self_mode = query is None
     cloud = np.ascontiguousarray(cloud, np.float32)
     query = cloud if self_mode else np.ascontiguousarray(query, np.float32)
+    own = np.arange(len(query)) if only is None else np.asarray(only, np.int64)      # the caller's row of every row worked
+    query = query[own]
     n, m = len(query), len(cloud)
     out = np.empty((n, keep), np.uint64)
     column = np.arange(m, dtype=np.uint64)[None, :]
@@ -51,7 +54,7 @@ def sorted_keys(query, cloud, dist_mode, max_d2=np.inf, keep=32, block=256):
         rows = d2.shape[0]
         keys = (d2.view(np.uint32).astype(np.uint64) << np.uint64(32)) | column
         if self_mode:
-            keys[np.arange(rows), lo + np.arange(rows)] = KEY_EMPTY
+            keys[np.arange(rows), own[lo:lo + rows]] = KEY_EMPTY
         keys[d2 > np.float32(max_d2)] = KEY_EMPTY
         if m < keep:
             keys = np.concatenate([keys, np.full((rows, keep - m), KEY_EMPTY, np.uint64)], axis=1)

@@ -40,15 +40,17 @@ def statistical(cloud, k, dist_mode, std_ratio, keys=None):
     return mu, count, st, mu <= st[2]
 
 
-def radius_counts(cloud, radius, dist_mode, block=256):
-    """int32 [n]: the points j != i (by index) with d2(i, j) <= float32(radius)^2 in the arithmetic of dist_mode."""
+def radius_counts(cloud, radius, dist_mode, block=256, only=None):
+    """int32 [n]: the points j != i (by index) with d2(i, j) <= float32(radius)^2 in the arithmetic of dist_mode.
+    only: the counts of the points `only` alone, [len(only)] -- what a large case can afford."""
     cloud = np.ascontiguousarray(cloud, np.float32)
     r2 = np.float32(radius) * np.float32(radius)
-    out = np.empty(len(cloud), np.int32)
-    for lo in range(0, len(cloud), block):
-        inside = K.d2_matrix(cloud[lo:lo + block], cloud, dist_mode) <= r2
+    own = np.arange(len(cloud)) if only is None else np.asarray(only, np.int64)
+    out = np.empty(len(own), np.int32)
+    for lo in range(0, len(own), block):
+        inside = K.d2_matrix(cloud[own[lo:lo + block]], cloud, dist_mode) <= r2
         rows = inside.shape[0]
-        inside[np.arange(rows), lo + np.arange(rows)] = False
+        inside[np.arange(rows), own[lo:lo + rows]] = False
         out[lo:lo + rows] = inside.sum(axis=1)
     return out
 
