@@ -27,6 +27,7 @@ STOP_RUNNING, STOP_CONVERGED, STOP_MAX_ITERATIONS, STOP_NO_PAIRS, STOP_ERROR_INC
  KERNEL_CPD_CONTRACT, KERNEL_CPD_MSTEP, KERNEL_CPD_FGT) = range(10)
 KERNEL_NAMES = ["nn", "moments", "solve", "transform", "finalize", "allreduce", "cpd_denom", "cpd_contract", "cpd_mstep", "cpd_fgt"]
 CPD_APPROX_NONE, CPD_APPROX_FULL, CPD_APPROX_HYBRID = 0, 1, 2
+(CPD_ROUTE_EXACT_MFMA, CPD_ROUTE_EXACT_VALU, CPD_ROUTE_SEQUENTIAL, CPD_ROUTE_TRUNC_CULLED, CPD_ROUTE_TRUNC_EVERY_PAIR, CPD_ROUTE_FGT) = range(6)
 UNIQUE_ID_BYTES = 128
 EXCHANGE_MIN_U64, EXCHANGE_SUM_F64 = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)      # mi_exchange_fn
@@ -41,7 +42,7 @@ EXPORTS = [
     "mi_prepare_params_default", "mi_prepare_cloud", "mi_voxel_index", "mi_voxel_downsample", "mi_voxel_downsample_times",
     "mi_knn_search", "mi_knn_search_times", "mi_estimate_normals", "mi_estimate_normals_times",
     "mi_outlier_params_default", "mi_remove_outliers", "mi_remove_outliers_times",
-    "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_selftest_icp_schedule", "mi_nn_kernel_name",
+    "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_selftest_icp_schedule", "mi_selftest_cpd_last", "mi_nn_kernel_name",
 ]
 
 
@@ -840,6 +841,28 @@ class Context:
         order, far = np.zeros(rows.value, np.int32), np.zeros(rows.value, np.uint8)
         _check(f(self._h, rows.value, order.ctypes.data, far.ctypes.data, C.byref(rows), cursors.ctypes.data, C.byref(ticket), sums.ctypes.data))
         return dict(order=order, far=far, cursors=cursors, ticket=int(ticket.value), sums=sums)
+
+    def selftest_cpd_last(self, m, n, arrays=True):
+        """What the last cpd_register / cpd_mstep left in the workspace (mi_selftest_cpd_last; it must be the next call on the context): dict(p1 [m],
+        pt1 [n], px [m,3], y [m,3] -- with arrays=False these four are left out --, xs float64[5], ks float64[14], R [3,3], t [3], scale, sigma2,
+        sigma2_init, constant, route, fused, rows_x, rows_k, reduced, iterations, stop_reason)."""
+        f = lib().mi_selftest_cpd_last
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 13
+        f.restype = C.c_int
+        m, n = int(m), int(n)
+        out = {}
+        if arrays:
+            out.update(p1=np.zeros(m, np.float32), pt1=np.zeros(n, np.float32), px=np.zeros((m, 3), np.float32), y=np.zeros((m, 3), np.float32))
+        xs, ks, R9, t3 = np.zeros(5, np.float64), np.zeros(14, np.float64), np.zeros(9, np.float32), np.zeros(3, np.float32)
+        sc = [C.c_float(0) for _ in range(4)]
+        info = np.zeros(8, np.int32)
+        ptr = [out[k].ctypes.data if arrays else None for k in ("p1", "pt1", "px", "y")]
+        _check(f(self._h, m, n, *ptr, xs.ctypes.data, ks.ctypes.data, R9.ctypes.data, t3.ctypes.data,
+                 *[C.cast(C.byref(v), C.c_void_p) for v in sc], info.ctypes.data))
+        out.update(xs=xs, ks=ks, R=R9.reshape(3, 3).T.copy(), t=t3, scale=np.float32(sc[0].value), sigma2=np.float32(sc[1].value),
+                   sigma2_init=np.float32(sc[2].value), constant=np.float32(sc[3].value))
+        out.update(zip(("route", "fused", "rows_x", "rows_k", "reduced", "iterations", "stop_reason"), (int(v) for v in info[:7])))
+        return out
 
     def nn_kernel_name(self, n_moving, m_fixed_local, nn_mode=NN_AUTO):
         lib().mi_nn_kernel_name.restype = C.c_char_p

@@ -87,6 +87,7 @@ struct PrepState;      // prepare_api.hip
 struct mi_ctx {
     int device = 0;
     std::vector<void*> retired;                          // outgrown device buffers waiting for the next drain of `stream` (retire_buffers)
+    unsigned long long entered = 0;                      // entry points opened on this context so far (CtxScope): lets mi_selftest_cpd_last tell that nothing ran in between
     hipStream_t stream = nullptr;
     int rank = 0, world = 1;
     ncclComm_t comm = nullptr;

@@ -72,6 +72,10 @@ struct CpdWorkspace {
     bool queries_sharded = false;
     int a_lo = 0, a_hi = 0, m_lo = 0, m_hi = 0;
     mi_cpd_params params{};
+    // what mi_selftest_cpd_last reports besides the arrays (host bookkeeping only: nothing on the device depends on it)
+    int last_estep = -1;                      // MI_CPD_ROUTE_* of the last E-step enqueued (-1: none, or the caller's arrays of mi_cpd_mstep)
+    int last_fused = 0, last_rows_x = 0, last_rows_k = 0, last_reduced = 0;   // the last M-step: rows left by the E-step's own kernels?  how many it summed; through cpd_reduce_sums?
+    unsigned long long last_call = 0;         // mi_ctx::entered when the last mi_cpd_register / mi_cpd_mstep returned (0: none yet)
 };
 
 void cpd_workspace_destroy(mi_ctx* c)
@@ -111,6 +115,7 @@ static void plan_chunks(const mi_ctx* c, int owners, int owner_r, int stream_len
 // Uploads both clouds and sizes every buffer.  y starts as a copy of b (transformedCloud = cloudBefore, :104).
 static int cpd_load(mi_ctx* c, CpdWorkspace* w, const float* before_xyz, int m, const float* after_xyz, int n)
 {
+    w->last_call = 0;        // nothing to read back until a registration or an M-step has finished on these clouds
     c->prob.icp_loaded = false;   // the moving-cloud buffers are shared with the ICP driver
     w->fgt.a.swept_K = 0;    // a new fixed cloud: its clustering starts over
     w->fgt.y.guess_K = 0;    // a new moving cloud: nothing to guess its sweep from
@@ -193,6 +198,7 @@ static int cpd_estep_enqueue(mi_ctx* c, CpdWorkspace* w, const CpdView& v, int e
         // parity mode: cpu-slam's summation order (cpd_kernels.hip); the M-step's sums then come from the stand-alone kernels (sums_fresh = false)
         { ProfScope ps(c, MI_KERNEL_CPD_DENOM); MI_HIP(cpd_estep_sequential(v, c->stream)); }
         w->sums_fresh = false;
+        w->last_estep = MI_CPD_ROUTE_SEQUENTIAL;
         return MI_OK;
     }
     // the two post kernels also accumulate the M-step's moments of what they have just produced (two launches less per EM iteration)
@@ -203,6 +209,7 @@ static int cpd_estep_enqueue(mi_ctx* c, CpdWorkspace* w, const CpdView& v, int e
     MI_HIP(cpd_post_contract(v, c->stream, w->part_k.p, nkb));
     w->sums_fresh = true;
     w->sum_rows_x = nxb; w->sum_rows_k = nkb;
+    w->last_estep = v.truncate ? MI_CPD_ROUTE_TRUNC_EVERY_PAIR : use_mfma_contraction(c) ? MI_CPD_ROUTE_EXACT_MFMA : MI_CPD_ROUTE_EXACT_VALU;
     return MI_OK;
 }
 
@@ -270,6 +277,7 @@ static int cpd_estep_trunc_enqueue(mi_ctx* c, CpdWorkspace* w, const CpdView& v)
     { ProfScope ps(c, MI_KERNEL_CPD_CONTRACT); MI_HIP(cpd_trunc_contract(t, w->part_k.p, nkb, c->stream)); }
     w->sums_fresh = true;
     w->sum_rows_x = nxb; w->sum_rows_k = nkb;
+    w->last_estep = MI_CPD_ROUTE_TRUNC_CULLED;
     return MI_OK;
 }
 
@@ -281,7 +289,9 @@ static int cpd_mstep_enqueue(mi_ctx* c, CpdWorkspace* w, const CpdView& v, const
         MI_HIP(cpd_xsums(v, w->part_x.p, nxb, c->stream));
         MI_HIP(cpd_ksums(v, w->part_k.p, nkb, c->stream));
     } else { nxb = w->sum_rows_x; nkb = w->sum_rows_k; }     // (the rows the E-step's own kernels left)
+    w->last_fused = w->sums_fresh ? 1 : 0; w->last_rows_x = nxb; w->last_rows_k = nkb;
     w->sums_fresh = false;
+    w->last_reduced = 0;
     if (!c->distributed() || (w->replicated && !w->queries_sharded)) {
         MI_HIP(cpd_solve(w->d_state, w->part_x.p, nxb, w->part_k.p, nkb, rules, update_loop_state, c->stream));
         return MI_OK;
@@ -291,6 +301,7 @@ static int cpd_mstep_enqueue(mi_ctx* c, CpdWorkspace* w, const CpdView& v, const
     // never travel.  Every rank then runs the same solve.
     static_assert(offsetof(CpdState, ks) == offsetof(CpdState, xs) + sizeof(double) * CPD_XSUMS, "xs and ks must be contiguous");
     MI_HIP(cpd_reduce_sums(w->d_state, w->part_x.p, nxb, w->part_k.p, nkb, c->stream));
+    w->last_reduced = 1;
     MI_TRY(allreduce_sum_f64(c, w->d_state->xs, (size_t)(CPD_XSUMS + CPD_KSUMS)));
     MI_HIP(cpd_solve(w->d_state, nullptr, 0, nullptr, 0, rules, update_loop_state, c->stream));
     return MI_OK;
@@ -529,6 +540,7 @@ static int cpd_estep_fgt_enqueue(mi_ctx* c, CpdWorkspace* w, const CpdView& v, f
     MI_HIP(fgt_predict(v.yx + m0, v.yy + m0, v.yz + m0, mn, ca.xc, f->Ba.p, K, 4, hsigma, ratio_of_far_field, t, Sy, f->v4.p, c->stream));
     MI_HIP(fgt_post_px(f->v4.p, Sy, mn, v.p1 + m0, v.px + 3 * (size_t)m0, c->stream, with_sums ? w->part_k.p : nullptr, nkb, v.bx + m0, v.by + m0, v.bz + m0));
     if (with_sums) { w->sums_fresh = true; w->sum_rows_x = nxb; w->sum_rows_k = nkb; }
+    w->last_estep = MI_CPD_ROUTE_FGT;
     return MI_OK;
 }
 
@@ -703,6 +715,7 @@ extern "C" int mi_cpd_register(mi_ctx* c, const float* before_xyz, int m_before,
     // (bench.py's timers around this call used to miss that tail) and the workspace is quiet when the caller gets it back.
     MI_HIP(hipStreamSynchronize(c->stream));
     cpd_state_to_outputs(w->h_state, out_sR_t, out_scale, iterations, error);
+    w->last_call = c->entered;
     return MI_OK;
 }
 
@@ -996,11 +1009,53 @@ extern "C" int mi_cpd_mstep(mi_ctx* c, const float* before_xyz, int m, const flo
     mi_cpd_params p;
     mi_cpd_params_default(&p);
     p.const_scale = const_scale;
+    w->last_estep = -1;
     MI_TRY(cpd_mstep_enqueue(c, w, v, cpd_rules(w, &p), 0));
     MI_TRY(cpd_fetch(c, w));
+    w->last_call = c->entered;
     memcpy(out_R9, w->h_state->R, sizeof(float) * 9);
     memcpy(out_t3, w->h_state->t, sizeof(float) * 3);
     *scale = w->h_state->scale;
     *sigma2 = w->h_state->sigma2;
+    return MI_OK;
+}
+
+// Test-only read-back of what the last mi_cpd_register / mi_cpd_mstep left in the workspace (mi_slam.h).  Copies only: no kernel, no state change.
+extern "C" int mi_selftest_cpd_last(mi_ctx* c, int m, int n, float* p1, float* pt1, float* px, float* y_xyz, double xs[5], double ks[14],
+                                    float R9[9], float t3[3], float* scale, float* sigma2, float* sigma2_init, float* constant, int info[8])
+{
+    if (!c) { set_error("mi_selftest_cpd_last: null context"); return MI_ERR_INVALID_ARG; }
+    CpdWorkspace* w = c->cpd;
+    // (any other entry point on the context since then may have reused the moving cloud's buffers: the read-back must be the next call)
+    if (!w || w->last_call == 0 || w->last_call != c->entered) { set_error("mi_selftest_cpd_last: the last call on this context was no mi_cpd_register / mi_cpd_mstep"); return MI_ERR_STATE; }
+    if (m != w->m || n != w->n) { set_error("mi_selftest_cpd_last: sizes (%d, %d) are not the loaded ones (%d, %d)", m, n, w->m, w->n); return MI_ERR_STATE; }
+    MI_ENTER(c);
+    w->last_call = c->entered;           // (a read-back may be repeated)
+    std::vector<float> soa;
+    if (y_xyz) soa.resize(3 * (size_t)m);
+    if (p1) MI_HIP(hipMemcpyAsync(p1, w->p1.p, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    if (pt1) MI_HIP(hipMemcpyAsync(pt1, w->pt1.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (px) MI_HIP(hipMemcpyAsync(px, w->px.p, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    if (y_xyz) {
+        const float* src[3] = {c->cx.p, c->cy.p, c->cz.p};
+        for (int d = 0; d < 3; d++) MI_HIP(hipMemcpyAsync(soa.data() + (size_t)d * m, src[d], sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    }
+    MI_HIP(hipStreamSynchronize(c->stream));
+    if (y_xyz)
+        for (size_t i = 0; i < (size_t)m; i++)
+            for (int d = 0; d < 3; d++) y_xyz[3 * i + d] = soa[(size_t)d * m + i];
+    const CpdState* s = w->h_state;      // (as cpd_fetch left it)
+    if (xs) memcpy(xs, s->xs, sizeof(double) * 5);
+    if (ks) memcpy(ks, s->ks, sizeof(double) * 14);
+    if (R9) memcpy(R9, s->R, sizeof(float) * 9);
+    if (t3) memcpy(t3, s->t, sizeof(float) * 3);
+    if (scale) *scale = s->scale;
+    if (sigma2) *sigma2 = s->sigma2;
+    if (sigma2_init) *sigma2_init = s->sigma2_init;
+    if (constant) *constant = s->constant;
+    if (info) {
+        info[0] = w->last_estep; info[1] = w->last_fused; info[2] = w->last_rows_x; info[3] = w->last_rows_k;
+        info[4] = w->last_reduced; info[5] = s->iterations; info[6] = s->stop_reason; info[7] = 0;
+    }
     return MI_OK;
 }

@@ -46,7 +46,7 @@ void retire_later(void* p)
     (void)hipDeviceSynchronize();               // outside any context call (not a path the library takes): nothing may still read it after this
     device_free(p);
 }
-CtxScope::CtxScope(mi_ctx* c) : ctx(c), outer(t_retire_sink) { t_retire_sink = &c->retired; }
+CtxScope::CtxScope(mi_ctx* c) : ctx(c), outer(t_retire_sink) { t_retire_sink = &c->retired; c->entered += 1; }
 CtxScope::~CtxScope()
 {
     t_retire_sink = outer;

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MI_SLAM_ABI_VERSION 4   /* 4: mi_profile_search_phases, mi_selftest_fail_loads, mi_runtime_info (additive: no signature of version 3 changed), later and additive again: mi_icp_register_batch, mi_cpd_register_batch, mi_voxel_index, mi_voxel_downsample, mi_voxel_downsample_times, mi_knn_search, mi_knn_search_times, mi_estimate_normals, mi_estimate_normals_times; 3: mi_icp_load_times, mi_cross_moments, mi_icp_auto_batch; 2: mi_cpd_params gained sigma2_mode; mi_dist_info, mi_source_share, mi_cpd_sigma_squared_mode, mi_profile_search_stats, mi_selftest_sort_pairs */
+#define MI_SLAM_ABI_VERSION 4   /* 4: mi_profile_search_phases, mi_selftest_fail_loads, mi_runtime_info (additive: no signature of version 3 changed), later and additive again: mi_icp_register_batch, mi_cpd_register_batch, mi_voxel_index, mi_voxel_downsample, mi_voxel_downsample_times, mi_knn_search, mi_knn_search_times, mi_estimate_normals, mi_estimate_normals_times, mi_selftest_cpd_last; 3: mi_icp_load_times, mi_cross_moments, mi_icp_auto_batch; 2: mi_cpd_params gained sigma2_mode; mi_dist_info, mi_source_share, mi_cpd_sigma_squared_mode, mi_profile_search_stats, mi_selftest_sort_pairs */
 
 enum {
     MI_OK = 0,
@@ -797,6 +797,26 @@ int mi_selftest_live_buffers(long long* count);
  * other pair zero); the arrival ticket of the rows reduction whose last workgroup solves (zero between launches); and the 16 moments and 2 error sums the
  * last solve read.  order / far may be NULL when cap_rows is 0.  Test use only. */
 int mi_selftest_icp_schedule(mi_ctx* ctx, int cap_rows, int* order, unsigned char* far, int* rows, int cursors[4], int* ticket, double sums[18]);
+/* What the last mi_cpd_register / mi_cpd_mstep on this context left in the CPD workspace, copied out: the arrays of its last E-step (p1[m], pt1[n],
+ * px[3m] row-major -- for mi_cpd_mstep the caller's own), the moving cloud as the last transform left it (y_xyz[3m]; mi_cpd_mstep transforms nothing:
+ * the cloud as loaded), and from the state block the call's last host read brought back: the M-step's moments xs[5] = { sum log den, sum pt1 a (3),
+ * sum pt1 |a|^2 } and ks[14] = { Np, sum p1 b (3), sum b_r px_c (9, row-major in r), sum p1 |b|^2 } as the last solve read them, R9 (column-major), t3, scale,
+ * sigma2, sigma2_init, constant.  info[8] = { MI_CPD_ROUTE_* of the last E-step (-1: none ran, mi_cpd_mstep), 1 if the M-step summed the rows the
+ * E-step's own kernels left (0: the stand-alone sums kernels ran), rows of x-sums, rows of k-sums it summed, 1 if the moments went through the state
+ * block (a distributed context's reduce + all-reduce), iterations, stop reason, 0 }.  Every output pointer may be NULL.  m, n: the sizes of that call
+ * (n: this rank's share of the fixed cloud).  MI_ERR_STATE when the last entry point called on the context was not one of the two (any call in between
+ * may have reused the buffers; the read-back itself may be repeated) or when m / n are not the loaded sizes.  Launches no kernel and changes nothing
+ * a later call reads.  Test use only. */
+enum {
+    MI_CPD_ROUTE_EXACT_MFMA = 0,        /* exact P, matrix-pipe contraction */
+    MI_CPD_ROUTE_EXACT_VALU = 1,        /* exact P, vector-pipe contraction (MISLAM_CPD_MFMA=0) */
+    MI_CPD_ROUTE_SEQUENTIAL = 2,        /* MI_ESTEP_CPU_SEQUENTIAL */
+    MI_CPD_ROUTE_TRUNC_CULLED = 3,      /* hybrid mode's truncated E-step, culled by tile boxes */
+    MI_CPD_ROUTE_TRUNC_EVERY_PAIR = 4,  /* ... every pair (MISLAM_CPD_TRUNC_CULL=0) */
+    MI_CPD_ROUTE_FGT = 5                /* Fast Gauss Transform */
+};
+int mi_selftest_cpd_last(mi_ctx* ctx, int m, int n, float* p1, float* pt1, float* px, float* y_xyz, double xs[5], double ks[14], float R9[9],
+                         float t3[3], float* scale, float* sigma2, float* sigma2_init, float* constant, int info[8]);
 /* Name of the correspondence-search kernel (MI_KERNEL_NN) a search of n_moving points against m_fixed_local fixed points runs
  * with this nn_mode and the current settings -- the name a rocprofv3 kernel trace shows (static string). */
 const char* mi_nn_kernel_name(const mi_ctx* ctx, int n_moving, int m_fixed_local, int nn_mode);
