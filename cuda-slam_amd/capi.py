@@ -23,6 +23,7 @@ SIGMA2_EXACT, SIGMA2_CPU_SEQUENTIAL = 0, 1
 ESTEP_DEFAULT, ESTEP_CPU_SEQUENTIAL = 0, 1
 NN_INDEX_MIN_POINTS = 10000         # MI_NN_AUTO switches to the cell grid at this many fixed points (mi_slam.h MI_NN_INDEX_MIN_POINTS)
 STOP_RUNNING, STOP_CONVERGED, STOP_MAX_ITERATIONS, STOP_NO_PAIRS, STOP_ERROR_INCREASED, STOP_TOLERANCE, STOP_SIGMA = range(7)
+STOP_DEGENERATE = 7                 # MI_STOP_DEGENERATE (mi_icp_plane_register)
 (KERNEL_NN, KERNEL_MOMENTS, KERNEL_SOLVE, KERNEL_TRANSFORM, KERNEL_FINALIZE, KERNEL_ALLREDUCE, KERNEL_CPD_DENOM,
  KERNEL_CPD_CONTRACT, KERNEL_CPD_MSTEP, KERNEL_CPD_FGT) = range(10)
 KERNEL_NAMES = ["nn", "moments", "solve", "transform", "finalize", "allreduce", "cpd_denom", "cpd_contract", "cpd_mstep", "cpd_fgt"]
@@ -42,6 +43,7 @@ EXPORTS = [
     "mi_prepare_params_default", "mi_prepare_cloud", "mi_voxel_index", "mi_voxel_downsample", "mi_voxel_downsample_times",
     "mi_knn_search", "mi_knn_search_times", "mi_estimate_normals", "mi_estimate_normals_times",
     "mi_outlier_params_default", "mi_remove_outliers", "mi_remove_outliers_times",
+    "mi_plane_params_default", "mi_icp_plane_register", "mi_plane_system", "mi_icp_plane_times",
     "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_selftest_icp_schedule", "mi_selftest_cpd_last", "mi_nn_kernel_name",
 ]
 
@@ -77,6 +79,11 @@ class OutlierParams(C.Structure):
 
 class OutlierStats(C.Structure):
     _fields_ = [("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double), ("kept", C.c_longlong), ("reserved", C.c_int * 4)]
+
+
+class PlaneParams(C.Structure):
+    _fields_ = [("eps_rotation", C.c_float), ("eps_translation", C.c_float), ("max_iterations", C.c_int), ("max_distance_squared", C.c_float),
+                ("dist_mode", C.c_int), ("sync_every", C.c_int), ("verbose", C.c_int), ("reserved", C.c_int * 9)]
 
 
 class MiSlamError(RuntimeError):
@@ -311,6 +318,44 @@ def remove_outliers_raw(handle, cloud, n, params, out_xyz, out_index, out_n, kee
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
     f.restype = C.c_int
     return f(handle, cloud, n, params, out_xyz, out_index, out_n, keep, mean_distance, neighbours, stats)
+
+
+def plane_params(**kw):
+    """mi_plane_params at its defaults (eps 1e-6 and 1e-6, 50 iterations, no distance limit, CPU rounding) with the given fields set."""
+    p = PlaneParams()
+    lib().mi_plane_params_default.restype = None
+    lib().mi_plane_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def icp_plane_register_raw(handle, before, n, after, normals, m, params, init_T, out_T, iterations, error, stop_reason):
+    """mi_icp_plane_register with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_icp_plane_register
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+    f.restype = C.c_int
+    return f(handle, before, n, after, normals, m, params, init_T, out_T, iterations, error, stop_reason)
+
+
+def plane_system_raw(handle, before, n, after, normals, m, T, dist_mode, max_d2, out_sums, out_centre, out_idx):
+    """mi_plane_system with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_plane_system
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    return f(handle, before, n, after, normals, m, T, dist_mode, max_d2, out_sums, out_centre, out_idx)
+
+
+def _T16(T):
+    """A transform as the C interface takes it: None, or 16 float32 column-major from a [4, 4] array indexed [row, col]."""
+    if T is None:
+        return None
+    T = np.asarray(T, np.float32)
+    if T.shape != (4, 4):
+        raise ValueError("a transform is a [4, 4] array indexed [row, col]")
+    return np.ascontiguousarray(T.T).reshape(16)
 
 
 def icp_auto_batch(n_moving_total, m_fixed_total, world, source_sharded, every_pair_search):
@@ -785,6 +830,44 @@ class Context:
         out = (C.c_double * 8)()
         _check(lib().mi_remove_outliers_times(self._h, out))
         return dict(zip(("workspace", "upload", "check", "grid", "order", "kernel", "finish", "total"), list(out)))
+
+    # ---- point-to-plane ICP
+    def icp_plane_register(self, before, after, after_normals, params, init=None):
+        """Point-to-plane ICP of `before` onto `after` with its normals (mi_icp_plane_register; params: plane_params(...); init: a [4, 4]
+        transform indexed [row, col], None for the identity) -> (R [3, 3], t [3], iterations, error, stop_reason)."""
+        before, after, normals = _cloud(before), _cloud(after), _cloud(after_normals)
+        if normals.shape != after.shape:
+            raise ValueError("after_normals must have one normal per fixed point")
+        T0 = _T16(init)
+        T = np.zeros(16, np.float32)
+        it, err, why = C.c_int(0), C.c_float(0), C.c_int(0)
+        _check(icp_plane_register_raw(self._h, before.ctypes.data, before.shape[0], after.ctypes.data, normals.ctypes.data, after.shape[0],
+                                      C.addressof(params), None if T0 is None else T0.ctypes.data, T.ctypes.data, C.addressof(it), C.addressof(err),
+                                      C.addressof(why)))
+        R, t = _T_to_Rt(T)
+        return R, t, it.value, err.value, why.value
+
+    def plane_system(self, before, after, after_normals, T=None, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_idx=True):
+        """One point-to-plane linearisation at transform T (mi_plane_system) -> (sums float64 [32], centre float32 [3], idx int32 [n] if asked
+        for: the fixed index of every moving point's pair, -1 where it has none)."""
+        before, after, normals = _cloud(before), _cloud(after), _cloud(after_normals)
+        if normals.shape != after.shape:
+            raise ValueError("after_normals must have one normal per fixed point")
+        T0 = _T16(T)
+        n = before.shape[0]
+        sums, centre = np.zeros(32, np.float64), np.zeros(3, np.float32)
+        idx = np.empty(n, np.int32) if want_idx else None
+        _check(plane_system_raw(self._h, before.ctypes.data, n, after.ctypes.data, normals.ctypes.data, after.shape[0],
+                                None if T0 is None else T0.ctypes.data, int(dist_mode), float(max_d2), sums.ctypes.data, centre.ctypes.data,
+                                None if idx is None else idx.ctypes.data))
+        return (sums, centre, idx) if want_idx else (sums, centre)
+
+    def icp_plane_times(self):
+        """ms per stage of the last icp_plane_register / plane_system: workspace, upload, check, grid, order, iterations, download, total
+        (mi_icp_plane_times)."""
+        out = (C.c_double * 8)()
+        _check(lib().mi_icp_plane_times(self._h, out))
+        return dict(zip(("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"), list(out)))
 
     # ---- profiling
     def profile_enable(self, on=True):

@@ -235,6 +235,19 @@ struct mi_ctx {
         double ms[MI_OUTLIER_STAGES] = {0};              // mi_remove_outliers_times
     } outlier;
 
+    // ---- mi_icp_plane_register, mi_plane_system: a search front end over the FIXED cloud with the moving cloud as its queries, the fixed
+    // cloud's normals, the rows of an iteration's sums and the loop's state block -- a sibling of the three above, nothing shared with mi_icp_*
+    struct PlaneBuffers {
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<float> nx, ny, nz;                // the normals, SoA, the caller's order (what their input check reads)
+        mislam::DevBuf<float4> normals;                  // the same, packed (what the step kernel gathers)
+        mislam::DevBuf<mislam::KnnState> nstate;         // the normals' input check
+        mislam::DevBuf<double> rows, parts;              // one row of PLANE_ROW sums per 64 moving points; the slabs' sums
+        mislam::DevBuf<mislam::PlaneState> state;
+        mislam::DevBuf<int> out_idx;                     // mi_plane_system's out_idx
+        double ms[MI_PLANE_STAGES] = {0};                // mi_icp_plane_times
+    } plane;
+
     // ---- mi_prepare_cloud: buffers of its own, like the voxel call's: the raw cloud, the prepared one, the caller's index vectors and draws
     struct PrepareBuffers {
         mislam::DevBuf<float> raw, out, partials, noise_unit, outlier_unit;
@@ -329,7 +342,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 
 // ---- the front end of a search over a cloud's cell grid (search_front.hip).  A driver calls, in this order: search_front_reserve and its own
 // reserves (every reserve comes before the first upload), clock.mark(0), search_front_upload_and_check (stages 1 and 2: nothing has been written
@@ -349,7 +362,7 @@ int search_front_upload_and_check(mi_ctx* c, SearchFrontBuffers& b, StageClock& 
 int search_front_index_and_order(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, const char* who, float points_per_cell, SearchFront* f);
 // the host-side shape check of what every search kernel indexes: q*, order, c*, the grid's offsets and points
 bool search_front_fits(const SearchFrontBuffers& b, const SearchFront& f);
-void search_front_destroy_events(mi_ctx* c);         // of all three calls' front ends (mi_ctx_destroy)
+void search_front_destroy_events(mi_ctx* c);         // of every call's front end (mi_ctx_destroy)
 // Stage 5: `launch` enqueues the call's search kernel.  With profiling on, the slot holds the launch's own HIP-event time instead of the host's.
 template <class Launch>
 static inline int search_front_timed_launch(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, Launch&& launch)

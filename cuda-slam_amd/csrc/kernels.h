@@ -339,6 +339,53 @@ struct OutlierCompactArgs {
 };
 hipError_t outlier_compact(const OutlierCompactArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K16 point-to-plane ICP (plane_kernels.hip; driver: plane_api.hip; the solve: plane_solve.hpp): K13's search with one key per lane
+// (NearestSink, knn_scan.hpp), the pair's 29 fp64 terms summed over the wave into one row per 64 moving points, the rows summed in a
+// fixed order, and one lane's 6 x 6 solve, pose update and stop rule in the device state block
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int PLANE_ROW = 32;                // doubles per row and per system: mi_plane_system's out_sums
+constexpr int PLANE_ONE_STAGE_ROWS = 1024;   // up to this many rows (65 536 moving points) one workgroup sums the rows and solves in one launch
+constexpr int PLANE_PARTS = 64;              // beyond: this many workgroups sum a slab of rows each first (a function of the row count alone)
+constexpr int MI_STOP_DEGENERATE_ = 7;       // mirror of MI_STOP_DEGENERATE (mi_slam.h; plane_api.hip asserts it)
+
+// Device-resident loop state of one plane registration.  The host only ever copies it back; every decision is taken on the device.
+struct PlaneState {
+    double R[9];             // running rotation, ROW-major
+    double t[3];             // running translation
+    double c0[3];            // the centre the moments are taken about, promoted from its fp32 value
+    double sums[PLANE_ROW];  // the last linearisation's system
+    double omega, v;         // lengths of the last update's two halves
+    double min_pivot;        // smallest pivot of the last solve (0: a bad diagonal)
+    int iterations;          // updates applied
+    int done;
+    int stop_reason;
+    int pad;
+};
+
+struct PlaneStepArgs {
+    const PlaneState* state;         // the pose to linearise at (rounded to fp32 by every lane), the centre, done
+    const float *bx, *by, *bz;       // the moving cloud along its curve order, SoA, n entries
+    const int* order;                // sorted slot -> the caller's moving index
+    const float *ax, *ay, *az;       // the fixed cloud in the caller's order, SoA: what a match's index points into
+    const float4* normals;           // the fixed cloud's normals in the caller's order (w unused)
+    int n;
+    float max_d2;                    // a match with d2 > this is no pair (+inf: no limit)
+    float hi[3];                     // upper corner of the fixed cloud's bounding box (the lower one is the grid's origin)
+    double* rows;                    // plane_row_count(n) x PLANE_ROW
+    int* idx;                        // may be null; n, the caller's order: the matched fixed index of a pair, -1 otherwise
+};
+struct PlaneRules {
+    double eps_rotation, eps_translation;
+    int max_iterations;
+    int solve;                       // 0: the sums go into the state and nothing else happens (mi_plane_system)
+};
+int plane_row_count(int n);          // rows of a moving cloud of n points: one per 64
+int plane_part_count(int nrows);     // 0: one launch sums the rows and solves; else the slabs of the first of two
+hipError_t plane_step(const NnGridView& g, const PlaneStepArgs& a, int fma, hipStream_t s);
+// rows -> state->sums -> (rules.solve) the solve, the update and the stop rule; parts: plane_part_count(nrows) x PLANE_ROW doubles, null where that is 0
+hipError_t plane_reduce_solve(PlaneState* state, const double* rows, int nrows, double* parts, const PlaneRules& rules, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -354,5 +401,6 @@ hipError_t preload_voxel_kernels();
 hipError_t preload_knn_kernels();
 hipError_t preload_normals_kernels();
 hipError_t preload_outlier_kernels();
+hipError_t preload_plane_kernels();
 
 }  // namespace mislam

@@ -1,6 +1,7 @@
-// K13 / K14 / K15 -- the search body of the kernels that walk a cloud's cell grid, stated once: the walk over Chebyshev shells of cells with
+// K13 / K14 / K15 / K16 -- the search body of the kernels that walk a cloud's cell grid, stated once: the walk over Chebyshev shells of cells with
 // its stop rule (shell_walk; the contract and the proof of the stop rule: the head of knn_kernels.hip), the sorted list of K keys in
-// registers that the exact k-NN kernels feed from it (knn_scan) and the counter of the fixed-radius kernel (radius_scan), and what the
+// registers that the exact k-NN kernels feed from it (knn_scan), the counter of the fixed-radius kernel (radius_scan) and the single key of
+// the plane ICP's match (NearestSink; plane_kernels.hip), and what the
 // kernels share around them: the lane's query (knn_lane) and the host's choice of an instantiation (knn_dispatch).
 // knn_search_kernel (knn_kernels.hip) writes the list out; knn_normals_kernel (normals_kernels.hip) and knn_outlier_score_kernel
 // (outlier_kernels.hip) go on with the keys still in registers.  One lane per query; no LDS, no scratch: every index into the list is static.
@@ -121,6 +122,25 @@ __device__ __forceinline__ void knn_scan(const NnGridView& g, const float (&q)[3
     KnnListSink<K> sink{l, skip, max_d2};
     shell_walk<FMA>(g, q, hi, sink);
 }
+
+// one key as a sink (K16's match): the smallest key (bits(d2) << 32) | j met so far, KNN_KEY_EMPTY until a candidate within max_d2 came; the
+// reach is min(best distance, max_d2), with KnnListSink's strict stop -- so the key is row 0 of mi_knn_search with k = 1, bit for bit
+struct NearestSink {
+    static constexpr bool LEAVES = false;
+    unsigned long long best;
+    float max_d2;
+    __device__ __forceinline__ bool take(float d2, unsigned int pj)
+    {
+        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | pj;
+        if (key < best && d2 <= max_d2) best = key;
+        return false;
+    }
+    __device__ __forceinline__ bool stop(float bound) const
+    {
+        const float nearest = __uint_as_float((unsigned int)(best >> 32));             // (+inf while nothing was taken)
+        return bound > nearest || bound > max_d2;
+    }
+};
 
 // a counter as a sink (K15's radius method): the reach is r2, and a point AT r2 counts
 template <bool EARLY>

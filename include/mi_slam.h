@@ -728,6 +728,96 @@ int mi_remove_outliers(mi_ctx* ctx, const float* cloud_xyz, int n, const mi_outl
 int mi_remove_outliers_times(mi_ctx* ctx, double out_ms[MI_OUTLIER_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * Point-to-plane ICP (no reference counterpart: the reference's ICP is point-to-point): the registration the normals are for
+ * (plane registration).  It minimises sum (n_j . (R b_i + t - a_j))^2 over the matched pairs, linearised about the
+ * current pose, and does not stall on surfaces that slide along themselves.  A sibling of mi_icp_register with buffers, state and
+ * kernels of its own; single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+#define MI_STOP_DEGENERATE 7      /* point-to-plane: the 6 x 6 system does not determine all six motions */
+
+typedef struct mi_plane_params {
+    float eps_rotation;           /* converged when |omega| <= this (radians) ...            default 1e-6 */
+    float eps_translation;        /* ... and |v| <= this (the clouds' units)                 default 1e-6 */
+    int   max_iterations;         /* >= 0; there is no unbounded mode                        default 50   */
+    float max_distance_squared;   /* a match with d2 > this is no pair; INFINITY: no limit   default INFINITY */
+    int   dist_mode;              /* MI_DIST_CPU_ROUNDING / MI_DIST_FMA, as mi_knn_search     default CPU_ROUNDING */
+    int   sync_every;             /* iterations enqueued between host reads of the state; 0 = 4; moves no bit */
+    int   verbose;
+    int   reserved[9];
+} mi_plane_params;
+void mi_plane_params_default(mi_plane_params* p);
+
+/* Registers the moving cloud `before` (n points) onto the fixed cloud `after` (m points) with normals, on the device.  Every rule below
+ * can be retraced in numpy (tests/plane_reference.py does).
+ *   Transform: T, init_T and out_T are column-major 4 x 4 like every transform of this library, T[4 * col + row]; only the rotation
+ *     block and the translation column are read.  The rotation block is used as given: neither checked for orthonormality nor
+ *     re-orthonormalised.  init_T (NULL: the identity) is promoted to fp64 exactly, and the running pose (R, t) is held in fp64 on the
+ *     device.  An iteration applies the pose's rounding to fp32: with every R_ij and t_i rounded once to fp32 and every operation below
+ *     rounded to fp32, in this order, q_x = ((R00*b_x + R01*b_y) + R02*b_z) + t_x, and likewise q_y and q_z.
+ *   Match: the pair of moving point i is row i of mi_knn_search(ctx, q, n, after_xyz, m, 1, dist_mode, max_distance_squared, ...), key
+ *     for key: the same distance arithmetic on the fp32 differences a_j - q_i, equal distance bits going to the lower index.  A query
+ *     without a candidate within the limit has no pair.  A query whose matched normal is exactly (0, 0, 0) has no pair either:
+ *     mi_estimate_normals writes that normal for a point with fewer than three neighbours.  Normals are otherwise used as given, unit
+ *     length or not.
+ *   Centre: c0 = 0.5f * (lo + hi) per axis, one fp32 addition and one fp32 multiplication, of the fixed cloud's bounding box.  The
+ *     moments are taken about c0, which keeps the system's conditioning independent of the clouds' offset from the origin.
+ *   Terms, every operand promoted to fp64 first: r = n . (q - a), J = [(q - c0) x n, n] (six numbers: the three of the rotation
+ *     about c0, then the three of the translation).
+ *   Sums (mi_plane_system's out_sums): [0, 21) the upper triangle of A = sum J J^T, row-major; [21, 27) g = sum J r; [27] sum r^2;
+ *     [28] sum d2 (the matches' fp32 squared distances); [29] the number of pairs; [30, 32) 0.  The sums are added in a fixed order
+ *     that depends on n alone, with no floating-point atomics: the same input gives the same bits on every call, whatever ran on the
+ *     context before.
+ *   Solve: fewer than 6 pairs stop the loop with MI_STOP_NO_PAIRS.  A diagonal entry of A that is <= 0 or not finite stops it with
+ *     MI_STOP_DEGENERATE (an exact plane has diagonal entries that are exactly 0).  Otherwise A is scaled to a unit diagonal,
+ *     S = D^-1/2 A D^-1/2, and S is factored as L D' L^T without pivoting in fp64; a pivot below 1e-10 stops the loop with
+ *     MI_STOP_DEGENERATE (a well-constrained scene has a smallest pivot of about 0.6).  Either stop leaves the pose of the previous
+ *     iteration untouched.  Otherwise x = (omega, v) solves A x = -g.
+ *   Update: dR = exp([omega]x) by Rodrigues' formula in fp64 (its series below |omega| = 1e-8); R <- dR R;
+ *     t <- dR (t - c0) + c0 + v.
+ *   Stop rule, tested in this order after every update: MI_STOP_CONVERGED when both |omega|_2 <= eps_rotation and
+ *     |v|_2 <= eps_translation; MI_STOP_MAX_ITERATIONS when `iterations` has reached max_iterations.  max_iterations = 0 returns init_T
+ *     (or the identity) with 0 iterations, error 0 and MI_STOP_MAX_ITERATIONS.
+ *   Outputs: out_T is the fp64 pose rounded once to fp32 (bottom row 0 0 0 1); *iterations counts the updates applied; *error is
+ *     sum r^2 / pairs of the last linearisation -- the one the last update, or the stop, was decided from -- rounded to fp32, and 0
+ *     when that linearisation had no pair; *stop_reason is one of the four MI_STOP_* above.  Any of the last three may be NULL.
+ *   sync_every: the iterations run on the device, sync_every of them enqueued between two host reads of the state block (0: 4); a
+ *     launch behind the stop returns at once.  It moves no bit of any output.
+ *   The search is exact for any start; the speed is only claimed for a start within a few cells of the fixed cloud, as mi_knn_search
+ *     says of itself.  A finite max_distance_squared bounds every walk.  Nothing bounds the pose: a huge init_T or a barely determined
+ *     solve can carry q to infinity or NaN; such a point has no pair and its lane walks the whole grid, so a diverged pose shows as
+ *     slow iterations that end in MI_STOP_NO_PAIRS, not as an error.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name and names the cause and, for a bad point, which array and
+ *     which index (the lowest); NO output has been written -- for a NULL ctx, before_xyz, after_xyz, after_normals_xyz, params or
+ *     out_T; n < 1 or m < 1; a dist_mode other than the two of mi_knn_search; max_distance_squared NaN or negative; eps_rotation or
+ *     eps_translation NaN or negative; max_iterations < 0; sync_every < 0; a non-finite entry of init_T's rotation block or translation
+ *     column; a non-finite coordinate or normal component, or one above 1e18 in magnitude.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything mi_knn_search, mi_estimate_normals and
+ *     mi_remove_outliers keep: it works in buffers of its own.
+ *   Synchronous, host in and host out. */
+int mi_icp_plane_register(mi_ctx* ctx, const float* before_xyz, int n,
+                          const float* after_xyz, const float* after_normals_xyz, int m,
+                          const mi_plane_params* params, const float init_T[16] /* may be NULL: identity */,
+                          float out_T[16], int* iterations, float* error, int* stop_reason);
+
+/* One linearisation at a given transform, for tests and callers who run their own loop: the sums above at the pose T (NULL: the
+ * identity, the same bits), the centre c0, and per moving point the fixed index of its pair, or -1 where it has none.  The same
+ * arguments are refused, with out_sums in the place of out_T; out_centre and out_idx may be NULL. */
+int mi_plane_system(mi_ctx* ctx, const float* before_xyz, int n, const float* after_xyz, const float* after_normals_xyz, int m,
+                    const float T[16] /* may be NULL */, int dist_mode, float max_distance_squared,
+                    double out_sums[32], float out_centre[3], int* out_idx /* may be NULL; n: matched fixed index or -1 */);
+
+/* Where the last mi_icp_plane_register or mi_plane_system of this context spent its host wall time, in ms (measurement hook,
+ * tools/plane_icp_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA (normals, fixed cloud, moving cloud, state)
+ *   out[2] input checks, bounding box, read-backs   out[3] cell grid over the fixed cloud
+ *   out[4] curve order of the moving cloud + permute out[5] the iterations, host reads of the state included
+ *   out[6] download of the results                  out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage). */
+#define MI_PLANE_STAGES 8
+int mi_icp_plane_times(mi_ctx* ctx, double out_ms[MI_PLANE_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
  * -------------------------------------------------------------------------------------------------------------- */
 enum {
