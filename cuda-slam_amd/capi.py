@@ -44,6 +44,7 @@ EXPORTS = [
     "mi_knn_search", "mi_knn_search_times", "mi_estimate_normals", "mi_estimate_normals_times",
     "mi_outlier_params_default", "mi_remove_outliers", "mi_remove_outliers_times",
     "mi_plane_params_default", "mi_icp_plane_register", "mi_plane_system", "mi_icp_plane_times",
+    "mi_estimate_covariances", "mi_icp_gicp_register", "mi_gicp_system", "mi_icp_gicp_times",
     "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_selftest_icp_schedule", "mi_selftest_cpd_last", "mi_nn_kernel_name",
 ]
 
@@ -346,6 +347,47 @@ def plane_system_raw(handle, before, n, after, normals, m, T, dist_mode, max_d2,
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     f.restype = C.c_int
     return f(handle, before, n, after, normals, m, T, dist_mode, max_d2, out_sums, out_centre, out_idx)
+
+
+COV_RAW, COV_PLANE = 0, 1     # MI_COV_*
+
+
+def estimate_covariances_raw(handle, cloud, n, k, dist_mode, max_d2, mode, epsilon, cov6, count):
+    """mi_estimate_covariances with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_estimate_covariances
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    return f(handle, cloud, n, k, dist_mode, max_d2, mode, epsilon, cov6, count)
+
+
+def icp_gicp_register_raw(handle, before, before_cov, n, after, after_cov, m, params, init_T, out_T, iterations, error, stop_reason):
+    """mi_icp_gicp_register with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_icp_gicp_register
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+    f.restype = C.c_int
+    return f(handle, before, before_cov, n, after, after_cov, m, params, init_T, out_T, iterations, error, stop_reason)
+
+
+def gicp_system_raw(handle, before, before_cov, n, after, after_cov, m, T, dist_mode, max_d2, out_sums, out_centre, out_idx):
+    """mi_gicp_system with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_gicp_system
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    return f(handle, before, before_cov, n, after, after_cov, m, T, dist_mode, max_d2, out_sums, out_centre, out_idx)
+
+
+def icp_gicp_times_raw(handle, out_ms):
+    """mi_icp_gicp_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_icp_gicp_times
+    f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
+    return f(handle, out_ms)
+
+
+def _cov6(a, points):
+    a = np.ascontiguousarray(a, np.float32)
+    if a.shape != (points, 6):
+        raise ValueError("covariances are [points, 6]: xx, xy, xz, yy, yz, zz per point")
+    return a
 
 
 def _T16(T):
@@ -867,6 +909,55 @@ class Context:
         (mi_icp_plane_times)."""
         out = (C.c_double * 8)()
         _check(lib().mi_icp_plane_times(self._h, out))
+        return dict(zip(("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"), list(out)))
+
+    # ---- generalized ICP
+    def estimate_covariances(self, cloud, k, mode=COV_PLANE, epsilon=1e-3, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_count=False):
+        """Per-point covariances from every point's k nearest neighbours (mi_estimate_covariances): [n, 6] float32, the upper triangle row by
+        row (xx, xy, xz, yy, yz, zz); COV_RAW: the neighbourhood's covariance, COV_PLANE: its eigenvalues replaced by (epsilon, 1, 1); six zeros
+        where a point has fewer than two neighbours; then count [n] if asked for."""
+        cloud = _cloud(cloud)
+        n = cloud.shape[0]
+        cov = np.empty((n, 6), np.float32)
+        count = np.empty(n, np.int32) if want_count else None
+        _check(estimate_covariances_raw(self._h, cloud.ctypes.data, n, int(k), int(dist_mode), float(max_d2), int(mode), float(epsilon), cov.ctypes.data,
+                                        None if count is None else count.ctypes.data))
+        return (cov, count) if want_count else cov
+
+    def icp_gicp_register(self, before, before_cov, after, after_cov, params, init=None):
+        """Generalized ICP of `before` onto `after` with both clouds' covariances [points, 6] (mi_icp_gicp_register; params:
+        plane_params(...); init: a [4, 4] transform indexed [row, col], None for the identity) -> (R [3, 3], t [3], iterations, error,
+        stop_reason)."""
+        before, after = _cloud(before), _cloud(after)
+        cb, ca = _cov6(before_cov, before.shape[0]), _cov6(after_cov, after.shape[0])
+        T0 = _T16(init)
+        T = np.zeros(16, np.float32)
+        it, err, why = C.c_int(0), C.c_float(0), C.c_int(0)
+        _check(icp_gicp_register_raw(self._h, before.ctypes.data, cb.ctypes.data, before.shape[0], after.ctypes.data, ca.ctypes.data, after.shape[0],
+                                     C.addressof(params), None if T0 is None else T0.ctypes.data, T.ctypes.data, C.addressof(it), C.addressof(err),
+                                     C.addressof(why)))
+        R, t = _T_to_Rt(T)
+        return R, t, it.value, err.value, why.value
+
+    def gicp_system(self, before, before_cov, after, after_cov, T=None, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_idx=True):
+        """One generalized-ICP linearisation at transform T (mi_gicp_system) -> (sums float64 [32], centre float32 [3], idx int32 [n] if asked
+        for: the fixed index of every moving point's pair, -1 where it has none)."""
+        before, after = _cloud(before), _cloud(after)
+        cb, ca = _cov6(before_cov, before.shape[0]), _cov6(after_cov, after.shape[0])
+        T0 = _T16(T)
+        n = before.shape[0]
+        sums, centre = np.zeros(32, np.float64), np.zeros(3, np.float32)
+        idx = np.empty(n, np.int32) if want_idx else None
+        _check(gicp_system_raw(self._h, before.ctypes.data, cb.ctypes.data, n, after.ctypes.data, ca.ctypes.data, after.shape[0],
+                               None if T0 is None else T0.ctypes.data, int(dist_mode), float(max_d2), sums.ctypes.data, centre.ctypes.data,
+                               None if idx is None else idx.ctypes.data))
+        return (sums, centre, idx) if want_idx else (sums, centre)
+
+    def icp_gicp_times(self):
+        """ms per stage of the last icp_gicp_register / gicp_system: workspace, upload, check, grid, order, iterations, download, total
+        (mi_icp_gicp_times)."""
+        out = (C.c_double * 8)()
+        _check(icp_gicp_times_raw(self._h, out))
         return dict(zip(("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"), list(out)))
 
     # ---- profiling

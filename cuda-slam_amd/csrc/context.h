@@ -248,6 +248,28 @@ struct mi_ctx {
         double ms[MI_PLANE_STAGES] = {0};                // mi_icp_plane_times
     } plane;
 
+    // ---- mi_estimate_covariances: mi_estimate_normals' sibling with six floats per point as its result, in buffers of its own
+    struct CovarianceBuffers {
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<float> out_cov;
+        mislam::DevBuf<int> out_count;
+        double ms[MI_NORMALS_STAGES] = {0};              // (the stages of mi_estimate_normals_times; no entry point reads them yet)
+    } cov;
+
+    // ---- mi_icp_gicp_register, mi_gicp_system: PlaneBuffers' sibling -- a search front end over the FIXED cloud with the moving cloud as its
+    // queries, both clouds' covariances, the rows of an iteration's sums and the loop's state block (K16's layout: its reduce and solve run on them)
+    struct GicpBuffers {
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<float> cov_staging;               // a cloud's covariances as uploaded, six floats each
+        mislam::DevBuf<float4> cov_a;                    // the fixed cloud's, two float4 each, the caller's order (what the step kernel gathers)
+        mislam::DevBuf<float4> cov_b_in, cov_b;          // the moving cloud's: the caller's order, and along the curve (what the step kernel streams)
+        mislam::DevBuf<int> cov_bad;                     // [0] the moving, [1] the fixed cloud's lowest refused covariance, or KNN_NO_POINT
+        mislam::DevBuf<double> rows, parts;
+        mislam::DevBuf<mislam::PlaneState> state;
+        mislam::DevBuf<int> out_idx;                     // mi_gicp_system's out_idx
+        double ms[MI_GICP_STAGES] = {0};                 // mi_icp_gicp_times
+    } gicp;
+
     // ---- mi_prepare_cloud: buffers of its own, like the voxel call's: the raw cloud, the prepared one, the caller's index vectors and draws
     struct PrepareBuffers {
         mislam::DevBuf<float> raw, out, partials, noise_unit, outlier_unit;
@@ -342,7 +364,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 
 // ---- the front end of a search over a cloud's cell grid (search_front.hip).  A driver calls, in this order: search_front_reserve and its own
 // reserves (every reserve comes before the first upload), clock.mark(0), search_front_upload_and_check (stages 1 and 2: nothing has been written

@@ -283,6 +283,20 @@ struct KnnNormalsArgs {
     int* count;                      // n, may be null
 };
 hipError_t knn_normals(const NnGridView& g, const KnnNormalsArgs& a, int fma, hipStream_t s);
+// the same search and moments with the covariance as the output (mi_estimate_covariances; K17's inputs)
+struct KnnCovariancesArgs {
+    const float *qx, *qy, *qz;       // as KnnNormalsArgs
+    const int* order;
+    const float *cx, *cy, *cz;
+    int n, k;
+    float max_d2;
+    float hi[3];
+    int plane;                       // 0: C itself (MI_COV_RAW); 1: I - (1 - epsilon) n n^T (MI_COV_PLANE)
+    double epsilon;                  // the caller's fp32 value, promoted
+    float* cov6;                     // n * 6, AoS, the caller's order: xx, xy, xz, yy, yz, zz
+    int* count;                      // n, may be null
+};
+hipError_t knn_covariances(const NnGridView& g, const KnnCovariancesArgs& a, int fma, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------------
 // K15 statistical and radius outlier removal (outlier_kernels.hip; driver: outlier_api.hip): K13's search in self mode with the
@@ -386,6 +400,31 @@ hipError_t plane_step(const NnGridView& g, const PlaneStepArgs& a, int fma, hipS
 // rows -> state->sums -> (rules.solve) the solve, the update and the stop rule; parts: plane_part_count(nrows) x PLANE_ROW doubles, null where that is 0
 hipError_t plane_reduce_solve(PlaneState* state, const double* rows, int nrows, double* parts, const PlaneRules& rules, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K17 generalized ICP (gicp_kernels.hip; driver: gicp_api.hip): K16's iteration with a 3 x 3 information matrix per pair where K16 has a
+// normal.  The step kernel writes K16's rows (PLANE_ROW doubles per 64 moving points, the same layout), so the rows reduce, the solve,
+// the state block and the rules are K16's own: plane_reduce_solve, PlaneState, PlaneRules.
+// ---------------------------------------------------------------------------------------------------------------
+struct GicpStepArgs {
+    const PlaneState* state;         // the pose to linearise at (rounded to fp32 by every lane), the centre, done
+    const float *bx, *by, *bz;       // the moving cloud along its curve order, SoA, n entries
+    const int* order;                // sorted slot -> the caller's moving index
+    const float *ax, *ay, *az;       // the fixed cloud in the caller's order, SoA: what a match's index points into
+    const float4* cov_a;             // the fixed cloud's covariances in the caller's order, two float4 each: (xx, xy, xz, 0), (yy, yz, zz, 0)
+    const float4* cov_b;             // the moving cloud's along its curve order, the same layout: read at the lane's own slot
+    int n;
+    float max_d2;                    // a match with d2 > this is no pair (+inf: no limit)
+    float hi[3];                     // upper corner of the fixed cloud's bounding box (the lower one is the grid's origin)
+    double* rows;                    // plane_row_count(n) x PLANE_ROW
+    int* idx;                        // may be null; n, the caller's order: the matched fixed index of a pair, -1 otherwise
+};
+hipError_t gicp_step(const NnGridView& g, const GicpStepArgs& a, int fma, hipStream_t s);
+// count covariances of six floats as uploaded -> two float4 each; *bad = min(*bad, the lowest index with a non-finite entry or one above
+// 1e18 in magnitude) -- the caller sets *bad to KNN_NO_POINT first
+hipError_t gicp_pack_covariances(const float* cov6, int count, float4* packed, int* bad, hipStream_t s);
+// out[2 s], out[2 s + 1] = in[2 order[s]], in[2 order[s] + 1]: the moving cloud's covariances along its curve
+hipError_t gicp_permute_covariances(const float4* in, const int* order, int n, float4* out, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -402,5 +441,6 @@ hipError_t preload_knn_kernels();
 hipError_t preload_normals_kernels();
 hipError_t preload_outlier_kernels();
 hipError_t preload_plane_kernels();
+hipError_t preload_gicp_kernels();
 
 }  // namespace mislam

@@ -818,6 +818,116 @@ int mi_plane_system(mi_ctx* ctx, const float* before_xyz, int n, const float* af
 int mi_icp_plane_times(mi_ctx* ctx, double out_ms[MI_PLANE_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * Generalized ICP (no reference counterpart), also called plane-to-plane or distribution-to-distribution ICP (Segal, Haehnel, Thrun:
+ * Generalized-ICP, RSS 2009; INTEGRATION.md: generalized registration).  It minimises sum d^T (C_a + R C_b R^T)^-1 d over the matched
+ * pairs, d = R b_i + t - a_j, with a 3 x 3 covariance per point of BOTH clouds: the surface model of both sides, so it tolerates the
+ * sampling mismatch between two scans of one surface that biases point-to-plane and stalls point-to-point.  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+#define MI_COV_RAW   0            /* the neighbourhood's covariance itself */
+#define MI_COV_PLANE 1            /* its eigenvalues replaced by (epsilon, 1, 1): the GICP regularisation */
+
+/* Per-point 3 x 3 covariances of a cloud, computed on the device: six floats per point, the upper triangle row by row
+ * (xx, xy, xz, yy, yz, zz).  Every rule can be retraced in numpy (tests/gicp_reference.py does).
+ *   Neighbourhood of point i: point i itself plus the neighbours that
+ *     mi_knn_search(ctx, NULL, n, cloud_xyz, n, k, dist_mode, max_distance_squared, ...) returns for row i -- the same set, bit for
+ *     bit: self mode skips by index, and a duplicate of point i stored elsewhere is a neighbour.  count[i] is that call's count[i].
+ *     A finite max_distance_squared makes it the "hybrid" k-and-radius neighbourhood; INFINITY is no limit.
+ *   Covariance: that of the neighbourhood's count + 1 points about their mean, divided by the number of points, in fp64.  It is formed
+ *     in one pass from the differences d = p_j - p_i, taken in fp64 (exact, or rounded at 2^-53): nine running sums S = sum d,
+ *     Q = sum d d^T (one product and one addition per entry and neighbour), added in the order of mi_knn_search's row i, nearest first;
+ *     then with c = count + 1, m = S / c and C_ab = Q_ab / c - m_a m_b (one division, one product, one subtraction);
+ *     the point itself contributes d = 0.  It is mi_estimate_normals' covariance: the same kernel body in the same order.
+ *   MI_COV_RAW: every entry of C rounded once to fp32.  epsilon is ignored.
+ *   MI_COV_PLANE: C's eigenvalues replaced by (epsilon, 1, 1), the smallest by epsilon: I - (1 - epsilon) n n^T, with n the unit
+ *     eigenvector of C's smallest eigenvalue from mi_estimate_normals' fp64 cyclic Jacobi iteration, normalised in fp64 and NOT rounded
+ *     to fp32.  In fp64, in this order: w = 1 - epsilon (epsilon promoted); u = w n (three products); entry ab = delta_ab - u_a n_b (one
+ *     product, one subtraction from 1 or 0), a <= b; each rounded once to fp32.  The sign of n cancels.  epsilon must be finite and in
+ *     [0, 1].
+ *   Too few points: with count[i] < 2 all six entries are 0 in both modes -- a covariance mi_icp_gicp_register treats as "none".
+ *   MI_ERR_INVALID_ARG -- mi_last_error names the cause and, for a bad point, its index; NO output array has been written -- for a
+ *     NULL ctx, cloud_xyz or cov6; n < 1; k outside [2, MI_KNN_MAX_K]; a dist_mode other than the two of mi_knn_search;
+ *     max_distance_squared NaN or negative; a mode other than the two above; with MI_COV_PLANE an epsilon that is not finite or outside
+ *     [0, 1]; a non-finite coordinate or one above 1e18 in magnitude.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls of this header keep: it works in buffers
+ *     of its own.  Synchronous, host in and host out. */
+int mi_estimate_covariances(mi_ctx* ctx,
+                            const float* cloud_xyz, int n,
+                            int k, int dist_mode,            /* 2 <= k <= MI_KNN_MAX_K; MI_DIST_CPU_ROUNDING or MI_DIST_FMA */
+                            float max_distance_squared,      /* INFINITY: no limit; else neighbours with d2 > this do not exist */
+                            int mode, float epsilon,         /* MI_COV_RAW / MI_COV_PLANE; epsilon in [0, 1], read by MI_COV_PLANE only */
+                            float* cov6,                     /* n*6 */
+                            int* count);                     /* may be NULL; n: neighbours used for point i (<= k) */
+
+/* Registers the moving cloud `before` (n points, covariances before_cov6) onto the fixed cloud `after` (m points, covariances
+ * after_cov6), on the device.  params is mi_plane_params, and every field means here what it means for mi_icp_plane_register.  Every
+ * rule below can be retraced in numpy (tests/gicp_reference.py does).
+ *   Transform, the pose's rounding to fp32, q, match, centre c0: exactly those of mi_icp_plane_register -- q = ((R00*b_x + R01*b_y) +
+ *     R02*b_z) + t_x in fp32 with the pose rounded once; the pair of moving point i is row i of mi_knn_search(ctx, q, n, after_xyz, m, 1,
+ *     dist_mode, max_distance_squared, ...), key for key; c0 = 0.5f * (lo + hi) of the fixed cloud's bounding box.
+ *   Covariances: six floats per point, the upper triangle row by row (xx, xy, xz, yy, yz, zz), as mi_estimate_covariances writes them.
+ *     They are used as given: not checked for symmetry (there is none to check: the lower triangle is the upper one) or definiteness,
+ *     only for finiteness and |x| <= 1e18.
+ *   Pair terms, every operand promoted to fp64 first and every operation rounded; Rf is the pose's rotation rounded to fp32 (the
+ *     rotation q was formed with) and promoted back; j the match of i; sums of three are formed left to right, (x + y) + z:
+ *       d = q - a_j
+ *       T = Rf C_b[i]:       T_rc = (Rf_r0 Cb_0c + Rf_r1 Cb_1c) + Rf_r2 Cb_2c
+ *       Sigma = C_a[j] + T Rf^T:  S_rc = Ca_rc + ((T_r0 Rf_c0 + T_r1 Rf_c1) + T_r2 Rf_c2) for r <= c; the lower triangle is never formed
+ *       cofactors:  c00 = S11 S22 - S12 S12   c01 = S02 S12 - S01 S22   c02 = S01 S12 - S02 S11
+ *                   c11 = S00 S22 - S02 S02   c12 = S01 S02 - S00 S12   c22 = S00 S11 - S01 S01   (two products, one subtraction)
+ *       det = (S00 c00 + S01 c01) + S02 c02;   M = Sigma^-1:  M_rc = c_rc / det
+ *     A pair whose det is <= 0 or not finite is no pair (out_idx -1).  Two zero covariances give det = 0; one zero and one proper
+ *     covariance is a valid point-to-distribution pair.
+ *   Linearisation: Gauss-Newton with M held fixed within the iteration.  With P = q - c0 the 3 x 6 Jacobian of the update (omega about
+ *     c0, then v) is J = [ -[P]x , I ].  Writing (P x y)_0 = P_y y_2 - P_z y_1, (P x y)_1 = P_z y_0 - P_x y_2, (P x y)_2 = P_x y_1 - P_y y_0
+ *     (two products, one subtraction each):
+ *       W = M J (3 x 6):     W_rb = (P x M_r)_b for b < 3, M_r the row r of M;  W_rb = M_r(b-3) for b >= 3
+ *       H = J^T W (6 x 6):   H_ab = (P x W_b)_a for a < 3, W_b the column b of W;  H_ab = W_(a-3)b for a >= 3;  the 21 entries a <= b
+ *       Md = M d:            Md_r = (M_r0 d_x + M_r1 d_y) + M_r2 d_z
+ *       g = J^T Md:          g_a = (P x Md)_a for a < 3;  g_a = Md_(a-3) for a >= 3
+ *       e = d^T Md:          e = (d_x Md_0 + d_y Md_1) + d_z Md_2
+ *   Sums (mi_gicp_system's out_sums), the layout of mi_plane_system: [0, 21) the upper triangle of sum H, row-major; [21, 27) sum g;
+ *     [27] sum e; [28] sum d2 (the matches' fp32 squared distances); [29] the number of pairs; [30, 32) 0.  The sums are added in a
+ *     fixed order that depends on n alone, with no floating-point atomics: the same input gives the same bits on every call, whatever
+ *     ran on the context before and whatever sync_every.
+ *   Solve, update, stop rule, outputs, sync_every, max_iterations = 0: those of mi_icp_plane_register, by the same code, with
+ *     x = (omega, v) solving (sum H) x = -(sum g): MI_STOP_NO_PAIRS below 6 pairs; MI_STOP_DEGENERATE on a diagonal entry that is <= 0
+ *     or not finite or a pivot of the scaled LDL^T below 1e-10 (the pose stays as it was); dR by Rodrigues' formula, R <- dR R,
+ *     t <- dR (t - c0) + c0 + v; MI_STOP_CONVERGED, then MI_STOP_MAX_ITERATIONS.  *error is sum e / pairs of the last linearisation,
+ *     rounded to fp32, 0 when it had no pair.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name and names the cause and, for a bad point or covariance, which
+ *     array and which index (the lowest); NO output has been written -- for a NULL ctx, before_xyz, before_cov6, after_xyz, after_cov6,
+ *     params or out_T; n < 1 or m < 1; a dist_mode other than the two of mi_knn_search; max_distance_squared NaN or negative;
+ *     eps_rotation or eps_translation NaN or negative; max_iterations < 0; sync_every < 0; a non-finite entry of init_T's rotation block
+ *     or translation column; a non-finite coordinate or covariance entry, or one above 1e18 in magnitude.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls of this header keep: it works in buffers
+ *     of its own.  Synchronous, host in and host out. */
+int mi_icp_gicp_register(mi_ctx* ctx, const float* before_xyz, const float* before_cov6, int n,
+                         const float* after_xyz, const float* after_cov6, int m,
+                         const mi_plane_params* params, const float init_T[16] /* may be NULL: identity */,
+                         float out_T[16], int* iterations, float* error, int* stop_reason);
+
+/* One linearisation at a given transform, as mi_plane_system: the sums above at the pose T (NULL: the identity, the same bits), the
+ * centre c0, and per moving point the fixed index of its pair, or -1 where it has none.  The same arguments are refused, with out_sums
+ * in the place of out_T; out_centre and out_idx may be NULL. */
+int mi_gicp_system(mi_ctx* ctx, const float* before_xyz, const float* before_cov6, int n,
+                   const float* after_xyz, const float* after_cov6, int m,
+                   const float T[16] /* may be NULL */, int dist_mode, float max_distance_squared,
+                   double out_sums[32], float out_centre[3], int* out_idx /* may be NULL; n: matched fixed index or -1 */);
+
+/* Where the last mi_icp_gicp_register or mi_gicp_system of this context spent its host wall time, in ms (measurement hook,
+ * tools/gicp_bench.py).  The stages are those of mi_icp_plane_times, the covariances in the place of the normals:
+ *   out[0] workspace (device allocations)           out[1] upload + repack (covariances, fixed cloud, moving cloud, state)
+ *   out[2] input checks, bounding box, read-backs   out[3] cell grid over the fixed cloud
+ *   out[4] curve order of the moving cloud + permute (its covariances with it)
+ *   out[5] the iterations, host reads of the state included
+ *   out[6] download of the results                  out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage). */
+#define MI_GICP_STAGES 8
+int mi_icp_gicp_times(mi_ctx* ctx, double out_ms[MI_GICP_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
  * -------------------------------------------------------------------------------------------------------------- */
 enum {
