@@ -45,6 +45,7 @@ EXPORTS = [
     "mi_outlier_params_default", "mi_remove_outliers", "mi_remove_outliers_times",
     "mi_plane_params_default", "mi_icp_plane_register", "mi_plane_system", "mi_icp_plane_times",
     "mi_estimate_covariances", "mi_icp_gicp_register", "mi_gicp_system", "mi_icp_gicp_times",
+    "mi_fpfh_features", "mi_fpfh_features_times",
     "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_selftest_icp_schedule", "mi_selftest_cpd_last", "mi_nn_kernel_name",
 ]
 
@@ -379,6 +380,24 @@ def gicp_system_raw(handle, before, before_cov, n, after, after_cov, m, T, dist_
 def icp_gicp_times_raw(handle, out_ms):
     """mi_icp_gicp_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
     f = lib().mi_icp_gicp_times
+    f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
+    return f(handle, out_ms)
+
+
+FPFH_BINS, FPFH_DIM = 11, 33     # MI_FPFH_BINS, MI_FPFH_DIM
+
+
+def fpfh_features_raw(handle, cloud, normals, n, k, dist_mode, max_d2, fpfh, counts, count):
+    """mi_fpfh_features with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_fpfh_features
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    return f(handle, cloud, normals, n, k, dist_mode, max_d2, fpfh, counts, count)
+
+
+def fpfh_features_times_raw(handle, out_ms):
+    """mi_fpfh_features_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_fpfh_features_times
     f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
     return f(handle, out_ms)
 
@@ -959,6 +978,29 @@ class Context:
         out = (C.c_double * 8)()
         _check(icp_gicp_times_raw(self._h, out))
         return dict(zip(("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"), list(out)))
+
+    # ---- local descriptors
+    def fpfh_features(self, cloud, normals, k, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_counts=False, want_count=False):
+        """FPFH descriptors of a cloud with normals from every point's k nearest neighbours (mi_fpfh_features): fpfh [n, 33] float32, the
+        blocks of theta, alpha and phi, each summing to 200 (33 zeros where a point has no neighbour); then counts [n, 33] uint8, the SPFH's
+        pair counts per bin, and count [n] int32, the neighbours, if asked for."""
+        cloud, normals = _cloud(cloud), _cloud(normals)
+        if normals.shape != cloud.shape:
+            raise ValueError("normals must have one normal per point")
+        n = cloud.shape[0]
+        fpfh = np.empty((n, FPFH_DIM), np.float32)
+        counts = np.empty((n, FPFH_DIM), np.uint8) if want_counts else None
+        count = np.empty(n, np.int32) if want_count else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _check(fpfh_features_raw(self._h, cloud.ctypes.data, normals.ctypes.data, n, int(k), int(dist_mode), float(max_d2), fpfh.ctypes.data, ptr(counts), ptr(count)))
+        res = [fpfh] + ([counts] if want_counts else []) + ([count] if want_count else [])
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def fpfh_features_times(self):
+        """ms per stage of the last fpfh_features: workspace, upload, check, grid, order, kernels, download, total (mi_fpfh_features_times)."""
+        out = (C.c_double * 8)()
+        _check(fpfh_features_times_raw(self._h, out))
+        return dict(zip(("workspace", "upload", "check", "grid", "order", "kernels", "download", "total"), list(out)))
 
     # ---- profiling
     def profile_enable(self, on=True):

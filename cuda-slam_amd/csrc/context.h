@@ -270,6 +270,19 @@ struct mi_ctx {
         double ms[MI_GICP_STAGES] = {0};                 // mi_icp_gicp_times
     } gicp;
 
+    // ---- mi_fpfh_features: a search front end in self mode, the normals beside the cloud, what K18 leaves for K19 and the results
+    struct FpfhBuffers {
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<float> nx, ny, nz;                // the normals, SoA, the caller's order
+        mislam::DevBuf<mislam::KnnState> nstate;         // the normals' input check
+        mislam::DevBuf<unsigned long long> keys;         // every point's sorted k-list (FpfhSpfhArgs::keys)
+        mislam::DevBuf<unsigned int> packed;             // every point's packed counts (FPFH_WORDS each)
+        mislam::DevBuf<float> out_fpfh;
+        mislam::DevBuf<unsigned char> out_counts;
+        mislam::DevBuf<int> out_count;
+        double ms[MI_FPFH_STAGES] = {0};                 // mi_fpfh_features_times
+    } fpfh;
+
     // ---- mi_prepare_cloud: buffers of its own, like the voxel call's: the raw cloud, the prepared one, the caller's index vectors and draws
     struct PrepareBuffers {
         mislam::DevBuf<float> raw, out, partials, noise_unit, outlier_unit;
@@ -364,7 +377,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 
 // ---- the front end of a search over a cloud's cell grid (search_front.hip).  A driver calls, in this order: search_front_reserve and its own
 // reserves (every reserve comes before the first upload), clock.mark(0), search_front_upload_and_check (stages 1 and 2: nothing has been written

@@ -1,0 +1,97 @@
+// mi_fpfh_features behind the C ABI: argument checks, the reserves of the call's own buffers in the context, the normals' upload and input
+// check, the search front end in self mode (search_front.hip: upload, input check and its one read-back, the cell grid over the cloud
+// under mi_knn_search's points-per-cell rule, the curve order), the arguments and the two launches of fpfh_kernels.hip, and the download
+// of what was asked for.
+#include <hip/hip_runtime.h>
+
+#include "context.h"
+#include "fpfh_pair.hpp"
+
+using namespace mislam;
+
+static_assert(FPFH_BINS == MI_FPFH_BINS && FPFH_DIM == MI_FPFH_DIM, "fpfh_pair.hpp mirrors MI_FPFH_*");
+
+extern "C" int mi_fpfh_features(mi_ctx* c, const float* cloud_xyz, const float* normals_xyz, int n, int k, int dist_mode, float max_distance_squared,
+                                float* fpfh33, unsigned char* spfh_counts33, int* count)
+{
+    const char* who = "mi_fpfh_features";
+    if (!c) { set_error("%s: null context", who); return MI_ERR_INVALID_ARG; }
+    if (!cloud_xyz || !normals_xyz || !fpfh33) { set_error("%s: null cloud_xyz, normals_xyz or fpfh33", who); return MI_ERR_INVALID_ARG; }
+    if (n < 1) { set_error("%s: empty cloud (n = %d)", who, n); return MI_ERR_INVALID_ARG; }
+    if (k < 1 || k > MI_KNN_MAX_K) { set_error("%s: k = %d outside [1, %d]", who, k, MI_KNN_MAX_K); return MI_ERR_INVALID_ARG; }
+    if (dist_mode != MI_DIST_CPU_ROUNDING && dist_mode != MI_DIST_FMA) { set_error("%s: bad dist_mode %d", who, dist_mode); return MI_ERR_INVALID_ARG; }
+    if (!(max_distance_squared >= 0.f)) { set_error("%s: max_distance_squared %g is NaN or negative", who, (double)max_distance_squared); return MI_ERR_INVALID_ARG; }
+    if (c->distributed()) { set_error("%s: single-GPU contexts only", who); return MI_ERR_STATE; }
+    MI_ENTER(c);
+    mi_ctx::FpfhBuffers& b = c->fpfh;
+    StageClock clock(c, b.ms);         // mi_fpfh_features_times
+
+    const size_t np = (size_t)n, rows = np * (size_t)k;
+    MI_TRY(search_front_reserve(b.front, np, np, true));
+    MI_TRY(b.nx.reserve(np)); MI_TRY(b.ny.reserve(np)); MI_TRY(b.nz.reserve(np)); MI_TRY(b.nstate.reserve(1));
+    MI_TRY(b.keys.reserve(rows)); MI_TRY(b.packed.reserve(FPFH_WORDS * np));
+    MI_TRY(b.out_fpfh.reserve(FPFH_DIM * np));
+    if (spfh_counts33) MI_TRY(b.out_counts.reserve(FPFH_DIM * np));
+    if (count) MI_TRY(b.out_count.reserve(np));
+    MI_TRY(clock.mark(0));
+
+    // the normals go first through the staging buffer and the check's partials, which the front end then takes over (one stream: in order)
+    MI_TRY(host_to_device(c, b.front.staging.p, normals_xyz, sizeof(float) * 3 * np));
+    MI_HIP(aos_to_soa(b.front.staging.p, n, n, b.nx.p, b.ny.p, b.nz.p, nullptr, c->stream));
+    MI_HIP(knn_check_inputs(b.nx.p, b.ny.p, b.nz.p, n, nullptr, nullptr, nullptr, 0, b.front.range_lo_hi.p, b.front.range_bad.p, b.nstate.p, c->stream));
+    SearchFront f;
+    MI_TRY(search_front_upload_and_check(c, b.front, clock, who, cloud_xyz, n, nullptr, n, &f));
+    KnnState ns;
+    MI_HIP(hipMemcpyAsync(&ns, b.nstate.p, sizeof ns, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    MI_TRY(clock.mark(2));
+    if (ns.bad_cloud != KNN_NO_POINT) {
+        set_error("%s: normals_xyz normal %d has a non-finite component or one above 1e18 in magnitude", who, ns.bad_cloud);
+        return MI_ERR_INVALID_ARG;
+    }
+    const float ppc = c->tune.knn_points_per_cell > 0.f ? c->tune.knn_points_per_cell : knn_default_points_per_cell(k);   // mi_knn_search's grid, cell size included
+    MI_TRY(search_front_index_and_order(c, b.front, clock, who, ppc, &f));
+
+    FpfhSpfhArgs a{};
+    a.qx = b.front.qx.p; a.qy = b.front.qy.p; a.qz = b.front.qz.p; a.order = b.front.order.p;
+    a.cx = b.front.cx.p; a.cy = b.front.cy.p; a.cz = b.front.cz.p;
+    a.nx = b.nx.p; a.ny = b.ny.p; a.nz = b.nz.p;
+    a.n = n; a.k = k; a.max_d2 = max_distance_squared;
+    for (int i = 0; i < 3; i++) a.hi[i] = f.bbox[3 + i];
+    a.keys = b.keys.p; a.packed = b.packed.p; a.count = count ? b.out_count.p : nullptr;
+    FpfhSumArgs sa{};
+    sa.order = b.front.order.p; sa.keys = b.keys.p; sa.packed = b.packed.p;
+    sa.n = n; sa.k = k;
+    sa.fpfh = b.out_fpfh.p; sa.counts = spfh_counts33 ? b.out_counts.p : nullptr;
+    // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
+    if (!search_front_fits(b.front, f) || b.nx.cap < np || b.ny.cap < np || b.nz.cap < np || b.keys.cap < rows || b.packed.cap < FPFH_WORDS * np ||
+        b.out_fpfh.cap < FPFH_DIM * np || (spfh_counts33 && b.out_counts.cap < FPFH_DIM * np) || (count && b.out_count.cap < np)) {
+        set_error("internal: %s buffers shorter than the launch", who);
+        return MI_ERR_STATE;
+    }
+    // with profiling on, K18's time is booked to MI_KERNEL_NN and K19's to MI_KERNEL_MOMENTS (mi_profile_get)
+    MI_TRY(search_front_timed_launch(c, b.front, clock, [&] {
+        {
+            ProfScope p(c, MI_KERNEL_NN);
+            const hipError_t e = fpfh_spfh(f.g, a, dist_mode == MI_DIST_FMA, c->stream);
+            if (e != hipSuccess) return e;
+        }
+        ProfScope p(c, MI_KERNEL_MOMENTS);
+        return fpfh_sum(sa, c->stream);
+    }));
+
+    MI_HIP(hipMemcpyAsync(fpfh33, b.out_fpfh.p, sizeof(float) * FPFH_DIM * np, hipMemcpyDeviceToHost, c->stream));
+    if (spfh_counts33) MI_HIP(hipMemcpyAsync(spfh_counts33, b.out_counts.p, FPFH_DIM * np, hipMemcpyDeviceToHost, c->stream));
+    if (count) MI_HIP(hipMemcpyAsync(count, b.out_count.p, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    MI_TRY(clock.mark(6));
+    clock.finish();
+    return MI_OK;
+}
+
+extern "C" int mi_fpfh_features_times(mi_ctx* c, double out_ms[MI_FPFH_STAGES])
+{
+    if (!c || !out_ms) { set_error("mi_fpfh_features_times: null argument"); return MI_ERR_INVALID_ARG; }
+    for (int i = 0; i < MI_FPFH_STAGES; i++) out_ms[i] = c->fpfh.ms[i];
+    return MI_OK;
+}

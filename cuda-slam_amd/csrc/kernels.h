@@ -425,6 +425,37 @@ hipError_t gicp_pack_covariances(const float* cov6, int count, float4* packed, i
 // out[2 s], out[2 s + 1] = in[2 order[s]], in[2 order[s] + 1]: the moving cloud's covariances along its curve
 hipError_t gicp_permute_covariances(const float4* in, const int* order, int n, float4* out, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K18 / K19 FPFH descriptors (fpfh_kernels.hip; driver: fpfh_api.hip; the pair features and bins: fpfh_pair.hpp): K13's search in self
+// mode with the pairs' bins counted while the keys are in registers, then the distance-weighted sums over every point's neighbours
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int FPFH_WORDS = 9;                // 32-bit words of a point's packed counts: per feature 11 bins as bytes of three words,
+                                             // bin b in byte b & 3 of word b >> 2; byte 3 of the third word: the point's neighbour count
+constexpr int FPFH_SUM_POINTS = 64;          // points per workgroup of K19 ...
+constexpr int FPFH_SUM_BLOCK = 3 * FPFH_SUM_POINTS;   // ... at three lanes a point, one per feature
+struct FpfhSpfhArgs {
+    const float *qx, *qy, *qz;       // the cloud along its curve order, SoA, n entries
+    const int* order;                // sorted slot -> the caller's index (the row the slot's answer goes to, and the candidate it skips)
+    const float *cx, *cy, *cz;       // the cloud in the caller's order, SoA: what the neighbours' indices point into
+    const float *nx, *ny, *nz;       // the normals, the same way
+    int n, k;
+    float max_d2;                    // candidates with d2 > this do not exist (+inf: no limit)
+    float hi[3];                     // upper corner of the cloud's bounding box (the lower one is the grid's origin)
+    unsigned long long* keys;        // n * k, the caller's order: row i of mi_knn_search as keys, KNN_KEY_EMPTY behind the filled slots
+    unsigned int* packed;            // n * FPFH_WORDS, the caller's order
+    int* count;                      // n, may be null
+};
+hipError_t fpfh_spfh(const NnGridView& g, const FpfhSpfhArgs& a, int fma, hipStream_t s);
+struct FpfhSumArgs {
+    const int* order;                // K18's: lanes next to each other work on points next to each other
+    const unsigned long long* keys;  // K18's
+    const unsigned int* packed;      // K18's
+    int n, k;
+    float* fpfh;                     // n * 33, the caller's order
+    unsigned char* counts;           // n * 33, may be null: the counts, unpacked
+};
+hipError_t fpfh_sum(const FpfhSumArgs& a, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -442,5 +473,6 @@ hipError_t preload_normals_kernels();
 hipError_t preload_outlier_kernels();
 hipError_t preload_plane_kernels();
 hipError_t preload_gicp_kernels();
+hipError_t preload_fpfh_kernels();
 
 }  // namespace mislam

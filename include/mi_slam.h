@@ -928,6 +928,69 @@ int mi_gicp_system(mi_ctx* ctx, const float* before_xyz, const float* before_cov
 int mi_icp_gicp_times(mi_ctx* ctx, double out_ms[MI_GICP_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * Local descriptors (no reference counterpart): Fast Point Feature Histograms (Rusu, Blodow, Beetz, ICRA 2009) of a cloud with normals,
+ * the descriptor a global registration matches to find the start that the local registrations above refine (INTEGRATION.md:
+ * descriptors).  Matching the descriptors is the caller's.  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+
+/* The 33-bin FPFH of every point of a cloud, computed on the device.  Every rule below can be retraced in numpy
+ * (tests/fpfh_reference.py does).  In the arithmetic below every operand is promoted to fp64 first and every operation is rounded;
+ * sums of three are formed left to right, (x + y) + z; a cross-product component is two products and one subtraction, as in the
+ * generalized-ICP section.
+ *   Neighbourhood of point i: row i of mi_knn_search(ctx, NULL, n, cloud_xyz, n, k, dist_mode, max_distance_squared, ...), bit for bit:
+ *     self is skipped by index, a duplicate of point i stored elsewhere is a neighbour at d2 = +0, and count[i] is that call's count[i].
+ *   Pair features of (i, j), p and n the points and normals as given (normals are neither checked for unit length nor normalised):
+ *       d = p_j - p_i,  len = sqrt((dx*dx + dy*dy) + dz*dz);  len == 0: the features are (0, 0, 0)
+ *       a1 = (n_i . d) / len,  a2 = (n_j . d) / len
+ *       |a1| < |a2| (strictly):  u = n_j, t = n_i, d = -d, phi = -a2;   otherwise:  u = n_i, t = n_j, phi = a1
+ *       v = d x u,  vl = sqrt((vx*vx + vy*vy) + vz*vz);  vl == 0: the features are (0, 0, 0), phi included
+ *       v = v / vl,  w = u x v,  alpha = v . t,  theta = atan2(w . t, u . t)
+ *     This is the Darboux-frame feature of PCL and Open3D, their test acos(|a1|) > acos(|a2|) stated without the acos.
+ *   Bins, with pi = 3.141592653589793:
+ *       b_theta = clamp(floor((11 * (theta + pi)) / (2 * pi)), 0, 10)
+ *       b_alpha = clamp(floor((11 * (alpha + 1)) * 0.5), 0, 10) + 11
+ *       b_phi   = clamp(floor((11 * (phi + 1)) * 0.5), 0, 10) + 22
+ *     A NaN feature (finite input gives none) goes to bin 0 of its block.
+ *   SPFH: c_b(i), b = 0 .. 32, is the number of neighbours of i whose pair falls into bin b -- integers, at most MI_KNN_MAX_K; each
+ *     block of 11 sums to exactly count[i], the degenerate pairs included (they land in bins 5, 16 and 27).  spfh_counts33 receives
+ *     them.  As a value s_b(i) = (100.0 * c_b(i)) / count[i], and 0 where count[i] == 0.
+ *   FPFH: with j_1 .. j_c the neighbours of i in key order, nearest first, and d2_r the key's fp32 distance promoted to fp64: for
+ *     every r with d2_r > 0, and b = 0 .. 32 ascending:  val = s_b(j_r) / d2_r,  F_b += val,  S_(b / 11) += val.  Then
+ *     scale_f = S_f != 0 ? 100.0 / S_f : 0  and  fpfh33[33 i + b] = (float)(F_b * scale_(b / 11) + s_b(i)), rounded once.  A point with
+ *     count[i] == 0 gets 33 zeros.  Every block of 11 of a point with a neighbour at d2 > 0 sums to 200 (Open3D's normalisation); a
+ *     point whose neighbours are all duplicates of it keeps its own SPFH, blocks of 100.
+ *   No floating-point atomics anywhere: the same input gives the same bits on every call, whatever ran on the context before.
+ *   fpfh33 (n*33), spfh_counts33 (n*33, may be NULL) and count (n, may be NULL) are row-major, one row per point.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name and names the cause and, for a bad point or normal, which
+ *     array and which index (the lowest; the cloud is looked at first); NO output has been written -- for a NULL ctx, cloud_xyz,
+ *     normals_xyz or fpfh33; n < 1; k outside [1, MI_KNN_MAX_K]; a dist_mode other than the two of mi_knn_search; max_distance_squared
+ *     NaN or negative; a non-finite coordinate or normal component, or one above 1e18 in magnitude.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls of this header keep: it works in buffers
+ *     of its own.  Synchronous, host in and host out. */
+#define MI_FPFH_BINS 11
+#define MI_FPFH_DIM  33
+int mi_fpfh_features(mi_ctx* ctx,
+                     const float* cloud_xyz, const float* normals_xyz, int n,
+                     int k, int dist_mode,             /* 1 <= k <= MI_KNN_MAX_K; MI_DIST_CPU_ROUNDING or MI_DIST_FMA */
+                     float max_distance_squared,       /* INFINITY: no limit; else neighbours with d2 > this do not exist */
+                     float* fpfh33,                    /* n*33 */
+                     unsigned char* spfh_counts33,     /* may be NULL; n*33 */
+                     int* count);                      /* may be NULL; n: neighbours of point i (<= k) */
+
+/* Where the last mi_fpfh_features of this context spent its host wall time, in ms (measurement hook, tools/fpfh_bench.py).  The stages
+ * are those of mi_estimate_normals_times:
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA (normals, cloud)
+ *   out[2] input checks, bounding box, read-backs   out[3] cell grid over the cloud
+ *   out[4] curve order of the cloud + permute       out[5] the SPFH search kernel plus the FPFH kernel
+ *   out[6] download of the results                  out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage, and out[5] is the two
+ * launches' own HIP-event time instead of host wall time; mi_profile_get then has the SPFH kernel under MI_KERNEL_NN and the FPFH
+ * kernel under MI_KERNEL_MOMENTS). */
+#define MI_FPFH_STAGES 8
+int mi_fpfh_features_times(mi_ctx* ctx, double out_ms[MI_FPFH_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
  * -------------------------------------------------------------------------------------------------------------- */
 enum {
