@@ -46,6 +46,8 @@ EXPORTS = [
     "mi_plane_params_default", "mi_icp_plane_register", "mi_plane_system", "mi_icp_plane_times",
     "mi_estimate_covariances", "mi_icp_gicp_register", "mi_gicp_system", "mi_icp_gicp_times",
     "mi_fpfh_features", "mi_fpfh_features_times",
+    "mi_feature_match", "mi_feature_match_times",
+    "mi_ransac_params_default", "mi_ransac_register", "mi_ransac_hypotheses", "mi_ransac_register_times",
     "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_selftest_icp_schedule", "mi_selftest_cpd_last", "mi_nn_kernel_name",
 ]
 
@@ -398,6 +400,66 @@ def fpfh_features_raw(handle, cloud, normals, n, k, dist_mode, max_d2, fpfh, cou
 def fpfh_features_times_raw(handle, out_ms):
     """mi_fpfh_features_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
     f = lib().mi_fpfh_features_times
+    f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
+    return f(handle, out_ms)
+
+
+FEATURE_MAX_DIM = 64             # MI_FEATURE_MAX_DIM
+
+
+def feature_match_raw(handle, query, n, target, m, dim, mutual, idx, d2):
+    """mi_feature_match with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_feature_match
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    return f(handle, query, n, target, m, dim, mutual, idx, d2)
+
+
+def feature_match_times_raw(handle, out_ms):
+    """mi_feature_match_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_feature_match_times
+    f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
+    return f(handle, out_ms)
+
+
+class RansacParams(C.Structure):
+    _fields_ = [("hypotheses", C.c_int), ("seed", C.c_ulonglong), ("max_distance", C.c_float), ("edge_similarity", C.c_float),
+                ("refine_iterations", C.c_int), ("reserved", C.c_int * 8)]
+
+
+def ransac_params(max_distance, **kw):
+    """mi_ransac_params_default with max_distance and any other field set: hypotheses, seed, edge_similarity, refine_iterations."""
+    p = RansacParams()
+    f = lib().mi_ransac_params_default
+    f.argtypes, f.restype = [C.c_void_p], None
+    f(C.byref(p))
+    p.max_distance = max_distance
+    for k, v in kw.items():
+        if k not in ("hypotheses", "seed", "edge_similarity", "refine_iterations"):
+            raise TypeError("mi_ransac_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def ransac_register_raw(handle, src, n, tgt, m, idx, params, R9, t3, inliers, rmse, best, nvalid, mask):
+    """mi_ransac_register with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_ransac_register
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 9
+    f.restype = C.c_int
+    return f(handle, src, n, tgt, m, idx, params, R9, t3, inliers, rmse, best, nvalid, mask)
+
+
+def ransac_hypotheses_raw(handle, src, n, tgt, m, idx, params, first, count, triples, valid, pose12, inlier_count):
+    """mi_ransac_hypotheses with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_ransac_hypotheses
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+    f.restype = C.c_int
+    return f(handle, src, n, tgt, m, idx, params, first, count, triples, valid, pose12, inlier_count)
+
+
+def ransac_register_times_raw(handle, out_ms):
+    """mi_ransac_register_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_ransac_register_times
     f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
     return f(handle, out_ms)
 
@@ -1001,6 +1063,61 @@ class Context:
         out = (C.c_double * 8)()
         _check(fpfh_features_times_raw(self._h, out))
         return dict(zip(("workspace", "upload", "check", "grid", "order", "kernels", "download", "total"), list(out)))
+
+    def feature_match(self, query, target, mutual=False, want_d2=False):
+        """The nearest row of target [m, dim] for every row of query [n, dim] in descriptor space, every pair looked at (mi_feature_match):
+        idx [n] int32 -- with mutual, -1 where the match is not reciprocal -- then d2 [n] float32 (+inf at -1) if asked for."""
+        query, target = np.ascontiguousarray(query, np.float32), np.ascontiguousarray(target, np.float32)
+        if query.ndim != 2 or target.ndim != 2 or query.shape[1] != target.shape[1]:
+            raise ValueError("query and target are [rows, dim] with the same dim")
+        n, m, dim = query.shape[0], target.shape[0], query.shape[1]
+        idx = np.empty(n, np.int32)
+        d2 = np.empty(n, np.float32) if want_d2 else None
+        _check(feature_match_raw(self._h, query.ctypes.data, n, target.ctypes.data, m, dim, 1 if mutual else 0, idx.ctypes.data,
+                                 None if d2 is None else d2.ctypes.data))
+        return (idx, d2) if want_d2 else idx
+
+    def feature_match_times(self):
+        """ms per stage of the last feature_match: workspace, upload, check, -, -, kernels, download, total (mi_feature_match_times)."""
+        out = (C.c_double * 8)()
+        _check(feature_match_times_raw(self._h, out))
+        return dict(zip(("workspace", "upload", "check", "unused3", "unused4", "kernels", "download", "total"), list(out)))
+
+    def ransac_register(self, src, tgt, idx, params, want_mask=False):
+        """A pose from correspondences src[i] <-> tgt[idx[i]] (idx -1: none) by hypothesise and verify (mi_ransac_register):
+        (R [3, 3] float32, t [3], inliers, rmse, best_hypothesis, valid_hypotheses), then the inlier mask [n] uint8 if asked for."""
+        src, tgt = _cloud(src), _cloud(tgt)
+        idx = np.ascontiguousarray(idx, np.int32)
+        if idx.shape != (src.shape[0],):
+            raise ValueError("idx has one entry per source point")
+        R9, t3 = np.empty(9, np.float32), np.empty(3, np.float32)
+        inl, best, nvalid, rmse = C.c_int(0), C.c_int(0), C.c_int(0), C.c_float(0)
+        mask = np.empty(src.shape[0], np.uint8) if want_mask else None
+        _check(ransac_register_raw(self._h, src.ctypes.data, src.shape[0], tgt.ctypes.data, tgt.shape[0], idx.ctypes.data, C.addressof(params), R9.ctypes.data,
+                                   t3.ctypes.data, C.addressof(inl), C.addressof(rmse), C.addressof(best), C.addressof(nvalid), None if mask is None else mask.ctypes.data))
+        out = (R9.reshape(3, 3).T.copy(), t3, inl.value, np.float32(rmse.value), best.value, nvalid.value)
+        return out + (mask,) if want_mask else out
+
+    def ransac_hypotheses(self, src, tgt, idx, params, first=0, count=None):
+        """Hypotheses first .. first + count - 1 of ransac_register (mi_ransac_hypotheses): triples [count, 3] int32 (source indices),
+        valid [count] uint8, pose12 [count, 12] float32 (R9 column-major, then t3), inlier_count [count] int32."""
+        src, tgt = _cloud(src), _cloud(tgt)
+        idx = np.ascontiguousarray(idx, np.int32)
+        if idx.shape != (src.shape[0],):
+            raise ValueError("idx has one entry per source point")
+        count = params.hypotheses - first if count is None else count
+        rows = max(count, 1)
+        triples, valid = np.empty((rows, 3), np.int32), np.empty(rows, np.uint8)
+        pose12, inl = np.empty((rows, 12), np.float32), np.empty(rows, np.int32)
+        _check(ransac_hypotheses_raw(self._h, src.ctypes.data, src.shape[0], tgt.ctypes.data, tgt.shape[0], idx.ctypes.data, C.addressof(params), int(first), int(count),
+                                     triples.ctypes.data, valid.ctypes.data, pose12.ctypes.data, inl.ctypes.data))
+        return triples, valid, pose12, inl
+
+    def ransac_register_times(self):
+        """ms per stage of the last ransac_register: workspace, upload, hypotheses, count, argmax, refine, -, total (mi_ransac_register_times)."""
+        out = (C.c_double * 8)()
+        _check(ransac_register_times_raw(self._h, out))
+        return dict(zip(("workspace", "upload", "hypotheses", "count", "argmax", "refine", "unused6", "total"), list(out)))
 
     # ---- profiling
     def profile_enable(self, on=True):

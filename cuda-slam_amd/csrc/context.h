@@ -283,6 +283,26 @@ struct mi_ctx {
         double ms[MI_FPFH_STAGES] = {0};                 // mi_fpfh_features_times
     } fpfh;
 
+    // ---- mi_feature_match: both descriptor arrays as uploaded, their norms, the packed minima of both directions and the results
+    struct MatchBuffers {
+        mislam::DevBuf<float> query, target, qq, tt;
+        mislam::DevBuf<int> bad;                         // [0] the queries', [1] the targets' lowest refused row, or MATCH_NO_ROW
+        mislam::DevBuf<unsigned long long> keys, rev_keys;
+        mislam::DevBuf<int> out_idx;
+        mislam::DevBuf<float> out_d2;
+        double ms[MI_MATCH_STAGES] = {0};                // mi_feature_match_times
+    } match;
+
+    // ---- mi_ransac_register, mi_ransac_hypotheses: the correspondences by rank, one row per hypothesis, and the final pose's flags and distances
+    struct RansacBuffers {
+        mislam::DevBuf<float> pairs6, pose12, pose;
+        mislam::DevBuf<int> src_index, triples, inlier_count, small;   // small: [0] valid hypotheses, [1] the final pose's inliers
+        mislam::DevBuf<unsigned char> valid, mask;
+        mislam::DevBuf<unsigned long long> best;
+        mislam::DevBuf<double> d2, sum;
+        double ms[MI_RANSAC_STAGES] = {0};               // mi_ransac_register_times
+    } ransac;
+
     // ---- mi_prepare_cloud: buffers of its own, like the voxel call's: the raw cloud, the prepared one, the caller's index vectors and draws
     struct PrepareBuffers {
         mislam::DevBuf<float> raw, out, partials, noise_unit, outlier_unit;
@@ -377,7 +397,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 
 // ---- the front end of a search over a cloud's cell grid (search_front.hip).  A driver calls, in this order: search_front_reserve and its own
 // reserves (every reserve comes before the first upload), clock.mark(0), search_front_upload_and_check (stages 1 and 2: nothing has been written

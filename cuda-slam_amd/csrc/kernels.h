@@ -456,6 +456,73 @@ struct FpfhSumArgs {
 };
 hipError_t fpfh_sum(const FpfhSumArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K20 - K22 descriptor matching (match_kernels.hip; driver: match_api.hip): every pair's dot product on the matrix pipe, the running minimum
+// of fmaf(-2, dot, |t|^2) per query, chunks of targets merged by a packed atomicMin
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int MATCH_MAX_DIM = 64;            // MI_FEATURE_MAX_DIM
+constexpr float MATCH_MAX_ABS = 1e15f;       // 64 * (1e15)^2 < FLT_MAX: no chain overflows
+constexpr int MATCH_TILE = 128;              // queries of a workgroup (32 per wave), and targets of an LDS tile
+constexpr int MATCH_BLOCK = 256;
+constexpr int MATCH_NO_ROW = 0x7fffffff;     // K20's *bad while no row has been refused
+// norm[i] = the fmaf chain of row i with itself; *bad = min(*bad, the lowest row with a non-finite component or one above MATCH_MAX_ABS)
+hipError_t match_norms(const float* feat, int rows, int dim, float* norm, int* bad, hipStream_t s);
+struct MatchArgs {
+    const float* query;              // n * dim, row-major: the side that searches
+    const float* target;             // m * dim: the side that is searched
+    const float* target_norm;        // m (K20)
+    int n, m, dim;
+    int chunk_len;                   // targets per workgroup column, a multiple of MATCH_TILE (match_chunk_len)
+    unsigned long long* keys;        // n, all ones before the launch: (ordered key << 32 | target) of the minimum
+};
+int match_chunk_len(int n, int m, int cu_count);
+hipError_t match_search(const MatchArgs& a, hipStream_t s);
+struct MatchFinishArgs {
+    const float *query, *target;
+    int n, m, dim;
+    const unsigned long long* keys;      // n: the forward search's
+    const unsigned long long* rev_keys;  // m: the reverse search's (the mutual filter), or null
+    int* idx;                        // n
+    float* d2;                       // n, may be null
+};
+hipError_t match_finish(const MatchFinishArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------------------------
+// K23 - K26 hypothesise and verify over correspondences (ransac_kernels.hip; driver: ransac_api.hip)
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int RANSAC_BLOCK = 256;
+struct RansacHypArgs {
+    const float* pairs6;             // C x (sx, sy, sz, tx, ty, tz): the correspondences by rank
+    const int* src_index;            // C: rank -> the source index i of the pair
+    int C;
+    unsigned long long seed;
+    double e2;                       // (double)edge_similarity squared
+    int first, count;                // hypotheses first .. first + count - 1; the outputs are indexed from 0
+    int* triples;                    // 3 * count: the source indices of the three draws
+    unsigned char* valid;            // count
+    float* pose12;                   // 12 * count: R9 column-major, then t3; the identity where invalid
+};
+hipError_t ransac_hypotheses(const RansacHypArgs& a, hipStream_t s);
+struct RansacCountArgs {
+    const float* pairs6; int C;
+    const float* pose12; const unsigned char* valid; int count;
+    double max_d2;                   // (double)max_distance squared
+    int chunk_len;                   // pairs per workgroup row, a multiple of RANSAC_BLOCK (ransac_chunk_len)
+    int* inlier_count;               // count, zero before the launch
+};
+int ransac_chunk_len(int count, int C, int cu_count);
+hipError_t ransac_count(const RansacCountArgs& a, hipStream_t s);
+// *best = max(*best, inliers << 32 | 0xFFFFFFFF - h) over the valid hypotheses, *nvalid += their number; both zero before the launch
+hipError_t ransac_argmax(const unsigned char* valid, const int* inlier_count, int count, unsigned long long* best, int* nvalid, hipStream_t s);
+struct RansacMaskArgs {
+    const float* pairs6; int C;
+    const float* pose;               // 12 floats on the device
+    double max_d2;
+    unsigned char* mask;             // C, by rank
+    double* d2;                      // C: the squared distance of an inlier, 0 otherwise
+};
+hipError_t ransac_mask_and_sum(const RansacMaskArgs& a, int* out_count, double* out_sum, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -474,5 +541,7 @@ hipError_t preload_outlier_kernels();
 hipError_t preload_plane_kernels();
 hipError_t preload_gicp_kernels();
 hipError_t preload_fpfh_kernels();
+hipError_t preload_match_kernels();
+hipError_t preload_ransac_kernels();
 
 }  // namespace mislam

@@ -930,7 +930,7 @@ int mi_icp_gicp_times(mi_ctx* ctx, double out_ms[MI_GICP_STAGES]);
 /* ----------------------------------------------------------------------------------------------------------------
  * Local descriptors (no reference counterpart): Fast Point Feature Histograms (Rusu, Blodow, Beetz, ICRA 2009) of a cloud with normals,
  * the descriptor a global registration matches to find the start that the local registrations above refine (INTEGRATION.md:
- * descriptors).  Matching the descriptors is the caller's.  Single-GPU contexts only.
+ * descriptors).  Matching the descriptors: mi_feature_match below (a start without odometry).  Single-GPU contexts only.
  * -------------------------------------------------------------------------------------------------------------- */
 
 /* The 33-bin FPFH of every point of a cloud, computed on the device.  Every rule below can be retraced in numpy
@@ -989,6 +989,127 @@ int mi_fpfh_features(mi_ctx* ctx,
  * kernel under MI_KERNEL_MOMENTS). */
 #define MI_FPFH_STAGES 8
 int mi_fpfh_features_times(mi_ctx* ctx, double out_ms[MI_FPFH_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
+ * Descriptor matching (no reference counterpart): the exact nearest neighbour of every row of one descriptor array among the rows of
+ * another, in up to MI_FEATURE_MAX_DIM dimensions -- the step between mi_fpfh_features and mi_ransac_register, which turns the
+ * matches into a start (a start without odometry).  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+
+/* idx[i] = the row of target_feat nearest to row i of query_feat, every pair looked at.  Every rule below can be retraced in numpy
+ * (tests/match_reference.py does, with the fp32 fmaf emulated exactly).  All arithmetic is fp32, every operation rounded once, fused
+ * where fmaf is written; q_i and t_j are rows i and j, b = 0 .. dim - 1 the components.
+ *   Dot product:  dot(i, j) = c_dim  with  c_0 = +0,  c_(b+1) = fmaf(q_i[b], t_j[b], c_b),  b ascending.  The product commutes, so
+ *     dot(i, j) is the same number whichever side is called the query: both directions of the mutual filter see the same bits.
+ *   Norms:  tt(j) is the same chain of t_j with itself, qq(i) that of q_i with itself.
+ *   Forward key:  h(i, j) = fmaf(-2.0f, dot(i, j), tt(j));  idx[i] = argmin_j h(i, j), strict <, j ascending: the lowest index wins a
+ *     tie.  h orders the targets as |q_i - t_j|^2 does (it is that minus qq(i)) without the cancellation-prone sum qq + tt - 2 dot.
+ *   Reverse key, mutual == 1 only:  g(j, i) = fmaf(-2.0f, dot(i, j), qq(i));  rev[j] = argmin_i g(j, i), the lowest i on ties.
+ *     idx[i] is kept iff rev[idx[i]] == i, else it becomes -1.
+ *   Distance of a kept match:  d2[i] = (float) sum_b ((double)q_i[b] - (double)t_j[b])^2 -- difference, product and sum each rounded
+ *     in fp64, b ascending, the sum rounded to fp32 once.  +INFINITY where idx[i] == -1.
+ *   Why the chain: it is bit for bit what the fp32-input matrix instructions of gfx950 compute (v_mfma_f32_32x32x2_f32,
+ *     v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain onto the accumulator, one rounding per product, nothing wider inside), and it is
+ *     what a loop of fmaf on the vector pipe computes.  So the contract does not say which pipe runs it; the library uses the matrix
+ *     pipe (32x32x2).  Padding dim with zero components up to the instruction's K changes no bit: fmaf(0, 0, c) = c for
+ *     every c but -0, and a chain that starts at +0 is at -0 only after a product that underflowed to -0, where +0 compares and adds
+ *     the same (h is never -0: tt(j) >= +0, and an exact zero sum rounds to +0).
+ *   Determinism: the minimum over chunks of targets is merged by an integer atomicMin on (key mapped to an order-preserving unsigned,
+ *     index); the same input gives the same bits on every call, whatever ran on the context before.  No floating-point atomics.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name; NO output has been written -- for a NULL ctx, query_feat,
+ *     target_feat or idx; n < 1 or m < 1, or either above MI_FEATURE_MAX_ROWS; dim outside [1, MI_FEATURE_MAX_DIM]; mutual neither 0
+ *     nor 1; a non-finite component or one above 1e15 in magnitude (64 * (1e15)^2 < FLT_MAX: no chain overflows): the message names
+ *     the array and the lowest row, query_feat first.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls of this header keep: it works in buffers
+ *     of its own.  Synchronous, host in and host out. */
+#define MI_FEATURE_MAX_DIM 64
+#define MI_FEATURE_MAX_ROWS (1 << 30)
+int mi_feature_match(mi_ctx* ctx,
+                     const float* query_feat, int n,   /* n*dim, row-major */
+                     const float* target_feat, int m,  /* m*dim */
+                     int dim,                          /* 1 .. MI_FEATURE_MAX_DIM; FPFH: 33 */
+                     int mutual,                       /* 0: every query keeps its match; 1: only reciprocal matches */
+                     int* idx,                         /* n: matched target, or -1 */
+                     float* d2);                       /* may be NULL; n */
+
+/* Where the last mi_feature_match of this context spent its host wall time, in ms (measurement hook, tools/global_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload of both arrays
+ *   out[2] norms, input check, its read-back        out[3], out[4] unused (0)
+ *   out[5] the searches (both directions) + finish  out[6] download of the results
+ *   out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage; mi_profile_get then has
+ * the search launches' own HIP-event time under MI_KERNEL_NN). */
+#define MI_MATCH_STAGES 8
+int mi_feature_match_times(mi_ctx* ctx, double out_ms[MI_MATCH_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
+ * A pose from correspondences (no reference counterpart): hypothesise and verify over the matches of mi_feature_match -- three draws, a
+ * Kabsch solve, a count of the matches it explains, every hypothesis evaluated, the best one refined.  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+#define MI_RANSAC_MAX_HYPOTHESES (1 << 22)
+#define MI_RANSAC_MAX_REFINE 8
+typedef struct mi_ransac_params {
+    int   hypotheses;          /* H: 1 .. MI_RANSAC_MAX_HYPOTHESES; every one of them is evaluated (no early exit) */
+    unsigned long long seed;
+    float max_distance;        /* inlier: |R s + t - t'| <= max_distance; > 0, finite */
+    float edge_similarity;     /* in [0, 1); 0 disables the edge check; Open3D's default is 0.9 */
+    int   refine_iterations;   /* 0 .. MI_RANSAC_MAX_REFINE: Kabsch over the inliers, recount, repeat */
+    int   reserved[8];
+} mi_ransac_params;
+void mi_ransac_params_default(mi_ransac_params* params);   /* 100000, 0, max_distance 0 (the caller must set it), 0.9f, 2 */
+
+/* Every rule below can be retraced in numpy (tests/ransac_reference.py does).
+ *   Correspondences: the pairs (i, idx[i]) with idx[i] >= 0 in ascending i are ranks 0 .. C - 1.
+ *   Draws, counter based (hypothesis h needs no state), in unsigned 64-bit arithmetic modulo 2^64:
+ *       u_r = mix(seed + 0x9E3779B97F4A7C15 * (3 h + r + 1)),  r = 0, 1, 2,   rank_r = ((u_r >> 32) * C) >> 32
+ *       mix(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31   (the splitmix64 finaliser)
+ *     Two equal ranks make the hypothesis invalid.  The triple reported is the three source indices i, in draw order.
+ *   Edge check, in fp64 from the fp32 coordinates, for the pairs of draws (0, 1), (1, 2), (0, 2): with d the difference of the two points,
+ *     ls2 = (dx*dx + dy*dy) + dz*dz in the source and lt2 likewise in the target; the hypothesis is valid iff ls2 >= e2 * lt2 and
+ *     lt2 >= e2 * ls2 for all three, e2 = (double)edge_similarity * (double)edge_similarity.
+ *   Pose of a hypothesis that is still valid: fp64 centroids ((p0 + p1) + p2) * (1.0 / 3.0) of source (cb) and target (ca); the
+ *     cross-covariance H[r][c] = (float)(((t0_r s0_c + t1_r s1_c) + t2_r s2_c) - 3.0 * ca_r * cb_c), rounded to fp32 as the ICP solve rounds
+ *     its moments; the Kabsch rotation of H by the library's 3 x 3 SVD in IEEE arithmetic (csrc/svd3.hpp, kabsch_rotation);
+ *     t_i = (float)ca_i - ((R_i0 (float)cb_0 + R_i1 (float)cb_1) + R_i2 (float)cb_2) in fp32.  R9 is column-major as mi_kabsch's.  Three
+ *     collinear points (the second singular value of H is 0) or a non-finite pose make the hypothesis invalid.  An invalid hypothesis
+ *     reports the identity and counts nothing.
+ *   Count, for every correspondence, in fp64 from the fp32 pose:  px = ((R00 x + R01 y) + R02 z) + tx and so on, d = p - t', and the pair is
+ *     an inlier iff (dx*dx + dy*dy) + dz*dz <= (double)max_distance * (double)max_distance.  inlier_count is an integer.
+ *   Winner: the valid hypothesis with the most inliers, the lowest h among equals (integers only: deterministic).  Without a valid
+ *     hypothesis the call returns MI_OK with *valid_hypotheses = 0, *inliers = 0, *best_hypothesis = -1, the identity, rmse = +INFINITY
+ *     and an all-zero mask.
+ *   Refinement, refine_iterations times while at least 3 inliers remain: mi_kabsch over the current inliers (its fixed-order fp64 moment
+ *     sums and solve), then a recount under the new pose.  An iteration that leaves fewer than 3 inliers is not taken, and refinement
+ *     stops there.  Refinement goes through mi_kabsch's buffers: a problem loaded by mi_icp_load does NOT survive a call that refines
+ *     (it does with refine_iterations = 0, and it survives mi_ransac_hypotheses).
+ *   rmse = (float)sqrt(S / inliers), S the fp64 sum of the final inliers' squared distances in a fixed order (rank r to partial sum
+ *     r mod 256 in ascending r, the partial sums added pairwise at strides 128, 64 .. 1).  No floating-point atomics anywhere.
+ *   inlier_mask (n, may be NULL): 1 where pair (i, idx[i]) is an inlier of the returned pose.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name; NO output has been written -- for a NULL ctx, src_xyz, tgt_xyz,
+ *     idx, params or required output; n < 1 or m < 1; hypotheses, max_distance, edge_similarity or refine_iterations outside the ranges
+ *     above; an idx[i] that is >= m or < -1 (the message names the lowest i); fewer than 3 correspondences.  MI_ERR_STATE on a distributed
+ *     context.  Synchronous, host in and host out. */
+int mi_ransac_register(mi_ctx* ctx, const float* src_xyz, int n, const float* tgt_xyz, int m,
+                       const int* idx,                 /* n: src[i] <-> tgt[idx[i]]; -1: no pair (mi_feature_match's output) */
+                       const mi_ransac_params* params,
+                       float out_R9[9], float out_t3[3],   /* as mi_kabsch: column-major R, t */
+                       int* inliers, float* rmse, int* best_hypothesis, int* valid_hypotheses,
+                       unsigned char* inlier_mask);    /* may be NULL; n */
+/* Test-grade primitive, like mi_plane_system: hypotheses first .. first + count - 1 of the call above (first >= 0, count >= 1,
+ * first + count <= params->hypotheses), each with its triple (3 source indices), valid flag, pose (R9 then t3) and inlier count.  Every
+ * output may be NULL.  The same checks and errors. */
+int mi_ransac_hypotheses(mi_ctx* ctx, const float* src_xyz, int n, const float* tgt_xyz, int m, const int* idx,
+                         const mi_ransac_params* params, int first, int count,
+                         int* triples /* 3*count */, unsigned char* valid /* count */, float* pose12 /* 12*count */, int* inlier_count /* count */);
+/* Where the last mi_ransac_register of this context spent its host wall time, in ms (measurement hook, tools/global_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload of the correspondences
+ *   out[2] the hypotheses kernel                    out[3] the counting kernel
+ *   out[4] arg-max, read-back, the winner's flags   out[5] refinement
+ *   out[6] unused (0)                               out[7] the whole device part of the call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage). */
+#define MI_RANSAC_STAGES 8
+int mi_ransac_register_times(mi_ctx* ctx, double out_ms[MI_RANSAC_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
