@@ -48,6 +48,7 @@ EXPORTS = [
     "mi_fpfh_features", "mi_fpfh_features_times",
     "mi_feature_match", "mi_feature_match_times",
     "mi_ransac_params_default", "mi_ransac_register", "mi_ransac_hypotheses", "mi_ransac_register_times",
+    "mi_ndt_constants", "mi_ndt_voxels", "mi_ndt_params_default", "mi_ndt_register", "mi_ndt_system", "mi_ndt_times",
     "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_selftest_icp_schedule", "mi_selftest_cpd_last", "mi_nn_kernel_name",
 ]
 
@@ -88,6 +89,11 @@ class OutlierStats(C.Structure):
 class PlaneParams(C.Structure):
     _fields_ = [("eps_rotation", C.c_float), ("eps_translation", C.c_float), ("max_iterations", C.c_int), ("max_distance_squared", C.c_float),
                 ("dist_mode", C.c_int), ("sync_every", C.c_int), ("verbose", C.c_int), ("reserved", C.c_int * 9)]
+
+
+class NdtParams(C.Structure):
+    _fields_ = [("eps_rotation", C.c_float), ("eps_translation", C.c_float), ("max_iterations", C.c_int), ("neighbourhood", C.c_int),
+                ("outlier_ratio", C.c_float), ("sync_every", C.c_int), ("verbose", C.c_int), ("reserved", C.c_int * 9)]
 
 
 class MiSlamError(RuntimeError):
@@ -382,6 +388,63 @@ def gicp_system_raw(handle, before, before_cov, n, after, after_cov, m, T, dist_
 def icp_gicp_times_raw(handle, out_ms):
     """mi_icp_gicp_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
     f = lib().mi_icp_gicp_times
+    f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
+    return f(handle, out_ms)
+
+
+def ndt_params(**kw):
+    """mi_ndt_params with the library's defaults, then the given fields"""
+    p = NdtParams()
+    lib().mi_ndt_params_default.restype = None
+    lib().mi_ndt_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def ndt_constants_raw(voxel, outlier_ratio, out):
+    """mi_ndt_constants with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_ndt_constants
+    f.argtypes, f.restype = [C.c_float, C.c_float, C.c_void_p], C.c_int
+    return f(voxel, outlier_ratio, out)
+
+
+def ndt_constants(voxel, outlier_ratio=0.55):
+    """(d1, d2, h, k) of the NDT score as float64 [4] (mi_ndt_constants, host only)"""
+    out = np.zeros(4, np.float64)
+    _check(ndt_constants_raw(float(voxel), float(outlier_ratio), out.ctypes.data))
+    return out
+
+
+def ndt_voxels_raw(handle, xyz, n, voxel, origin, min_points, eig_ratio, out_coord, out_mean, out_icov, out_n, out_count, out_cov, out_origin):
+    """mi_ndt_voxels with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_ndt_voxels
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 7
+    f.restype = C.c_int
+    return f(handle, xyz, n, voxel, origin, min_points, eig_ratio, out_coord, out_mean, out_icov, out_n, out_count, out_cov, out_origin)
+
+
+def ndt_register_raw(handle, before, n, coord, mean, icov, nv, voxel, origin, params, init_T, out_T, iterations, score, stop_reason):
+    """mi_ndt_register with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_ndt_register
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 7
+    f.restype = C.c_int
+    return f(handle, before, n, coord, mean, icov, nv, voxel, origin, params, init_T, out_T, iterations, score, stop_reason)
+
+
+def ndt_system_raw(handle, before, n, coord, mean, icov, nv, voxel, origin, T, neighbourhood, outlier_ratio, out_sums, out_centre, out_idx, out_terms):
+    """mi_ndt_system with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_ndt_system
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 4
+    f.restype = C.c_int
+    return f(handle, before, n, coord, mean, icov, nv, voxel, origin, T, neighbourhood, outlier_ratio, out_sums, out_centre, out_idx, out_terms)
+
+
+def ndt_times_raw(handle, out_ms):
+    """mi_ndt_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_ndt_times
     f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
     return f(handle, out_ms)
 
@@ -1040,6 +1103,68 @@ class Context:
         out = (C.c_double * 8)()
         _check(icp_gicp_times_raw(self._h, out))
         return dict(zip(("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"), list(out)))
+
+    # ---- registration against a voxel map
+    def ndt_voxels(self, xyz, voxel, origin=None, min_points=6, eig_ratio=0.01, want_cov=False):
+        """One Gaussian per occupied voxel (mi_ndt_voxels) -> dict(coord int32 [rows, 3], mean float32 [rows, 3], icov float32 [rows, 6]: the
+        inverse covariances (six zeros: no distribution), count int32 [rows], origin float32 [3], voxel; cov float32 [rows, 6] if asked for).
+        The dict is what ndt_register and ndt_system take as their map."""
+        xyz = _cloud(xyz)
+        n = xyz.shape[0]
+        o = None if origin is None else np.ascontiguousarray(origin, np.float32).reshape(3)
+        coord, mean, icov = np.empty((n, 3), np.int32), np.empty((n, 3), np.float32), np.empty((n, 6), np.float32)
+        count, cov, used = np.empty(n, np.int32), (np.empty((n, 6), np.float32) if want_cov else None), np.zeros(3, np.float32)
+        rows = C.c_int(0)
+        _check(ndt_voxels_raw(self._h, xyz.ctypes.data, n, float(voxel), None if o is None else o.ctypes.data, int(min_points), float(eig_ratio),
+                              coord.ctypes.data, mean.ctypes.data, icov.ctypes.data, C.addressof(rows), count.ctypes.data,
+                              None if cov is None else cov.ctypes.data, used.ctypes.data))
+        r = rows.value
+        out = dict(coord=coord[:r].copy(), mean=mean[:r].copy(), icov=icov[:r].copy(), count=count[:r].copy(), origin=used, voxel=float(voxel))
+        if want_cov:
+            out["cov"] = cov[:r].copy()
+        return out
+
+    @staticmethod
+    def _ndt_map(vox):
+        coord = np.ascontiguousarray(vox["coord"], np.int32)
+        mean, icov = np.ascontiguousarray(vox["mean"], np.float32), np.ascontiguousarray(vox["icov"], np.float32)
+        origin = np.ascontiguousarray(vox["origin"], np.float32).reshape(3)
+        if coord.ndim != 2 or coord.shape[1] != 3 or mean.shape != coord.shape or icov.shape != (coord.shape[0], 6):
+            raise ValueError("a voxel map holds coord [nv, 3], mean [nv, 3] and icov [nv, 6]")
+        return coord, mean, icov, origin, float(vox["voxel"])
+
+    def ndt_register(self, before, vox, params, init=None):
+        """NDT registration of `before` onto the voxel map `vox` (a dict as ndt_voxels returns; mi_ndt_register; params: ndt_params(...);
+        init: a [4, 4] transform indexed [row, col], None for the identity) -> (R [3, 3], t [3], iterations, score, stop_reason)."""
+        before = _cloud(before)
+        coord, mean, icov, origin, voxel = self._ndt_map(vox)
+        T0 = _T16(init)
+        T = np.zeros(16, np.float32)
+        it, score, why = C.c_int(0), C.c_float(0), C.c_int(0)
+        _check(ndt_register_raw(self._h, before.ctypes.data, before.shape[0], coord.ctypes.data, mean.ctypes.data, icov.ctypes.data, coord.shape[0], voxel,
+                                origin.ctypes.data, C.addressof(params), None if T0 is None else T0.ctypes.data, T.ctypes.data, C.addressof(it),
+                                C.addressof(score), C.addressof(why)))
+        R, t = _T_to_Rt(T)
+        return R, t, it.value, score.value, why.value
+
+    def ndt_system(self, before, vox, T=None, neighbourhood=7, outlier_ratio=0.55):
+        """One NDT linearisation at transform T (mi_ndt_system) -> (sums float64 [32], centre float32 [3], idx int32 [n]: the row of every
+        point's own voxel or -1, terms uint8 [n]: every point's number of terms)."""
+        before = _cloud(before)
+        coord, mean, icov, origin, voxel = self._ndt_map(vox)
+        T0 = _T16(T)
+        n = before.shape[0]
+        sums, centre, idx, terms = np.zeros(32, np.float64), np.zeros(3, np.float32), np.empty(n, np.int32), np.empty(n, np.uint8)
+        _check(ndt_system_raw(self._h, before.ctypes.data, n, coord.ctypes.data, mean.ctypes.data, icov.ctypes.data, coord.shape[0], voxel, origin.ctypes.data,
+                              None if T0 is None else T0.ctypes.data, int(neighbourhood), float(outlier_ratio), sums.ctypes.data, centre.ctypes.data,
+                              idx.ctypes.data, terms.ctypes.data))
+        return sums, centre, idx, terms
+
+    def ndt_times(self):
+        """ms per stage of the last ndt_register / ndt_system: workspace, upload, check, table, order, iterations, download, total (mi_ndt_times)."""
+        out = (C.c_double * 8)()
+        _check(ndt_times_raw(self._h, out))
+        return dict(zip(("workspace", "upload", "check", "table", "order", "iterations", "download", "total"), list(out)))
 
     # ---- local descriptors
     def fpfh_features(self, cloud, normals, k, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_counts=False, want_count=False):

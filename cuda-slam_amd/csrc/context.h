@@ -303,6 +303,30 @@ struct mi_ctx {
         double ms[MI_RANSAC_STAGES] = {0};               // mi_ransac_register_times
     } ransac;
 
+    // ---- mi_ndt_voxels: the voxel filter's buffers once more (its front end runs on them: voxel_front_run), the scatter's partials and the results;
+    // mi_ndt_register, mi_ndt_system: the moving cloud and its curve order, the listed voxels, their table, K16's rows and state block
+    struct NdtBuffers {
+        VoxelBuffers vox;
+        mislam::DevBuf<double> q6, front, back;
+        mislam::DevBuf<int> fix;
+        mislam::DevBuf<float> icov, cov;
+        double voxel_ms[8] = {0};                        // (the stages of mi_voxel_downsample_times; no entry point reads them yet)
+        mislam::DevBuf<float> staging, ux, uy, uz, qx, qy, qz, range_lo_hi;
+        mislam::DevBuf<int> range_bad, order;
+        mislam::DevBuf<mislam::KnnState> kstate;         // the moving cloud's input check
+        mislam::MortonScratch morton;
+        mislam::DevBuf<int> vcoord, hvals;
+        mislam::DevBuf<float> vmean, vicov;              // the listed voxels as uploaded
+        mislam::DevBuf<float4> mean4, icov4;             // ... and packed (what the step kernel gathers)
+        mislam::DevBuf<mislam::NdtMapState> mstate;
+        mislam::DevBuf<unsigned long long> hkeys;
+        mislam::DevBuf<double> rows, parts;
+        mislam::DevBuf<mislam::PlaneState> state;
+        mislam::DevBuf<int> out_idx;
+        mislam::DevBuf<unsigned char> out_terms;
+        double ms[MI_NDT_STAGES] = {0};                  // mi_ndt_times
+    } ndt;
+
     // ---- mi_prepare_cloud: buffers of its own, like the voxel call's: the raw cloud, the prepared one, the caller's index vectors and draws
     struct PrepareBuffers {
         mislam::DevBuf<float> raw, out, partials, noise_unit, outlier_unit;
@@ -397,7 +421,14 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+
+// ---- the voxel filter's front end (voxel_api.hip), for mi_voxel_downsample and mi_ndt_voxels: the reserves, the upload, the range pass and its
+// read-back with everything that can refuse the cloud (nothing has been written to a caller's array then), the keys, the sort, the rows and the
+// segmented sums (stages 0 - 4 of mi_voxel_downsample_times).  Behind it *a names the arrays of b the kernels filled and *st (the context's
+// pinned scratch) holds the range pass's facts; rows is not read back yet.
+int voxel_front_run(mi_ctx* c, const char* who, mi_ctx::VoxelBuffers& b, StageClock& clock, const float* xyz, int n, float voxel_size, const float* origin3,
+                    VoxArgs* a, VoxState** st);
 
 // ---- the front end of a search over a cloud's cell grid (search_front.hip).  A driver calls, in this order: search_front_reserve and its own
 // reserves (every reserve comes before the first upload), clock.mark(0), search_front_upload_and_check (stages 1 and 2: nothing has been written

@@ -523,6 +523,76 @@ struct RansacMaskArgs {
 };
 hipError_t ransac_mask_and_sum(const RansacMaskArgs& a, int* out_count, double* out_sum, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K27 - K31 NDT registration (ndt_kernels.hip; driver: ndt_api.hip; the term of a pair: ndt_term.hpp).  mi_ndt_voxels: the voxel filter's
+// own front end (VoxArgs above: coordinates, counts and means are mi_voxel_downsample's by construction), then a second segmented pass
+// over the sorted order for the scatter about the fp32 mean and one lane per voxel for the eigenvalue floor and the inverse.
+// mi_ndt_register: the listed voxels in an open-addressing hash table, the step kernel writing K16's rows from a direct lookup per point,
+// and K16's own reduce and solve behind the rows.
+// ---------------------------------------------------------------------------------------------------------------
+struct NdtScatterArgs {
+    VoxArgs v;                       // the front end's arrays, as vox_sums left them (out_xyz: the fp32 means)
+    double *front, *back;            // per sum tile, 6 doubles: as VoxArgs::front / back, of the six products
+    int* fix;                        // per sum tile: as VoxArgs::fix
+    double* q6;                      // rows x 6: sum (p_a - mu_a)(p_b - mu_b), xx xy xz yy yz zz
+};
+hipError_t ndt_scatter(const NdtScatterArgs& a, hipStream_t s);
+// one lane per voxel, rows_at_most lanes (>= st->rows, which the device knows): C = Q / (count - 1), the eigenvalue floor, C' (cov6, may be
+// null) and M = C'^-1, six floats each (zeros: no distribution)
+hipError_t ndt_voxel_finish(const double* q6, const int* count, const VoxState* st, int rows_at_most, int min_points, float eig_ratio, float* icov6,
+                            float* cov6, hipStream_t s);
+
+constexpr int NDT_NO_ROW = 0x7fffffff;       // NdtMapState's bad_* while no row has been refused
+constexpr unsigned long long NDT_KEY_EMPTY = 0xffffffffffffffffull;   // a free slot of the table (a key has 60 bits)
+// Device-resident facts of the listed voxels; the host sets the starts, the check kernel folds every row in with integer atomics (minima
+// and maxima: the same answer in any order), and the host reads it back once, before anything is written.
+struct NdtMapState {
+    int bad_mean, bad_icov, bad_coord, bad_order;    // lowest refused row of each kind, or NDT_NO_ROW
+    int cmin[3], cmax[3];            // per-axis range of the listed coordinates
+    unsigned int lo[3], hi[3];       // bounding box of the means of the rows with a distribution, as ordered keys (ndt_float_key)
+    int with_distribution;           // such rows
+};
+// an fp32 value as an unsigned key of the same order, and back (-0 below +0; the check has refused NaN before a key is formed)
+__host__ __device__ __forceinline__ unsigned int ndt_float_key(float v)
+{
+    union { float f; unsigned int u; } x;
+    x.f = v;
+    return (x.u & 0x80000000u) ? ~x.u : (x.u | 0x80000000u);
+}
+__host__ __device__ __forceinline__ float ndt_key_float(unsigned int k)
+{
+    union { float f; unsigned int u; } x;
+    x.u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    return x.f;
+}
+
+struct NdtMapView {
+    const unsigned long long* keys;  // capacity slots: the packed coordinate of the voxel stored there, or NDT_KEY_EMPTY
+    const int* vals;                 // its row in the caller's list
+    unsigned long long mask;         // capacity - 1, capacity a power of two >= 2 nv
+    int cmin[3], ext[3];             // the key of (cx, cy, cz) is (cx - cmin_x) | (cy - cmin_y) << 20 | (cz - cmin_z) << 40, each in [0, ext) <= 2^20
+    const float4* mean;              // nv: (x, y, z, 0)
+    const float4* icov;              // 2 nv: (xx, xy, xz, 0), (yy, yz, zz, 0)
+};
+// the listed voxels as uploaded -> packed means and matrices, and the facts of NdtMapState
+hipError_t ndt_check_voxels(const int* coord, const float* mean, const float* icov6, int nv, float4* mean4, float4* icov4, NdtMapState* st, hipStream_t s);
+// the rows with a distribution into the table (keys all NDT_KEY_EMPTY before the launch)
+hipError_t ndt_hash_build(const int* coord, const float4* icov4, int nv, const NdtMapView& map, unsigned long long* keys, int* vals, hipStream_t s);
+
+struct NdtStepArgs {
+    const PlaneState* state;         // the pose to linearise at (rounded to fp32 by every lane), the centre, done
+    const float *bx, *by, *bz;       // the moving cloud along its curve order, SoA, n entries
+    const int* order;                // sorted slot -> the caller's moving index
+    int n;
+    NdtMapView map;
+    float origin[3], voxel;          // mi_voxel_index's operands
+    double h, k;                     // mi_ndt_constants' out[2], out[3]
+    double* rows;                    // plane_row_count(n) x PLANE_ROW
+    int* idx;                        // may be null; n, the caller's order: the row of the point's own voxel, or -1
+    unsigned char* terms;            // may be null; n, the caller's order: the point's number of terms
+};
+hipError_t ndt_step(const NdtStepArgs& a, int neighbourhood, hipStream_t s);      // neighbourhood 1, 7 or 27
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -543,5 +613,6 @@ hipError_t preload_gicp_kernels();
 hipError_t preload_fpfh_kernels();
 hipError_t preload_match_kernels();
 hipError_t preload_ransac_kernels();
+hipError_t preload_ndt_kernels();
 
 }  // namespace mislam

@@ -1,0 +1,357 @@
+// mi_ndt_constants, mi_ndt_voxels, mi_ndt_register and mi_ndt_system behind the C ABI.  The voxel call is mi_voxel_downsample's front end
+// (voxel_front_run, voxel_api.hip) on buffers of its own, then the scatter pass, the per-voxel finish (ndt_kernels.hip) and the download.
+// The registration is mi_icp_gicp_register's driver with a voxel list in the place of the fixed cloud: argument checks, the reserves of the
+// call's own buffers in the context, the uploads, the checks of the moving cloud (knn_check_inputs) and of the list (K29) with their
+// read-backs, the table (K30), the moving cloud along its curve (morton_order / permute_soa), the state block, the iterations -- the step of
+// ndt_kernels.hip, then plane_kernels.hip's own reduce and solve -- in batches of sync_every between host reads of the state, and the results.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "context.h"
+#include "ndt_term.hpp"
+
+using namespace mislam;
+
+namespace {
+
+constexpr long long NDT_MAX_EXTENT = 1ll << 20;      // listed voxels per axis between the lowest and the highest one: 20 bits of the key each
+
+bool finite_f(float v) { return std::fabs(v) < INFINITY; }      // (false for NaN)
+
+}  // namespace
+
+extern "C" int mi_ndt_constants(float voxel_size, float outlier_ratio, double out[4])
+{
+    if (!out) { set_error("mi_ndt_constants: null out"); return MI_ERR_INVALID_ARG; }
+    if (!finite_f(voxel_size) || !(voxel_size > 0.f)) { set_error("mi_ndt_constants: voxel_size %g is not a positive finite number", (double)voxel_size); return MI_ERR_INVALID_ARG; }
+    if (!(outlier_ratio > 0.f && outlier_ratio < 1.f)) { set_error("mi_ndt_constants: outlier_ratio %g is not in (0, 1)", (double)outlier_ratio); return MI_ERR_INVALID_ARG; }
+    double k[4];
+    ndt_constants((double)voxel_size, (double)outlier_ratio, k);
+    for (int i = 0; i < 4; i++)
+        if (!std::isfinite(k[i])) { set_error("mi_ndt_constants: voxel_size %g and outlier_ratio %g leave fp64", (double)voxel_size, (double)outlier_ratio); return MI_ERR_INVALID_ARG; }
+    for (int i = 0; i < 4; i++) out[i] = k[i];
+    return MI_OK;
+}
+
+extern "C" int mi_ndt_voxels(mi_ctx* c, const float* xyz, int n, float voxel_size, const float* origin3, int min_points, float eig_ratio, int* out_coord,
+                             float* out_mean, float* out_icov6, int* out_n, int* out_count, float* out_cov6, float out_origin[3])
+{
+    const char* who = "mi_ndt_voxels";
+    if (!c) { set_error("%s: null context", who); return MI_ERR_INVALID_ARG; }
+    if (!xyz || !out_coord || !out_mean || !out_icov6 || !out_n) { set_error("%s: null xyz, out_coord, out_mean, out_icov6 or out_n", who); return MI_ERR_INVALID_ARG; }
+    if (n < 1) { set_error("%s: empty cloud (n = %d)", who, n); return MI_ERR_INVALID_ARG; }
+    if (!finite_f(voxel_size) || !(voxel_size > 0.f)) { set_error("%s: voxel_size %g is not a positive finite number", who, (double)voxel_size); return MI_ERR_INVALID_ARG; }
+    if (origin3 && !(finite_f(origin3[0]) && finite_f(origin3[1]) && finite_f(origin3[2]))) { set_error("%s: non-finite origin", who); return MI_ERR_INVALID_ARG; }
+    if (min_points < 3) { set_error("%s: min_points %d is below 3", who, min_points); return MI_ERR_INVALID_ARG; }
+    if (!(eig_ratio > 0.f && eig_ratio <= 1.f)) { set_error("%s: eig_ratio %g is not in (0, 1]", who, (double)eig_ratio); return MI_ERR_INVALID_ARG; }
+    if (c->distributed()) { set_error("%s: single-GPU contexts only", who); return MI_ERR_STATE; }
+    MI_ENTER(c);
+    mi_ctx::NdtBuffers& b = c->ndt;
+    StageClock clock(c, b.voxel_ms);
+
+    const size_t np = (size_t)n;
+    const size_t sum_tiles = (np + VOX_SUM_TILE - 1) / VOX_SUM_TILE;
+    MI_TRY(b.q6.reserve(6 * np)); MI_TRY(b.front.reserve(6 * sum_tiles)); MI_TRY(b.back.reserve(6 * sum_tiles)); MI_TRY(b.fix.reserve(sum_tiles));
+    MI_TRY(b.icov.reserve(6 * np));
+    if (out_cov6) MI_TRY(b.cov.reserve(6 * np));
+    NdtScatterArgs a{};
+    VoxState* st = nullptr;
+    MI_TRY(voxel_front_run(c, who, b.vox, clock, xyz, n, voxel_size, origin3, &a.v, &st));
+    const float origin[3] = {st->origin[0], st->origin[1], st->origin[2]};      // (st is the context's scratch: the rows' read-back below lands in it)
+
+    a.front = b.front.p; a.back = b.back.p; a.fix = b.fix.p; a.q6 = b.q6.p;
+    // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
+    if (b.q6.cap < 6 * np || b.front.cap < 6 * sum_tiles || b.back.cap < 6 * sum_tiles || b.fix.cap < sum_tiles || b.icov.cap < 6 * np ||
+        (out_cov6 && b.cov.cap < 6 * np) || b.vox.out_xyz.cap < 3 * np || b.vox.out_count.cap < np || b.vox.row_of.cap < np || b.vox.run_start.cap < np + 1) {
+        set_error("internal: %s buffers shorter than the launch", who);
+        return MI_ERR_STATE;
+    }
+    MI_HIP(ndt_scatter(a, c->stream));
+    MI_HIP(ndt_voxel_finish(b.q6.p, b.vox.out_count.p, b.vox.state.p, n, min_points, eig_ratio, b.icov.p, out_cov6 ? b.cov.p : nullptr, c->stream));
+    MI_TRY(clock.mark(4));
+
+    MI_HIP(hipMemcpyAsync(&st->rows, &b.vox.state.p->rows, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    const int rows = st->rows;
+    if (rows < 1 || rows > n) { set_error("internal: %s counted %d rows for %d points", who, rows, n); return MI_ERR_STATE; }
+    const size_t r = (size_t)rows;
+    MI_HIP(hipMemcpyAsync(out_coord, b.vox.out_coord.p, sizeof(int) * 3 * r, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipMemcpyAsync(out_mean, b.vox.out_xyz.p, sizeof(float) * 3 * r, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipMemcpyAsync(out_icov6, b.icov.p, sizeof(float) * 6 * r, hipMemcpyDeviceToHost, c->stream));
+    if (out_count) MI_HIP(hipMemcpyAsync(out_count, b.vox.out_count.p, sizeof(int) * r, hipMemcpyDeviceToHost, c->stream));
+    if (out_cov6) MI_HIP(hipMemcpyAsync(out_cov6, b.cov.p, sizeof(float) * 6 * r, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    *out_n = rows;
+    if (out_origin)
+        for (int k = 0; k < 3; k++) out_origin[k] = origin[k];
+    MI_TRY(clock.mark(5));
+    clock.finish();
+    return MI_OK;
+}
+
+extern "C" void mi_ndt_params_default(mi_ndt_params* p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof *p);
+    p->eps_rotation = 1e-6f;
+    p->eps_translation = 1e-6f;
+    p->max_iterations = 50;
+    p->neighbourhood = 7;
+    p->outlier_ratio = 0.55f;
+}
+
+namespace {
+
+// what both entry points refuse alike, before the context is touched
+int check_arguments(const char* who, mi_ctx* c, const float* before_xyz, int n, const int* vox_coord, const float* vox_mean, const float* vox_icov6, int nv,
+                    float voxel_size, const float* origin3, int neighbourhood, float outlier_ratio, const float* T)
+{
+    if (!c) { set_error("%s: null context", who); return MI_ERR_INVALID_ARG; }
+    if (!before_xyz || !vox_coord || !vox_mean || !vox_icov6 || !origin3) { set_error("%s: null before_xyz, vox_coord, vox_mean, vox_icov6 or origin3", who); return MI_ERR_INVALID_ARG; }
+    if (n < 1 || nv < 1) { set_error("%s: empty moving cloud or voxel list (n = %d, nv = %d)", who, n, nv); return MI_ERR_INVALID_ARG; }
+    if (!finite_f(voxel_size) || !(voxel_size > 0.f)) { set_error("%s: voxel_size %g is not a positive finite number", who, (double)voxel_size); return MI_ERR_INVALID_ARG; }
+    if (!(finite_f(origin3[0]) && finite_f(origin3[1]) && finite_f(origin3[2]))) { set_error("%s: non-finite origin", who); return MI_ERR_INVALID_ARG; }
+    if (neighbourhood != 1 && neighbourhood != 7 && neighbourhood != 27) { set_error("%s: neighbourhood %d is not 1, 7 or 27", who, neighbourhood); return MI_ERR_INVALID_ARG; }
+    if (!(outlier_ratio > 0.f && outlier_ratio < 1.f)) { set_error("%s: outlier_ratio %g is not in (0, 1)", who, (double)outlier_ratio); return MI_ERR_INVALID_ARG; }
+    if (T)
+        for (int i = 0; i < 16; i++)       // the rotation block and the translation column: the bottom row is never read
+            if (i % 4 != 3 && !std::isfinite(T[i])) { set_error("%s: transform entry %d is not finite (%g)", who, i, (double)T[i]); return MI_ERR_INVALID_ARG; }
+    return MI_OK;
+}
+
+// Stages 0 - 4 of either call and the state block at pose T: after it the step kernel's arguments are complete and checked against the buffers.
+int ndt_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* before_xyz, int n, const int* vox_coord, const float* vox_mean,
+                const float* vox_icov6, int nv, float voxel_size, const float* origin3, float outlier_ratio, const float* T, bool want_idx, bool want_terms,
+                NdtStepArgs* a, PlaneState* h)
+{
+    mi_ctx::NdtBuffers& b = c->ndt;
+    const size_t np = (size_t)n, vp = (size_t)nv;
+    const int nrows = plane_row_count(n), nparts = plane_part_count(nrows);
+    unsigned long long capacity = 2;
+    while (capacity < 2 * (unsigned long long)nv) capacity <<= 1;
+    double constants[4];
+    ndt_constants((double)voxel_size, (double)outlier_ratio, constants);
+    for (int i = 0; i < 4; i++)
+        if (!std::isfinite(constants[i])) { set_error("%s: voxel_size %g and outlier_ratio %g leave fp64", who, (double)voxel_size, (double)outlier_ratio); return MI_ERR_INVALID_ARG; }
+
+    MI_TRY(b.staging.reserve(3 * np));
+    MI_TRY(b.ux.reserve(np)); MI_TRY(b.uy.reserve(np)); MI_TRY(b.uz.reserve(np)); MI_TRY(b.qx.reserve(np)); MI_TRY(b.qy.reserve(np)); MI_TRY(b.qz.reserve(np));
+    MI_TRY(b.range_lo_hi.reserve(2 * 6 * KNN_RANGE_BLOCKS)); MI_TRY(b.range_bad.reserve(2 * KNN_RANGE_BLOCKS)); MI_TRY(b.kstate.reserve(1)); MI_TRY(b.order.reserve(np));
+    MI_TRY(b.vcoord.reserve(3 * vp)); MI_TRY(b.vmean.reserve(3 * vp)); MI_TRY(b.vicov.reserve(6 * vp)); MI_TRY(b.mean4.reserve(vp)); MI_TRY(b.icov4.reserve(2 * vp));
+    MI_TRY(b.mstate.reserve(1)); MI_TRY(b.hkeys.reserve((size_t)capacity)); MI_TRY(b.hvals.reserve((size_t)capacity));
+    MI_TRY(b.rows.reserve((size_t)nrows * PLANE_ROW));
+    if (nparts > 0) MI_TRY(b.parts.reserve((size_t)nparts * PLANE_ROW));
+    MI_TRY(b.state.reserve(1));
+    if (want_idx) MI_TRY(b.out_idx.reserve(np));
+    if (want_terms) MI_TRY(b.out_terms.reserve(np));
+    MortonArgs ma{};
+    MI_TRY(morton_args(b.morton, b.ux.p, b.uy.p, b.uz.p, n, b.order.p, &ma));
+    MI_TRY(clock.mark(0));
+
+    NdtMapState ms;
+    ms.bad_mean = ms.bad_icov = ms.bad_coord = ms.bad_order = NDT_NO_ROW;
+    for (int k = 0; k < 3; k++) { ms.cmin[k] = 0x7fffffff; ms.cmax[k] = -0x7fffffff - 1; ms.lo[k] = 0xffffffffu; ms.hi[k] = 0u; }
+    ms.with_distribution = 0;
+    MI_TRY(host_to_device(c, b.mstate.p, &ms, sizeof ms));
+    MI_TRY(host_to_device(c, b.vcoord.p, vox_coord, sizeof(int) * 3 * vp));
+    MI_TRY(host_to_device(c, b.vmean.p, vox_mean, sizeof(float) * 3 * vp));
+    MI_TRY(host_to_device(c, b.vicov.p, vox_icov6, sizeof(float) * 6 * vp));
+    MI_TRY(host_to_device(c, b.staging.p, before_xyz, sizeof(float) * 3 * np));
+    MI_HIP(aos_to_soa(b.staging.p, n, n, b.ux.p, b.uy.p, b.uz.p, nullptr, c->stream));
+    MI_TRY(clock.mark(1));
+
+    MI_HIP(knn_check_inputs(b.ux.p, b.uy.p, b.uz.p, n, nullptr, nullptr, nullptr, 0, b.range_lo_hi.p, b.range_bad.p, b.kstate.p, c->stream));
+    MI_HIP(ndt_check_voxels(b.vcoord.p, b.vmean.p, b.vicov.p, nv, b.mean4.p, b.icov4.p, b.mstate.p, c->stream));
+    KnnState* ks = reinterpret_cast<KnnState*>(c->h_scratch);                    // (pinned, 256 bytes: both read-backs fit)
+    NdtMapState* hs = reinterpret_cast<NdtMapState*>(c->h_scratch + 16);
+    static_assert(sizeof(KnnState) <= 16 * sizeof(float) && sizeof(NdtMapState) <= 48 * sizeof(float), "both states must fit the context's pinned scratch");
+    MI_HIP(hipMemcpyAsync(ks, b.kstate.p, sizeof(KnnState), hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipMemcpyAsync(hs, b.mstate.p, sizeof(NdtMapState), hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    MI_TRY(clock.mark(2));
+    // everything that can refuse the input is known here, before any output array has been touched
+    if (ks->bad_cloud != KNN_NO_POINT) {
+        set_error("%s: before_xyz point %d has a non-finite coordinate or one above 1e18 in magnitude", who, ks->bad_cloud);
+        return MI_ERR_INVALID_ARG;
+    }
+    if (hs->bad_mean != NDT_NO_ROW) { set_error("%s: vox_mean row %d has a non-finite entry or one above 1e18 in magnitude", who, hs->bad_mean); return MI_ERR_INVALID_ARG; }
+    if (hs->bad_icov != NDT_NO_ROW) { set_error("%s: vox_icov6 row %d has a non-finite entry or one above 1e18 in magnitude", who, hs->bad_icov); return MI_ERR_INVALID_ARG; }
+    if (hs->bad_coord != NDT_NO_ROW) { set_error("%s: vox_coord row %d has a coordinate outside [-2^30, 2^30)", who, hs->bad_coord); return MI_ERR_INVALID_ARG; }
+    if (hs->bad_order != NDT_NO_ROW) {
+        set_error("%s: vox_coord row %d does not come behind row %d in ascending (cz, cy, cx) order", who, hs->bad_order, hs->bad_order - 1);
+        return MI_ERR_INVALID_ARG;
+    }
+    NdtMapView map{};
+    for (int k = 0; k < 3; k++) {
+        const long long extent = (long long)hs->cmax[k] - (long long)hs->cmin[k] + 1;
+        if (extent < 1 || extent > NDT_MAX_EXTENT) {
+            set_error("%s: the listed voxels span %lld along axis %d (limit 2^20 = %lld)", who, extent, k, NDT_MAX_EXTENT);
+            return MI_ERR_INVALID_ARG;
+        }
+        map.cmin[k] = hs->cmin[k]; map.ext[k] = (int)extent;
+    }
+    map.keys = b.hkeys.p; map.vals = b.hvals.p; map.mask = capacity - 1;
+    map.mean = b.mean4.p; map.icov = b.icov4.p;
+    const bool any = hs->with_distribution > 0;
+    float centre[3] = {0.f, 0.f, 0.f};       // (no row with a distribution: no term can arise, and the centre is never used)
+    for (int k = 0; k < 3 && any; k++) centre[k] = 0.5f * (ndt_key_float(hs->lo[k]) + ndt_key_float(hs->hi[k]));
+
+    MI_HIP(hipMemsetAsync(b.hkeys.p, 0xff, sizeof(unsigned long long) * (size_t)capacity, c->stream));      // every slot NDT_KEY_EMPTY
+    if (b.hkeys.cap < capacity || b.hvals.cap < capacity || b.vcoord.cap < 3 * vp || b.icov4.cap < 2 * vp || b.mean4.cap < vp) {
+        set_error("internal: %s buffers shorter than the launch", who);
+        return MI_ERR_STATE;
+    }
+    MI_HIP(ndt_hash_build(b.vcoord.p, b.icov4.p, nv, map, b.hkeys.p, b.hvals.p, c->stream));
+    MI_TRY(clock.mark(3));
+
+    // the moving cloud along its curve: order[s] = the caller's index of sorted slot s
+    MI_HIP(morton_order(ma, c->stream));
+    MI_HIP(permute_soa(b.ux.p, b.uy.p, b.uz.p, b.order.p, n, n, b.qx.p, b.qy.p, b.qz.p, c->stream));
+    MI_TRY(clock.mark(4));
+
+    std::memset(h, 0, sizeof *h);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) h->R[3 * i + j] = T ? (double)T[4 * j + i] : (i == j ? 1.0 : 0.0);      // column-major in, row-major kept
+        h->t[i] = T ? (double)T[12 + i] : 0.0;
+        h->c0[i] = (double)centre[i];
+    }
+    MI_TRY(host_to_device(c, b.state.p, h, sizeof *h));
+    MI_TRY(clock.mark(1));
+
+    *a = NdtStepArgs{};
+    a->state = b.state.p;
+    a->bx = b.qx.p; a->by = b.qy.p; a->bz = b.qz.p; a->order = b.order.p;
+    a->n = n;
+    a->map = map;
+    for (int i = 0; i < 3; i++) a->origin[i] = origin3[i];
+    a->voxel = voxel_size;
+    a->h = constants[2]; a->k = constants[3];
+    a->rows = b.rows.p;
+    a->idx = want_idx ? b.out_idx.p : nullptr;
+    a->terms = want_terms ? b.out_terms.p : nullptr;
+    // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
+    if (b.qx.cap < np || b.qy.cap < np || b.qz.cap < np || b.order.cap < np || b.rows.cap < (size_t)nrows * PLANE_ROW || b.state.cap < 1 ||
+        (nparts > 0 && b.parts.cap < (size_t)nparts * PLANE_ROW) || (want_idx && b.out_idx.cap < np) || (want_terms && b.out_terms.cap < np)) {
+        set_error("internal: %s buffers shorter than the launch", who);
+        return MI_ERR_STATE;
+    }
+    return MI_OK;
+}
+
+// one iteration's launches: the step, then K16's rows -> sums -> (rules.solve) solve, update, stop rule.  With profiling on, the step's time
+// is booked to MI_KERNEL_NN and the other launches' to MI_KERNEL_SOLVE (mi_profile_get).
+int ndt_enqueue_iteration(mi_ctx* c, const NdtStepArgs& a, int neighbourhood, const PlaneRules& rules)
+{
+    mi_ctx::NdtBuffers& b = c->ndt;
+    const int nrows = plane_row_count(a.n);
+    {
+        ProfScope p(c, MI_KERNEL_NN);
+        MI_HIP(ndt_step(a, neighbourhood, c->stream));
+    }
+    {
+        ProfScope p(c, MI_KERNEL_SOLVE);
+        MI_HIP(plane_reduce_solve(b.state.p, b.rows.p, nrows, plane_part_count(nrows) > 0 ? b.parts.p : nullptr, rules, c->stream));
+    }
+    return MI_OK;
+}
+
+}  // namespace
+
+extern "C" int mi_ndt_register(mi_ctx* c, const float* before_xyz, int n, const int* vox_coord, const float* vox_mean, const float* vox_icov6, int nv,
+                               float voxel_size, const float origin3[3], const mi_ndt_params* p, const float init_T[16], float out_T[16], int* iterations,
+                               float* score, int* stop_reason)
+{
+    const char* who = "mi_ndt_register";
+    if (c && (!p || !out_T)) { set_error("%s: null params or out_T", who); return MI_ERR_INVALID_ARG; }
+    MI_TRY(check_arguments(who, c, before_xyz, n, vox_coord, vox_mean, vox_icov6, nv, voxel_size, origin3, p ? p->neighbourhood : 1, p ? p->outlier_ratio : 0.5f, init_T));
+    if (!(p->eps_rotation >= 0.f) || !(p->eps_translation >= 0.f)) {
+        set_error("%s: eps_rotation %g or eps_translation %g is NaN or negative", who, (double)p->eps_rotation, (double)p->eps_translation);
+        return MI_ERR_INVALID_ARG;
+    }
+    if (p->max_iterations < 0) { set_error("%s: max_iterations %d is negative (there is no unbounded mode)", who, p->max_iterations); return MI_ERR_INVALID_ARG; }
+    if (p->sync_every < 0) { set_error("%s: sync_every %d is negative", who, p->sync_every); return MI_ERR_INVALID_ARG; }
+    if (c->distributed()) { set_error("%s: single-GPU contexts only", who); return MI_ERR_STATE; }
+    MI_ENTER(c);
+    mi_ctx::NdtBuffers& b = c->ndt;
+    StageClock clock(c, b.ms);         // mi_ndt_times
+
+    NdtStepArgs a;
+    PlaneState h;
+    MI_TRY(ndt_prepare(c, who, clock, before_xyz, n, vox_coord, vox_mean, vox_icov6, nv, voxel_size, origin3, p->outlier_ratio, init_T, false, false, &a, &h));
+
+    PlaneRules rules{};
+    rules.eps_rotation = (double)p->eps_rotation; rules.eps_translation = (double)p->eps_translation;
+    rules.max_iterations = p->max_iterations; rules.solve = 1;
+    const int batch = p->sync_every > 0 ? p->sync_every : 4;
+    int enqueued = 0;
+    if (p->max_iterations == 0) { h.done = 1; h.stop_reason = MI_STOP_MAX_ITERATIONS; }
+    while (!h.done) {
+        if (enqueued >= p->max_iterations) { set_error("internal: %s ran %d iterations without a stop", who, enqueued); return MI_ERR_STATE; }
+        const int todo = std::min(batch, p->max_iterations - enqueued);
+        for (int i = 0; i < todo; i++) MI_TRY(ndt_enqueue_iteration(c, a, p->neighbourhood, rules));
+        enqueued += todo;
+        MI_HIP(hipMemcpyAsync(&h, b.state.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        MI_HIP(hipStreamSynchronize(c->stream));
+        if (p->verbose)
+            fprintf(stderr, "%s: %d enqueued, %d applied, |omega| %.3e |v| %.3e, terms %.0f, stop %d\n", who, enqueued, h.iterations, h.omega, h.v, h.sums[29],
+                    h.stop_reason);
+    }
+    MI_TRY(clock.mark(5));
+
+    for (int i = 0; i < 16; i++) out_T[i] = 0.f;
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) out_T[4 * j + i] = (float)h.R[3 * i + j];
+        out_T[12 + i] = (float)h.t[i];
+    }
+    out_T[15] = 1.f;
+    if (iterations) *iterations = h.iterations;
+    if (score) *score = h.sums[29] > 0.0 ? (float)(h.sums[27] / h.sums[29]) : 0.f;
+    if (stop_reason) *stop_reason = h.stop_reason;
+    MI_TRY(clock.mark(6));
+    clock.finish();
+    return MI_OK;
+}
+
+extern "C" int mi_ndt_system(mi_ctx* c, const float* before_xyz, int n, const int* vox_coord, const float* vox_mean, const float* vox_icov6, int nv,
+                             float voxel_size, const float origin3[3], const float T[16], int neighbourhood, float outlier_ratio, double out_sums[32],
+                             float out_centre[3], int* out_idx, unsigned char* out_terms)
+{
+    const char* who = "mi_ndt_system";
+    if (c && !out_sums) { set_error("%s: null out_sums", who); return MI_ERR_INVALID_ARG; }
+    MI_TRY(check_arguments(who, c, before_xyz, n, vox_coord, vox_mean, vox_icov6, nv, voxel_size, origin3, neighbourhood, outlier_ratio, T));
+    if (c->distributed()) { set_error("%s: single-GPU contexts only", who); return MI_ERR_STATE; }
+    MI_ENTER(c);
+    mi_ctx::NdtBuffers& b = c->ndt;
+    StageClock clock(c, b.ms);         // mi_ndt_times
+
+    NdtStepArgs a;
+    PlaneState h;
+    MI_TRY(ndt_prepare(c, who, clock, before_xyz, n, vox_coord, vox_mean, vox_icov6, nv, voxel_size, origin3, outlier_ratio, T, out_idx != nullptr,
+                       out_terms != nullptr, &a, &h));
+
+    PlaneRules rules{};                // solve = 0: the sums and nothing else
+    MI_TRY(ndt_enqueue_iteration(c, a, neighbourhood, rules));
+    MI_HIP(hipMemcpyAsync(&h, b.state.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    MI_TRY(clock.mark(5));
+
+    if (out_idx) MI_HIP(hipMemcpyAsync(out_idx, b.out_idx.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (out_terms) MI_HIP(hipMemcpyAsync(out_terms, b.out_terms.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < PLANE_ROW; i++) out_sums[i] = h.sums[i];
+    if (out_centre)
+        for (int i = 0; i < 3; i++) out_centre[i] = (float)h.c0[i];
+    MI_TRY(clock.mark(6));
+    clock.finish();
+    return MI_OK;
+}
+
+extern "C" int mi_ndt_times(mi_ctx* c, double out_ms[MI_NDT_STAGES])
+{
+    if (!c || !out_ms) { set_error("mi_ndt_times: null argument"); return MI_ERR_INVALID_ARG; }
+    for (int i = 0; i < MI_NDT_STAGES; i++) out_ms[i] = c->ndt.ms[i];
+    return MI_OK;
+}

@@ -34,19 +34,9 @@ extern "C" int mi_voxel_index(const float p[3], const float origin[3], float vox
     return MI_OK;
 }
 
-extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float voxel_size, const float* origin3, float* out_xyz, int* out_n,
-                                   int* out_count, int* out_coord, int* voxel_of_point)
+int mislam::voxel_front_run(mi_ctx* c, const char* who, mi_ctx::VoxelBuffers& b, StageClock& clock, const float* xyz, int n, float voxel_size,
+                            const float* origin3, VoxArgs* args, VoxState** state)
 {
-    if (!c) { set_error("mi_voxel_downsample: null context"); return MI_ERR_INVALID_ARG; }
-    if (!xyz || !out_xyz || !out_n) { set_error("mi_voxel_downsample: null xyz, out_xyz or out_n"); return MI_ERR_INVALID_ARG; }
-    if (n < 1) { set_error("mi_voxel_downsample: empty cloud (n = %d)", n); return MI_ERR_INVALID_ARG; }
-    if (!finite_f(voxel_size) || !(voxel_size > 0.f)) { set_error("mi_voxel_downsample: voxel_size %g is not a positive finite number", (double)voxel_size); return MI_ERR_INVALID_ARG; }
-    if (origin3 && !(finite_f(origin3[0]) && finite_f(origin3[1]) && finite_f(origin3[2]))) { set_error("mi_voxel_downsample: non-finite origin"); return MI_ERR_INVALID_ARG; }
-    if (c->distributed()) { set_error("mi_voxel_downsample: single-GPU contexts only"); return MI_ERR_STATE; }
-    MI_ENTER(c);
-    mi_ctx::VoxelBuffers& b = c->vox;
-    StageClock clock(c, b.ms);         // mi_voxel_downsample_times
-
     const size_t np = (size_t)n;
     const int scan_tiles = (n + VOX_SCAN_TILE - 1) / VOX_SCAN_TILE, sum_tiles = (n + VOX_SUM_TILE - 1) / VOX_SUM_TILE;
     MI_TRY(b.staging.reserve(3 * np)); MI_TRY(b.x.reserve(np)); MI_TRY(b.y.reserve(np)); MI_TRY(b.z.reserve(np)); MI_TRY(b.pts.reserve(np));
@@ -62,19 +52,20 @@ extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float vox
     MI_HIP(aos_to_soa(b.staging.p, n, n, b.x.p, b.y.p, b.z.p, b.pts.p, c->stream));
     MI_TRY(clock.mark(1));
 
-    VoxArgs a{};
+    VoxArgs& a = *args;
+    a = VoxArgs{};
     a.n = n; a.voxel = voxel_size; a.state = b.state.p;
     a.x = b.x.p; a.y = b.y.p; a.z = b.z.p; a.pts = b.pts.p;
     a.range_lo_hi = b.range_lo_hi.p; a.range_bad = b.range_bad.p;
     MI_HIP(vox_range(a, origin3, c->stream));
-    VoxState* st = reinterpret_cast<VoxState*>(c->h_scratch);     // (pinned, 256 bytes)
+    VoxState* st = *state = reinterpret_cast<VoxState*>(c->h_scratch);     // (pinned, 256 bytes)
     static_assert(sizeof(VoxState) <= 64 * sizeof(float), "VoxState must fit the context's pinned scratch");
     MI_HIP(hipMemcpyAsync(st, b.state.p, sizeof(VoxState), hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
     MI_TRY(clock.mark(2));
     // everything that can refuse the cloud is known here, before any output array has been touched
     if (st->bad_index != VOX_NO_POINT) {
-        set_error("mi_voxel_downsample: point %d has a non-finite coordinate", st->bad_index);
+        set_error("%s: point %d has a non-finite coordinate", who, st->bad_index);
         return MI_ERR_INVALID_ARG;
     }
     if (st->range_bad != 0) {                // (rare: the host names the first such point; the device only knows that the minimum or the maximum is one)
@@ -82,14 +73,14 @@ extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float vox
         for (int i = 0; i < n && first < 0; i++)
             for (int k = 0; k < 3; k++)
                 if (!voxel_axis(xyz[3 * (size_t)i + k], st->origin[k], voxel_size, &cc[k])) { first = i; break; }
-        set_error("mi_voxel_downsample: point %d: voxel coordinate outside [-2^30, 2^30)", first);
+        set_error("%s: point %d: voxel coordinate outside [-2^30, 2^30)", who, first);
         return MI_ERR_INVALID_ARG;
     }
     long long extent[3];
     for (int k = 0; k < 3; k++) {
         extent[k] = (long long)st->imax[k] - (long long)st->imin[k] + 1;
         if (extent[k] > VOX_MAX_EXTENT) {
-            set_error("mi_voxel_downsample: the occupied voxels span %lld along axis %d (limit 2^20 = %lld): a larger voxel_size is needed", extent[k], k, VOX_MAX_EXTENT);
+            set_error("%s: the occupied voxels span %lld along axis %d (limit 2^20 = %lld): a larger voxel_size is needed", who, extent[k], k, VOX_MAX_EXTENT);
             return MI_ERR_INVALID_ARG;
         }
     }
@@ -119,6 +110,27 @@ extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float vox
     MI_HIP(vox_rows(a, c->stream));
     MI_HIP(vox_sums(a, c->stream));
     MI_TRY(clock.mark(4));
+
+    return MI_OK;
+}
+
+extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float voxel_size, const float* origin3, float* out_xyz, int* out_n,
+                                   int* out_count, int* out_coord, int* voxel_of_point)
+{
+    if (!c) { set_error("mi_voxel_downsample: null context"); return MI_ERR_INVALID_ARG; }
+    if (!xyz || !out_xyz || !out_n) { set_error("mi_voxel_downsample: null xyz, out_xyz or out_n"); return MI_ERR_INVALID_ARG; }
+    if (n < 1) { set_error("mi_voxel_downsample: empty cloud (n = %d)", n); return MI_ERR_INVALID_ARG; }
+    if (!finite_f(voxel_size) || !(voxel_size > 0.f)) { set_error("mi_voxel_downsample: voxel_size %g is not a positive finite number", (double)voxel_size); return MI_ERR_INVALID_ARG; }
+    if (origin3 && !(finite_f(origin3[0]) && finite_f(origin3[1]) && finite_f(origin3[2]))) { set_error("mi_voxel_downsample: non-finite origin"); return MI_ERR_INVALID_ARG; }
+    if (c->distributed()) { set_error("mi_voxel_downsample: single-GPU contexts only"); return MI_ERR_STATE; }
+    MI_ENTER(c);
+    mi_ctx::VoxelBuffers& b = c->vox;
+    StageClock clock(c, b.ms);         // mi_voxel_downsample_times
+
+    const size_t np = (size_t)n;
+    VoxArgs a;
+    VoxState* st = nullptr;
+    MI_TRY(voxel_front_run(c, "mi_voxel_downsample", b, clock, xyz, n, voxel_size, origin3, &a, &st));
 
     MI_HIP(hipMemcpyAsync(&st->rows, &b.state.p->rows, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));

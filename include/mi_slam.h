@@ -1112,6 +1112,128 @@ int mi_ransac_hypotheses(mi_ctx* ctx, const float* src_xyz, int n, const float* 
 int mi_ransac_register_times(mi_ctx* ctx, double out_ms[MI_RANSAC_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * Registration against a voxel map (no reference counterpart): the Normal Distributions Transform (Biber & Strasser, IROS 2003; Magnusson,
+ * 2009), as in PCL's NormalDistributionsTransform (registration against a voxel map).  The fixed side is summarised ONCE as
+ * one Gaussian per occupied voxel (mi_ndt_voxels); a scan is then registered against those Gaussians by a direct voxel lookup per point,
+ * with no neighbour search: an iteration is O(n) whatever the size of the map, and the basin of convergence is set by the voxel size, so
+ * the same call runs coarse to fine.  The optimiser is the Gauss-Newton / reweighted form below -- NOT PCL's full Newton Hessian with the
+ * More-Thuente line search.  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+
+/* The constants of the NDT score for a voxel size r and an outlier ratio o, in fp64 on the host (no context), with r and o promoted
+ * and every operation rounded:  c1 = 10 (1 - o);  c2 = o / ((r r) r);  d3 = -log(c2);  d1 = -log(c1 + c2) - d3;
+ * d2 = -2 log((-log(c1 exp(-0.5) + c2) - d3) / d1).   out = d1, d2, h = -0.5 d2, k = -(d1 d2).
+ * MI_ERR_INVALID_ARG (out untouched) for a NULL out, a voxel_size that is not positive and finite, an outlier_ratio outside (0, 1), or
+ * values that leave fp64. */
+int mi_ndt_constants(float voxel_size, float outlier_ratio, double out[4]);
+
+/* One Gaussian per occupied voxel of a cloud, computed on the device.  Every rule can be retraced in numpy (tests/ndt_reference.py does).
+ *   Voxel of a point, output order, count, mean: exactly mi_voxel_downsample's, by the same kernels -- mi_voxel_index's arithmetic with
+ *     origin3 (NULL: the per-axis minimum), rows ascending by (cz, cy, cx), a per-axis extent of at most 2^20, the mean the fp64 sum over
+ *     the count rounded once to fp32.  out_coord, out_count and out_mean equal that call's out_coord, out_count and out_xyz bit for bit on
+ *     the same input; out_origin is the origin used.
+ *   Scatter about the fp32 mean promoted back to fp64 (so it can be retraced from the outputs): d = p - mu (one fp64 subtraction per
+ *     coordinate), Q_ab = sum d_a d_b (one product and one addition per entry and point), a <= b.  The order of the sum is a function of
+ *     the sorted order alone, and there is no floating-point atomic: the same input gives the same bits.  C = Q / (count - 1).
+ *   Regularisation (PCL's): lambda_0 <= lambda_1 <= lambda_2 and the unit eigenvectors V (columns) of C by mi_estimate_normals' cyclic
+ *     Jacobi iteration in fp64;  lambda_i' = max(lambda_i, eig_ratio lambda_2), eig_ratio promoted;  with x_i = 1 / lambda_i',
+ *     M_ab = ((V_a0 x_0) V_b0 + (V_a1 x_1) V_b1) + (V_a2 x_2) V_b2, and C'_ab the same with lambda_i' in the place of x_i -- except that,
+ *     as in PCL, C' is C itself where no eigenvalue was raised.  Six entries each (xx, xy, xz, yy, yz, zz), each rounded once to fp32:
+ *     out_icov6 = M, out_cov6 = C'.
+ *   No distribution: a voxel with count < min_points, or with a lambda_2 that is <= 0 or not finite (identical points), still has its
+ *     row; its out_icov6 (and out_cov6) is six zeros, which mi_ndt_register treats as "no Gaussian here".
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name and, for a bad point, names its index (the lowest); NO output
+ *     has been written -- for a NULL ctx, xyz, out_coord, out_mean, out_icov6 or out_n; n < 1; a voxel_size that is not positive and
+ *     finite; a non-finite origin; min_points < 3; an eig_ratio outside (0, 1]; a non-finite coordinate; a voxel coordinate outside
+ *     [-2^30, 2^30); occupied voxels that span more than 2^20 along an axis.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls of this header keep: it works in buffers
+ *     of its own.  Synchronous, host in and host out. */
+int mi_ndt_voxels(mi_ctx* ctx, const float* xyz, int n, float voxel_size,
+                  const float* origin3,            /* may be NULL: the per-axis minimum of the cloud */
+                  int min_points,                  /* >= 3; PCL: 6 */
+                  float eig_ratio,                 /* in (0, 1]; PCL: 0.01 */
+                  int* out_coord,                  /* capacity n*3: (cx, cy, cz) of every row */
+                  float* out_mean,                 /* capacity n*3 */
+                  float* out_icov6,                /* capacity n*6 */
+                  int* out_n,                      /* rows written */
+                  int* out_count,                  /* may be NULL; capacity n */
+                  float* out_cov6,                 /* may be NULL; capacity n*6 */
+                  float out_origin[3]);            /* may be NULL */
+
+typedef struct mi_ndt_params {
+    float eps_rotation;           /* converged when |omega| <= this (radians) ...            default 1e-6 */
+    float eps_translation;        /* ... and |v| <= this (the clouds' units)                 default 1e-6 */
+    int   max_iterations;         /* >= 0; there is no unbounded mode                        default 50   */
+    int   neighbourhood;          /* voxels looked up per point: 1, 7 or 27                  default 7    */
+    float outlier_ratio;          /* in (0, 1)                                               default 0.55 */
+    int   sync_every;             /* iterations enqueued between host reads of the state; 0 = 4; moves no bit */
+    int   verbose;
+    int   reserved[9];
+} mi_ndt_params;
+void mi_ndt_params_default(mi_ndt_params* p);
+
+/* Registers the moving cloud `before` (n points) onto nv voxel Gaussians (vox_coord, vox_mean, vox_icov6 as mi_ndt_voxels writes them,
+ * with the voxel_size and the origin of that call), on the device.  Every rule below can be retraced in numpy (tests/ndt_reference.py does).
+ *   Transform, the pose's rounding to fp32, q, the update, the solve, the stop rules and their order, sync_every, max_iterations = 0:
+ *     exactly those of mi_icp_plane_register, by the same code -- q = ((R00*b_x + R01*b_y) + R02*b_z) + t_x in fp32 with the pose rounded
+ *     once; x = (omega, v) solving (sum H) x = -(sum g) by the scaled LDL^T with a pivot floor of 1e-10 (MI_STOP_DEGENERATE below it or on
+ *     a bad diagonal, the pose staying as it was); R <- dR R, t <- dR (t - c0) + c0 + v; MI_STOP_CONVERGED, then MI_STOP_MAX_ITERATIONS.
+ *     MI_STOP_NO_PAIRS fires below 6 terms.
+ *   Centre: c0 = 0.5f * (lo + hi) per axis of the bounding box of vox_mean over the rows that have a distribution (0 where none has).
+ *   Constants: h and k of mi_ndt_constants(voxel_size, outlier_ratio).
+ *   Lookup: the voxel of q is mi_voxel_index(q, origin3, voxel_size), bit for bit; a q that function refuses has no term.  The
+ *     neighbourhood is that voxel plus offsets in this fixed order -- 1: none; 7: -x, +x, -y, +y, -z, +z behind the voxel itself; 27: all
+ *     (dz, dy, dx) in {-1, 0, 1}^3 ascending, the voxel itself in its place (the 14th).  A voxel that is not listed, or whose six
+ *     vox_icov6 entries are all zero, gives no term.
+ *   Term of (q, voxel v), every operand promoted to fp64 first and every operation rounded, sums of three formed left to right:
+ *       d = q - mu_v;   Md_r = (M_r0 d_x + M_r1 d_y) + M_r2 d_z;   m = (d_x Md_0 + d_y Md_1) + d_z Md_2
+ *     an m that is negative or not finite (an indefinite matrix given by the caller) is no term;  e = exp(h m);  w = k e.
+ *   Per point, from +0 and in the offsets' order: A += w M_v (six entries, one product and one addition each), b += w Md (three),
+ *     E += e.  With P = q - c0 the 21 entries of H are formed from A exactly as mi_icp_gicp_register forms them from M, and the six of g
+ *     from b as it forms them from Md: Gauss-Newton on sum -d1 exp(-d2 m / 2) with the weights held fixed within the iteration.
+ *   Sums (mi_ndt_system's out_sums), the layout of mi_plane_system: [0, 21) the upper triangle of sum H, row-major; [21, 27) sum g;
+ *     [27] sum E; [28] the number of points with at least one term; [29] the number of terms; [30, 32) 0.  The sums are added in a fixed
+ *     order that depends on n alone, with no floating-point atomics: the same input gives the same bits on every call, whatever ran on
+ *     the context before and whatever sync_every.
+ *   Outputs: out_T as mi_icp_plane_register's; *iterations counts the updates applied; *score is sums[27] / sums[29] of the last
+ *     linearisation rounded to fp32 -- the mean likelihood per term, in (0, 1], higher is better; 0 without terms; *stop_reason is one
+ *     of MI_STOP_CONVERGED, MI_STOP_MAX_ITERATIONS, MI_STOP_NO_PAIRS, MI_STOP_DEGENERATE.  Any of the last three may be NULL.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name and names the cause and, for a bad point or row, which array
+ *     and which index (the lowest); NO output has been written -- for a NULL ctx, before_xyz, vox_coord, vox_mean, vox_icov6, origin3,
+ *     params or out_T; n < 1 or nv < 1; a voxel_size that is not positive and finite; a non-finite origin; an outlier_ratio outside
+ *     (0, 1); a neighbourhood other than 1, 7 or 27; eps_rotation or eps_translation NaN or negative; max_iterations < 0; sync_every < 0;
+ *     a non-finite entry of init_T's rotation block or translation column; a non-finite point, mean or vox_icov6 entry, or one above 1e18
+ *     in magnitude; a vox_coord coordinate outside [-2^30, 2^30); vox_coord rows that are not strictly ascending by (cz, cy, cx) (the
+ *     message names the first row that does not come behind its predecessor; duplicates are such rows); listed voxels that span more
+ *     than 2^20 along an axis.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls of this header keep: it works in buffers
+ *     of its own; the voxel list is uploaded by every call and not kept.  Synchronous, host in and host out. */
+int mi_ndt_register(mi_ctx* ctx, const float* before_xyz, int n,
+                    const int* vox_coord, const float* vox_mean, const float* vox_icov6, int nv, float voxel_size, const float origin3[3],
+                    const mi_ndt_params* params, const float init_T[16] /* may be NULL: identity */,
+                    float out_T[16], int* iterations, float* score, int* stop_reason);
+
+/* One linearisation at a given transform, as mi_plane_system: the sums above at the pose T (NULL: the identity, the same bits), the
+ * centre c0, per moving point out_idx[i] -- the row of q_i's own voxel if it is listed with a distribution, else -1 -- and out_terms[i],
+ * the point's number of terms.  The same arguments are refused, with out_sums in the place of out_T; out_centre, out_idx and out_terms
+ * may be NULL. */
+int mi_ndt_system(mi_ctx* ctx, const float* before_xyz, int n,
+                  const int* vox_coord, const float* vox_mean, const float* vox_icov6, int nv, float voxel_size, const float origin3[3],
+                  const float T[16] /* may be NULL */, int neighbourhood, float outlier_ratio,
+                  double out_sums[32], float out_centre[3], int* out_idx /* may be NULL; n */, unsigned char* out_terms /* may be NULL; n */);
+
+/* Where the last mi_ndt_register or mi_ndt_system of this context spent its host wall time, in ms (measurement hook, tools/ndt_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA (voxel list, moving cloud, state)
+ *   out[2] input checks, bounding box, read-backs   out[3] the voxels' hash table
+ *   out[4] curve order of the moving cloud + permute out[5] the iterations, host reads of the state included
+ *   out[6] download of the results                  out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage). */
+#define MI_NDT_STAGES 8
+int mi_ndt_times(mi_ctx* ctx, double out_ms[MI_NDT_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
  * -------------------------------------------------------------------------------------------------------------- */
 enum {
