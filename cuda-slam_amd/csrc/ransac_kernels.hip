@@ -1,7 +1,7 @@
 // K23 - K26 hypothesise and verify over correspondences (driver: ransac_api.hip; the contract: mi_ransac_register in mi_slam.h).
 //   K23 ransac_hypothesis: one lane per hypothesis.  The three counter-based draws, the edge check in fp64, the Kabsch solve of the three
-//                          pairs (fp64 moments rounded to fp32 as solve_from_moments does, kabsch_rotation in the IEEE form).  Writes the
-//                          triple, the valid flag and the fp32 pose.
+//                          pairs (fp64 moments rounded to fp32 as solve_from_moments does, kabsch_rotation in the IEEE form, one
+//                          Newton-Schulz step in fp64 towards the nearest rotation).  Writes the triple, the valid flag and the fp32 pose.
 //   K24 ransac_count:      the hot path, O(H C).  One lane per hypothesis with its pose in registers as fp64; the workgroup stages 256 pairs
 //                          at a time in the LDS and every lane reads the same pair at the same time (an LDS broadcast).  Invalid hypotheses
 //                          are NOT compacted away first: a lane of an invalid hypothesis walks along with a flag that keeps its count at
@@ -73,9 +73,18 @@ __global__ __launch_bounds__(RANSAC_BLOCK) void ransac_hypothesis_kernel(const R
                 H.a[r][c] = (float)(m - 3.0 * ca[r] * cb[c]);
             }
         const Kabsch3 kb = kabsch_rotation<false>(H);                               // the IEEE form, inline
+        // The sweeps of the 3 x 3 SVD never re-orthonormalise U and V: over thousands of hypotheses |R^T R - I| reaches 45 eps.  One
+        // Newton-Schulz step in fp64, R (1.5 I - 0.5 R^T R), rounded to fp32 once, brings the pose to a rotation within an eps (mi_slam.h)
+        double M[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                const double g = ((double)kb.R.a[0][i] * (double)kb.R.a[0][j] + (double)kb.R.a[1][i] * (double)kb.R.a[1][j]) + (double)kb.R.a[2][i] * (double)kb.R.a[2][j];
+                M[i][j] = (i == j ? 1.5 : 0.0) - 0.5 * g;
+            }
         float Ri[9], ti[3];
         for (int c = 0; c < 3; c++)
-            for (int r = 0; r < 3; r++) Ri[3 * c + r] = kb.R.a[r][c];
+            for (int r = 0; r < 3; r++)
+                Ri[3 * c + r] = (float)(((double)kb.R.a[r][0] * M[0][c] + (double)kb.R.a[r][1] * M[1][c]) + (double)kb.R.a[r][2] * M[2][c]);
         const float fcb[3] = {(float)cb[0], (float)cb[1], (float)cb[2]}, fca[3] = {(float)ca[0], (float)ca[1], (float)ca[2]};
         for (int i = 0; i < 3; i++) ti[i] = fca[i] - ((Ri[i] * fcb[0] + Ri[3 + i] * fcb[1]) + Ri[6 + i] * fcb[2]);
         bool finite = true;

@@ -1070,7 +1070,10 @@ void mi_ransac_params_default(mi_ransac_params* params);   /* 100000, 0, max_dis
  *     lt2 >= e2 * ls2 for all three, e2 = (double)edge_similarity * (double)edge_similarity.
  *   Pose of a hypothesis that is still valid: fp64 centroids ((p0 + p1) + p2) * (1.0 / 3.0) of source (cb) and target (ca); the
  *     cross-covariance H[r][c] = (float)(((t0_r s0_c + t1_r s1_c) + t2_r s2_c) - 3.0 * ca_r * cb_c), rounded to fp32 as the ICP solve rounds
- *     its moments; the Kabsch rotation of H by the library's 3 x 3 SVD in IEEE arithmetic (csrc/svd3.hpp, kabsch_rotation);
+ *     its moments; the Kabsch rotation K of H by the library's 3 x 3 SVD in IEEE arithmetic (csrc/svd3.hpp, kabsch_rotation), then one
+ *     Newton-Schulz step towards the nearest rotation in fp64 from the fp32 entries of K (the sweeps of the SVD do not re-orthonormalise:
+ *     |K^T K - I| reaches 45 eps over thousands of hypotheses; |R^T R - I| stays within an eps):
+ *     G_ij = (K_0i K_0j + K_1i K_1j) + K_2i K_2j,  M = 1.5 I - 0.5 G,  R_ij = (float)((K_i0 M_0j + K_i1 M_1j) + K_i2 M_2j);
  *     t_i = (float)ca_i - ((R_i0 (float)cb_0 + R_i1 (float)cb_1) + R_i2 (float)cb_2) in fp32.  R9 is column-major as mi_kabsch's.  Three
  *     collinear points (the second singular value of H is 0) or a non-finite pose make the hypothesis invalid.  An invalid hypothesis
  *     reports the identity and counts nothing.
@@ -1085,6 +1088,8 @@ void mi_ransac_params_default(mi_ransac_params* params);   /* 100000, 0, max_dis
  *     (it does with refine_iterations = 0, and it survives mi_ransac_hypotheses).
  *   rmse = (float)sqrt(S / inliers), S the fp64 sum of the final inliers' squared distances in a fixed order (rank r to partial sum
  *     r mod 256 in ascending r, the partial sums added pairwise at strides 128, 64 .. 1).  No floating-point atomics anywhere.
+ *     A winner with fewer than 3 inliers is not refined: the call returns that hypothesis's own pose, and with *inliers = 0 an all-zero
+ *     mask and rmse = +INFINITY (beside *valid_hypotheses > 0 and a pose that is not the identity).
  *   inlier_mask (n, may be NULL): 1 where pair (i, idx[i]) is an inlier of the returned pose.
  *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name; NO output has been written -- for a NULL ctx, src_xyz, tgt_xyz,
  *     idx, params or required output; n < 1 or m < 1; hypotheses, max_distance, edge_similarity or refine_iterations outside the ranges

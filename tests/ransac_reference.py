@@ -107,11 +107,12 @@ def kabsch_pairs64(s, t):
     return R[0], ca - R[0] @ cb
 
 
-def planted(seed=2026):
+def planted(seed=2026, n=2000):
     """The planted problem of the GPU suite: 2 000 source points uniform in a cube, target = R0 source + t0 + 1e-3 noise with a rotation of
-    100 degrees; idx true for 30 % of the points, uniformly random for 60 %, -1 for 10 %.  (src, tgt, idx, R0, t0, true mask)"""
+    100 degrees; idx true for 30 % of the points, uniformly random for 60 %, -1 for 10 %.  (src, tgt, idx, R0, t0, true mask)
+    n: the same recipe with another number of points (a multiple of 10)."""
     rng = np.random.default_rng(seed)
-    n = 2000
+    a30, a90 = 3 * n // 10, 9 * n // 10
     src = rng.uniform(-1, 1, (n, 3)).astype(np.float32)
     axis = np.array([0.3, -0.5, 0.8])
     axis /= np.linalg.norm(axis)
@@ -122,8 +123,8 @@ def planted(seed=2026):
     tgt = (src.astype(np.float64) @ R0.T + t0 + 1e-3 * rng.uniform(-1, 1, (n, 3)) / np.sqrt(3)).astype(np.float32)
     kind = rng.permutation(n)
     idx = np.arange(n, dtype=np.int32)
-    idx[kind[600:1800]] = rng.integers(0, n, 1200)
-    idx[kind[1800:]] = -1
+    idx[kind[a30:a90]] = rng.integers(0, n, a90 - a30)
+    idx[kind[a90:]] = -1
     true = np.zeros(n, bool)
-    true[kind[:600]] = True
+    true[kind[:a30]] = True
     return src, tgt, idx, R0, t0, true

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 import ransac_reference as R
-from kabsch_catalogue import EPS, WELL_POSED, kabsch64, objective_deficit, orthogonality, posedness
+from ransac_scale_cases import check_poses, check_refined_pose
 
 pytestmark = pytest.mark.gpu
 
@@ -60,19 +60,7 @@ def test_triples_and_valid_flags(dumped):
 def test_every_valid_pose_against_float64(dumped):
     triples, valid, pose12, counts = dumped
     ref = reference()
-    v = valid != 0
-    Rd = pose12[v, :9].reshape(-1, 3, 3).transpose(0, 2, 1)          # column-major -> [row, col]
-    assert np.isfinite(pose12).all()
-    e, de = orthogonality(Rd)
-    assert e.max() <= 32 * EPS and de.max() <= 32 * EPS
-    Hm, S, d, g = ref["H"][v], ref["S"][v], ref["d"][v], ref["g"][v]
-    assert objective_deficit(Rd, Hm, S, d).max() <= 16 * EPS
-    cond, well, _ = posedness(S, g)
-    dR = np.abs(Rd.astype(np.float64) - ref["R64"][v]).max(axis=(1, 2))
-    assert well.sum() >= 0.5 * v.sum() and (dR[well] <= 32 * (cond[well] + EPS)).all()
-    cb, ca = ref["cb"][v], ref["ca"][v]
-    tol = 3 * np.abs(cb).max(axis=1) * dR + 8 * EPS * (np.abs(ca).max(axis=1) + 3 * np.abs(cb).max(axis=1))
-    assert (np.abs(pose12[v, 9:].astype(np.float64) - ref["t64"][v]).max(axis=1)[well] <= tol[well]).all()
+    check_poses(valid, pose12, ref)
 
 
 def test_counts_equal_a_float64_recount_under_the_device_pose(dumped):
@@ -96,13 +84,6 @@ def register(ctx, capi):
             cache[refine] = ctx.ransac_register(src, tgt, idx, capi.ransac_params(MAXD, hypotheses=H, seed=SEED, refine_iterations=refine), want_mask=True)
         return cache[refine]
     return run
-
-
-def moments_h32(s, t):
-    """the fp32-rounded cross-covariance of the pairs s -> t as the solve forms it from fp64 moments, as float64 [1, 3, 3]"""
-    n = float(len(s))
-    cb, ca = s.sum(axis=0) / n, t.sum(axis=0) / n
-    return (t.T @ s - n * np.outer(ca, cb)).astype(np.float32).astype(np.float64)[None], cb, ca
 
 
 @pytest.mark.parametrize("refine", (0, 1, 2))
@@ -131,18 +112,7 @@ def test_register(register, dumped, refine):
         before = d20[0] <= float(np.float32(MAXD)) ** 2
     else:
         before = register(refine - 1)[6][i] != 0
-    assert before.sum() >= 3
-    Hm, cb, ca = moments_h32(s[before], t[before])
-    R64, S, d, g = kabsch64(Hm)
-    e, de = orthogonality(Rr[None])
-    assert e[0] <= 32 * EPS and de[0] <= 32 * EPS
-    assert objective_deficit(Rr[None], Hm, S, d)[0] <= 16 * EPS
-    cond, well, _ = posedness(S, g)
-    assert well[0]                                         # hundreds of pairs in a cube: far from any tie
-    dR = np.abs(Rr.astype(np.float64) - R64[0]).max()
-    assert dR <= 32 * (cond[0] + EPS)
-    tol = 3 * np.abs(cb).max() * dR + 8 * EPS * (np.abs(ca).max() + 3 * np.abs(cb).max())
-    assert np.abs(tr.astype(np.float64) - (ca - R64[0] @ cb)).max() <= tol
+    check_refined_pose(Rr, tr, s, t, before)
     # the planted problem's condition: every true pair is an inlier, every point within max_distance of its true image
     moved = src.astype(np.float64) @ Rr.astype(np.float64).T + tr
     assert (mask[true] != 0).all()
