@@ -49,7 +49,7 @@ EXPORTS = [
     "mi_feature_match", "mi_feature_match_times",
     "mi_ransac_params_default", "mi_ransac_register", "mi_ransac_hypotheses", "mi_ransac_register_times",
     "mi_ndt_constants", "mi_ndt_voxels", "mi_ndt_params_default", "mi_ndt_register", "mi_ndt_system", "mi_ndt_times",
-    "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_selftest_icp_schedule", "mi_selftest_cpd_last", "mi_nn_kernel_name",
+    "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_selftest_icp_schedule", "mi_selftest_cpd_last", "mi_selftest_nicp_candidates", "mi_nn_kernel_name",
 ]
 
 
@@ -1321,6 +1321,19 @@ class Context:
                    sigma2_init=np.float32(sc[2].value), constant=np.float32(sc[3].value))
         out.update(zip(("route", "fused", "rows_x", "rows_k", "reduced", "iterations", "stop_reason"), (int(v) for v in info[:7])))
         return out
+
+    def selftest_nicp_candidates(self, before, after, order_heads):
+        """The moments stage and the candidates of nicp_register without its driver (mi_selftest_nicp_candidates): (raw float64[32] -- the sums of the
+        clouds taken about their first points --, R [reps, 3, 3], t [reps, 3], approx [reps]) for order_heads [reps, 3]."""
+        f = lib().mi_selftest_nicp_candidates
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        before, after = _cloud(before), _cloud(after)
+        heads = np.ascontiguousarray(order_heads, np.int32).reshape(-1, 3)
+        raw, out = np.zeros(32, np.float64), np.zeros((len(heads), 13), np.float32)
+        _check(f(self._h, before.ctypes.data, before.shape[0], after.ctypes.data, after.shape[0], heads.ctypes.data, len(heads), raw.ctypes.data,
+                 out.ctypes.data))
+        return raw, out[:, :9].reshape(-1, 3, 3).copy(), out[:, 9:12].copy(), out[:, 12].copy()
 
     def nn_kernel_name(self, n_moving, m_fixed_local, nn_mode=NN_AUTO):
         lib().mi_nn_kernel_name.restype = C.c_char_p

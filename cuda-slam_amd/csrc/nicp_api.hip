@@ -36,22 +36,29 @@ namespace mislam {
 constexpr int NICP_SUMS = 32;
 // 0-2 sum b | 3-8 sum b b^T (xx xy xz yy yz zz) | 9-11 sum a | 12-17 sum a a^T | pairs i < min(m, n): 18-20 sum a_i, 21 sum |a_i|^2,
 // 22-30 sum a_i b_i^T (row-major in a) | 31 spare
+// Every b_i and a_i enters as its difference from the cloud's FIRST point (ob, oa: exact in fp64 for fp32 points a factor 2^29 apart at
+// most), so the centred quantities sums_from_raw forms from the sums cancel at the scale of the cloud's extent, not of its distance from
+// the origin: sum x x^T - n c c^T of raw coordinates loses (distance / extent)^2 of the fp64 precision, which a cloud 100 units out shows
+// in the approximated error of its best candidates.
+struct NicpOrigins {
+    float b[3], a[3];
+};
 
 __global__ __launch_bounds__(256) void nicp_moments_kernel(const float* __restrict__ bx, const float* __restrict__ by, const float* __restrict__ bz,
                                                            int m, const float* __restrict__ ax, const float* __restrict__ ay,
-                                                           const float* __restrict__ az, int n, double* __restrict__ partials)
+                                                           const float* __restrict__ az, int n, NicpOrigins o, double* __restrict__ partials)
 {
     double acc[NICP_SUMS] = {0};
     const int top = max(m, n);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < top; i += gridDim.x * 256) {
         double b[3] = {0, 0, 0}, a[3] = {0, 0, 0};
         if (i < m) {
-            b[0] = bx[i]; b[1] = by[i]; b[2] = bz[i];
+            b[0] = (double)bx[i] - (double)o.b[0]; b[1] = (double)by[i] - (double)o.b[1]; b[2] = (double)bz[i] - (double)o.b[2];
             acc[0] += b[0]; acc[1] += b[1]; acc[2] += b[2];
             acc[3] += b[0] * b[0]; acc[4] += b[0] * b[1]; acc[5] += b[0] * b[2]; acc[6] += b[1] * b[1]; acc[7] += b[1] * b[2]; acc[8] += b[2] * b[2];
         }
         if (i < n) {
-            a[0] = ax[i]; a[1] = ay[i]; a[2] = az[i];
+            a[0] = (double)ax[i] - (double)o.a[0]; a[1] = (double)ay[i] - (double)o.a[1]; a[2] = (double)az[i] - (double)o.a[2];
             acc[9] += a[0]; acc[10] += a[1]; acc[11] += a[2];
             acc[12] += a[0] * a[0]; acc[13] += a[0] * a[1]; acc[14] += a[0] * a[2]; acc[15] += a[1] * a[1]; acc[16] += a[1] * a[2]; acc[17] += a[2] * a[2];
         }
@@ -196,6 +203,8 @@ static void svd_u_from_gram(const double G[3][3], const double rows[3][3], doubl
 }
 
 struct NicpSums {
+    double ob[3], oa[3];          // the first points, which the sums are taken about
+    double sb[3], sa[3];          // centroids about the first points
     double cb[3], ca[3];          // centroids
     double Gb[3][3], Ga[3][3];    // Gram matrices of the centred clouds
     double Saa;                   // sum |a_i - ca|^2 over the pairs i < m
@@ -203,22 +212,28 @@ struct NicpSums {
     int m, n;
 };
 
-static void sums_from_raw(const double* s, int m, int n, NicpSums* o)
+static void sums_from_raw(const double* s, int m, int n, const NicpOrigins& org, NicpSums* o)
 {
     o->m = m; o->n = n;
-    for (int d = 0; d < 3; d++) { o->cb[d] = s[d] / m; o->ca[d] = s[9 + d] / n; }
+    for (int d = 0; d < 3; d++) {
+        o->ob[d] = org.b[d]; o->oa[d] = org.a[d];
+        o->sb[d] = s[d] / m; o->sa[d] = s[9 + d] / n;
+        o->cb[d] = o->ob[d] + o->sb[d]; o->ca[d] = o->oa[d] + o->sa[d];
+    }
+    const double* cb = o->sb;     // the centred quantities do not depend on the origin: formed about the first points
+    const double* ca = o->sa;
     const int sym[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) {
-            o->Gb[i][j] = s[3 + sym[i][j]] - m * o->cb[i] * o->cb[j];
-            o->Ga[i][j] = s[12 + sym[i][j]] - n * o->ca[i] * o->ca[j];
+            o->Gb[i][j] = s[3 + sym[i][j]] - m * cb[i] * cb[j];
+            o->Ga[i][j] = s[12 + sym[i][j]] - n * ca[i] * ca[j];
         }
     const int pairs = std::min(m, n);
-    o->Saa = s[21] - 2.0 * (o->ca[0] * s[18] + o->ca[1] * s[19] + o->ca[2] * s[20])
-           + pairs * (o->ca[0] * o->ca[0] + o->ca[1] * o->ca[1] + o->ca[2] * o->ca[2]);
+    o->Saa = s[21] - 2.0 * (ca[0] * s[18] + ca[1] * s[19] + ca[2] * s[20])
+           + pairs * (ca[0] * ca[0] + ca[1] * ca[1] + ca[2] * ca[2]);
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++)
-            o->Sab[r][c] = s[22 + 3 * r + c] - o->ca[r] * s[c] - s[18 + r] * o->cb[c] + pairs * o->ca[r] * o->cb[c];
+            o->Sab[r][c] = s[22 + 3 * r + c] - ca[r] * s[c] - s[18 + r] * cb[c] + pairs * ca[r] * cb[c];
 }
 
 struct NicpCandidate {
@@ -232,8 +247,8 @@ static NicpCandidate nicp_candidate(const NicpSums& s, const float* before, cons
     double rb[3][3], ra[3][3], Ub[3][3], Ua[3][3], R[3][3];
     for (int i = 0; i < 3; i++)
         for (int d = 0; d < 3; d++) {
-            rb[i][d] = (double)before[3 * (size_t)head[i] + d] - s.cb[d];
-            ra[i][d] = (double)after[3 * (size_t)head[i] + d] - s.ca[d];
+            rb[i][d] = ((double)before[3 * (size_t)head[i] + d] - s.ob[d]) - s.sb[d];
+            ra[i][d] = ((double)after[3 * (size_t)head[i] + d] - s.oa[d]) - s.sa[d];
         }
     svd_u_from_gram(s.Gb, rb, Ub);
     svd_u_from_gram(s.Ga, ra, Ua);
@@ -275,6 +290,42 @@ static void store_if_optimal(std::vector<NicpCandidate>& list, const NicpCandida
     }
 }
 
+// The moments stage of a registration: both clouds go up, one pass sums them about their first points, one launch adds the rows.
+// raw (may be null) receives the 32 sums as they came back.  The caller has checked the sizes and entered the context.
+static int nicp_moments(mi_ctx* c, const float* before_xyz, int m_before, const float* after_xyz, int n_after, double* raw_out, NicpSums* sums)
+{
+    c->prob.icp_loaded = false;
+    const int m_pad = (m_before + NN_SRC_PAD - 1) / NN_SRC_PAD * NN_SRC_PAD;
+    MI_TRY(c->bx.reserve(m_pad)); MI_TRY(c->by.reserve(m_pad)); MI_TRY(c->bz.reserve(m_pad));
+    MI_TRY(upload_soa(c, before_xyz, m_before, m_pad, c->bx.p, c->by.p, c->bz.p, nullptr));
+    MI_TRY(upload_target_shard(c, after_xyz, n_after));
+    const int nb = icp_reduce_blocks(std::max(m_before, n_after));
+    MI_TRY(c->part_mom.reserve((size_t)ICP_MAX_PARTIAL_BLOCKS * NICP_SUMS + NICP_SUMS));
+    double* d_sums = c->part_mom.p + (size_t)ICP_MAX_PARTIAL_BLOCKS * NICP_SUMS;
+    NicpOrigins org;
+    for (int d = 0; d < 3; d++) { org.b[d] = before_xyz[d]; org.a[d] = after_xyz[d]; }
+    {
+        ProfScope ps(c, MI_KERNEL_MOMENTS);
+        hipLaunchKernelGGL(nicp_moments_kernel, dim3(nb), dim3(256), 0, c->stream, c->bx.p, c->by.p, c->bz.p, m_before, c->tx.p, c->ty.p,
+                           c->tz.p, n_after, org, c->part_mom.p);
+        hipLaunchKernelGGL(nicp_reduce_kernel, dim3(1), dim3(256), 0, c->stream, c->part_mom.p, nb, d_sums);
+        MI_HIP(hipGetLastError());
+    }
+    double raw[NICP_SUMS];
+    MI_HIP(hipMemcpyAsync(raw, d_sums, sizeof raw, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    sums_from_raw(raw, m_before, n_after, org, sums);
+    if (raw_out) memcpy(raw_out, raw, sizeof raw);
+    return MI_OK;
+}
+
+static bool nicp_heads_in_range(const char* who, const int* order_heads, int reps, int size)
+{
+    for (int i = 0; i < 3 * reps; i++)
+        if (order_heads[i] < 0 || order_heads[i] >= size) { set_error("%s: order_heads[%d] = %d outside [0, %d)", who, i, order_heads[i], size); return false; }
+    return true;
+}
+
 }  // namespace mislam
 
 extern "C" void mi_nicp_params_default(mi_nicp_params* p)
@@ -304,35 +355,14 @@ extern "C" int mi_nicp_register(mi_ctx* c, const float* before_xyz, int m_before
     if (max_rep == -1) max_rep = 20;                                  // noniterative.cpp:207-208
     if (max_rep < 0) { set_error("mi_nicp_register: max_repetitions %d", max_rep); return MI_ERR_INVALID_ARG; }
     const int size = std::min(m_before, n_after);
-    for (int i = 0; i < 3 * max_rep; i++)
-        if (order_heads[i] < 0 || order_heads[i] >= size) { set_error("mi_nicp_register: order_heads[%d] = %d outside [0, %d)", i, order_heads[i], size); return MI_ERR_INVALID_ARG; }
+    if (!nicp_heads_in_range("mi_nicp_register", order_heads, max_rep, size)) return MI_ERR_INVALID_ARG;
     if (subcloud_n < 1 || subcloud_n > m_before) { set_error("mi_nicp_register: subcloud of %d points", subcloud_n); return MI_ERR_INVALID_ARG; }
     if (subcloud_idx)
         for (int i = 0; i < subcloud_n; i++)
             if (subcloud_idx[i] < 0 || subcloud_idx[i] >= m_before) { set_error("mi_nicp_register: subcloud_idx[%d] out of range", i); return MI_ERR_INVALID_ARG; }
     MI_ENTER(c);
-    c->prob.icp_loaded = false;
-
-    // ---- one pass over both clouds: centroids, Gram matrices, pair sums
-    const int m_pad = (m_before + NN_SRC_PAD - 1) / NN_SRC_PAD * NN_SRC_PAD;
-    MI_TRY(c->bx.reserve(m_pad)); MI_TRY(c->by.reserve(m_pad)); MI_TRY(c->bz.reserve(m_pad));
-    MI_TRY(upload_soa(c, before_xyz, m_before, m_pad, c->bx.p, c->by.p, c->bz.p, nullptr));
-    MI_TRY(upload_target_shard(c, after_xyz, n_after));
-    const int nb = icp_reduce_blocks(std::max(m_before, n_after));
-    MI_TRY(c->part_mom.reserve((size_t)ICP_MAX_PARTIAL_BLOCKS * NICP_SUMS + NICP_SUMS));
-    double* d_sums = c->part_mom.p + (size_t)ICP_MAX_PARTIAL_BLOCKS * NICP_SUMS;
-    {
-        ProfScope ps(c, MI_KERNEL_MOMENTS);
-        hipLaunchKernelGGL(nicp_moments_kernel, dim3(nb), dim3(256), 0, c->stream, c->bx.p, c->by.p, c->bz.p, m_before, c->tx.p, c->ty.p,
-                           c->tz.p, n_after, c->part_mom.p);
-        hipLaunchKernelGGL(nicp_reduce_kernel, dim3(1), dim3(256), 0, c->stream, c->part_mom.p, nb, d_sums);
-        MI_HIP(hipGetLastError());
-    }
-    double raw[NICP_SUMS];
-    MI_HIP(hipMemcpyAsync(raw, d_sums, sizeof raw, hipMemcpyDeviceToHost, c->stream));
-    MI_HIP(hipStreamSynchronize(c->stream));
     NicpSums sums;
-    sums_from_raw(raw, m_before, n_after, &sums);
+    MI_TRY(nicp_moments(c, before_xyz, m_before, after_xyz, n_after, nullptr, &sums));
 
     // ---- the comparison subcloud becomes the moving cloud of the error evaluations
     const int sn = subcloud_n, sn_pad = (sn + NN_SRC_PAD - 1) / NN_SRC_PAD * NN_SRC_PAD;
@@ -377,6 +407,7 @@ extern "C" int mi_nicp_register(mi_ctx* c, const float* before_xyz, int m_before
         if (params->approximation == MI_CPD_APPROX_NONE) {
             MI_TRY(exact_error(cand.rt, error));
             if (params->verbose) printf("repetition %d, error: %f\n", rep + 1, *error);
+            if (rep == 0) best = cand;      // no point of the subcloud within the limit: 0 / 0 compares false below, the first candidate stands
             if (*error < min_error) {
                 min_error = *error;
                 best = cand;
@@ -390,6 +421,7 @@ extern "C" int mi_nicp_register(mi_ctx* c, const float* before_xyz, int m_before
         min_error = FLT_MAX;
         for (size_t i = 0; i < best_list.size() && !early; i++) {
             MI_TRY(exact_error(best_list[i].rt, error));
+            if (i == 0) best = best_list[0];
             if (*error < min_error) {
                 min_error = *error;
                 best = best_list[i];
@@ -403,6 +435,32 @@ extern "C" int mi_nicp_register(mi_ctx* c, const float* before_xyz, int m_before
         out_T[4 * col + 3] = 0.f;
     }
     out_T[12] = best.rt.t[0]; out_T[13] = best.rt.t[1]; out_T[14] = best.rt.t[2]; out_T[15] = 1.f;
+    return MI_OK;
+}
+
+// The moments stage and the candidates of a registration without its driver: the same uploads, launches and host solve, no search.
+extern "C" int mi_selftest_nicp_candidates(mi_ctx* c, const float* before_xyz, int m_before, const float* after_xyz, int n_after,
+                                           const int* order_heads, int reps, double raw_sums[32], float* R9_t3_approx)
+{
+    static_assert(NICP_SUMS == 32, "the size mi_slam.h states");
+    if (!c) { set_error("mi_selftest_nicp_candidates: null context"); return MI_ERR_INVALID_ARG; }
+    if (!before_xyz || !after_xyz || !order_heads || !raw_sums || !R9_t3_approx) { set_error("mi_selftest_nicp_candidates: null argument"); return MI_ERR_INVALID_ARG; }
+    if (m_before < 3 || n_after < 3) { set_error("mi_selftest_nicp_candidates: clouds need at least 3 points (m=%d, n=%d)", m_before, n_after); return MI_ERR_INVALID_ARG; }
+    if (c->world != 1) { set_error("mi_selftest_nicp_candidates: single-GPU contexts only"); return MI_ERR_STATE; }
+    if (reps < 0) { set_error("mi_selftest_nicp_candidates: %d repetitions", reps); return MI_ERR_INVALID_ARG; }
+    if (!nicp_heads_in_range("mi_selftest_nicp_candidates", order_heads, reps, std::min(m_before, n_after))) return MI_ERR_INVALID_ARG;
+    MI_ENTER(c);
+    NicpSums sums;
+    double raw[NICP_SUMS];
+    MI_TRY(nicp_moments(c, before_xyz, m_before, after_xyz, n_after, raw, &sums));
+    memcpy(raw_sums, raw, sizeof raw);
+    for (int rep = 0; rep < reps; rep++) {
+        const NicpCandidate cand = nicp_candidate(sums, before_xyz, after_xyz, order_heads + 3 * (size_t)rep);
+        float* o = R9_t3_approx + 13 * (size_t)rep;
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) o[3 * i + j] = cand.rt.R[3 * j + i];   // row-major out of the column-major candidate
+        o[9] = cand.rt.t[0]; o[10] = cand.rt.t[1]; o[11] = cand.rt.t[2];
+        o[12] = cand.approx;
+    }
     return MI_OK;
 }
 

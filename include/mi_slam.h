@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MI_SLAM_ABI_VERSION 4   /* 4: mi_profile_search_phases, mi_selftest_fail_loads, mi_runtime_info (additive: no signature of version 3 changed), later and additive again: mi_icp_register_batch, mi_cpd_register_batch, mi_voxel_index, mi_voxel_downsample, mi_voxel_downsample_times, mi_knn_search, mi_knn_search_times, mi_estimate_normals, mi_estimate_normals_times, mi_selftest_cpd_last; 3: mi_icp_load_times, mi_cross_moments, mi_icp_auto_batch; 2: mi_cpd_params gained sigma2_mode; mi_dist_info, mi_source_share, mi_cpd_sigma_squared_mode, mi_profile_search_stats, mi_selftest_sort_pairs */
+#define MI_SLAM_ABI_VERSION 4   /* 4: mi_profile_search_phases, mi_selftest_fail_loads, mi_runtime_info (additive: no signature of version 3 changed), later and additive again: mi_icp_register_batch, mi_cpd_register_batch, mi_voxel_index, mi_voxel_downsample, mi_voxel_downsample_times, mi_knn_search, mi_knn_search_times, mi_estimate_normals, mi_estimate_normals_times, mi_selftest_cpd_last, mi_selftest_nicp_candidates; 3: mi_icp_load_times, mi_cross_moments, mi_icp_auto_batch; 2: mi_cpd_params gained sigma2_mode; mi_dist_info, mi_source_share, mi_cpd_sigma_squared_mode, mi_profile_search_stats, mi_selftest_sort_pairs */
 
 enum {
     MI_OK = 0,
@@ -476,7 +476,11 @@ typedef struct {
 
 void mi_nicp_params_default(mi_nicp_params* p);
 
-/* out_T: column-major 4x4 (R | t).  *repetitions and *error as the reference leaves them. */
+/* out_T: column-major 4x4 (R | t).  *repetitions and *error as the reference leaves them.
+ * A candidate's error is the mean over the subcloud points whose nearest squared distance is below 1e6 (maxDistanceForComparison).  When NO point
+ * of any scored candidate is that close, every error is 0 / 0 and compares false, and the reference returns an uninitialised pair; here the call
+ * returns MI_OK with out_T = the first candidate that was scored (repetition 0 in MI_CPD_APPROX_NONE, the head of the ranked list otherwise: a rigid
+ * transform like every candidate), *error = FLT_MAX and *repetitions = max_repetitions. */
 int mi_nicp_register(mi_ctx* ctx, const float* before_xyz, int m_before, const float* after_xyz, int n_after,
                      const mi_nicp_params* params, const int* order_heads, const int* subcloud_idx, int subcloud_n,
                      float out_T[16], int* repetitions, float* error);
@@ -1328,6 +1332,16 @@ enum {
 };
 int mi_selftest_cpd_last(mi_ctx* ctx, int m, int n, float* p1, float* pt1, float* px, float* y_xyz, double xs[5], double ks[14], float R9[9],
                          float t3[3], float* scale, float* sigma2, float* sigma2_init, float* constant, int info[8]);
+/* The moments stage and the candidates of mi_nicp_register without its driver loop: the same uploads, the same moments and reduce launches and the
+ * same host solve per repetition, no search and no pick.  raw_sums receives the 32 fp64 sums as the device left them, every point taken about the
+ * FIRST point of its cloud (b_i - b_0, a_i - a_0, exact in fp64): 0-2 sum b, 3-8 sum b b^T (xx xy xz yy yz zz), 9-11 sum a, 12-17 sum a a^T, and over
+ * the pairs i < min(m, n) 18-20 sum a_i, 21 sum |a_i|^2, 22-30 sum a_i b_i^T (row-major in a); 31 is spare and 0.  R9_t3_approx receives 13 floats
+ * per repetition: the candidate's R (ROW-major), t and approximated error, for order_heads[3 r .. 3 r + 2] as in mi_nicp_register.  Sizes and heads
+ * are checked as there (m > n is allowed, as in MI_CPD_APPROX_NONE, the one mode that reads no approximated error: for m > n that output is
+ * not defined); a refused call leaves its outputs untouched.  Like the registration it reuses
+ * the context's cloud buffers, so no ICP problem stays loaded behind it; it keeps no state of its own.  Test use only. */
+int mi_selftest_nicp_candidates(mi_ctx* ctx, const float* before_xyz, int m_before, const float* after_xyz, int n_after, const int* order_heads,
+                                int reps, double raw_sums[32], float* R9_t3_approx);
 /* Name of the correspondence-search kernel (MI_KERNEL_NN) a search of n_moving points against m_fixed_local fixed points runs
  * with this nn_mode and the current settings -- the name a rocprofv3 kernel trace shows (static string). */
 const char* mi_nn_kernel_name(const mi_ctx* ctx, int n_moving, int m_fixed_local, int nn_mode);
