@@ -74,6 +74,14 @@ struct SearchFrontBuffers {
     hipEvent_t ev[2] = {nullptr, nullptr};           // around the call's search launch while profiling; destroyed by mi_ctx_destroy (search_front_destroy_events)
 };
 
+// What the pose loop of plane ICP, generalized ICP and NDT iterates on (pose_loop.hip).  One instance per registration (mi_ctx::plane, gicp, ndt):
+// nothing is shared between calls.
+struct PoseLoopBuffers {
+    DevBuf<double> rows, parts;                      // one row of PLANE_ROW sums per 64 moving points; the slabs' sums
+    DevBuf<PlaneState> state;
+    DevBuf<int> out_idx;                             // the *_system call's out_idx
+};
+
 struct ProfileSpan {
     int kernel;
     hipEvent_t e0, e1;
@@ -242,9 +250,7 @@ struct mi_ctx {
         mislam::DevBuf<float> nx, ny, nz;                // the normals, SoA, the caller's order (what their input check reads)
         mislam::DevBuf<float4> normals;                  // the same, packed (what the step kernel gathers)
         mislam::DevBuf<mislam::KnnState> nstate;         // the normals' input check
-        mislam::DevBuf<double> rows, parts;              // one row of PLANE_ROW sums per 64 moving points; the slabs' sums
-        mislam::DevBuf<mislam::PlaneState> state;
-        mislam::DevBuf<int> out_idx;                     // mi_plane_system's out_idx
+        mislam::PoseLoopBuffers loop;
         double ms[MI_PLANE_STAGES] = {0};                // mi_icp_plane_times
     } plane;
 
@@ -264,9 +270,7 @@ struct mi_ctx {
         mislam::DevBuf<float4> cov_a;                    // the fixed cloud's, two float4 each, the caller's order (what the step kernel gathers)
         mislam::DevBuf<float4> cov_b_in, cov_b;          // the moving cloud's: the caller's order, and along the curve (what the step kernel streams)
         mislam::DevBuf<int> cov_bad;                     // [0] the moving, [1] the fixed cloud's lowest refused covariance, or KNN_NO_POINT
-        mislam::DevBuf<double> rows, parts;
-        mislam::DevBuf<mislam::PlaneState> state;
-        mislam::DevBuf<int> out_idx;                     // mi_gicp_system's out_idx
+        mislam::PoseLoopBuffers loop;
         double ms[MI_GICP_STAGES] = {0};                 // mi_icp_gicp_times
     } gicp;
 
@@ -320,10 +324,8 @@ struct mi_ctx {
         mislam::DevBuf<float4> mean4, icov4;             // ... and packed (what the step kernel gathers)
         mislam::DevBuf<mislam::NdtMapState> mstate;
         mislam::DevBuf<unsigned long long> hkeys;
-        mislam::DevBuf<double> rows, parts;
-        mislam::DevBuf<mislam::PlaneState> state;
-        mislam::DevBuf<int> out_idx;
-        mislam::DevBuf<unsigned char> out_terms;
+        mislam::PoseLoopBuffers loop;
+        mislam::DevBuf<unsigned char> out_terms;         // mi_ndt_system's out_terms
         double ms[MI_NDT_STAGES] = {0};                  // mi_ndt_times
     } ndt;
 
@@ -442,9 +444,10 @@ struct SearchFront {
     size_t n_cells = 0;
 };
 int search_front_reserve(SearchFrontBuffers& b, size_t n, size_t m, bool self);
-// query_xyz null: self mode, the cloud is its own query set (n == m)
+// query_xyz null: self mode, the cloud is its own query set (n == m); cloud_name, query_name: what a refusal calls the two arrays
 int search_front_upload_and_check(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, const char* who, const float* cloud_xyz, int m,
-                                  const float* query_xyz, int n, SearchFront* f);
+                                  const float* query_xyz, int n, SearchFront* f, const char* cloud_name = "cloud_xyz",
+                                  const char* query_name = "query_xyz");
 int search_front_index_and_order(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, const char* who, float points_per_cell, SearchFront* f);
 // the host-side shape check of what every search kernel indexes: q*, order, c*, the grid's offsets and points
 bool search_front_fits(const SearchFrontBuffers& b, const SearchFront& f);
@@ -467,6 +470,78 @@ static inline int search_front_timed_launch(mi_ctx* c, SearchFrontBuffers& b, St
         MI_HIP(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
         clock.ms[5] = (double)ms;
     }
+    return MI_OK;
+}
+
+// ---- the pose loop of mi_icp_plane_register, mi_icp_gicp_register, mi_ndt_register and their *_system probes (pose_loop.hip; the host arithmetic:
+// pose_block.hpp): everything behind "the step kernel's arguments are complete".  A driver calls pose_check_transform among its argument checks
+// (and pose_check_fields behind them), pose_loop_reserve among its reserves (every reserve comes before the first upload), pose_loop_upload_state
+// behind its last stage (it books stage 1), pose_loop_fits beside the check of its own buffers, and then either pose_loop_run and
+// pose_loop_results, or pose_loop_system_run and pose_loop_system_finish.  `step` enqueues the driver's step kernel.
+struct PoseLoopFields {
+    float eps_rotation, eps_translation;
+    int max_iterations, sync_every, verbose;
+    const char* noun;                                // what the verbose line counts: "pairs" or "terms"
+};
+int pose_check_transform(const char* who, const float* T);                     // T null: nothing to refuse
+int pose_check_fields(const char* who, const PoseLoopFields& p);
+int pose_loop_reserve(PoseLoopBuffers& b, int n, bool want_idx);
+bool pose_loop_fits(const PoseLoopBuffers& b, int n, bool want_idx);           // the host-side shape check of what the step and the reduce index
+// *h = the block at pose T (null: the identity) about the fp32 centre, and its upload
+int pose_loop_upload_state(mi_ctx* c, PoseLoopBuffers& b, StageClock& clock, const float* T, const float centre[3], PlaneState* h);
+int pose_loop_read_state(mi_ctx* c, PoseLoopBuffers& b, PlaneState* h);        // the copy back and the wait for it
+// stage 6 of a registration: out_T, iterations, error and stop_reason from the state
+int pose_loop_results(StageClock& clock, const PlaneState& h, float out_T[16], int* iterations, float* error, int* stop_reason);
+// stage 6 of a *_system call: the wait for the copies in flight, then out_sums and out_centre from the state
+int pose_loop_system_finish(mi_ctx* c, StageClock& clock, const PlaneState& h, double out_sums[PLANE_ROW], float out_centre[3]);
+
+// one iteration's launches: the step, then rows -> sums -> (rules.solve) solve, update, stop rule.  With profiling on, the step's time
+// is booked to MI_KERNEL_NN and the other launches' to MI_KERNEL_SOLVE (mi_profile_get).
+template <class Step>
+static inline int pose_loop_iteration(mi_ctx* c, PoseLoopBuffers& b, int n, const PlaneRules& rules, Step&& step)
+{
+    const int nrows = plane_row_count(n);
+    {
+        ProfScope p(c, MI_KERNEL_NN);
+        MI_HIP(step());
+    }
+    {
+        ProfScope p(c, MI_KERNEL_SOLVE);
+        MI_HIP(plane_reduce_solve(b.state.p, b.rows.p, nrows, plane_part_count(nrows) > 0 ? b.parts.p : nullptr, rules, c->stream));
+    }
+    return MI_OK;
+}
+// Stage 5 of a registration: batches of sync_every (0: 4) iterations between host reads of the state, until it says done.  The device enforces
+// the iteration cap; the host never enqueues beyond it.
+template <class Step>
+static inline int pose_loop_run(mi_ctx* c, PoseLoopBuffers& b, StageClock& clock, const char* who, int n, const PoseLoopFields& p, PlaneState* h, Step&& step)
+{
+    PlaneRules rules{};
+    rules.eps_rotation = (double)p.eps_rotation; rules.eps_translation = (double)p.eps_translation;
+    rules.max_iterations = p.max_iterations; rules.solve = 1;
+    const int batch = pose_batch(p.sync_every);
+    int enqueued = 0;
+    if (p.max_iterations == 0) { h->done = 1; h->stop_reason = MI_STOP_MAX_ITERATIONS; }
+    while (!h->done) {
+        if (enqueued >= p.max_iterations) { set_error("internal: %s ran %d iterations without a stop", who, enqueued); return MI_ERR_STATE; }
+        const int todo = pose_batch_todo(batch, p.max_iterations, enqueued);
+        for (int i = 0; i < todo; i++) MI_TRY(pose_loop_iteration(c, b, n, rules, step));
+        enqueued += todo;
+        MI_TRY(pose_loop_read_state(c, b, h));
+        if (p.verbose)
+            fprintf(stderr, "%s: %d enqueued, %d applied, |omega| %.3e |v| %.3e, %s %.0f, stop %d\n", who, enqueued, h->iterations, h->omega, h->v, p.noun,
+                    h->sums[29], h->stop_reason);
+    }
+    return clock.mark(5);
+}
+// Stage 5 of a *_system call: one iteration with solve = 0 (the sums and nothing else), the state's read-back, and out_idx on its way
+template <class Step>
+static inline int pose_loop_system_run(mi_ctx* c, PoseLoopBuffers& b, StageClock& clock, int n, PlaneState* h, int* out_idx, Step&& step)
+{
+    MI_TRY(pose_loop_iteration(c, b, n, PlaneRules{}, step));
+    MI_TRY(pose_loop_read_state(c, b, h));
+    MI_TRY(clock.mark(5));
+    if (out_idx) MI_HIP(hipMemcpyAsync(out_idx, b.out_idx.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     return MI_OK;
 }
 

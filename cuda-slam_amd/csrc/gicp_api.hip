@@ -1,15 +1,12 @@
 // mi_estimate_covariances, mi_icp_gicp_register and mi_gicp_system behind the C ABI.  The covariance call is mi_estimate_normals' driver with
-// another kernel and result (normals_kernels.hip: the same search and moments).  The registration is mi_icp_plane_register's driver with the
-// covariances of both clouds in the place of the normals: argument checks, the reserves of the call's own buffers in the context, the
-// covariances' upload, repack and input check (gicp_kernels.hip), the search front end with the fixed cloud as the cloud and the moving cloud
-// as the queries (search_front.hip), the moving cloud's covariances along its curve order, the state block, the iterations -- the step of
-// gicp_kernels.hip, then plane_kernels.hip's own reduce and solve -- in batches of sync_every between host reads of the state, and the results.
+// another kernel and result (normals_kernels.hip: the same search and moments).  The registration, up to the step kernel's arguments: argument
+// checks, the reserves of the call's own buffers in the context, the covariances' upload, repack and input check (gicp_kernels.hip), the search
+// front end with the fixed cloud as the cloud and the moving cloud as the queries (search_front.hip), the moving cloud's covariances along its
+// curve order.  The state block, the iterations -- the step of gicp_kernels.hip, then plane_kernels.hip's own reduce and solve -- in batches of
+// sync_every between host reads of the state, and the results are the pose loop's (pose_loop.hip), which gets the step's launch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <string>
 
 #include "context.h"
 
@@ -68,16 +65,6 @@ extern "C" int mi_estimate_covariances(mi_ctx* c, const float* cloud_xyz, int n,
 
 namespace {
 
-// the front end names its arrays as mi_knn_search does; here they are the fixed and the moving cloud
-void rename_in_error(const char* from, const char* to)
-{
-    std::string msg = mi_last_error();
-    const size_t at = msg.find(from);
-    if (at == std::string::npos) return;
-    msg.replace(at, std::strlen(from), to);
-    set_error("%s", msg.c_str());
-}
-
 // what both entry points refuse alike, before the context is touched
 int check_arguments(const char* who, mi_ctx* c, const float* before_xyz, const float* before_cov6, int n, const float* after_xyz, const float* after_cov6, int m,
                     int dist_mode, float max_d2, const float* T)
@@ -87,10 +74,7 @@ int check_arguments(const char* who, mi_ctx* c, const float* before_xyz, const f
     if (n < 1 || m < 1) { set_error("%s: empty moving or fixed cloud (n = %d, m = %d)", who, n, m); return MI_ERR_INVALID_ARG; }
     if (dist_mode != MI_DIST_CPU_ROUNDING && dist_mode != MI_DIST_FMA) { set_error("%s: bad dist_mode %d", who, dist_mode); return MI_ERR_INVALID_ARG; }
     if (!(max_d2 >= 0.f)) { set_error("%s: max_distance_squared %g is NaN or negative", who, (double)max_d2); return MI_ERR_INVALID_ARG; }
-    if (T)
-        for (int i = 0; i < 16; i++)       // the rotation block and the translation column: the bottom row is never read
-            if (i % 4 != 3 && !std::isfinite(T[i])) { set_error("%s: transform entry %d is not finite (%g)", who, i, (double)T[i]); return MI_ERR_INVALID_ARG; }
-    return MI_OK;
+    return pose_check_transform(who, T);
 }
 
 // Stages 0 - 4 of either call and the state block at pose T: after it the step kernel's arguments are complete and checked against the buffers.
@@ -99,14 +83,10 @@ int gicp_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* bef
 {
     mi_ctx::GicpBuffers& b = c->gicp;
     const size_t np = (size_t)n, mp = (size_t)m;
-    const int nrows = plane_row_count(n), nparts = plane_part_count(nrows);
     MI_TRY(search_front_reserve(b.front, np, mp, false));
     MI_TRY(b.cov_staging.reserve(6 * std::max(np, mp)));
     MI_TRY(b.cov_a.reserve(2 * mp)); MI_TRY(b.cov_b_in.reserve(2 * np)); MI_TRY(b.cov_b.reserve(2 * np)); MI_TRY(b.cov_bad.reserve(2));
-    MI_TRY(b.rows.reserve((size_t)nrows * PLANE_ROW));
-    if (nparts > 0) MI_TRY(b.parts.reserve((size_t)nparts * PLANE_ROW));
-    MI_TRY(b.state.reserve(1));
-    if (want_idx) MI_TRY(b.out_idx.reserve(np));
+    MI_TRY(pose_loop_reserve(b.loop, n, want_idx));
     MI_TRY(clock.mark(0));
 
     // the covariances go first, each cloud's through the staging buffer (one stream: in order), repacked and checked in one pass
@@ -116,11 +96,7 @@ int gicp_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* bef
     MI_HIP(gicp_pack_covariances(b.cov_staging.p, n, b.cov_b_in.p, b.cov_bad.p, c->stream));
     MI_TRY(host_to_device(c, b.cov_staging.p, after_cov6, sizeof(float) * 6 * mp));
     MI_HIP(gicp_pack_covariances(b.cov_staging.p, m, b.cov_a.p, b.cov_bad.p + 1, c->stream));
-    const int rc = search_front_upload_and_check(c, b.front, clock, who, after_xyz, m, before_xyz, n, f);
-    if (rc != MI_OK) {
-        if (rc == MI_ERR_INVALID_ARG) { rename_in_error("cloud_xyz", "after_xyz"); rename_in_error("query_xyz", "before_xyz"); }
-        return rc;
-    }
+    MI_TRY(search_front_upload_and_check(c, b.front, clock, who, after_xyz, m, before_xyz, n, f, "after_xyz", "before_xyz"));
     MI_HIP(hipMemcpyAsync(bad, b.cov_bad.p, sizeof bad, hipMemcpyDeviceToHost, c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
     MI_TRY(clock.mark(2));
@@ -137,47 +113,23 @@ int gicp_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* bef
     MI_HIP(gicp_permute_covariances(b.cov_b_in.p, b.front.order.p, n, b.cov_b.p, c->stream));
     MI_TRY(clock.mark(4));
 
-    std::memset(h, 0, sizeof *h);
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) h->R[3 * i + j] = T ? (double)T[4 * j + i] : (i == j ? 1.0 : 0.0);      // column-major in, row-major kept
-        h->t[i] = T ? (double)T[12 + i] : 0.0;
-        const float centre = 0.5f * (f->bbox[i] + f->bbox[3 + i]);
-        h->c0[i] = (double)centre;
-    }
-    MI_TRY(host_to_device(c, b.state.p, h, sizeof *h));
-    MI_TRY(clock.mark(1));
+    float centre[3];
+    for (int i = 0; i < 3; i++) centre[i] = 0.5f * (f->bbox[i] + f->bbox[3 + i]);
+    MI_TRY(pose_loop_upload_state(c, b.loop, clock, T, centre, h));
 
     *a = GicpStepArgs{};
-    a->state = b.state.p;
+    a->state = b.loop.state.p;
     a->bx = b.front.qx.p; a->by = b.front.qy.p; a->bz = b.front.qz.p; a->order = b.front.order.p;
     a->ax = b.front.cx.p; a->ay = b.front.cy.p; a->az = b.front.cz.p;
     a->cov_a = b.cov_a.p; a->cov_b = b.cov_b.p;
     a->n = n; a->max_d2 = max_d2;
     for (int i = 0; i < 3; i++) a->hi[i] = f->bbox[3 + i];
-    a->rows = b.rows.p;
-    a->idx = want_idx ? b.out_idx.p : nullptr;
+    a->rows = b.loop.rows.p;
+    a->idx = want_idx ? b.loop.out_idx.p : nullptr;
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (!search_front_fits(b.front, *f) || b.cov_a.cap < 2 * mp || b.cov_b.cap < 2 * np || b.rows.cap < (size_t)nrows * PLANE_ROW || b.state.cap < 1 ||
-        (nparts > 0 && b.parts.cap < (size_t)nparts * PLANE_ROW) || (want_idx && b.out_idx.cap < np)) {
+    if (!search_front_fits(b.front, *f) || b.cov_a.cap < 2 * mp || b.cov_b.cap < 2 * np || !pose_loop_fits(b.loop, n, want_idx)) {
         set_error("internal: %s buffers shorter than the launch", who);
         return MI_ERR_STATE;
-    }
-    return MI_OK;
-}
-
-// one iteration's launches: the step, then K16's rows -> sums -> (rules.solve) solve, update, stop rule.  With profiling on, the step's time
-// is booked to MI_KERNEL_NN and the other launches' to MI_KERNEL_SOLVE (mi_profile_get).
-int gicp_enqueue_iteration(mi_ctx* c, const SearchFront& f, const GicpStepArgs& a, int fma, const PlaneRules& rules)
-{
-    mi_ctx::GicpBuffers& b = c->gicp;
-    const int nrows = plane_row_count(a.n);
-    {
-        ProfScope p(c, MI_KERNEL_NN);
-        MI_HIP(gicp_step(f.g, a, fma, c->stream));
-    }
-    {
-        ProfScope p(c, MI_KERNEL_SOLVE);
-        MI_HIP(plane_reduce_solve(b.state.p, b.rows.p, nrows, plane_part_count(nrows) > 0 ? b.parts.p : nullptr, rules, c->stream));
     }
     return MI_OK;
 }
@@ -190,12 +142,8 @@ extern "C" int mi_icp_gicp_register(mi_ctx* c, const float* before_xyz, const fl
     const char* who = "mi_icp_gicp_register";
     if (c && (!p || !out_T)) { set_error("%s: null params or out_T", who); return MI_ERR_INVALID_ARG; }
     MI_TRY(check_arguments(who, c, before_xyz, before_cov6, n, after_xyz, after_cov6, m, p ? p->dist_mode : 0, p ? p->max_distance_squared : 0.f, init_T));
-    if (!(p->eps_rotation >= 0.f) || !(p->eps_translation >= 0.f)) {
-        set_error("%s: eps_rotation %g or eps_translation %g is NaN or negative", who, (double)p->eps_rotation, (double)p->eps_translation);
-        return MI_ERR_INVALID_ARG;
-    }
-    if (p->max_iterations < 0) { set_error("%s: max_iterations %d is negative (there is no unbounded mode)", who, p->max_iterations); return MI_ERR_INVALID_ARG; }
-    if (p->sync_every < 0) { set_error("%s: sync_every %d is negative", who, p->sync_every); return MI_ERR_INVALID_ARG; }
+    const PoseLoopFields loop{p->eps_rotation, p->eps_translation, p->max_iterations, p->sync_every, p->verbose, "pairs"};
+    MI_TRY(pose_check_fields(who, loop));
     if (c->distributed()) { set_error("%s: single-GPU contexts only", who); return MI_ERR_STATE; }
     MI_ENTER(c);
     mi_ctx::GicpBuffers& b = c->gicp;
@@ -206,38 +154,9 @@ extern "C" int mi_icp_gicp_register(mi_ctx* c, const float* before_xyz, const fl
     PlaneState h;
     MI_TRY(gicp_prepare(c, who, clock, before_xyz, before_cov6, n, after_xyz, after_cov6, m, p->max_distance_squared, init_T, false, &f, &a, &h));
 
-    PlaneRules rules{};
-    rules.eps_rotation = (double)p->eps_rotation; rules.eps_translation = (double)p->eps_translation;
-    rules.max_iterations = p->max_iterations; rules.solve = 1;
-    const int batch = p->sync_every > 0 ? p->sync_every : 4;
     const int fma = p->dist_mode == MI_DIST_FMA;
-    int enqueued = 0;
-    if (p->max_iterations == 0) { h.done = 1; h.stop_reason = MI_STOP_MAX_ITERATIONS; }
-    while (!h.done) {
-        if (enqueued >= p->max_iterations) { set_error("internal: %s ran %d iterations without a stop", who, enqueued); return MI_ERR_STATE; }
-        const int todo = std::min(batch, p->max_iterations - enqueued);
-        for (int i = 0; i < todo; i++) MI_TRY(gicp_enqueue_iteration(c, f, a, fma, rules));
-        enqueued += todo;
-        MI_HIP(hipMemcpyAsync(&h, b.state.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-        MI_HIP(hipStreamSynchronize(c->stream));
-        if (p->verbose)
-            fprintf(stderr, "%s: %d enqueued, %d applied, |omega| %.3e |v| %.3e, pairs %.0f, stop %d\n", who, enqueued, h.iterations, h.omega, h.v, h.sums[29],
-                    h.stop_reason);
-    }
-    MI_TRY(clock.mark(5));
-
-    for (int i = 0; i < 16; i++) out_T[i] = 0.f;
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) out_T[4 * j + i] = (float)h.R[3 * i + j];
-        out_T[12 + i] = (float)h.t[i];
-    }
-    out_T[15] = 1.f;
-    if (iterations) *iterations = h.iterations;
-    if (error) *error = h.sums[29] > 0.0 ? (float)(h.sums[27] / h.sums[29]) : 0.f;
-    if (stop_reason) *stop_reason = h.stop_reason;
-    MI_TRY(clock.mark(6));
-    clock.finish();
-    return MI_OK;
+    MI_TRY(pose_loop_run(c, b.loop, clock, who, n, loop, &h, [&] { return gicp_step(f.g, a, fma, c->stream); }));
+    return pose_loop_results(clock, h, out_T, iterations, error, stop_reason);
 }
 
 extern "C" int mi_gicp_system(mi_ctx* c, const float* before_xyz, const float* before_cov6, int n, const float* after_xyz, const float* after_cov6, int m,
@@ -256,20 +175,9 @@ extern "C" int mi_gicp_system(mi_ctx* c, const float* before_xyz, const float* b
     PlaneState h;
     MI_TRY(gicp_prepare(c, who, clock, before_xyz, before_cov6, n, after_xyz, after_cov6, m, max_distance_squared, T, out_idx != nullptr, &f, &a, &h));
 
-    PlaneRules rules{};                // solve = 0: the sums and nothing else
-    MI_TRY(gicp_enqueue_iteration(c, f, a, dist_mode == MI_DIST_FMA, rules));
-    MI_HIP(hipMemcpyAsync(&h, b.state.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    MI_HIP(hipStreamSynchronize(c->stream));
-    MI_TRY(clock.mark(5));
-
-    if (out_idx) MI_HIP(hipMemcpyAsync(out_idx, b.out_idx.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    MI_HIP(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < PLANE_ROW; i++) out_sums[i] = h.sums[i];
-    if (out_centre)
-        for (int i = 0; i < 3; i++) out_centre[i] = (float)h.c0[i];
-    MI_TRY(clock.mark(6));
-    clock.finish();
-    return MI_OK;
+    const int fma = dist_mode == MI_DIST_FMA;
+    MI_TRY(pose_loop_system_run(c, b.loop, clock, n, &h, out_idx, [&] { return gicp_step(f.g, a, fma, c->stream); }));
+    return pose_loop_system_finish(c, clock, h, out_sums, out_centre);
 }
 
 extern "C" int mi_icp_gicp_times(mi_ctx* c, double out_ms[MI_GICP_STAGES])

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pose_block.hpp"
+
 namespace mislam {
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -354,28 +356,15 @@ struct OutlierCompactArgs {
 hipError_t outlier_compact(const OutlierCompactArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------------
-// K16 point-to-plane ICP (plane_kernels.hip; driver: plane_api.hip; the solve: plane_solve.hpp): K13's search with one key per lane
+// K16 point-to-plane ICP (plane_kernels.hip; driver: plane_api.hip up to the step's arguments, then pose_loop.hip, the one loop of K16, K17
+// and K31; the solve: plane_solve.hpp): K13's search with one key per lane
 // (NearestSink, knn_scan.hpp), the pair's 29 fp64 terms summed over the wave into one row per 64 moving points, the rows summed in a
 // fixed order, and one lane's 6 x 6 solve, pose update and stop rule in the device state block
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int PLANE_ROW = 32;                // doubles per row and per system: mi_plane_system's out_sums
+// PLANE_ROW (32 doubles per row and per system) and PlaneState, the device-resident loop state: pose_block.hpp, which needs no HIP
 constexpr int PLANE_ONE_STAGE_ROWS = 1024;   // up to this many rows (65 536 moving points) one workgroup sums the rows and solves in one launch
 constexpr int PLANE_PARTS = 64;              // beyond: this many workgroups sum a slab of rows each first (a function of the row count alone)
-constexpr int MI_STOP_DEGENERATE_ = 7;       // mirror of MI_STOP_DEGENERATE (mi_slam.h; plane_api.hip asserts it)
-
-// Device-resident loop state of one plane registration.  The host only ever copies it back; every decision is taken on the device.
-struct PlaneState {
-    double R[9];             // running rotation, ROW-major
-    double t[3];             // running translation
-    double c0[3];            // the centre the moments are taken about, promoted from its fp32 value
-    double sums[PLANE_ROW];  // the last linearisation's system
-    double omega, v;         // lengths of the last update's two halves
-    double min_pivot;        // smallest pivot of the last solve (0: a bad diagonal)
-    int iterations;          // updates applied
-    int done;
-    int stop_reason;
-    int pad;
-};
+constexpr int MI_STOP_DEGENERATE_ = 7;       // mirror of MI_STOP_DEGENERATE (mi_slam.h; pose_loop.hip asserts it)
 
 struct PlaneStepArgs {
     const PlaneState* state;         // the pose to linearise at (rounded to fp32 by every lane), the centre, done
@@ -401,7 +390,7 @@ hipError_t plane_step(const NnGridView& g, const PlaneStepArgs& a, int fma, hipS
 hipError_t plane_reduce_solve(PlaneState* state, const double* rows, int nrows, double* parts, const PlaneRules& rules, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------------
-// K17 generalized ICP (gicp_kernels.hip; driver: gicp_api.hip): K16's iteration with a 3 x 3 information matrix per pair where K16 has a
+// K17 generalized ICP (gicp_kernels.hip; driver: gicp_api.hip, then pose_loop.hip): K16's iteration with a 3 x 3 information matrix per pair where K16 has a
 // normal.  The step kernel writes K16's rows (PLANE_ROW doubles per 64 moving points, the same layout), so the rows reduce, the solve,
 // the state block and the rules are K16's own: plane_reduce_solve, PlaneState, PlaneRules.
 // ---------------------------------------------------------------------------------------------------------------
@@ -524,7 +513,7 @@ struct RansacMaskArgs {
 hipError_t ransac_mask_and_sum(const RansacMaskArgs& a, int* out_count, double* out_sum, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------------
-// K27 - K31 NDT registration (ndt_kernels.hip; driver: ndt_api.hip; the term of a pair: ndt_term.hpp).  mi_ndt_voxels: the voxel filter's
+// K27 - K31 NDT registration (ndt_kernels.hip; driver: ndt_api.hip, then pose_loop.hip for the iterations; the term of a pair: ndt_term.hpp).  mi_ndt_voxels: the voxel filter's
 // own front end (VoxArgs above: coordinates, counts and means are mi_voxel_downsample's by construction), then a second segmented pass
 // over the sorted order for the scatter about the fp32 mean and one lane per voxel for the eigenvalue floor and the inverse.
 // mi_ndt_register: the listed voxels in an open-addressing hash table, the step kernel writing K16's rows from a direct lookup per point,

@@ -1,9 +1,9 @@
 // mi_ndt_constants, mi_ndt_voxels, mi_ndt_register and mi_ndt_system behind the C ABI.  The voxel call is mi_voxel_downsample's front end
 // (voxel_front_run, voxel_api.hip) on buffers of its own, then the scatter pass, the per-voxel finish (ndt_kernels.hip) and the download.
-// The registration is mi_icp_gicp_register's driver with a voxel list in the place of the fixed cloud: argument checks, the reserves of the
-// call's own buffers in the context, the uploads, the checks of the moving cloud (knn_check_inputs) and of the list (K29) with their
-// read-backs, the table (K30), the moving cloud along its curve (morton_order / permute_soa), the state block, the iterations -- the step of
-// ndt_kernels.hip, then plane_kernels.hip's own reduce and solve -- in batches of sync_every between host reads of the state, and the results.
+// The registration, up to the step kernel's arguments: argument checks, the reserves of the call's own buffers in the context, the uploads, the
+// checks of the moving cloud (knn_check_inputs) and of the list (K29) with their read-backs, the table (K30), the moving cloud along its curve
+// (morton_order / permute_soa).  The state block, the iterations -- the step of ndt_kernels.hip, then plane_kernels.hip's own reduce and solve --
+// in batches of sync_every between host reads of the state, and the results are the pose loop's (pose_loop.hip), which gets the step's launch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -116,10 +116,7 @@ int check_arguments(const char* who, mi_ctx* c, const float* before_xyz, int n, 
     if (!(finite_f(origin3[0]) && finite_f(origin3[1]) && finite_f(origin3[2]))) { set_error("%s: non-finite origin", who); return MI_ERR_INVALID_ARG; }
     if (neighbourhood != 1 && neighbourhood != 7 && neighbourhood != 27) { set_error("%s: neighbourhood %d is not 1, 7 or 27", who, neighbourhood); return MI_ERR_INVALID_ARG; }
     if (!(outlier_ratio > 0.f && outlier_ratio < 1.f)) { set_error("%s: outlier_ratio %g is not in (0, 1)", who, (double)outlier_ratio); return MI_ERR_INVALID_ARG; }
-    if (T)
-        for (int i = 0; i < 16; i++)       // the rotation block and the translation column: the bottom row is never read
-            if (i % 4 != 3 && !std::isfinite(T[i])) { set_error("%s: transform entry %d is not finite (%g)", who, i, (double)T[i]); return MI_ERR_INVALID_ARG; }
-    return MI_OK;
+    return pose_check_transform(who, T);
 }
 
 // Stages 0 - 4 of either call and the state block at pose T: after it the step kernel's arguments are complete and checked against the buffers.
@@ -129,7 +126,6 @@ int ndt_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* befo
 {
     mi_ctx::NdtBuffers& b = c->ndt;
     const size_t np = (size_t)n, vp = (size_t)nv;
-    const int nrows = plane_row_count(n), nparts = plane_part_count(nrows);
     unsigned long long capacity = 2;
     while (capacity < 2 * (unsigned long long)nv) capacity <<= 1;
     double constants[4];
@@ -142,10 +138,7 @@ int ndt_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* befo
     MI_TRY(b.range_lo_hi.reserve(2 * 6 * KNN_RANGE_BLOCKS)); MI_TRY(b.range_bad.reserve(2 * KNN_RANGE_BLOCKS)); MI_TRY(b.kstate.reserve(1)); MI_TRY(b.order.reserve(np));
     MI_TRY(b.vcoord.reserve(3 * vp)); MI_TRY(b.vmean.reserve(3 * vp)); MI_TRY(b.vicov.reserve(6 * vp)); MI_TRY(b.mean4.reserve(vp)); MI_TRY(b.icov4.reserve(2 * vp));
     MI_TRY(b.mstate.reserve(1)); MI_TRY(b.hkeys.reserve((size_t)capacity)); MI_TRY(b.hvals.reserve((size_t)capacity));
-    MI_TRY(b.rows.reserve((size_t)nrows * PLANE_ROW));
-    if (nparts > 0) MI_TRY(b.parts.reserve((size_t)nparts * PLANE_ROW));
-    MI_TRY(b.state.reserve(1));
-    if (want_idx) MI_TRY(b.out_idx.reserve(np));
+    MI_TRY(pose_loop_reserve(b.loop, n, want_idx));
     if (want_terms) MI_TRY(b.out_terms.reserve(np));
     MortonArgs ma{};
     MI_TRY(morton_args(b.morton, b.ux.p, b.uy.p, b.uz.p, n, b.order.p, &ma));
@@ -212,48 +205,24 @@ int ndt_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* befo
     MI_HIP(permute_soa(b.ux.p, b.uy.p, b.uz.p, b.order.p, n, n, b.qx.p, b.qy.p, b.qz.p, c->stream));
     MI_TRY(clock.mark(4));
 
-    std::memset(h, 0, sizeof *h);
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) h->R[3 * i + j] = T ? (double)T[4 * j + i] : (i == j ? 1.0 : 0.0);      // column-major in, row-major kept
-        h->t[i] = T ? (double)T[12 + i] : 0.0;
-        h->c0[i] = (double)centre[i];
-    }
-    MI_TRY(host_to_device(c, b.state.p, h, sizeof *h));
-    MI_TRY(clock.mark(1));
+    MI_TRY(pose_loop_upload_state(c, b.loop, clock, T, centre, h));
 
     *a = NdtStepArgs{};
-    a->state = b.state.p;
+    a->state = b.loop.state.p;
     a->bx = b.qx.p; a->by = b.qy.p; a->bz = b.qz.p; a->order = b.order.p;
     a->n = n;
     a->map = map;
     for (int i = 0; i < 3; i++) a->origin[i] = origin3[i];
     a->voxel = voxel_size;
     a->h = constants[2]; a->k = constants[3];
-    a->rows = b.rows.p;
-    a->idx = want_idx ? b.out_idx.p : nullptr;
+    a->rows = b.loop.rows.p;
+    a->idx = want_idx ? b.loop.out_idx.p : nullptr;
     a->terms = want_terms ? b.out_terms.p : nullptr;
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (b.qx.cap < np || b.qy.cap < np || b.qz.cap < np || b.order.cap < np || b.rows.cap < (size_t)nrows * PLANE_ROW || b.state.cap < 1 ||
-        (nparts > 0 && b.parts.cap < (size_t)nparts * PLANE_ROW) || (want_idx && b.out_idx.cap < np) || (want_terms && b.out_terms.cap < np)) {
+    if (b.qx.cap < np || b.qy.cap < np || b.qz.cap < np || b.order.cap < np || !pose_loop_fits(b.loop, n, want_idx) ||
+        (want_terms && b.out_terms.cap < np)) {
         set_error("internal: %s buffers shorter than the launch", who);
         return MI_ERR_STATE;
-    }
-    return MI_OK;
-}
-
-// one iteration's launches: the step, then K16's rows -> sums -> (rules.solve) solve, update, stop rule.  With profiling on, the step's time
-// is booked to MI_KERNEL_NN and the other launches' to MI_KERNEL_SOLVE (mi_profile_get).
-int ndt_enqueue_iteration(mi_ctx* c, const NdtStepArgs& a, int neighbourhood, const PlaneRules& rules)
-{
-    mi_ctx::NdtBuffers& b = c->ndt;
-    const int nrows = plane_row_count(a.n);
-    {
-        ProfScope p(c, MI_KERNEL_NN);
-        MI_HIP(ndt_step(a, neighbourhood, c->stream));
-    }
-    {
-        ProfScope p(c, MI_KERNEL_SOLVE);
-        MI_HIP(plane_reduce_solve(b.state.p, b.rows.p, nrows, plane_part_count(nrows) > 0 ? b.parts.p : nullptr, rules, c->stream));
     }
     return MI_OK;
 }
@@ -267,12 +236,8 @@ extern "C" int mi_ndt_register(mi_ctx* c, const float* before_xyz, int n, const 
     const char* who = "mi_ndt_register";
     if (c && (!p || !out_T)) { set_error("%s: null params or out_T", who); return MI_ERR_INVALID_ARG; }
     MI_TRY(check_arguments(who, c, before_xyz, n, vox_coord, vox_mean, vox_icov6, nv, voxel_size, origin3, p ? p->neighbourhood : 1, p ? p->outlier_ratio : 0.5f, init_T));
-    if (!(p->eps_rotation >= 0.f) || !(p->eps_translation >= 0.f)) {
-        set_error("%s: eps_rotation %g or eps_translation %g is NaN or negative", who, (double)p->eps_rotation, (double)p->eps_translation);
-        return MI_ERR_INVALID_ARG;
-    }
-    if (p->max_iterations < 0) { set_error("%s: max_iterations %d is negative (there is no unbounded mode)", who, p->max_iterations); return MI_ERR_INVALID_ARG; }
-    if (p->sync_every < 0) { set_error("%s: sync_every %d is negative", who, p->sync_every); return MI_ERR_INVALID_ARG; }
+    const PoseLoopFields loop{p->eps_rotation, p->eps_translation, p->max_iterations, p->sync_every, p->verbose, "terms"};
+    MI_TRY(pose_check_fields(who, loop));
     if (c->distributed()) { set_error("%s: single-GPU contexts only", who); return MI_ERR_STATE; }
     MI_ENTER(c);
     mi_ctx::NdtBuffers& b = c->ndt;
@@ -282,37 +247,8 @@ extern "C" int mi_ndt_register(mi_ctx* c, const float* before_xyz, int n, const 
     PlaneState h;
     MI_TRY(ndt_prepare(c, who, clock, before_xyz, n, vox_coord, vox_mean, vox_icov6, nv, voxel_size, origin3, p->outlier_ratio, init_T, false, false, &a, &h));
 
-    PlaneRules rules{};
-    rules.eps_rotation = (double)p->eps_rotation; rules.eps_translation = (double)p->eps_translation;
-    rules.max_iterations = p->max_iterations; rules.solve = 1;
-    const int batch = p->sync_every > 0 ? p->sync_every : 4;
-    int enqueued = 0;
-    if (p->max_iterations == 0) { h.done = 1; h.stop_reason = MI_STOP_MAX_ITERATIONS; }
-    while (!h.done) {
-        if (enqueued >= p->max_iterations) { set_error("internal: %s ran %d iterations without a stop", who, enqueued); return MI_ERR_STATE; }
-        const int todo = std::min(batch, p->max_iterations - enqueued);
-        for (int i = 0; i < todo; i++) MI_TRY(ndt_enqueue_iteration(c, a, p->neighbourhood, rules));
-        enqueued += todo;
-        MI_HIP(hipMemcpyAsync(&h, b.state.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-        MI_HIP(hipStreamSynchronize(c->stream));
-        if (p->verbose)
-            fprintf(stderr, "%s: %d enqueued, %d applied, |omega| %.3e |v| %.3e, terms %.0f, stop %d\n", who, enqueued, h.iterations, h.omega, h.v, h.sums[29],
-                    h.stop_reason);
-    }
-    MI_TRY(clock.mark(5));
-
-    for (int i = 0; i < 16; i++) out_T[i] = 0.f;
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) out_T[4 * j + i] = (float)h.R[3 * i + j];
-        out_T[12 + i] = (float)h.t[i];
-    }
-    out_T[15] = 1.f;
-    if (iterations) *iterations = h.iterations;
-    if (score) *score = h.sums[29] > 0.0 ? (float)(h.sums[27] / h.sums[29]) : 0.f;
-    if (stop_reason) *stop_reason = h.stop_reason;
-    MI_TRY(clock.mark(6));
-    clock.finish();
-    return MI_OK;
+    MI_TRY(pose_loop_run(c, b.loop, clock, who, n, loop, &h, [&] { return ndt_step(a, p->neighbourhood, c->stream); }));
+    return pose_loop_results(clock, h, out_T, iterations, score, stop_reason);
 }
 
 extern "C" int mi_ndt_system(mi_ctx* c, const float* before_xyz, int n, const int* vox_coord, const float* vox_mean, const float* vox_icov6, int nv,
@@ -332,21 +268,9 @@ extern "C" int mi_ndt_system(mi_ctx* c, const float* before_xyz, int n, const in
     MI_TRY(ndt_prepare(c, who, clock, before_xyz, n, vox_coord, vox_mean, vox_icov6, nv, voxel_size, origin3, outlier_ratio, T, out_idx != nullptr,
                        out_terms != nullptr, &a, &h));
 
-    PlaneRules rules{};                // solve = 0: the sums and nothing else
-    MI_TRY(ndt_enqueue_iteration(c, a, neighbourhood, rules));
-    MI_HIP(hipMemcpyAsync(&h, b.state.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    MI_HIP(hipStreamSynchronize(c->stream));
-    MI_TRY(clock.mark(5));
-
-    if (out_idx) MI_HIP(hipMemcpyAsync(out_idx, b.out_idx.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(pose_loop_system_run(c, b.loop, clock, n, &h, out_idx, [&] { return ndt_step(a, neighbourhood, c->stream); }));
     if (out_terms) MI_HIP(hipMemcpyAsync(out_terms, b.out_terms.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    MI_HIP(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < PLANE_ROW; i++) out_sums[i] = h.sums[i];
-    if (out_centre)
-        for (int i = 0; i < 3; i++) out_centre[i] = (float)h.c0[i];
-    MI_TRY(clock.mark(6));
-    clock.finish();
-    return MI_OK;
+    return pose_loop_system_finish(c, clock, h, out_sums, out_centre);
 }
 
 extern "C" int mi_ndt_times(mi_ctx* c, double out_ms[MI_NDT_STAGES])

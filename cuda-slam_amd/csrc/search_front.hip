@@ -30,7 +30,7 @@ int search_front_reserve(SearchFrontBuffers& b, size_t n, size_t m, bool self)
 }
 
 int search_front_upload_and_check(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, const char* who, const float* cloud_xyz, int m,
-                                  const float* query_xyz, int n, SearchFront* f)
+                                  const float* query_xyz, int n, SearchFront* f, const char* cloud_name, const char* query_name)
 {
     const bool self = query_xyz == nullptr;
     MI_TRY(host_to_device(c, b.staging.p, cloud_xyz, sizeof(float) * 3 * (size_t)m));
@@ -50,11 +50,11 @@ int search_front_upload_and_check(mi_ctx* c, SearchFrontBuffers& b, StageClock& 
     MI_TRY(clock.mark(2));
     // everything that can refuse the input is known here, before any output array has been touched
     if (st->bad_cloud != KNN_NO_POINT) {
-        set_error("%s: cloud_xyz point %d has a non-finite coordinate or one above 1e18 in magnitude", who, st->bad_cloud);
+        set_error("%s: %s point %d has a non-finite coordinate or one above 1e18 in magnitude", who, cloud_name, st->bad_cloud);
         return MI_ERR_INVALID_ARG;
     }
     if (st->bad_query != KNN_NO_POINT) {
-        set_error("%s: query_xyz point %d has a non-finite coordinate or one above 1e18 in magnitude", who, st->bad_query);
+        set_error("%s: %s point %d has a non-finite coordinate or one above 1e18 in magnitude", who, query_name, st->bad_query);
         return MI_ERR_INVALID_ARG;
     }
     for (int i = 0; i < 3; i++) { f->bbox[i] = st->lo[i]; f->bbox[3 + i] = st->hi[i]; }
