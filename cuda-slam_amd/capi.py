@@ -43,6 +43,7 @@ EXPORTS = [
     "mi_prepare_params_default", "mi_prepare_cloud", "mi_voxel_index", "mi_voxel_downsample", "mi_voxel_downsample_times",
     "mi_knn_search", "mi_knn_search_times", "mi_estimate_normals", "mi_estimate_normals_times",
     "mi_outlier_params_default", "mi_remove_outliers", "mi_remove_outliers_times",
+    "mi_iss_params_default", "mi_iss_keypoints", "mi_iss_keypoints_times",
     "mi_plane_params_default", "mi_icp_plane_register", "mi_plane_system", "mi_icp_plane_times",
     "mi_estimate_covariances", "mi_icp_gicp_register", "mi_gicp_system", "mi_icp_gicp_times",
     "mi_fpfh_features", "mi_fpfh_features_times",
@@ -84,6 +85,11 @@ class OutlierParams(C.Structure):
 
 class OutlierStats(C.Structure):
     _fields_ = [("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double), ("kept", C.c_longlong), ("reserved", C.c_int * 4)]
+
+
+class IssParams(C.Structure):
+    _fields_ = [("salient_radius", C.c_float), ("non_max_radius", C.c_float), ("gamma_21", C.c_float), ("gamma_32", C.c_float),
+                ("min_neighbours", C.c_int), ("dist_mode", C.c_int), ("reserved", C.c_int * 10)]
 
 
 class PlaneParams(C.Structure):
@@ -328,6 +334,26 @@ def remove_outliers_raw(handle, cloud, n, params, out_xyz, out_index, out_n, kee
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
     f.restype = C.c_int
     return f(handle, cloud, n, params, out_xyz, out_index, out_n, keep, mean_distance, neighbours, stats)
+
+
+def iss_params(**kw):
+    """mi_iss_params at its defaults (gamma 0.975 and 0.975, min_neighbours 5, CPU rounding; both radii 0: set them) with the given fields set."""
+    p = IssParams()
+    lib().mi_iss_params_default.restype = None
+    lib().mi_iss_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def iss_keypoints_raw(handle, cloud, n, params, out_xyz, out_index, out_n, is_keypoint, saliency, eigenvalues, neighbours):
+    """mi_iss_keypoints with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_iss_keypoints
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+    f.restype = C.c_int
+    return f(handle, cloud, n, params, out_xyz, out_index, out_n, is_keypoint, saliency, eigenvalues, neighbours)
 
 
 def plane_params(**kw):
@@ -1016,6 +1042,31 @@ class Context:
         out = (C.c_double * 8)()
         _check(lib().mi_remove_outliers_times(self._h, out))
         return dict(zip(("workspace", "upload", "check", "grid", "order", "kernel", "finish", "total"), list(out)))
+
+    # ---- ISS keypoints
+    def iss_keypoints(self, cloud, params, want_is_keypoint=False, want_saliency=False, want_eigenvalues=False, want_neighbours=False):
+        """ISS keypoint detection (mi_iss_keypoints; params: iss_params(salient_radius=..., non_max_radius=...)): the keypoints [kept, 3]
+        with the input's bits and their indices [kept] int32, ascending; then, as asked for and in this order: is_keypoint [n] uint8,
+        saliency [n] float32, eigenvalues [n, 3] float32 (ascending) and neighbours [n] int32 (the salient ball's count)."""
+        cloud = _cloud(cloud)
+        n = cloud.shape[0]
+        out_xyz, out_index, out_n = np.empty((n, 3), np.float32), np.empty(n, np.int32), C.c_int(0)
+        is_keypoint = np.empty(n, np.uint8) if want_is_keypoint else None
+        saliency = np.empty(n, np.float32) if want_saliency else None
+        eigenvalues = np.empty((n, 3), np.float32) if want_eigenvalues else None
+        neighbours = np.empty(n, np.int32) if want_neighbours else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _check(iss_keypoints_raw(self._h, cloud.ctypes.data, n, C.addressof(params), out_xyz.ctypes.data, out_index.ctypes.data, C.addressof(out_n),
+                                 ptr(is_keypoint), ptr(saliency), ptr(eigenvalues), ptr(neighbours)))
+        res = [out_xyz[:out_n.value].copy(), out_index[:out_n.value].copy()]
+        res += [a for a in (is_keypoint, saliency, eigenvalues, neighbours) if a is not None]
+        return tuple(res)
+
+    def iss_keypoints_times(self):
+        """ms per stage of the last iss_keypoints: workspace, upload, check, grid, order, saliency, finish, total (mi_iss_keypoints_times)."""
+        out = (C.c_double * 8)()
+        _check(lib().mi_iss_keypoints_times(self._h, out))
+        return dict(zip(("workspace", "upload", "check", "grid", "order", "saliency", "finish", "total"), list(out)))
 
     # ---- point-to-plane ICP
     def icp_plane_register(self, before, after, after_normals, params, init=None):

@@ -125,7 +125,7 @@ struct mi_ctx {
         int fgt_shard_queries = 1;                       // MISLAM_FGT_SHARD_QUERIES=0: the FGT / hybrid CPD modes run replicated on a multi-rank context, no collective (rounds 4-5)
         int fgt_model_splits = 1;                        // MISLAM_FGT_MODEL_SPLITS=0: one workgroup per cell in the FGT model build whatever the cells' sizes (rounds 1-4)
         float knn_points_per_cell = 0.f;                 // MISLAM_KNN_POINTS_PER_CELL: cell size of mi_knn_search's grid (0: the default for the call's k, knn_default_points_per_cell of search_front.hip)
-        float outlier_radius_cell = 1.f;                 // MISLAM_OUTLIER_RADIUS_CELL: cell edge of mi_remove_outliers' radius grid in radii (outlier_api.hip)
+        float outlier_radius_cell = 1.f;                 // MISLAM_OUTLIER_RADIUS_CELL: cell edge of mi_remove_outliers' radius grid and of mi_iss_keypoints' grid in radii (radius_points_per_cell, search_front.hip)
         int fgt_replay = 1;                              // MISLAM_FGT_REPLAY=0: sweep the moving cloud step by step every E-step (no guess replayed)
     } tune;
 
@@ -242,6 +242,16 @@ struct mi_ctx {
         mislam::DevBuf<mislam::OutlierState> ostate;
         double ms[MI_OUTLIER_STAGES] = {0};              // mi_remove_outliers_times
     } outlier;
+
+    // ---- mi_iss_keypoints: OutlierBuffers' sibling -- a search front end in self mode, K32's per-point results, K33's flags and their compaction
+    struct IssBuffers {
+        mislam::SearchFrontBuffers front;                // (front.staging, the cloud as uploaded, is what the compaction gathers from)
+        mislam::DevBuf<float> saliency, eigenvalues, out_xyz;
+        mislam::DevBuf<int> neighbours, tile_counts, out_index;
+        mislam::DevBuf<unsigned char> flag;              // is_keypoint, the caller's order
+        mislam::DevBuf<mislam::OutlierState> ostate;     // (kept: the number of keypoints)
+        double ms[MI_ISS_STAGES] = {0};                  // mi_iss_keypoints_times
+    } iss;
 
     // ---- mi_icp_plane_register, mi_plane_system: a search front end over the FIXED cloud with the moving cloud as its queries, the fixed
     // cloud's normals, the rows of an iteration's sums and the loop's state block -- a sibling of the three above, nothing shared with mi_icp_*
@@ -423,7 +433,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 
 // ---- the voxel filter's front end (voxel_api.hip), for mi_voxel_downsample and mi_ndt_voxels: the reserves, the upload, the range pass and its
 // read-back with everything that can refuse the cloud (nothing has been written to a caller's array then), the keys, the sort, the rows and the

@@ -1,0 +1,125 @@
+// mi_iss_keypoints behind the C ABI: argument checks, the reserves of the call's own buffers in the context, the search front end in
+// self mode (search_front.hip: upload, input check and its one read-back, ONE cell grid over the cloud with cells about the larger of the
+// two radii long, the curve order), K32 and K33 of iss_kernels.hip over that grid, the compaction of K33's flags (outlier_compact, K15's)
+// and the download of what was asked for.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "context.h"
+
+using namespace mislam;
+
+extern "C" void mi_iss_params_default(mi_iss_params* p)
+{
+    if (!p) return;
+    *p = mi_iss_params{};
+    p->salient_radius = 0.0f;
+    p->non_max_radius = 0.0f;
+    p->gamma_21 = 0.975f;
+    p->gamma_32 = 0.975f;
+    p->min_neighbours = 5;
+    p->dist_mode = MI_DIST_CPU_ROUNDING;
+}
+static_assert(sizeof(mi_iss_params) == 64, "mi_iss_params is 64 bytes (mi_slam.h)");
+
+extern "C" int mi_iss_keypoints(mi_ctx* c, const float* cloud_xyz, int n, const mi_iss_params* p, float* out_xyz, int* out_index, int* out_n,
+                                unsigned char* is_keypoint, float* saliency, float* eigenvalues, int* neighbours)
+{
+    if (!c) { set_error("mi_iss_keypoints: null context"); return MI_ERR_INVALID_ARG; }
+    if (!cloud_xyz || !p || !out_n) { set_error("mi_iss_keypoints: null cloud_xyz, params or out_n"); return MI_ERR_INVALID_ARG; }
+    if (n < 1) { set_error("mi_iss_keypoints: empty cloud (n = %d)", n); return MI_ERR_INVALID_ARG; }
+    if (p->dist_mode != MI_DIST_CPU_ROUNDING && p->dist_mode != MI_DIST_FMA) { set_error("mi_iss_keypoints: bad dist_mode %d", p->dist_mode); return MI_ERR_INVALID_ARG; }
+    const float r2s = p->salient_radius * p->salient_radius, r2n = p->non_max_radius * p->non_max_radius;   // one IEEE fp32 multiplication each (-ffp-contract=off)
+    if (!(std::isfinite(p->salient_radius) && p->salient_radius > 0.f)) { set_error("mi_iss_keypoints: salient_radius %g is NaN, infinite or not positive", (double)p->salient_radius); return MI_ERR_INVALID_ARG; }
+    if (!std::isfinite(r2s)) { set_error("mi_iss_keypoints: the square of salient_radius %g is not finite", (double)p->salient_radius); return MI_ERR_INVALID_ARG; }
+    if (!(std::isfinite(p->non_max_radius) && p->non_max_radius > 0.f)) { set_error("mi_iss_keypoints: non_max_radius %g is NaN, infinite or not positive", (double)p->non_max_radius); return MI_ERR_INVALID_ARG; }
+    if (!std::isfinite(r2n)) { set_error("mi_iss_keypoints: the square of non_max_radius %g is not finite", (double)p->non_max_radius); return MI_ERR_INVALID_ARG; }
+    if (!(std::isfinite(p->gamma_21) && p->gamma_21 > 0.f)) { set_error("mi_iss_keypoints: gamma_21 %g is NaN, infinite or not positive", (double)p->gamma_21); return MI_ERR_INVALID_ARG; }
+    if (!(std::isfinite(p->gamma_32) && p->gamma_32 > 0.f)) { set_error("mi_iss_keypoints: gamma_32 %g is NaN, infinite or not positive", (double)p->gamma_32); return MI_ERR_INVALID_ARG; }
+    const int min_nb = p->min_neighbours;
+    if (min_nb < 1) { set_error("mi_iss_keypoints: min_neighbours = %d below 1", min_nb); return MI_ERR_INVALID_ARG; }
+    if (c->distributed()) { set_error("mi_iss_keypoints: single-GPU contexts only"); return MI_ERR_STATE; }
+    MI_ENTER(c);
+    mi_ctx::IssBuffers& b = c->iss;
+    StageClock clock(c, b.ms);         // mi_iss_keypoints_times
+
+    const size_t np = (size_t)n;
+    const int tiles = outlier_scan_tiles(n);
+    MI_TRY(search_front_reserve(b.front, np, np, true));
+    MI_TRY(b.ostate.reserve(1));
+    MI_TRY(b.saliency.reserve(np)); MI_TRY(b.flag.reserve(np)); MI_TRY(b.tile_counts.reserve((size_t)tiles));
+    if (eigenvalues) MI_TRY(b.eigenvalues.reserve(3 * np));
+    if (neighbours) MI_TRY(b.neighbours.reserve(np));
+    if (out_xyz) MI_TRY(b.out_xyz.reserve(3 * np));
+    if (out_index) MI_TRY(b.out_index.reserve(np));
+    MI_TRY(clock.mark(0));
+
+    SearchFront f;
+    MI_TRY(search_front_upload_and_check(c, b.front, clock, "mi_iss_keypoints", cloud_xyz, n, nullptr, n, &f));
+    // one cell grid for both walks: a cell about the larger radius long, by the rule of mi_remove_outliers' radius method
+    const float ppc = c->tune.knn_points_per_cell > 0.f
+                          ? c->tune.knn_points_per_cell
+                          : radius_points_per_cell(f.bbox, n, std::max(p->salient_radius, p->non_max_radius), c->tune.outlier_radius_cell);
+    MI_TRY(search_front_index_and_order(c, b.front, clock, "mi_iss_keypoints", ppc, &f));
+
+    // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
+    if (!search_front_fits(b.front, f) || b.front.staging.cap < 3 * np || b.saliency.cap < np || b.flag.cap < np || b.tile_counts.cap < (size_t)tiles ||
+        (eigenvalues && b.eigenvalues.cap < 3 * np) || (neighbours && b.neighbours.cap < np) || (out_xyz && b.out_xyz.cap < 3 * np) ||
+        (out_index && b.out_index.cap < np)) {
+        set_error("internal: mi_iss_keypoints buffers shorter than the launch");
+        return MI_ERR_STATE;
+    }
+    const int fma = p->dist_mode == MI_DIST_FMA;
+    MI_TRY(search_front_timed_launch(c, b.front, clock, [&] {
+        IssSaliencyArgs a{};
+        a.qx = b.front.qx.p; a.qy = b.front.qy.p; a.qz = b.front.qz.p; a.order = b.front.order.p;
+        a.cx = b.front.cx.p; a.cy = b.front.cy.p; a.cz = b.front.cz.p;
+        a.n = n; a.r2 = r2s; a.min_neighbours = min_nb;
+        a.gamma_21 = (double)p->gamma_21; a.gamma_32 = (double)p->gamma_32;
+        for (int i = 0; i < 3; i++) a.hi[i] = f.bbox[3 + i];
+        a.saliency = b.saliency.p; a.eigenvalues = eigenvalues ? b.eigenvalues.p : nullptr; a.neighbours = neighbours ? b.neighbours.p : nullptr;
+        return iss_saliency(f.g, a, fma, c->stream);
+    }));
+
+    IssSuppressArgs sa{};
+    sa.qx = b.front.qx.p; sa.qy = b.front.qy.p; sa.qz = b.front.qz.p; sa.order = b.front.order.p;
+    sa.n = n; sa.r2 = r2n; sa.min_neighbours = min_nb;
+    for (int i = 0; i < 3; i++) sa.hi[i] = f.bbox[3 + i];
+    sa.saliency = b.saliency.p; sa.is_keypoint = b.flag.p;
+    MI_HIP(iss_suppress(f.g, sa, fma, c->stream));
+
+    MI_HIP(hipMemsetAsync(b.ostate.p, 0, sizeof(OutlierState), c->stream));
+    OutlierCompactArgs ca{};
+    ca.keep = b.flag.p; ca.xyz = b.front.staging.p; ca.n = n; ca.tile_counts = b.tile_counts.p;
+    ca.out_index = out_index ? b.out_index.p : nullptr; ca.out_xyz = out_xyz ? b.out_xyz.p : nullptr; ca.state = b.ostate.p;
+    MI_HIP(outlier_compact(ca, c->stream));
+
+    // the state once, with the per-point results; then the keypoints' rows, whose number the state has brought
+    OutlierState* os = reinterpret_cast<OutlierState*>(c->h_scratch);
+    MI_HIP(hipMemcpyAsync(os, b.ostate.p, sizeof(OutlierState), hipMemcpyDeviceToHost, c->stream));
+    if (is_keypoint) MI_HIP(hipMemcpyAsync(is_keypoint, b.flag.p, np, hipMemcpyDeviceToHost, c->stream));
+    if (saliency) MI_HIP(hipMemcpyAsync(saliency, b.saliency.p, sizeof(float) * np, hipMemcpyDeviceToHost, c->stream));
+    if (eigenvalues) MI_HIP(hipMemcpyAsync(eigenvalues, b.eigenvalues.p, sizeof(float) * 3 * np, hipMemcpyDeviceToHost, c->stream));
+    if (neighbours) MI_HIP(hipMemcpyAsync(neighbours, b.neighbours.p, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    const long long found = os->kept;
+    if (found < 0 || found > (long long)n) { set_error("internal: mi_iss_keypoints counted %lld keypoints among %d points", found, n); return MI_ERR_STATE; }
+    if (found > 0) {
+        if (out_xyz) MI_HIP(hipMemcpyAsync(out_xyz, b.out_xyz.p, sizeof(float) * 3 * (size_t)found, hipMemcpyDeviceToHost, c->stream));
+        if (out_index) MI_HIP(hipMemcpyAsync(out_index, b.out_index.p, sizeof(int) * (size_t)found, hipMemcpyDeviceToHost, c->stream));
+        if (out_xyz || out_index) MI_HIP(hipStreamSynchronize(c->stream));
+    }
+    *out_n = (int)found;
+    MI_TRY(clock.mark(6));
+    clock.finish();
+    return MI_OK;
+}
+
+extern "C" int mi_iss_keypoints_times(mi_ctx* c, double out_ms[MI_ISS_STAGES])
+{
+    if (!c || !out_ms) { set_error("mi_iss_keypoints_times: null argument"); return MI_ERR_INVALID_ARG; }
+    for (int i = 0; i < MI_ISS_STAGES; i++) out_ms[i] = c->iss.ms[i];
+    return MI_OK;
+}

@@ -266,6 +266,8 @@ hipError_t knn_check_inputs(const float* cx, const float* cy, const float* cz, i
 hipError_t knn_search(const NnGridView& g, const KnnSearchArgs& a, int fma, hipStream_t s);
 int knn_list_size(int k);            // registers' worth of list the search of this k is instantiated with: 8, 16 or 32
 float knn_default_points_per_cell(int k);    // cell size of the k-NN grid unless MISLAM_KNN_POINTS_PER_CELL says otherwise (search_front.hip)
+// points per cell of a fixed-radius search's grid: a cell's edge is cell_in_radii radii long (search_front.hip; mi_remove_outliers' radius method, mi_iss_keypoints)
+float radius_points_per_cell(const float bbox[6], int n, float radius, float cell_in_radii);
 
 // ---------------------------------------------------------------------------------------------------------------
 // K14 surface normals and curvature (normals_kernels.hip; driver: normals_api.hip): K13's search in self mode and, with the keys
@@ -582,6 +584,39 @@ struct NdtStepArgs {
 };
 hipError_t ndt_step(const NdtStepArgs& a, int neighbourhood, hipStream_t s);      // neighbourhood 1, 7 or 27
 
+// ---------------------------------------------------------------------------------------------------------------
+// K32 / K33 ISS keypoints (iss_kernels.hip; driver: iss_api.hip): the fixed-radius walk of K15 over one cell grid, twice.  K32 takes the
+// fp64 scatter of the salient ball as it walks, and behind the walk the eigenvalues (eig3.hpp), the gate and the fp32 saliency; K33 walks
+// the non-max ball of every candidate, gathers the neighbours' saliencies and leaves at the first one that dominates.  The flags are
+// compacted by K15's outlier_compact.
+// ---------------------------------------------------------------------------------------------------------------
+struct IssSaliencyArgs {
+    const float *qx, *qy, *qz;       // the cloud along its curve order, SoA, n entries
+    const int* order;                // sorted slot -> the caller's index (the row the slot's answer goes to, and the candidate it skips)
+    const float *cx, *cy, *cz;       // the cloud in the caller's order, SoA: what the neighbours' indices point into
+    int n;
+    float r2;                        // a point j != row (by index) with d2 <= r2 is in the salient ball
+    int min_neighbours;
+    double gamma_21, gamma_32;       // the caller's fp32 values, promoted
+    float hi[3];                     // upper corner of the cloud's bounding box (the lower one is the grid's origin)
+    float* saliency;                 // n, the caller's order: max((float)lambda0, 0) where the gate holds, +0 elsewhere
+    float* eigenvalues;              // n * 3, ascending, may be null
+    int* neighbours;                 // n, may be null
+};
+hipError_t iss_saliency(const NnGridView& g, const IssSaliencyArgs& a, int fma, hipStream_t s);
+
+struct IssSuppressArgs {
+    const float *qx, *qy, *qz;       // as above
+    const int* order;
+    int n;
+    float r2;                        // the non-max ball
+    int min_neighbours;
+    float hi[3];
+    const float* saliency;           // n, the caller's order (K32's)
+    unsigned char* is_keypoint;      // n, the caller's order: every row is written
+};
+hipError_t iss_suppress(const NnGridView& g, const IssSuppressArgs& a, int fma, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -603,5 +638,6 @@ hipError_t preload_fpfh_kernels();
 hipError_t preload_match_kernels();
 hipError_t preload_ransac_kernels();
 hipError_t preload_ndt_kernels();
+hipError_t preload_iss_kernels();
 
 }  // namespace mislam

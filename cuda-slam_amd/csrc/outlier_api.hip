@@ -23,23 +23,6 @@ extern "C" void mi_outlier_params_default(mi_outlier_params* p)
     p->min_neighbours = 1;
 }
 
-// Points per cell of the radius method's grid: the number that makes a cell's edge `cell_in_radii` radii long (1 unless
-// MISLAM_OUTLIER_RADIUS_CELL says otherwise), so that a ball reaches into the 27 cells around its point's and rarely further.  An axis
-// shorter than that edge is one layer of cells.  Bounded below by the k-NN rule's floor (at most one cell per point: a small radius in a
-// sparse cloud must not buy more cells than points) and above by n (one cell); grid_plan keeps the counts within GRID_MAX_DIM.
-// A rule by reasoning, not by measurement.
-static float radius_points_per_cell(const float bbox[6], int n, float radius, float cell_in_radii)
-{
-    const double edge = (double)cell_in_radii * (double)radius;
-    double cells = 1.0;
-    for (int a = 0; a < 3; a++) {
-        const double ext = (double)bbox[3 + a] - (double)bbox[a];
-        if (ext > edge) cells *= ext / edge;
-    }
-    const double ppc = (double)n / cells;                                          // (cells >= 1, possibly +inf: ppc in [0, n])
-    return (float)std::min(std::max(ppc, (double)knn_default_points_per_cell(1)), (double)n);
-}
-
 extern "C" int mi_remove_outliers(mi_ctx* c, const float* cloud_xyz, int n, const mi_outlier_params* p, float* out_xyz, int* out_index, int* out_n,
                                   unsigned char* keep, float* mean_distance, int* neighbours, mi_outlier_stats* stats)
 {

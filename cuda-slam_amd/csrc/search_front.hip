@@ -18,6 +18,24 @@ static_assert(sizeof(KnnState) <= 64 * sizeof(float), "KnnState must fit the con
 // shells walked.  An estimate: the sweep of tools/knn_bench.py --sweep has not been run yet.
 float knn_default_points_per_cell(int k) { return std::max(1.0f, 0.5f * (float)k); }
 
+// Points per cell of a fixed-radius search's grid (mi_remove_outliers' radius method; mi_iss_keypoints, with the larger of its two
+// radii): the number that makes a cell's edge `cell_in_radii` radii long (1 unless MISLAM_OUTLIER_RADIUS_CELL says otherwise), so that
+// a ball reaches into the 27 cells around its point's and rarely further.  An axis
+// shorter than that edge is one layer of cells.  Bounded below by the k-NN rule's floor (at most one cell per point: a small radius in a
+// sparse cloud must not buy more cells than points) and above by n (one cell); grid_plan keeps the counts within GRID_MAX_DIM.
+// A rule by reasoning, not by measurement.
+float radius_points_per_cell(const float bbox[6], int n, float radius, float cell_in_radii)
+{
+    const double edge = (double)cell_in_radii * (double)radius;
+    double cells = 1.0;
+    for (int a = 0; a < 3; a++) {
+        const double ext = (double)bbox[3 + a] - (double)bbox[a];
+        if (ext > edge) cells *= ext / edge;
+    }
+    const double ppc = (double)n / cells;                                          // (cells >= 1, possibly +inf: ppc in [0, n])
+    return (float)std::min(std::max(ppc, (double)knn_default_points_per_cell(1)), (double)n);
+}
+
 int search_front_reserve(SearchFrontBuffers& b, size_t n, size_t m, bool self)
 {
     MI_TRY(b.staging.reserve(3 * std::max(n, m)));
@@ -94,7 +112,7 @@ bool search_front_fits(const SearchFrontBuffers& b, const SearchFront& f)
 
 void search_front_destroy_events(mi_ctx* c)
 {
-    for (SearchFrontBuffers* b : {&c->knn.front, &c->normals.front, &c->outlier.front, &c->plane.front, &c->cov.front, &c->gicp.front, &c->fpfh.front})
+    for (SearchFrontBuffers* b : {&c->knn.front, &c->normals.front, &c->outlier.front, &c->plane.front, &c->cov.front, &c->gicp.front, &c->fpfh.front, &c->iss.front})
         for (hipEvent_t e : b->ev) if (e) (void)hipEventDestroy(e);
 }
 

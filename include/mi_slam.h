@@ -732,6 +732,76 @@ int mi_remove_outliers(mi_ctx* ctx, const float* cloud_xyz, int n, const mi_outl
 int mi_remove_outliers_times(mi_ctx* ctx, double out_ms[MI_OUTLIER_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * ISS keypoints (Intrinsic Shape Signatures, Zhong 2009; no reference counterpart): the few per cent of a cloud's points whose
+ * neighbourhood is distinctive, to be taken between mi_estimate_normals and mi_fpfh_features so that only their descriptors are
+ * matched (keypoints).  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    float salient_radius;    /* finite, > 0, square finite: the ball the scatter matrix is taken over     default 0: the caller must set it */
+    float non_max_radius;    /* finite, > 0, square finite: the ball of the non-maximum suppression       default 0: the caller must set it */
+    float gamma_21;          /* finite, > 0                                                                default 0.975f */
+    float gamma_32;          /* finite, > 0                                                                default 0.975f */
+    int   min_neighbours;    /* >= 1: in BOTH balls                                                         default 5 */
+    int   dist_mode;         /* MI_DIST_CPU_ROUNDING / MI_DIST_FMA, as mi_knn_search                        default CPU_ROUNDING */
+    int   reserved[10];
+} mi_iss_params;             /* 64 bytes */
+void mi_iss_params_default(mi_iss_params* p);
+
+/* The ISS keypoints of a cloud, computed on the device.  Every rule below can be retraced in numpy (tests/iss_reference.py does).
+ *   Radii: r2s = salient_radius * salient_radius and r2n = non_max_radius * non_max_radius, one IEEE fp32 multiplication each.  The two
+ *     radii are independent: either may be the larger.
+ *   Salient neighbourhood of point i: { j != i (by index) : d2(i, j) <= r2s } in the dist_mode arithmetic of mi_knn_search.
+ *     neighbours[i] is its size: exactly the count mi_remove_outliers gives in radius mode at the same radius with its neighbours
+ *     output.  A point AT the radius belongs; a duplicate of point i stored elsewhere is a neighbour.
+ *   Scatter: the covariance rule of mi_estimate_covariances, taken over the ball instead of a k-list.  c = neighbours[i] + 1 (the point
+ *     itself contributes d = 0); d = p_j - p_i in fp64 (exact, or rounded at 2^-53); nine running fp64 sums S = sum d and Q = sum d d^T
+ *     (upper triangle), one product and one addition per entry and neighbour; m = S / c, C_ab = Q_ab / c - m_a m_b.  The summation order
+ *     is the walk's over the call's cell grid: a function of the cloud, the radii and the context's tuning alone.
+ *   Eigenvalues: lambda0 <= lambda1 <= lambda2 of C by the fp64 cyclic Jacobi of mi_estimate_normals; eigenvalues[3 i .. 3 i + 2] are
+ *     those, each rounded once to fp32, written for EVERY point, gated or not; 0, 0, 0 where neighbours[i] = 0.
+ *   Gate, in fp64: point i passes when neighbours[i] >= min_neighbours, lambda1 < (double)gamma_21 * lambda2 and
+ *     lambda0 < (double)gamma_32 * lambda1.  Products, not quotients: a zero matrix fails and nothing divides by 0.
+ *   Saliency: saliency[i] = max((float)lambda0, 0) where the gate holds, +0 elsewhere.  Point i is a candidate iff saliency[i] > 0.  An
+ *     exact plane z = const gives lambda0 = 0 exactly (the Jacobi sweep skips zero off-diagonal entries), so none of its points is a
+ *     candidate; a cloud of identical points has none either.
+ *   Non-maximum suppression, on the fp32 saliency values alone: candidate i is a keypoint iff its non-max ball
+ *     { j != i : d2(i, j) <= r2n } holds at least min_neighbours points and, for every j in it, saliency[i] > saliency[j], or
+ *     saliency[i] == saliency[j] and i < j.  The index tie-break departs from Open3D, whose strict ">" drops both of two tied points:
+ *     two nearby points often share the set ball + self, hence the covariance and, after the rounding, the saliency; here exactly one
+ *     point of such a cluster survives.
+ *   Outputs: is_keypoint is 0 / 1 per point; out_index holds the indices of the ones, ascending; out_xyz their coordinates, the input's
+ *     bits; *out_n their number.  Rows beyond *out_n are not written.  Asking for fewer optional outputs moves no bit of the rest.
+ *   Deterministic: the same call gives the same bits whatever ran on the context before.  No floating-point atomics.
+ *   Cost: a point's work is proportional to the number of points in its balls (and its cell's neighbourhood), so a radius that holds a
+ *     large share of the cloud makes the call quadratic.  The cloud's resolution comes from mi_remove_outliers (statistical, k = 1:
+ *     stats->mean); six and four times that resolution are the usual radii.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with "mi_iss_keypoints" and names the cause and, for a bad point, its index (the
+ *     lowest); NO output has been written -- for a NULL ctx, cloud_xyz, params or out_n; n < 1; an unknown dist_mode; a radius that is
+ *     NaN, infinite or <= 0, or whose square is not finite; a gamma that is NaN, infinite or <= 0; min_neighbours < 1; a non-finite
+ *     coordinate or one above 1e18 in magnitude.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls keep: it works in buffers of its own.
+ *   Synchronous, host in and host out. */
+int mi_iss_keypoints(mi_ctx* ctx, const float* cloud_xyz, int n, const mi_iss_params* params,
+                     float* out_xyz,            /* may be NULL; capacity n points: the keypoints, input bits, ascending caller index */
+                     int* out_index,            /* may be NULL; capacity n */
+                     int* out_n,                /* non-NULL */
+                     unsigned char* is_keypoint,/* may be NULL; n */
+                     float* saliency,           /* may be NULL; n */
+                     float* eigenvalues,        /* may be NULL; 3n: ascending per point */
+                     int* neighbours);          /* may be NULL; n: points in the salient ball */
+
+/* Where the last mi_iss_keypoints of this context spent its host wall time, in ms (measurement hook, tools/iss_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA
+ *   out[2] input check, bounding box, its read-back out[3] cell grid over the cloud
+ *   out[4] curve order of the cloud + permute       out[5] the saliency kernel (K32)
+ *   out[6] suppression (K33) + compaction + download    out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage, and out[5] is the
+ * launch's own HIP-event time instead of host wall time). */
+#define MI_ISS_STAGES 8
+int mi_iss_keypoints_times(mi_ctx* ctx, double out_ms[MI_ISS_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Point-to-plane ICP (no reference counterpart: the reference's ICP is point-to-point): the registration the normals are for
  * (plane registration).  It minimises sum (n_j . (R b_i + t - a_j))^2 over the matched pairs, linearised about the
  * current pose, and does not stall on surfaces that slide along themselves.  A sibling of mi_icp_register with buffers, state and
