@@ -459,8 +459,18 @@ int search_front_upload_and_check(mi_ctx* c, SearchFrontBuffers& b, StageClock& 
                                   const float* query_xyz, int n, SearchFront* f, const char* cloud_name = "cloud_xyz",
                                   const char* query_name = "query_xyz");
 int search_front_index_and_order(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, const char* who, float points_per_cell, SearchFront* f);
-// the host-side shape check of what every search kernel indexes: q*, order, c*, the grid's offsets and points
+// What a search kernel is handed beside the grid f.g.  No driver reads these buffers for a launch itself, so search_front_fits, the host-side
+// shape check of what every search kernel indexes (q*, order, c*, the grid's offsets and points), checks what was handed out.
+SearchQueries search_front_queries(const SearchFrontBuffers& b, const SearchFront& f);
+SearchCloud search_front_cloud(const SearchFrontBuffers& b);
 bool search_front_fits(const SearchFrontBuffers& b, const SearchFront& f);
+// A call with normals beside its cloud (m of them; mi_icp_plane_register, mi_fpfh_features) puts search_front_upload_and_check between these
+// two.  enqueue: the normals go first through the staging buffer and the check's partials, which the front end then takes over (one stream:
+// in order), into nx, ny, nz (and packed, unless null), checked into *nstate.  refuse: the one read-back of *nstate behind the front end's,
+// stage 2, and the refusal of a normal with an unusable component; name: what it calls the array.
+int search_front_enqueue_normals(mi_ctx* c, SearchFrontBuffers& b, const float* normals_xyz, int m, float* nx, float* ny, float* nz, float4* packed,
+                                 KnnState* nstate);
+int search_front_refuse_normals(mi_ctx* c, StageClock& clock, const char* who, const char* name, const KnnState* nstate);
 void search_front_destroy_events(mi_ctx* c);         // of every call's front end (mi_ctx_destroy)
 // Stage 5: `launch` enqueues the call's search kernel.  With profiling on, the slot holds the launch's own HIP-event time instead of the host's.
 template <class Launch>
@@ -540,7 +550,7 @@ static inline int pose_loop_run(mi_ctx* c, PoseLoopBuffers& b, StageClock& clock
         MI_TRY(pose_loop_read_state(c, b, h));
         if (p.verbose)
             fprintf(stderr, "%s: %d enqueued, %d applied, |omega| %.3e |v| %.3e, %s %.0f, stop %d\n", who, enqueued, h->iterations, h->omega, h->v, p.noun,
-                    h->sums[29], h->stop_reason);
+                    h->sums[PLANE_ROW_COUNT], h->stop_reason);
     }
     return clock.mark(5);
 }

@@ -35,32 +35,21 @@ extern "C" int mi_fpfh_features(mi_ctx* c, const float* cloud_xyz, const float* 
     if (count) MI_TRY(b.out_count.reserve(np));
     MI_TRY(clock.mark(0));
 
-    // the normals go first through the staging buffer and the check's partials, which the front end then takes over (one stream: in order)
-    MI_TRY(host_to_device(c, b.front.staging.p, normals_xyz, sizeof(float) * 3 * np));
-    MI_HIP(aos_to_soa(b.front.staging.p, n, n, b.nx.p, b.ny.p, b.nz.p, nullptr, c->stream));
-    MI_HIP(knn_check_inputs(b.nx.p, b.ny.p, b.nz.p, n, nullptr, nullptr, nullptr, 0, b.front.range_lo_hi.p, b.front.range_bad.p, b.nstate.p, c->stream));
+    MI_TRY(search_front_enqueue_normals(c, b.front, normals_xyz, n, b.nx.p, b.ny.p, b.nz.p, nullptr, b.nstate.p));
     SearchFront f;
     MI_TRY(search_front_upload_and_check(c, b.front, clock, who, cloud_xyz, n, nullptr, n, &f));
-    KnnState ns;
-    MI_HIP(hipMemcpyAsync(&ns, b.nstate.p, sizeof ns, hipMemcpyDeviceToHost, c->stream));
-    MI_HIP(hipStreamSynchronize(c->stream));
-    MI_TRY(clock.mark(2));
-    if (ns.bad_cloud != KNN_NO_POINT) {
-        set_error("%s: normals_xyz normal %d has a non-finite component or one above 1e18 in magnitude", who, ns.bad_cloud);
-        return MI_ERR_INVALID_ARG;
-    }
+    MI_TRY(search_front_refuse_normals(c, clock, who, "normals_xyz", b.nstate.p));
     const float ppc = c->tune.knn_points_per_cell > 0.f ? c->tune.knn_points_per_cell : knn_default_points_per_cell(k);   // mi_knn_search's grid, cell size included
     MI_TRY(search_front_index_and_order(c, b.front, clock, who, ppc, &f));
 
     FpfhSpfhArgs a{};
-    a.qx = b.front.qx.p; a.qy = b.front.qy.p; a.qz = b.front.qz.p; a.order = b.front.order.p;
-    a.cx = b.front.cx.p; a.cy = b.front.cy.p; a.cz = b.front.cz.p;
+    a.q = search_front_queries(b.front, f);
+    a.c = search_front_cloud(b.front);
     a.nx = b.nx.p; a.ny = b.ny.p; a.nz = b.nz.p;
-    a.n = n; a.k = k; a.max_d2 = max_distance_squared;
-    for (int i = 0; i < 3; i++) a.hi[i] = f.bbox[3 + i];
+    a.k = k; a.max_d2 = max_distance_squared;
     a.keys = b.keys.p; a.packed = b.packed.p; a.count = count ? b.out_count.p : nullptr;
     FpfhSumArgs sa{};
-    sa.order = b.front.order.p; sa.keys = b.keys.p; sa.packed = b.packed.p;
+    sa.order = a.q.order; sa.keys = b.keys.p; sa.packed = b.packed.p;
     sa.n = n; sa.k = k;
     sa.fpfh = b.out_fpfh.p; sa.counts = spfh_counts33 ? b.out_counts.p : nullptr;
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume

@@ -53,15 +53,15 @@ template <int K, bool FMA>
 __global__ __launch_bounds__(KNN_BLOCK) void fpfh_spfh_kernel(NnGridView g, FpfhSpfhArgs a)
 {
     const int s = blockIdx.x * KNN_BLOCK + (int)threadIdx.x;
-    if (s >= a.n) return;
-    const float q[3] = {a.qx[s], a.qy[s], a.qz[s]};
-    const int row_out = a.order[s];
+    if (s >= a.q.n) return;
+    const float q[3] = {a.q.x[s], a.q.y[s], a.q.z[s]};
+    const int row_out = a.q.order[s];
     const int k = a.k;
 
     unsigned long long l[K];
 #pragma unroll
     for (int i = 0; i < K; i++) l[i] = i < K - k ? 0ull : KNN_KEY_EMPTY;
-    knn_scan<K, FMA>(g, q, a.hi, (unsigned int)row_out, k, a.max_d2, l);
+    knn_scan<K, FMA>(g, q, a.q.hi, (unsigned int)row_out, k, a.max_d2, l);
 
     unsigned long long* keys = a.keys + (size_t)row_out * (size_t)k;
 #pragma unroll
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void fpfh_spfh_kernel(NnGridView g, Fpfh
         if ((unsigned int)(key >> 32) < 0x7f800000u) {                             // a filled slot of the k-list
             const unsigned int j = (unsigned int)(key & 0xffffffffull);            // (< n: the index the grid build stored)
             double theta, alpha, phi;
-            fpfh_pair_features(pix, piy, piz, nix, niy, niz, (double)a.cx[j], (double)a.cy[j], (double)a.cz[j], (double)a.nx[j], (double)a.ny[j],
+            fpfh_pair_features(pix, piy, piz, nix, niy, niz, (double)a.c.x[j], (double)a.c.y[j], (double)a.c.z[j], (double)a.nx[j], (double)a.ny[j],
                                (double)a.nz[j], theta, alpha, phi);
             fpfh_count_bin(t0, t1, t2, fpfh_bin_angle(theta));
             fpfh_count_bin(a0, a1, a2, fpfh_bin_cosine(alpha));
@@ -156,8 +156,8 @@ __global__ __launch_bounds__(FPFH_SUM_BLOCK) void fpfh_sum_kernel(FpfhSumArgs a)
 
 hipError_t fpfh_spfh(const NnGridView& g, const FpfhSpfhArgs& a, int fma, hipStream_t s)
 {
-    if (a.n < 1 || a.k < 1 || a.k > KNN_MAX_K) return hipErrorInvalidValue;
-    knn_dispatch(a.n, a.k, fma, [&](auto list, auto fused, dim3 grid) {
+    if (a.q.n < 1 || a.k < 1 || a.k > KNN_MAX_K) return hipErrorInvalidValue;
+    knn_dispatch(a.q.n, a.k, fma, [&](auto list, auto fused, dim3 grid) {
         hipLaunchKernelGGL((fpfh_spfh_kernel<decltype(list)::value, decltype(fused)::value>), grid, dim3(KNN_BLOCK), 0, s, g, a);
     });
     return hipGetLastError();

@@ -41,10 +41,12 @@ extern "C" int mi_estimate_covariances(mi_ctx* c, const float* cloud_xyz, int n,
     MI_TRY(search_front_index_and_order(c, b.front, clock, who, ppc, &f));
 
     KnnCovariancesArgs a{};
-    a.qx = b.front.qx.p; a.qy = b.front.qy.p; a.qz = b.front.qz.p; a.order = b.front.order.p;
-    a.cx = b.front.cx.p; a.cy = b.front.cy.p; a.cz = b.front.cz.p;
-    a.n = n; a.k = k; a.max_d2 = max_distance_squared;
-    for (int i = 0; i < 3; i++) a.hi[i] = f.bbox[3 + i];
+    const SearchQueries q = search_front_queries(b.front, f);
+    const SearchCloud cl = search_front_cloud(b.front);
+    a.qx = q.x; a.qy = q.y; a.qz = q.z; a.order = q.order;      // (the kernel keeps the fields of its own: kernels.h)
+    a.cx = cl.x; a.cy = cl.y; a.cz = cl.z;
+    a.n = q.n; a.k = k; a.max_d2 = max_distance_squared;
+    for (int i = 0; i < 3; i++) a.hi[i] = q.hi[i];
     a.plane = mode == MI_COV_PLANE ? 1 : 0;
     a.epsilon = a.plane ? (double)epsilon : 0.0;
     a.cov6 = b.out_cov.p; a.count = count ? b.out_count.p : nullptr;
@@ -110,20 +112,19 @@ int gicp_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* bef
     }
     const float ppc = c->tune.knn_points_per_cell > 0.f ? c->tune.knn_points_per_cell : knn_default_points_per_cell(1);   // mi_knn_search's grid for k = 1
     MI_TRY(search_front_index_and_order(c, b.front, clock, who, ppc, f));
-    MI_HIP(gicp_permute_covariances(b.cov_b_in.p, b.front.order.p, n, b.cov_b.p, c->stream));
+    *a = GicpStepArgs{};
+    a->q = search_front_queries(b.front, *f);
+    a->c = search_front_cloud(b.front);
+    MI_HIP(gicp_permute_covariances(b.cov_b_in.p, a->q.order, n, b.cov_b.p, c->stream));
     MI_TRY(clock.mark(4));
 
     float centre[3];
     for (int i = 0; i < 3; i++) centre[i] = 0.5f * (f->bbox[i] + f->bbox[3 + i]);
     MI_TRY(pose_loop_upload_state(c, b.loop, clock, T, centre, h));
 
-    *a = GicpStepArgs{};
     a->state = b.loop.state.p;
-    a->bx = b.front.qx.p; a->by = b.front.qy.p; a->bz = b.front.qz.p; a->order = b.front.order.p;
-    a->ax = b.front.cx.p; a->ay = b.front.cy.p; a->az = b.front.cz.p;
     a->cov_a = b.cov_a.p; a->cov_b = b.cov_b.p;
-    a->n = n; a->max_d2 = max_d2;
-    for (int i = 0; i < 3; i++) a->hi[i] = f->bbox[3 + i];
+    a->max_d2 = max_d2;
     a->rows = b.loop.rows.p;
     a->idx = want_idx ? b.loop.out_idx.p : nullptr;
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume

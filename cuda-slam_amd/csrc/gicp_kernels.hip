@@ -2,8 +2,7 @@
 // 3 x 3 information matrix per pair where K16 has a normal: the step kernel below writes K16's rows, and everything behind the rows -- the
 // fixed-order sums, the 6 x 6 solve, the pose update, the stop rule, the state block -- is K16's own launch (plane_reduce_solve).
 //
-//   step    one lane per sorted slot of the moving cloud, workgroups of one wave (KNN_BLOCK), no LDS.  Pose, q and match exactly as in
-//           plane_step_kernel (the key of mi_knn_search for q with k = 1, bit for bit).  Then, every operand promoted to fp64 and every
+//   step    the lane's move, match and row are pose_step.hpp's.  Behind the match, every operand promoted to fp64 and every
 //           operation rounded (-ffp-contract=off), with Rf the pose's rotation rounded to fp32 and C_b read at the lane's own slot:
 //             T = Rf C_b              T_ic = (Rf_i0 Cb_0c + Rf_i1 Cb_1c) + Rf_i2 Cb_2c
 //             Sigma = C_a + T Rf^T    S_ij = Ca_ij + ((T_i0 Rf_j0 + T_i1 Rf_j1) + T_i2 Rf_j2), i <= j
@@ -15,7 +14,7 @@
 //             W = M J    W_ib = (P x M_i)_b for b < 3 (M_i: row i of M), M_i(b-3) beyond
 //             H = J^T W  H_ab = (P x W_b)_a for a < 3 (W_b: column b of W), W_(a-3)b beyond; the 21 entries with a <= b
 //             Md_i = (M_i0 d_x + M_i1 d_y) + M_i2 d_z;  g_a = (P x Md)_a for a < 3, Md_(a-3) beyond;  e = (d_x Md_0 + d_y Md_1) + d_z Md_2
-//           The lane keeps P, M and d alive and forms the 29 numbers one at a time into wave_sum, as K16 does; lane 0 writes the row.
+//           The lane keeps P, M and d alive and hands the row its entries of H, g and e one at a time.
 // No float atomics anywhere: the same input gives the same bits on every call.
 #include <hip/hip_runtime.h>
 
@@ -25,6 +24,7 @@
 #include "kernels.h"
 #include "knn_scan.hpp"
 #include "nn_grid.h"
+#include "pose_step.hpp"
 #include "reduce.hpp"
 
 namespace mislam {
@@ -38,22 +38,17 @@ __global__ __launch_bounds__(KNN_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)
     if (st->done != 0) return;
     const int lane = (int)threadIdx.x;
     const int s = blockIdx.x * KNN_BLOCK + lane;
-    const bool live = s < a.n;
+    const bool live = s < a.q.n;
 
     bool pair = false;
     int match = -1;
     // (a lane without a pair holds zeros in M, P and d: its terms are +0)
     double M[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, P[3] = {0.0, 0.0, 0.0}, d[3] = {0.0, 0.0, 0.0}, d2d = 0.0;
     if (live) {
-        const float bx = a.bx[s], by = a.by[s], bz = a.bz[s];
-        const float q[3] = {(((float)st->R[0] * bx + (float)st->R[1] * by) + (float)st->R[2] * bz) + (float)st->t[0],
-                            (((float)st->R[3] * bx + (float)st->R[4] * by) + (float)st->R[5] * bz) + (float)st->t[1],
-                            (((float)st->R[6] * bx + (float)st->R[7] * by) + (float)st->R[8] * bz) + (float)st->t[2]};
-        NearestSink sink{KNN_KEY_EMPTY, a.max_d2};
-        shell_walk<FMA>(g, q, a.hi, sink);
-        const unsigned int d2_bits = (unsigned int)(sink.best >> 32);
-        if (d2_bits < 0x7f800000u) {                                                 // a candidate within the limit, at a finite distance
-            const unsigned int j = (unsigned int)(sink.best & 0xffffffffull);       // (< m: the index the grid build stored)
+        float q[3];
+        pose_move(st, a.q.x[s], a.q.y[s], a.q.z[s], q);
+        unsigned int j, d2_bits;
+        if (nearest_match<FMA>(g, q, a.q.hi, a.max_d2, j, d2_bits)) {
             __asm__ volatile("" ::: "memory");        // the pose is read again here (scalar loads) instead of living in VGPRs through the search
             const float Rf[9] = {(float)st->R[0], (float)st->R[1], (float)st->R[2], (float)st->R[3], (float)st->R[4], (float)st->R[5],
                                  (float)st->R[6], (float)st->R[7], (float)st->R[8]};
@@ -80,39 +75,21 @@ __global__ __launch_bounds__(KNN_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)
                 match = (int)j;
                 M[0] = c00 / det; M[1] = c01 / det; M[2] = c02 / det; M[3] = c11 / det; M[4] = c12 / det; M[5] = c22 / det;
                 const double qx = (double)q[0], qy = (double)q[1], qz = (double)q[2];
-                d[0] = qx - (double)a.ax[j]; d[1] = qy - (double)a.ay[j]; d[2] = qz - (double)a.az[j];
+                d[0] = qx - (double)a.c.x[j]; d[1] = qy - (double)a.c.y[j]; d[2] = qz - (double)a.c.z[j];
                 P[0] = qx - st->c0[0]; P[1] = qy - st->c0[1]; P[2] = qz - st->c0[2];
                 d2d = (double)__uint_as_float(d2_bits);
             }
         }
-        if (a.idx) a.idx[a.order[s]] = match;
+        if (a.idx) a.idx[a.q.order[s]] = match;
     }
 
-    double* __restrict__ row = a.rows + (size_t)blockIdx.x * PLANE_ROW;
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-#pragma unroll
-        for (int j = i; j < 6; j++) {
-            const double v = wave_sum(gicp_h(M, P, i, j));
-            if (lane == 0) row[k] = v;
-            k++;
-        }
-    }
     const double Md0 = (M[0] * d[0] + M[1] * d[1]) + M[2] * d[2];
     const double Md1 = (M[1] * d[0] + M[3] * d[1]) + M[4] * d[2];
     const double Md2 = (M[2] * d[0] + M[4] * d[1]) + M[5] * d[2];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        const double v = wave_sum(i < 3 ? cross_at(P, i, Md0, Md1, Md2) : (i == 3 ? Md0 : (i == 4 ? Md1 : Md2)));
-        if (lane == 0) row[21 + i] = v;
-    }
-    const double ee = wave_sum((d[0] * Md0 + d[1] * Md1) + d[2] * Md2), dd = wave_sum(d2d);
-    const int pairs = __popcll(__ballot(pair));
-    if (lane == 0) {
-        row[27] = ee; row[28] = dd; row[29] = (double)pairs;
-        row[30] = 0.0; row[31] = 0.0;
-    }
+    pose_row_write(
+        lane, a.rows + (size_t)blockIdx.x * PLANE_ROW, [&](int i, int j) { return gicp_h(M, P, i, j); },
+        [&](int i) { return i < 3 ? cross_at(P, i, Md0, Md1, Md2) : (i == 3 ? Md0 : (i == 4 ? Md1 : Md2)); }, (d[0] * Md0 + d[1] * Md1) + d[2] * Md2,
+        d2d, pair ? 1.0 : 0.0);
 }
 
 __global__ __launch_bounds__(256) void gicp_pack_covariances_kernel(const float* __restrict__ cov6, int count, float4* __restrict__ packed, int* __restrict__ bad)
@@ -142,8 +119,8 @@ __global__ __launch_bounds__(256) void gicp_permute_covariances_kernel(const flo
 
 hipError_t gicp_step(const NnGridView& g, const GicpStepArgs& a, int fma, hipStream_t s)
 {
-    if (a.n < 1) return hipErrorInvalidValue;
-    const dim3 grid(plane_row_count(a.n));
+    if (a.q.n < 1) return hipErrorInvalidValue;
+    const dim3 grid(plane_row_count(a.q.n));
     if (fma) hipLaunchKernelGGL(gicp_step_kernel<true>, grid, dim3(KNN_BLOCK), 0, s, g, a);
     else hipLaunchKernelGGL(gicp_step_kernel<false>, grid, dim3(KNN_BLOCK), 0, s, g, a);
     return hipGetLastError();

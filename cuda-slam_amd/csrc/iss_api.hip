@@ -74,19 +74,17 @@ extern "C" int mi_iss_keypoints(mi_ctx* c, const float* cloud_xyz, int n, const 
     const int fma = p->dist_mode == MI_DIST_FMA;
     MI_TRY(search_front_timed_launch(c, b.front, clock, [&] {
         IssSaliencyArgs a{};
-        a.qx = b.front.qx.p; a.qy = b.front.qy.p; a.qz = b.front.qz.p; a.order = b.front.order.p;
-        a.cx = b.front.cx.p; a.cy = b.front.cy.p; a.cz = b.front.cz.p;
-        a.n = n; a.r2 = r2s; a.min_neighbours = min_nb;
+        a.q = search_front_queries(b.front, f);
+        a.c = search_front_cloud(b.front);
+        a.r2 = r2s; a.min_neighbours = min_nb;
         a.gamma_21 = (double)p->gamma_21; a.gamma_32 = (double)p->gamma_32;
-        for (int i = 0; i < 3; i++) a.hi[i] = f.bbox[3 + i];
         a.saliency = b.saliency.p; a.eigenvalues = eigenvalues ? b.eigenvalues.p : nullptr; a.neighbours = neighbours ? b.neighbours.p : nullptr;
         return iss_saliency(f.g, a, fma, c->stream);
     }));
 
     IssSuppressArgs sa{};
-    sa.qx = b.front.qx.p; sa.qy = b.front.qy.p; sa.qz = b.front.qz.p; sa.order = b.front.order.p;
-    sa.n = n; sa.r2 = r2n; sa.min_neighbours = min_nb;
-    for (int i = 0; i < 3; i++) sa.hi[i] = f.bbox[3 + i];
+    sa.q = search_front_queries(b.front, f);
+    sa.r2 = r2n; sa.min_neighbours = min_nb;
     sa.saliency = b.saliency.p; sa.is_keypoint = b.flag.p;
     MI_HIP(iss_suppress(f.g, sa, fma, c->stream));
 

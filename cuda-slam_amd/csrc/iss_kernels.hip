@@ -75,11 +75,11 @@ __global__ __launch_bounds__(KNN_BLOCK) void iss_saliency_kernel(NnGridView g, I
 {
     float q[3];
     int row_out;
-    if (!knn_lane(a.qx, a.qy, a.qz, a.order, a.n, q, row_out)) return;
+    if (!knn_lane(a.q, q, row_out)) return;
 
-    IssScatterSink sink{(unsigned int)row_out, a.r2, a.cx, a.cy, a.cz, (double)q[0], (double)q[1], (double)q[2],
+    IssScatterSink sink{(unsigned int)row_out, a.r2, a.c.x, a.c.y, a.c.z, (double)q[0], (double)q[1], (double)q[2],
                         0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0};
-    shell_walk<FMA>(g, q, a.hi, sink);
+    shell_walk<FMA>(g, q, a.q.hi, sink);
 
     const double c = (double)(sink.found + 1);                                      // the point itself contributes d = 0
     const double mx = sink.sx / c, my = sink.sy / c, mz = sink.sz / c;
@@ -103,12 +103,12 @@ __global__ __launch_bounds__(KNN_BLOCK) void iss_suppress_kernel(NnGridView g, I
 {
     float q[3];
     int row_out;
-    if (!knn_lane(a.qx, a.qy, a.qz, a.order, a.n, q, row_out)) return;
+    if (!knn_lane(a.q, q, row_out)) return;
     const float mine = a.saliency[row_out];
     unsigned char flag = 0;
     if (mine > 0.f) {
         IssDominanceSink sink{(unsigned int)row_out, a.r2, a.saliency, mine, 0, false};
-        shell_walk<FMA>(g, q, a.hi, sink);
+        shell_walk<FMA>(g, q, a.q.hi, sink);
         flag = !sink.dominated && sink.found >= a.min_neighbours ? 1 : 0;
     }
     a.is_keypoint[row_out] = flag;
@@ -118,8 +118,8 @@ __global__ __launch_bounds__(KNN_BLOCK) void iss_suppress_kernel(NnGridView g, I
 
 hipError_t iss_saliency(const NnGridView& g, const IssSaliencyArgs& a, int fma, hipStream_t s)
 {
-    if (a.n < 1 || a.min_neighbours < 1 || !(a.r2 >= 0.f) || !a.saliency || !a.cx || !a.cy || !a.cz) return hipErrorInvalidValue;
-    const dim3 grid((a.n + KNN_BLOCK - 1) / KNN_BLOCK), block(KNN_BLOCK);
+    if (a.q.n < 1 || a.min_neighbours < 1 || !(a.r2 >= 0.f) || !a.saliency || !a.c.x || !a.c.y || !a.c.z) return hipErrorInvalidValue;
+    const dim3 grid((a.q.n + KNN_BLOCK - 1) / KNN_BLOCK), block(KNN_BLOCK);
     if (fma) hipLaunchKernelGGL((iss_saliency_kernel<true>), grid, block, 0, s, g, a);
     else hipLaunchKernelGGL((iss_saliency_kernel<false>), grid, block, 0, s, g, a);
     return hipGetLastError();
@@ -127,8 +127,8 @@ hipError_t iss_saliency(const NnGridView& g, const IssSaliencyArgs& a, int fma, 
 
 hipError_t iss_suppress(const NnGridView& g, const IssSuppressArgs& a, int fma, hipStream_t s)
 {
-    if (a.n < 1 || a.min_neighbours < 1 || !(a.r2 >= 0.f) || !a.saliency || !a.is_keypoint) return hipErrorInvalidValue;
-    const dim3 grid((a.n + KNN_BLOCK - 1) / KNN_BLOCK), block(KNN_BLOCK);
+    if (a.q.n < 1 || a.min_neighbours < 1 || !(a.r2 >= 0.f) || !a.saliency || !a.is_keypoint) return hipErrorInvalidValue;
+    const dim3 grid((a.q.n + KNN_BLOCK - 1) / KNN_BLOCK), block(KNN_BLOCK);
     if (fma) hipLaunchKernelGGL((iss_suppress_kernel<true>), grid, block, 0, s, g, a);
     else hipLaunchKernelGGL((iss_suppress_kernel<false>), grid, block, 0, s, g, a);
     return hipGetLastError();

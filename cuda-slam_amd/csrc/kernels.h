@@ -248,13 +248,25 @@ struct KnnState {
 };
 
 struct NnGridView;           // nn_grid.h
-struct KnnSearchArgs {
-    const float *qx, *qy, *qz;       // the queries along their curve order, SoA, n entries
+// What every kernel that walks a cloud's cell grid is handed beside the grid (search_front_queries, search_front_cloud: search_front.hip).
+// In self mode the queries are the cloud's own points, and order[s] is also the one candidate slot s skips, by index.
+struct SearchQueries {
+    const float *x, *y, *z;          // the queries along their curve order, SoA, n entries
     const int* order;                // sorted slot -> the caller's query index (the row the slot's answer goes to)
+    int n;
+    float hi[3];                     // upper corner of the cloud's bounding box (the lower one is the grid's origin)
+};
+struct SearchCloud {
+    const float *x, *y, *z;          // the cloud in the caller's order, SoA: what a neighbour's or a match's index points into
+};
+
+struct KnnSearchArgs {
+    const float *qx, *qy, *qz;       // SearchQueries' fields, laid out as before the view: with it inside, the search stage of
+    const int* order;                // mi_knn_search measured 1.5 to 3 % slower (behind K33)
     int n, k;
     int self;                        // queries are the cloud's own points: candidate order[s] is skipped, by index
     float max_d2;                    // candidates with d2 > this do not exist (+inf: no limit)
-    float hi[3];                     // upper corner of the cloud's bounding box (the lower one is the grid's origin)
+    float hi[3];
     int* idx;                        // n * k
     float* d2;                       // n * k
     int* count;                      // n
@@ -274,12 +286,10 @@ float radius_points_per_cell(const float bbox[6], int n, float radius, float cel
 // still in registers, the neighbourhood's fp64 covariance and its smallest eigenvector (eig3.hpp)
 // ---------------------------------------------------------------------------------------------------------------
 struct KnnNormalsArgs {
-    const float *qx, *qy, *qz;       // the cloud along its curve order, SoA, n entries
-    const int* order;                // sorted slot -> the caller's index (the row the slot's answer goes to, and the candidate it skips)
-    const float *cx, *cy, *cz;       // the cloud in the caller's order, SoA: what the neighbours' indices point into
-    int n, k;
+    SearchQueries q;                 // the cloud itself (self mode)
+    SearchCloud c;
+    int k;
     float max_d2;                    // candidates with d2 > this do not exist (+inf: no limit)
-    float hi[3];                     // upper corner of the cloud's bounding box (the lower one is the grid's origin)
     int oriented;                    // view holds a viewpoint: normals are turned towards it
     double view[3];
     float* normals;                  // n * 3, AoS, the caller's order
@@ -289,8 +299,8 @@ struct KnnNormalsArgs {
 hipError_t knn_normals(const NnGridView& g, const KnnNormalsArgs& a, int fma, hipStream_t s);
 // the same search and moments with the covariance as the output (mi_estimate_covariances; K17's inputs)
 struct KnnCovariancesArgs {
-    const float *qx, *qy, *qz;       // as KnnNormalsArgs
-    const int* order;
+    const float *qx, *qy, *qz;       // SearchQueries' and SearchCloud's fields, laid out as before the two views: through them
+    const int* order;                // knn_covariances_kernel<32> takes one more VGPR
     const float *cx, *cy, *cz;
     int n, k;
     float max_d2;
@@ -318,22 +328,17 @@ struct OutlierState {
 };
 
 struct KnnOutlierArgs {
-    const float *qx, *qy, *qz;       // the cloud along its curve order, SoA, n entries
-    const int* order;                // sorted slot -> the caller's index (the row the slot's answer goes to, and the candidate it skips)
-    int n, k;
-    float hi[3];                     // upper corner of the cloud's bounding box (the lower one is the grid's origin)
+    SearchQueries q;                 // the cloud itself (self mode)
+    int k;
     double* score;                   // n: (sum of sqrt((double)d2) over the filled slots, nearest first) / count, 0 where count is 0
     int* count;                      // n, may be null
 };
 hipError_t knn_outlier_score(const NnGridView& g, const KnnOutlierArgs& a, int fma, hipStream_t s);
 
 struct RadiusCountArgs {
-    const float *qx, *qy, *qz;       // as above
-    const int* order;
-    int n;
+    SearchQueries q;                 // as above
     float r2;                        // a point j != row (by index) with d2 <= r2 counts
     int min_neighbours;              // early: a lane leaves its loops once it has counted this many
-    float hi[3];
     int* count;                      // n: the number of neighbours, or (early) min(that, some value >= min_neighbours)
 };
 hipError_t radius_count(const NnGridView& g, const RadiusCountArgs& a, int fma, int early, hipStream_t s);
@@ -370,13 +375,10 @@ constexpr int MI_STOP_DEGENERATE_ = 7;       // mirror of MI_STOP_DEGENERATE (mi
 
 struct PlaneStepArgs {
     const PlaneState* state;         // the pose to linearise at (rounded to fp32 by every lane), the centre, done
-    const float *bx, *by, *bz;       // the moving cloud along its curve order, SoA, n entries
-    const int* order;                // sorted slot -> the caller's moving index
-    const float *ax, *ay, *az;       // the fixed cloud in the caller's order, SoA: what a match's index points into
+    SearchQueries q;                 // the moving cloud
+    SearchCloud c;                   // the fixed cloud
     const float4* normals;           // the fixed cloud's normals in the caller's order (w unused)
-    int n;
     float max_d2;                    // a match with d2 > this is no pair (+inf: no limit)
-    float hi[3];                     // upper corner of the fixed cloud's bounding box (the lower one is the grid's origin)
     double* rows;                    // plane_row_count(n) x PLANE_ROW
     int* idx;                        // may be null; n, the caller's order: the matched fixed index of a pair, -1 otherwise
 };
@@ -398,14 +400,11 @@ hipError_t plane_reduce_solve(PlaneState* state, const double* rows, int nrows, 
 // ---------------------------------------------------------------------------------------------------------------
 struct GicpStepArgs {
     const PlaneState* state;         // the pose to linearise at (rounded to fp32 by every lane), the centre, done
-    const float *bx, *by, *bz;       // the moving cloud along its curve order, SoA, n entries
-    const int* order;                // sorted slot -> the caller's moving index
-    const float *ax, *ay, *az;       // the fixed cloud in the caller's order, SoA: what a match's index points into
+    SearchQueries q;                 // the moving cloud
+    SearchCloud c;                   // the fixed cloud
     const float4* cov_a;             // the fixed cloud's covariances in the caller's order, two float4 each: (xx, xy, xz, 0), (yy, yz, zz, 0)
     const float4* cov_b;             // the moving cloud's along its curve order, the same layout: read at the lane's own slot
-    int n;
     float max_d2;                    // a match with d2 > this is no pair (+inf: no limit)
-    float hi[3];                     // upper corner of the fixed cloud's bounding box (the lower one is the grid's origin)
     double* rows;                    // plane_row_count(n) x PLANE_ROW
     int* idx;                        // may be null; n, the caller's order: the matched fixed index of a pair, -1 otherwise
 };
@@ -425,13 +424,11 @@ constexpr int FPFH_WORDS = 9;                // 32-bit words of a point's packed
 constexpr int FPFH_SUM_POINTS = 64;          // points per workgroup of K19 ...
 constexpr int FPFH_SUM_BLOCK = 3 * FPFH_SUM_POINTS;   // ... at three lanes a point, one per feature
 struct FpfhSpfhArgs {
-    const float *qx, *qy, *qz;       // the cloud along its curve order, SoA, n entries
-    const int* order;                // sorted slot -> the caller's index (the row the slot's answer goes to, and the candidate it skips)
-    const float *cx, *cy, *cz;       // the cloud in the caller's order, SoA: what the neighbours' indices point into
-    const float *nx, *ny, *nz;       // the normals, the same way
-    int n, k;
+    SearchQueries q;                 // the cloud itself (self mode)
+    SearchCloud c;
+    const float *nx, *ny, *nz;       // the normals, as the cloud: SoA, the caller's order
+    int k;
     float max_d2;                    // candidates with d2 > this do not exist (+inf: no limit)
-    float hi[3];                     // upper corner of the cloud's bounding box (the lower one is the grid's origin)
     unsigned long long* keys;        // n * k, the caller's order: row i of mi_knn_search as keys, KNN_KEY_EMPTY behind the filled slots
     unsigned int* packed;            // n * FPFH_WORDS, the caller's order
     int* count;                      // n, may be null
@@ -591,14 +588,11 @@ hipError_t ndt_step(const NdtStepArgs& a, int neighbourhood, hipStream_t s);    
 // compacted by K15's outlier_compact.
 // ---------------------------------------------------------------------------------------------------------------
 struct IssSaliencyArgs {
-    const float *qx, *qy, *qz;       // the cloud along its curve order, SoA, n entries
-    const int* order;                // sorted slot -> the caller's index (the row the slot's answer goes to, and the candidate it skips)
-    const float *cx, *cy, *cz;       // the cloud in the caller's order, SoA: what the neighbours' indices point into
-    int n;
+    SearchQueries q;                 // the cloud itself (self mode)
+    SearchCloud c;
     float r2;                        // a point j != row (by index) with d2 <= r2 is in the salient ball
     int min_neighbours;
     double gamma_21, gamma_32;       // the caller's fp32 values, promoted
-    float hi[3];                     // upper corner of the cloud's bounding box (the lower one is the grid's origin)
     float* saliency;                 // n, the caller's order: max((float)lambda0, 0) where the gate holds, +0 elsewhere
     float* eigenvalues;              // n * 3, ascending, may be null
     int* neighbours;                 // n, may be null
@@ -606,12 +600,9 @@ struct IssSaliencyArgs {
 hipError_t iss_saliency(const NnGridView& g, const IssSaliencyArgs& a, int fma, hipStream_t s);
 
 struct IssSuppressArgs {
-    const float *qx, *qy, *qz;       // as above
-    const int* order;
-    int n;
+    SearchQueries q;                 // as above
     float r2;                        // the non-max ball
     int min_neighbours;
-    float hi[3];
     const float* saliency;           // n, the caller's order (K32's)
     unsigned char* is_keypoint;      // n, the caller's order: every row is written
 };

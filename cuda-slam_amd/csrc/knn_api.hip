@@ -38,9 +38,10 @@ extern "C" int mi_knn_search(mi_ctx* c, const float* query_xyz, int n, const flo
     MI_TRY(search_front_index_and_order(c, b.front, clock, "mi_knn_search", ppc, &f));
 
     KnnSearchArgs a{};
-    a.qx = b.front.qx.p; a.qy = b.front.qy.p; a.qz = b.front.qz.p; a.order = b.front.order.p;
-    a.n = n; a.k = k; a.self = self ? 1 : 0; a.max_d2 = max_distance_squared;
-    for (int i = 0; i < 3; i++) a.hi[i] = f.bbox[3 + i];
+    const SearchQueries q = search_front_queries(b.front, f);
+    a.qx = q.x; a.qy = q.y; a.qz = q.z; a.order = q.order;      // (the kernel keeps the fields of its own: kernels.h)
+    a.n = q.n; a.k = k; a.self = self ? 1 : 0; a.max_d2 = max_distance_squared;
+    for (int i = 0; i < 3; i++) a.hi[i] = q.hi[i];
     a.idx = b.out_idx.p; a.d2 = d2 ? b.out_d2.p : nullptr; a.count = count ? b.out_count.p : nullptr;
     // host-side shape checks before the hand-written kernel runs: every array it indexes is as long as the launch assumes
     if (!search_front_fits(b.front, f) || b.out_idx.cap < rows || (d2 && b.out_d2.cap < rows) || (count && b.out_count.cap < np)) {

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_search_kernel(NnGridView g, Knn
 {
     float q[3];
     int row_out;
-    if (!knn_lane(a.qx, a.qy, a.qz, a.order, a.n, q, row_out)) return;
+    if (!knn_lane(SearchQueries{a.qx, a.qy, a.qz, a.order, a.n, {}}, q, row_out)) return;      // (KnnSearchArgs keeps its own fields: kernels.h)
     const unsigned int skip = a.self ? (unsigned int)row_out : 0xffffffffu;      // (no cloud point has index 2^32 - 1)
     const int k = a.k;
 

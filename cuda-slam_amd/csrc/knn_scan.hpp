@@ -31,12 +31,12 @@ __device__ __forceinline__ void knn_insert(unsigned long long (&l)[K], unsigned 
 
 // The lane of a search kernel: its sorted slot's query into q and the caller's row that slot answers for (in self mode also the one candidate
 // it skips) into row_out; false for a lane beyond the n queries.  (knn_normals_kernel keeps these lines of its own: see there.)
-__device__ __forceinline__ bool knn_lane(const float* qx, const float* qy, const float* qz, const int* order, int n, float (&q)[3], int& row_out)
+__device__ __forceinline__ bool knn_lane(const SearchQueries& v, float (&q)[3], int& row_out)
 {
     const int s = blockIdx.x * KNN_BLOCK + (int)threadIdx.x;
-    if (s >= n) return false;
-    q[0] = qx[s]; q[1] = qy[s]; q[2] = qz[s];
-    row_out = order[s];
+    if (s >= v.n) return false;
+    q[0] = v.x[s]; q[1] = v.y[s]; q[2] = v.z[s];
+    row_out = v.order[s];
     return true;
 }
 

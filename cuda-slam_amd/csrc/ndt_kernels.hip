@@ -11,11 +11,10 @@
 //   K30 table     open addressing, linear probing, capacity a power of two >= 2 nv: one lane per listed voxel with a distribution claims
 //                 the first free slot from its hash by a 64-bit compare-and-swap.  Keys are unique (the list is strictly ascending), so
 //                 a lookup finds the same row whatever order the lanes arrived in.
-//   K31 step      one lane per sorted slot of the moving cloud, workgroups of one wave (KNN_BLOCK), no LDS.  Pose and q exactly as in
-//                 plane_step_kernel.  The voxel of q by voxel_axis (mi_voxel_index's arithmetic), then per offset of the neighbourhood a
+//   K31 step      the lane's move and row are pose_step.hpp's.  The voxel of q by voxel_axis (mi_voxel_index's arithmetic), then per offset of the neighbourhood a
 //                 box test on the voxel index, the key, the probe and -- on a hit -- ndt_term.hpp's term, folded into ten running fp64
-//                 numbers: A = sum w M (6), b = sum w Md (3), E = sum e.  With P = q - c0 the lane then forms K17's 21 + 6 entries from A and
-//                 b (gicp_terms.hpp) one at a time into wave_sum, and lane 0 writes K16's row: everything behind it is plane_reduce_solve.
+//                 numbers: A = sum w M (6), b = sum w Md (3), E = sum e.  With P = q - c0 the row's entries are K17's 21 + 6 from A and
+//                 b (gicp_terms.hpp), and everything behind the row is plane_reduce_solve.
 //                 Per term: 3 subtractions, 9 + 3 products and 6 + 2 additions for Md and m, one exp, 1 + 9 products and 10 additions for
 //                 the fold -- about 45 fp64 operations and one exp, against the ~420 of K17's 27 entries, which are paid once per point.
 // No float atomics anywhere: the same input gives the same bits on every call.
@@ -25,6 +24,7 @@
 #include "gicp_terms.hpp"
 #include "kernels.h"
 #include "ndt_term.hpp"
+#include "pose_step.hpp"
 #include "reduce.hpp"
 
 namespace mislam {
@@ -267,10 +267,8 @@ __global__ __launch_bounds__(KNN_BLOCK) void ndt_step_kernel(NdtStepArgs a)
     ndt_point_clear(&acc);
     double P[3] = {0.0, 0.0, 0.0};
     if (live) {
-        const float bx = a.bx[s], by = a.by[s], bz = a.bz[s];
-        const float q[3] = {(((float)st->R[0] * bx + (float)st->R[1] * by) + (float)st->R[2] * bz) + (float)st->t[0],
-                            (((float)st->R[3] * bx + (float)st->R[4] * by) + (float)st->R[5] * bz) + (float)st->t[1],
-                            (((float)st->R[6] * bx + (float)st->R[7] * by) + (float)st->R[8] * bz) + (float)st->t[2]};
+        float q[3];
+        pose_move(st, a.bx[s], a.by[s], a.bz[s], q);
         int c[3] = {0, 0, 0}, own = -1;
         bool inside = voxel_axis(q[0], a.origin[0], a.voxel, &c[0]);             // (false: mi_voxel_index refuses q, NaN and the infinities included)
         inside = voxel_axis(q[1], a.origin[1], a.voxel, &c[1]) && inside;
@@ -300,28 +298,10 @@ __global__ __launch_bounds__(KNN_BLOCK) void ndt_step_kernel(NdtStepArgs a)
         if (a.terms) a.terms[a.order[s]] = (unsigned char)acc.terms;
     }
 
-    double* __restrict__ row = a.rows + (size_t)blockIdx.x * PLANE_ROW;
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-#pragma unroll
-        for (int j = i; j < 6; j++) {
-            const double v = wave_sum(gicp_h(acc.A, P, i, j));
-            if (lane == 0) row[k] = v;
-            k++;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        const double v = wave_sum(i < 3 ? cross_at(P, i, acc.b[0], acc.b[1], acc.b[2]) : (i == 3 ? acc.b[0] : (i == 4 ? acc.b[1] : acc.b[2])));
-        if (lane == 0) row[21 + i] = v;
-    }
-    const double ee = wave_sum(acc.E), nt = wave_sum((double)acc.terms);
-    const int points = __popcll(__ballot(acc.terms > 0));
-    if (lane == 0) {
-        row[27] = ee; row[28] = (double)points; row[29] = nt;
-        row[30] = 0.0; row[31] = 0.0;
-    }
+    pose_row_write(
+        lane, a.rows + (size_t)blockIdx.x * PLANE_ROW, [&](int i, int j) { return gicp_h(acc.A, P, i, j); },
+        [&](int i) { return i < 3 ? cross_at(P, i, acc.b[0], acc.b[1], acc.b[2]) : (i == 3 ? acc.b[0] : (i == 4 ? acc.b[1] : acc.b[2])); }, acc.E,
+        acc.terms > 0 ? 1.0 : 0.0, (double)acc.terms);
 }
 
 }  // namespace

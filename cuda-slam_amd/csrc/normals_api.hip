@@ -40,10 +40,9 @@ extern "C" int mi_estimate_normals(mi_ctx* c, const float* cloud_xyz, int n, int
     MI_TRY(search_front_index_and_order(c, b.front, clock, "mi_estimate_normals", ppc, &f));
 
     KnnNormalsArgs a{};
-    a.qx = b.front.qx.p; a.qy = b.front.qy.p; a.qz = b.front.qz.p; a.order = b.front.order.p;
-    a.cx = b.front.cx.p; a.cy = b.front.cy.p; a.cz = b.front.cz.p;
-    a.n = n; a.k = k; a.max_d2 = max_distance_squared;
-    for (int i = 0; i < 3; i++) a.hi[i] = f.bbox[3 + i];
+    a.q = search_front_queries(b.front, f);
+    a.c = search_front_cloud(b.front);
+    a.k = k; a.max_d2 = max_distance_squared;
     a.oriented = viewpoint3 ? 1 : 0;
     for (int i = 0; i < 3; i++) a.view[i] = viewpoint3 ? (double)viewpoint3[i] : 0.0;
     a.normals = b.out_normals.p; a.curvature = curvature ? b.out_curvature.p : nullptr; a.count = count ? b.out_count.p : nullptr;

@@ -78,12 +78,12 @@ template <int K, bool FMA>
 __global__ __launch_bounds__(KNN_BLOCK) void knn_normals_kernel(NnGridView g, KnnNormalsArgs a)
 {
     const int s = blockIdx.x * KNN_BLOCK + (int)threadIdx.x;
-    if (s >= a.n) return;
-    const float q[3] = {a.qx[s], a.qy[s], a.qz[s]};     // (not knn_lane: through it this kernel takes one more SGPR at K = 8)
-    const int row_out = a.order[s];
+    if (s >= a.q.n) return;
+    const float q[3] = {a.q.x[s], a.q.y[s], a.q.z[s]};     // (not knn_lane: through it this kernel takes one more SGPR at K = 8)
+    const int row_out = a.q.order[s];
 
     double cov[6];
-    const int found = knn_neighbourhood_covariance<K, FMA>(g, q, a.hi, row_out, a.k, a.max_d2, a.cx, a.cy, a.cz, cov);
+    const int found = knn_neighbourhood_covariance<K, FMA>(g, q, a.q.hi, row_out, a.k, a.max_d2, a.c.x, a.c.y, a.c.z, cov);
 
     double nx = 0.0, ny = 0.0, nz = 0.0, curv = 0.0;
     if (found >= 2) {
@@ -139,8 +139,8 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_covariances_kernel(NnGridView g
 
 hipError_t knn_normals(const NnGridView& g, const KnnNormalsArgs& a, int fma, hipStream_t s)
 {
-    if (a.n < 1 || a.k < 2 || a.k > KNN_MAX_K) return hipErrorInvalidValue;
-    knn_dispatch(a.n, a.k, fma, [&](auto list, auto fused, dim3 grid) {
+    if (a.q.n < 1 || a.k < 2 || a.k > KNN_MAX_K) return hipErrorInvalidValue;
+    knn_dispatch(a.q.n, a.k, fma, [&](auto list, auto fused, dim3 grid) {
         hipLaunchKernelGGL((knn_normals_kernel<decltype(list)::value, decltype(fused)::value>), grid, dim3(KNN_BLOCK), 0, s, g, a);
     });
     return hipGetLastError();

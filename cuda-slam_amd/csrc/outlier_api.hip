@@ -77,16 +77,14 @@ extern "C" int mi_remove_outliers(mi_ctx* c, const float* cloud_xyz, int n, cons
     MI_TRY(search_front_timed_launch(c, b.front, clock, [&] {
         if (statistical) {
             KnnOutlierArgs a{};
-            a.qx = b.front.qx.p; a.qy = b.front.qy.p; a.qz = b.front.qz.p; a.order = b.front.order.p;
-            a.n = n; a.k = k;
-            for (int i = 0; i < 3; i++) a.hi[i] = f.bbox[3 + i];
+            a.q = search_front_queries(b.front, f);
+            a.k = k;
             a.score = b.score.p; a.count = neighbours ? b.count.p : nullptr;
             return knn_outlier_score(f.g, a, fma, c->stream);
         }
         RadiusCountArgs a{};
-        a.qx = b.front.qx.p; a.qy = b.front.qy.p; a.qz = b.front.qz.p; a.order = b.front.order.p;
-        a.n = n; a.r2 = r2; a.min_neighbours = min_nb;
-        for (int i = 0; i < 3; i++) a.hi[i] = f.bbox[3 + i];
+        a.q = search_front_queries(b.front, f);
+        a.r2 = r2; a.min_neighbours = min_nb;
         a.count = b.count.p;
         return radius_count(f.g, a, fma, neighbours ? 0 : 1, c->stream);
     }));

@@ -28,13 +28,13 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_outlier_score_kernel(NnGridView
 {
     float q[3];
     int row_out;
-    if (!knn_lane(a.qx, a.qy, a.qz, a.order, a.n, q, row_out)) return;
+    if (!knn_lane(a.q, q, row_out)) return;
     const int k = a.k;
 
     unsigned long long l[K];
 #pragma unroll
     for (int i = 0; i < K; i++) l[i] = i < K - k ? 0ull : KNN_KEY_EMPTY;
-    knn_scan<K, FMA>(g, q, a.hi, (unsigned int)row_out, k, __builtin_inff(), l);
+    knn_scan<K, FMA>(g, q, a.q.hi, (unsigned int)row_out, k, __builtin_inff(), l);
 
     double sum = 0.0;
     int found = 0;
@@ -55,8 +55,8 @@ __global__ __launch_bounds__(KNN_BLOCK) void radius_count_kernel(NnGridView g, R
 {
     float q[3];
     int row_out;
-    if (!knn_lane(a.qx, a.qy, a.qz, a.order, a.n, q, row_out)) return;
-    a.count[row_out] = radius_scan<FMA, EARLY>(g, q, a.hi, (unsigned int)row_out, a.r2, a.min_neighbours);
+    if (!knn_lane(a.q, q, row_out)) return;
+    a.count[row_out] = radius_scan<FMA, EARLY>(g, q, a.q.hi, (unsigned int)row_out, a.r2, a.min_neighbours);
 }
 
 // ---- statistics: DEV false: the sum of the scores; true: the sum of their squared deviations about state->mean
@@ -193,8 +193,8 @@ __global__ __launch_bounds__(256) void outlier_scatter_kernel(OutlierCompactArgs
 
 hipError_t knn_outlier_score(const NnGridView& g, const KnnOutlierArgs& a, int fma, hipStream_t s)
 {
-    if (a.n < 1 || a.k < 1 || a.k > KNN_MAX_K || !a.score) return hipErrorInvalidValue;
-    knn_dispatch(a.n, a.k, fma, [&](auto list, auto fused, dim3 grid) {
+    if (a.q.n < 1 || a.k < 1 || a.k > KNN_MAX_K || !a.score) return hipErrorInvalidValue;
+    knn_dispatch(a.q.n, a.k, fma, [&](auto list, auto fused, dim3 grid) {
         hipLaunchKernelGGL((knn_outlier_score_kernel<decltype(list)::value, decltype(fused)::value>), grid, dim3(KNN_BLOCK), 0, s, g, a);
     });
     return hipGetLastError();
@@ -202,8 +202,8 @@ hipError_t knn_outlier_score(const NnGridView& g, const KnnOutlierArgs& a, int f
 
 hipError_t radius_count(const NnGridView& g, const RadiusCountArgs& a, int fma, int early, hipStream_t s)
 {
-    if (a.n < 1 || a.min_neighbours < 1 || !(a.r2 >= 0.f) || !a.count) return hipErrorInvalidValue;
-    const dim3 grid((a.n + KNN_BLOCK - 1) / KNN_BLOCK), block(KNN_BLOCK);
+    if (a.q.n < 1 || a.min_neighbours < 1 || !(a.r2 >= 0.f) || !a.count) return hipErrorInvalidValue;
+    const dim3 grid((a.q.n + KNN_BLOCK - 1) / KNN_BLOCK), block(KNN_BLOCK);
     if (fma && early) hipLaunchKernelGGL((radius_count_kernel<true, true>), grid, block, 0, s, g, a);
     else if (fma) hipLaunchKernelGGL((radius_count_kernel<true, false>), grid, block, 0, s, g, a);
     else if (early) hipLaunchKernelGGL((radius_count_kernel<false, true>), grid, block, 0, s, g, a);

@@ -49,19 +49,9 @@ int plane_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* be
     MI_TRY(pose_loop_reserve(b.loop, n, want_idx));
     MI_TRY(clock.mark(0));
 
-    // the normals go first through the staging buffer and the check's partials, which the front end then takes over (one stream: in order)
-    MI_TRY(host_to_device(c, b.front.staging.p, normals_xyz, sizeof(float) * 3 * mp));
-    MI_HIP(aos_to_soa(b.front.staging.p, m, m, b.nx.p, b.ny.p, b.nz.p, b.normals.p, c->stream));
-    MI_HIP(knn_check_inputs(b.nx.p, b.ny.p, b.nz.p, m, nullptr, nullptr, nullptr, 0, b.front.range_lo_hi.p, b.front.range_bad.p, b.nstate.p, c->stream));
+    MI_TRY(search_front_enqueue_normals(c, b.front, normals_xyz, m, b.nx.p, b.ny.p, b.nz.p, b.normals.p, b.nstate.p));
     MI_TRY(search_front_upload_and_check(c, b.front, clock, who, after_xyz, m, before_xyz, n, f, "after_xyz", "before_xyz"));
-    KnnState ns;
-    MI_HIP(hipMemcpyAsync(&ns, b.nstate.p, sizeof ns, hipMemcpyDeviceToHost, c->stream));
-    MI_HIP(hipStreamSynchronize(c->stream));
-    MI_TRY(clock.mark(2));
-    if (ns.bad_cloud != KNN_NO_POINT) {
-        set_error("%s: after_normals_xyz normal %d has a non-finite component or one above 1e18 in magnitude", who, ns.bad_cloud);
-        return MI_ERR_INVALID_ARG;
-    }
+    MI_TRY(search_front_refuse_normals(c, clock, who, "after_normals_xyz", b.nstate.p));
     const float ppc = c->tune.knn_points_per_cell > 0.f ? c->tune.knn_points_per_cell : knn_default_points_per_cell(1);   // mi_knn_search's grid for k = 1
     MI_TRY(search_front_index_and_order(c, b.front, clock, who, ppc, f));
 
@@ -71,11 +61,10 @@ int plane_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* be
 
     *a = PlaneStepArgs{};
     a->state = b.loop.state.p;
-    a->bx = b.front.qx.p; a->by = b.front.qy.p; a->bz = b.front.qz.p; a->order = b.front.order.p;
-    a->ax = b.front.cx.p; a->ay = b.front.cy.p; a->az = b.front.cz.p;
+    a->q = search_front_queries(b.front, *f);
+    a->c = search_front_cloud(b.front);
     a->normals = b.normals.p;
-    a->n = n; a->max_d2 = max_d2;
-    for (int i = 0; i < 3; i++) a->hi[i] = f->bbox[3 + i];
+    a->max_d2 = max_d2;
     a->rows = b.loop.rows.p;
     a->idx = want_idx ? b.loop.out_idx.p : nullptr;
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume

@@ -1,14 +1,9 @@
 // K16 -- point-to-plane ICP on the device (mi_icp_plane_register, mi_plane_system; driver: plane_api.hip).  An iteration is two launches
 // (three beyond PLANE_ONE_STAGE_ROWS rows), and nothing in it goes through the host:
 //
-//   step    one lane per sorted slot of the moving cloud, workgroups of one wave (KNN_BLOCK), no LDS.  The lane rounds the state block's
-//           fp64 pose to fp32 and moves its point with it in the stated order, q = ((R0 b_x + R1 b_y) + R2 b_z) + t, every operation
-//           rounded (the build has -ffp-contract=off).  Its match is K13's search with a single key (shell_walk with NearestSink,
-//           knn_scan.hpp): the key mi_knn_search gives for q with k = 1, bit for bit.  A lane without a candidate within the limit, or
-//           whose matched normal is exactly (0, 0, 0), has no pair.  The pair's numbers in fp64: r = n . (q - a), J = [(q - c0) x n, n].
-//           The 21 products J_i J_j, the 6 products J_i r, r^2 and d2 are formed one at a time and summed over the wave (wave_sum,
-//           reduce.hpp: a fixed tree), so a lane keeps J and r alive and no accumulator; lane 0 writes the row, 32 doubles per 64 slots:
-//           [0, 21) sum J J^T, [21, 27) sum J r, [27] sum r^2, [28] sum d2, [29] pairs, [30, 32) 0.
+//   step    the lane's move, match and row are pose_step.hpp's.  A lane without a candidate within the limit, or whose matched normal is
+//           exactly (0, 0, 0), has no pair.  The pair's numbers in fp64: r = n . (q - a), J = [(q - c0) x n, n]; the row's entries are
+//           the products J_i J_j, J_i r and r^2, so a lane keeps J and r alive (the row's layout: pose_block.hpp).
 //   sums    the rows are added in a fixed order that depends on their number alone (reduce_partials, reduce.hpp): up to
 //           PLANE_ONE_STAGE_ROWS rows by the solve's own workgroup; beyond, PLANE_PARTS workgroups add a slab of rows each first.
 //   solve   lane 0 of one workgroup: the stop on too few pairs, plane_solve6 / plane_rodrigues / plane_compose (plane_solve.hpp), the
@@ -21,6 +16,7 @@
 #include "knn_scan.hpp"
 #include "nn_grid.h"
 #include "plane_solve.hpp"
+#include "pose_step.hpp"
 #include "reduce.hpp"
 
 namespace mislam {
@@ -34,28 +30,23 @@ __global__ __launch_bounds__(KNN_BLOCK) void plane_step_kernel(NnGridView g, Pla
     if (st->done != 0) return;
     const int lane = (int)threadIdx.x;
     const int s = blockIdx.x * KNN_BLOCK + lane;
-    const bool live = s < a.n;
+    const bool live = s < a.q.n;
 
     bool pair = false;
     int match = -1;
     double J0 = 0.0, J1 = 0.0, J2 = 0.0, J3 = 0.0, J4 = 0.0, J5 = 0.0, r = 0.0, d2d = 0.0;
     if (live) {
-        const float bx = a.bx[s], by = a.by[s], bz = a.bz[s];
-        const float q[3] = {(((float)st->R[0] * bx + (float)st->R[1] * by) + (float)st->R[2] * bz) + (float)st->t[0],
-                            (((float)st->R[3] * bx + (float)st->R[4] * by) + (float)st->R[5] * bz) + (float)st->t[1],
-                            (((float)st->R[6] * bx + (float)st->R[7] * by) + (float)st->R[8] * bz) + (float)st->t[2]};
-        NearestSink sink{KNN_KEY_EMPTY, a.max_d2};
-        shell_walk<FMA>(g, q, a.hi, sink);
-        const unsigned int d2_bits = (unsigned int)(sink.best >> 32);
-        if (d2_bits < 0x7f800000u) {                                                 // a candidate within the limit, at a finite distance
-            const unsigned int j = (unsigned int)(sink.best & 0xffffffffull);       // (< m: the index the grid build stored)
+        float q[3];
+        pose_move(st, a.q.x[s], a.q.y[s], a.q.z[s], q);
+        unsigned int j, d2_bits;
+        if (nearest_match<FMA>(g, q, a.q.hi, a.max_d2, j, d2_bits)) {
             const float4 nf = a.normals[j];
             if (nf.x != 0.f || nf.y != 0.f || nf.z != 0.f) {
                 pair = true;
                 match = (int)j;
                 const double nx = (double)nf.x, ny = (double)nf.y, nz = (double)nf.z;
                 const double qx = (double)q[0], qy = (double)q[1], qz = (double)q[2];
-                const double dx = qx - (double)a.ax[j], dy = qy - (double)a.ay[j], dz = qz - (double)a.az[j];
+                const double dx = qx - (double)a.c.x[j], dy = qy - (double)a.c.y[j], dz = qz - (double)a.c.z[j];
                 const double px = qx - st->c0[0], py = qy - st->c0[1], pz = qz - st->c0[2];
                 r = (nx * dx + ny * dy) + nz * dz;
                 J0 = py * nz - pz * ny; J1 = pz * nx - px * nz; J2 = px * ny - py * nx;
@@ -63,33 +54,12 @@ __global__ __launch_bounds__(KNN_BLOCK) void plane_step_kernel(NnGridView g, Pla
                 d2d = (double)__uint_as_float(d2_bits);
             }
         }
-        if (a.idx) a.idx[a.order[s]] = match;
+        if (a.idx) a.idx[a.q.order[s]] = match;
     }
 
-    // (a lane without a pair holds zeros in J, r and d2d: its terms are +0)
-    double* __restrict__ row = a.rows + (size_t)blockIdx.x * PLANE_ROW;
     const double J[6] = {J0, J1, J2, J3, J4, J5};
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-#pragma unroll
-        for (int j = i; j < 6; j++) {
-            const double v = wave_sum(J[i] * J[j]);
-            if (lane == 0) row[k] = v;
-            k++;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        const double v = wave_sum(J[i] * r);
-        if (lane == 0) row[21 + i] = v;
-    }
-    const double rr = wave_sum(r * r), dd = wave_sum(d2d);
-    const int pairs = __popcll(__ballot(pair));
-    if (lane == 0) {
-        row[27] = rr; row[28] = dd; row[29] = (double)pairs;
-        row[30] = 0.0; row[31] = 0.0;
-    }
+    pose_row_write(lane, a.rows + (size_t)blockIdx.x * PLANE_ROW, [&](int i, int j) { return J[i] * J[j]; }, [&](int i) { return J[i] * r; }, r * r,
+                   d2d, pair ? 1.0 : 0.0);
 }
 
 // slab p of `parts` slabs of the rows -> parts_out[p]: rows [p * per, min((p + 1) * per, nrows)), per = ceil(nrows / parts)
@@ -117,12 +87,12 @@ __global__ __launch_bounds__(256) void plane_reduce_solve_kernel(PlaneState* __r
     for (int i = 0; i < PLANE_ROW; i++) st->sums[i] = sums[i];
     if (!rules.solve) return;
 
-    if (sums[29] < (double)PLANE_MIN_PAIRS) { st->done = 1; st->stop_reason = MI_STOP_NO_PAIRS_; return; }
+    if (sums[PLANE_ROW_COUNT] < (double)PLANE_MIN_PAIRS) { st->done = 1; st->stop_reason = MI_STOP_NO_PAIRS_; return; }
     double A[21], gvec[6], x[6], min_pivot;
 #pragma unroll
-    for (int i = 0; i < 21; i++) A[i] = sums[i];
+    for (int i = 0; i < PLANE_ROW_G; i++) A[i] = sums[i];
 #pragma unroll
-    for (int i = 0; i < 6; i++) gvec[i] = sums[21 + i];
+    for (int i = 0; i < 6; i++) gvec[i] = sums[PLANE_ROW_G + i];
     const bool solved = plane_solve6(A, gvec, x, &min_pivot);
     st->min_pivot = min_pivot;
     if (!solved) { st->done = 1; st->stop_reason = MI_STOP_DEGENERATE_; return; }
@@ -155,8 +125,8 @@ int plane_part_count(int nrows) { return nrows > PLANE_ONE_STAGE_ROWS ? PLANE_PA
 
 hipError_t plane_step(const NnGridView& g, const PlaneStepArgs& a, int fma, hipStream_t s)
 {
-    if (a.n < 1) return hipErrorInvalidValue;
-    const dim3 grid(plane_row_count(a.n));
+    if (a.q.n < 1) return hipErrorInvalidValue;
+    const dim3 grid(plane_row_count(a.q.n));
     if (fma) hipLaunchKernelGGL(plane_step_kernel<true>, grid, dim3(KNN_BLOCK), 0, s, g, a);
     else hipLaunchKernelGGL(plane_step_kernel<false>, grid, dim3(KNN_BLOCK), 0, s, g, a);
     return hipGetLastError();

@@ -7,7 +7,18 @@
 
 namespace mislam {
 
+// A row: what a step kernel sums over the 64 moving points of one wave (pose_row_write, pose_step.hpp), and a system: the rows' sum.
+//   [0, 21)                        H, the upper triangle of the 6 x 6 matrix row by row: sum J J^T (K16), sum J^T M J (K17, K31)
+//   [PLANE_ROW_G, PLANE_ROW_G + 6) g: sum J r (K16), sum J^T M d (K17), sum J^T b (K31)
+//   [PLANE_ROW_E]                  the objective: sum r^2 (K16), sum d^T M d (K17), sum e (K31)
+//   [PLANE_ROW_AUX]                sum d2 over the pairs (K16, K17); points with a term (K31)
+//   [PLANE_ROW_COUNT]              pairs (K16, K17); terms (K31)
+//   [30, 32)                       0
 constexpr int PLANE_ROW = 32;                // doubles per row and per system: mi_plane_system's out_sums
+constexpr int PLANE_ROW_G = 21;              // (= the entries of H before it)
+constexpr int PLANE_ROW_E = 27;
+constexpr int PLANE_ROW_AUX = 28;
+constexpr int PLANE_ROW_COUNT = 29;
 
 // Device-resident loop state of one plane registration.  The host only ever copies it back; every decision is taken on the device.
 struct PlaneState {
@@ -55,7 +66,7 @@ inline void pose_out_T(const PlaneState& h, float out_T[16])
 }
 
 // the last linearisation's objective per pair (or term); 0 where there was none
-inline float pose_error(const PlaneState& h) { return h.sums[29] > 0.0 ? (float)(h.sums[27] / h.sums[29]) : 0.f; }
+inline float pose_error(const PlaneState& h) { return h.sums[PLANE_ROW_COUNT] > 0.0 ? (float)(h.sums[PLANE_ROW_E] / h.sums[PLANE_ROW_COUNT]) : 0.f; }
 
 // iterations enqueued between two host reads of the state, and how many of them the next batch holds under the cap
 inline int pose_batch(int sync_every) { return sync_every > 0 ? sync_every : 4; }

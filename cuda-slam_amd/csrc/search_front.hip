@@ -1,8 +1,9 @@
 // The front end of a search over a cloud's cell grid, stated once for mi_knn_search, mi_estimate_normals and mi_remove_outliers (declared in
 // context.h): the common reserves, the uploads, the input check and its one read-back (knn_check_inputs), the cell grid over the cloud
 // (grid_reserve / grid_build_into of nn_grid.h with the call's buffers), the curve order of the queries (morton_order / permute_soa of
-// nn_tree.h).  A driver keeps its own argument checks, its own reserves, its kernel's arguments, its launch (search_front_timed_launch) and
-// its download.  `who` is the entry point's name: every message a call can refuse with reads the same in all three but for it.
+// nn_tree.h), the views of the queries and the cloud that a search kernel is handed (search_front_queries, search_front_cloud), and for the
+// calls that bring normals along their upload and check (search_front_enqueue_normals, search_front_refuse_normals).  A driver keeps its own
+// argument checks, its own reserves, the rest of its kernel's arguments, its launch (search_front_timed_launch) and its download.  `who` is the entry point's name: every message a call can refuse with reads the same in all three but for it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -102,6 +103,39 @@ int search_front_index_and_order(mi_ctx* c, SearchFrontBuffers& b, StageClock& c
     MI_TRY(clock.mark(4));
     return MI_OK;
 }
+
+int search_front_enqueue_normals(mi_ctx* c, SearchFrontBuffers& b, const float* normals_xyz, int m, float* nx, float* ny, float* nz, float4* packed,
+                                 KnnState* nstate)
+{
+    MI_TRY(host_to_device(c, b.staging.p, normals_xyz, sizeof(float) * 3 * (size_t)m));
+    MI_HIP(aos_to_soa(b.staging.p, m, m, nx, ny, nz, packed, c->stream));
+    MI_HIP(knn_check_inputs(nx, ny, nz, m, nullptr, nullptr, nullptr, 0, b.range_lo_hi.p, b.range_bad.p, nstate, c->stream));
+    return MI_OK;
+}
+
+int search_front_refuse_normals(mi_ctx* c, StageClock& clock, const char* who, const char* name, const KnnState* nstate)
+{
+    KnnState ns;
+    MI_HIP(hipMemcpyAsync(&ns, nstate, sizeof ns, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    MI_TRY(clock.mark(2));
+    if (ns.bad_cloud != KNN_NO_POINT) {
+        set_error("%s: %s normal %d has a non-finite component or one above 1e18 in magnitude", who, name, ns.bad_cloud);
+        return MI_ERR_INVALID_ARG;
+    }
+    return MI_OK;
+}
+
+SearchQueries search_front_queries(const SearchFrontBuffers& b, const SearchFront& f)
+{
+    SearchQueries q{};
+    q.x = b.qx.p; q.y = b.qy.p; q.z = b.qz.p; q.order = b.order.p;
+    q.n = f.n;
+    for (int i = 0; i < 3; i++) q.hi[i] = f.bbox[3 + i];
+    return q;
+}
+
+SearchCloud search_front_cloud(const SearchFrontBuffers& b) { return SearchCloud{b.cx.p, b.cy.p, b.cz.p}; }
 
 bool search_front_fits(const SearchFrontBuffers& b, const SearchFront& f)
 {

@@ -37,6 +37,16 @@ int main()
 {
     static_assert(sizeof(PlaneState) == (9 + 3 + 3 + PLANE_ROW + 3) * sizeof(double) + 4 * sizeof(int), "PlaneState: the layout the kernels take by pointer");
     static_assert(PLANE_ROW == 32, "mi_plane_system's out_sums");
+    // the named entries of a row: behind the 21 of H, inside the row, g's six ending where E stands, no two the same
+    static_assert(PLANE_ROW_G >= 21 && PLANE_ROW_G + 6 == PLANE_ROW_E, "g: six entries between H and E");
+    static_assert(PLANE_ROW_E >= 21 && PLANE_ROW_E < PLANE_ROW && PLANE_ROW_AUX >= 21 && PLANE_ROW_AUX < PLANE_ROW && PLANE_ROW_COUNT >= 21 &&
+                      PLANE_ROW_COUNT < PLANE_ROW && PLANE_ROW_G < PLANE_ROW,
+                  "the named entries lie in [21, 32)");
+    static_assert(PLANE_ROW_G != PLANE_ROW_E && PLANE_ROW_G != PLANE_ROW_AUX && PLANE_ROW_G != PLANE_ROW_COUNT && PLANE_ROW_E != PLANE_ROW_AUX &&
+                      PLANE_ROW_E != PLANE_ROW_COUNT && PLANE_ROW_AUX != PLANE_ROW_COUNT,
+                  "the named entries are distinct");
+    static_assert((PLANE_ROW_AUX < PLANE_ROW_G || PLANE_ROW_AUX >= PLANE_ROW_G + 6) && (PLANE_ROW_COUNT < PLANE_ROW_G || PLANE_ROW_COUNT >= PLANE_ROW_G + 6),
+                  "neither counter stands inside g");
     const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
     // values no fp32 arithmetic would reproduce by accident: thirds and a denormal
     const float centre[3] = {1.0f / 3.0f, -1234567.875f, 1e-42f};
@@ -102,6 +112,20 @@ int main()
         CHECK(same_bits(pose_error(h), 0.f));
         h.sums[27] = (double)nan; h.sums[29] = 0.0;
         CHECK(same_bits(pose_error(h), 0.f));
+    }
+    {   // the error reads E and COUNT by their names and nothing else: every other entry of the block is poisoned (NaN, or bytes of 0xa5)
+        PlaneState h;
+        std::memset(&h, 0xa5, sizeof h);
+        for (int i = 0; i < PLANE_ROW; i++) h.sums[i] = (double)nan;
+        h.sums[PLANE_ROW_E] = 0.1; h.sums[PLANE_ROW_COUNT] = 7.0;
+        CHECK(same_bits(pose_error(h), (float)(0.1 / 7.0)));
+        h.sums[PLANE_ROW_E] = 5.0; h.sums[PLANE_ROW_COUNT] = 0.0;
+        CHECK(same_bits(pose_error(h), 0.f));
+        // ... and a poisoned E or COUNT shows: the two are read
+        h.sums[PLANE_ROW_E] = (double)nan; h.sums[PLANE_ROW_COUNT] = 7.0;
+        CHECK(std::isnan(pose_error(h)));
+        h.sums[PLANE_ROW_E] = 0.1; h.sums[PLANE_ROW_COUNT] = (double)nan;
+        CHECK(same_bits(pose_error(h), 0.f));          // (NaN > 0 is false: no pair)
     }
     {   // the batch rule
         CHECK(pose_batch(0) == 4);
