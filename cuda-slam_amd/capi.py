@@ -44,6 +44,7 @@ EXPORTS = [
     "mi_knn_search", "mi_knn_search_times", "mi_estimate_normals", "mi_estimate_normals_times",
     "mi_outlier_params_default", "mi_remove_outliers", "mi_remove_outliers_times",
     "mi_iss_params_default", "mi_iss_keypoints", "mi_iss_keypoints_times",
+    "mi_cluster_params_default", "mi_cluster_dbscan", "mi_cluster_dbscan_times",
     "mi_plane_params_default", "mi_icp_plane_register", "mi_plane_system", "mi_icp_plane_times",
     "mi_estimate_covariances", "mi_icp_gicp_register", "mi_gicp_system", "mi_icp_gicp_times",
     "mi_fpfh_features", "mi_fpfh_features_times",
@@ -90,6 +91,11 @@ class OutlierStats(C.Structure):
 class IssParams(C.Structure):
     _fields_ = [("salient_radius", C.c_float), ("non_max_radius", C.c_float), ("gamma_21", C.c_float), ("gamma_32", C.c_float),
                 ("min_neighbours", C.c_int), ("dist_mode", C.c_int), ("reserved", C.c_int * 10)]
+
+
+class ClusterParams(C.Structure):
+    _fields_ = [("radius", C.c_float), ("min_points", C.c_int), ("min_cluster_size", C.c_int), ("max_cluster_size", C.c_int),
+                ("dist_mode", C.c_int), ("reserved", C.c_int * 11)]
 
 
 class PlaneParams(C.Structure):
@@ -354,6 +360,26 @@ def iss_keypoints_raw(handle, cloud, n, params, out_xyz, out_index, out_n, is_ke
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
     f.restype = C.c_int
     return f(handle, cloud, n, params, out_xyz, out_index, out_n, is_keypoint, saliency, eigenvalues, neighbours)
+
+
+def cluster_params(**kw):
+    """mi_cluster_params at its defaults (min_points 1, min_cluster_size 1, no upper limit, CPU rounding; radius 0: set it) with the given fields set."""
+    p = ClusterParams()
+    lib().mi_cluster_params_default.restype = None
+    lib().mi_cluster_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def cluster_dbscan_raw(handle, cloud, n, params, labels, n_clusters, cluster_sizes, cluster_cap, is_core, grouped_index, n_grouped):
+    """mi_cluster_dbscan with ctypes pointers (or None) as given: returns the error code, raises nothing."""
+    f = lib().mi_cluster_dbscan
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3
+    f.restype = C.c_int
+    return f(handle, cloud, n, params, labels, n_clusters, cluster_sizes, cluster_cap, is_core, grouped_index, n_grouped)
 
 
 def plane_params(**kw):
@@ -1067,6 +1093,30 @@ class Context:
         out = (C.c_double * 8)()
         _check(lib().mi_iss_keypoints_times(self._h, out))
         return dict(zip(("workspace", "upload", "check", "grid", "order", "saliency", "finish", "total"), list(out)))
+
+    # ---- density-based clustering
+    def cluster_dbscan(self, cloud, params, want_sizes=False, want_core=False, want_grouped=False):
+        """DBSCAN / Euclidean clustering (mi_cluster_dbscan; params: cluster_params(radius=...)): labels [n] int32 (-1: noise or a dissolved
+        cluster) and the number of clusters; then, as asked for and in this order: cluster_sizes [n_clusters] int32, is_core [n] uint8 and
+        grouped_index [n_grouped] int32 (the labelled points by (label, index); cluster c starts at cluster_sizes[:c].sum())."""
+        cloud = _cloud(cloud)
+        n = cloud.shape[0]
+        labels, n_clusters, n_grouped = np.empty(n, np.int32), C.c_int(0), C.c_int(0)
+        sizes = np.empty(n, np.int32) if want_sizes else None
+        core = np.empty(n, np.uint8) if want_core else None
+        grouped = np.empty(n, np.int32) if want_grouped else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _check(cluster_dbscan_raw(self._h, cloud.ctypes.data, n, C.addressof(params), labels.ctypes.data, C.addressof(n_clusters), ptr(sizes), n, ptr(core),
+                                  ptr(grouped), C.addressof(n_grouped) if want_grouped else None))
+        res = [labels, n_clusters.value]
+        res += ([sizes[:n_clusters.value].copy()] if want_sizes else []) + ([core] if want_core else []) + ([grouped[:n_grouped.value].copy()] if want_grouped else [])
+        return tuple(res)
+
+    def cluster_dbscan_times(self):
+        """ms per stage of the last cluster_dbscan: workspace, upload (with the check), grid (with the order), count, link, resolve, finish, total (mi_cluster_dbscan_times)."""
+        out = (C.c_double * 8)()
+        _check(lib().mi_cluster_dbscan_times(self._h, out))
+        return dict(zip(("workspace", "upload", "grid", "count", "link", "resolve", "finish", "total"), list(out)))
 
     # ---- point-to-plane ICP
     def icp_plane_register(self, before, after, after_normals, params, init=None):

@@ -253,6 +253,19 @@ struct mi_ctx {
         double ms[MI_ISS_STAGES] = {0};                  // mi_iss_keypoints_times
     } iss;
 
+    // ---- mi_cluster_dbscan: a search front end in self mode, the core count, the union-find's parents, every point's root, the clusters' sizes,
+    // the flags and scan tiles of the two compactions (the surviving roots; the labelled points) and the grouping's sort
+    struct ClusterBuffers {
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<int> count, parent, root_of, size, rank, roots, labels, tile_counts, sizes_out;
+        mislam::DevBuf<unsigned char> keep, labelled, core;
+        mislam::DevBuf<mislam::OutlierState> ostate;     // [0] kept: the surviving clusters; [1] kept: the labelled points
+        mislam::DevBuf<unsigned int> keys_a, keys_b;     // the grouping: labels of the labelled points, ping and pong
+        mislam::DevBuf<int> group_a, group_b;            // ... and their indices
+        mislam::DevBuf<unsigned char> sort_temp;
+        double ms[MI_CLUSTER_STAGES] = {0};              // mi_cluster_dbscan_times
+    } cluster;
+
     // ---- mi_icp_plane_register, mi_plane_system: a search front end over the FIXED cloud with the moving cloud as its queries, the fixed
     // cloud's normals, the rows of an iteration's sums and the loop's state block -- a sibling of the three above, nothing shared with mi_icp_*
     struct PlaneBuffers {
@@ -433,7 +446,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 
 // ---- the voxel filter's front end (voxel_api.hip), for mi_voxel_downsample and mi_ndt_voxels: the reserves, the upload, the range pass and its
 // read-back with everything that can refuse the cloud (nothing has been written to a caller's array then), the keys, the sort, the rows and the

@@ -608,6 +608,51 @@ struct IssSuppressArgs {
 };
 hipError_t iss_suppress(const NnGridView& g, const IssSuppressArgs& a, int fma, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K34 - K38 density-based clustering (cluster_kernels.hip; driver: cluster_api.hip): the core flags are K15's early radius count; K34 links
+// the core points of every ball in a lock-free union-find over the caller's indices (the argument: the head of cluster_kernels.hip); K35
+// resolves every point to the root of its cluster (a core point's own, a border point's nearest core neighbour's); K36 counts the clusters'
+// sizes and flags the roots that pass the size filter, K15's outlier_compact numbers them, K37 scatters ranks and sizes, K38 writes the labels.
+// ---------------------------------------------------------------------------------------------------------------
+struct ClusterLinkArgs {
+    SearchQueries q;                 // the cloud itself (self mode)
+    float r2;                        // a point j != row (by index) with d2 <= r2 is a neighbour
+    const int* count;                // n, the caller's order: K15's early count; null: every point is core
+    int need;                        // point j is core iff count[j] >= need (= min_points - 1)
+    int* parent;                     // n, the caller's order, the identity before the launch; parent[x] <= x always
+};
+hipError_t cluster_identity(int* parent, int n, hipStream_t s);
+hipError_t cluster_link(const NnGridView& g, const ClusterLinkArgs& a, int fma, hipStream_t s);
+struct ClusterResolveArgs {
+    SearchQueries q;                 // as above
+    float r2;
+    const int* count;                // as above
+    int need;
+    const int* parent;               // K34's, read only
+    int* root_of;                    // n, the caller's order: the root (= smallest core index) of the point's cluster, or -1 (noise)
+    unsigned char* is_core;          // n, the caller's order: every row is written
+};
+hipError_t cluster_resolve(const NnGridView& g, const ClusterResolveArgs& a, int fma, hipStream_t s);
+struct ClusterNumberArgs {
+    int n;
+    const int* root_of;              // K35's
+    int* size;                       // n, zero before cluster_count_sizes: size[r] = the points whose root is r
+    int min_size, max_size;          // max_size 0: no upper limit
+    unsigned char* keep;             // n: root_of[i] == i and size[i] within the limits -- the surviving roots (what outlier_compact numbers)
+    const int* roots;                // outlier_compact's out_index over keep: the surviving roots, ascending
+    const OutlierState* state;       // ... and its kept: their number
+    int* rank;                       // n: rank[roots[c]] = c; other entries are not written (cluster_labels reads it where keep is 1 only)
+    int* sizes_out;                  // may be null; cap entries: size[roots[c]] for c < min(kept, cap)
+    int cap;
+    int* labels;                     // n
+    unsigned char* labelled;         // may be null; n: labels[i] >= 0
+};
+hipError_t cluster_count_sizes(const ClusterNumberArgs& a, hipStream_t s);      // K36: size, then keep
+hipError_t cluster_ranks(const ClusterNumberArgs& a, hipStream_t s);      // K37: rank, sizes_out
+hipError_t cluster_labels(const ClusterNumberArgs& a, hipStream_t s);     // K38: labels, labelled
+// keys[k] = (unsigned)labels[index[k]] >> shift for k < count: the sort keys of the grouping
+hipError_t cluster_group_keys(const int* labels, const int* index, int count, int shift, unsigned int* keys, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -630,5 +675,6 @@ hipError_t preload_match_kernels();
 hipError_t preload_ransac_kernels();
 hipError_t preload_ndt_kernels();
 hipError_t preload_iss_kernels();
+hipError_t preload_cluster_kernels();
 
 }  // namespace mislam

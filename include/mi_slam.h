@@ -802,6 +802,75 @@ int mi_iss_keypoints(mi_ctx* ctx, const float* cloud_xyz, int n, const mi_iss_pa
 int mi_iss_keypoints_times(mi_ctx* ctx, double out_ms[MI_ISS_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * Density-based clustering (DBSCAN, Ester et al. 1996; with min_points = 1 Euclidean cluster extraction; no reference counterpart):
+ * splits a scene into its objects, drops clutter by component size, and yields the per-object clouds that mi_icp_register_batch and
+ * mi_cpd_register_batch take (clustering).  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+typedef struct mi_cluster_params {
+    float radius;            /* eps: finite, > 0, square finite                                            default 0: the caller must set it */
+    int   min_points;        /* >= 1: a point is CORE if its ball holds >= min_points points, ITSELF INCLUDED (Open3D, sklearn)   default 1: Euclidean clustering */
+    int   min_cluster_size;  /* >= 1                                                                        default 1 */
+    int   max_cluster_size;  /* 0: no upper limit; else >= min_cluster_size                                 default 0 */
+    int   dist_mode;         /* MI_DIST_CPU_ROUNDING / MI_DIST_FMA, as mi_knn_search                        default CPU_ROUNDING */
+    int   reserved[11];
+} mi_cluster_params;         /* 64 bytes */
+void mi_cluster_params_default(mi_cluster_params* p);
+
+/* The clusters of a cloud, computed on the device.  The result is a pure integer function of the input: every rule below can be retraced
+ * in numpy (tests/cluster_reference.py does), and the same input gives the same bits on every run.
+ *   Neighbours: j is a neighbour of i when j != i (by index) and d2(i, j) <= r2, with r2 = radius * radius, one IEEE fp32 multiplication
+ *     on the host, and d2 the fp32 squared distance of dist_mode, exactly as in mi_remove_outliers' radius method and mi_iss_keypoints.  A
+ *     point AT the radius belongs; a duplicate of point i stored elsewhere is a neighbour.  d2 is symmetric bit for bit in both modes: the
+ *     three differences of (j, i) are the exact negations of those of (i, j), a square does not see the sign, and the sum is taken in
+ *     the same order -- so "i is a neighbour of j" and "j is a neighbour of i" are one statement.
+ *   Core: point i is core when 1 + (the number of its neighbours) >= min_points.  is_core[i] is 1 for a core point and 0 otherwise; the
+ *     size filter below does not change it.
+ *   Clusters: two core points are in one cluster when a chain of core points, each a neighbour of the next, joins them.
+ *   Border: a point that is not core and has at least one core neighbour joins the cluster of the core neighbour j with the smallest
+ *     packed key (bits(d2(i, j)) << 32) | j: the nearest one, the lower index on an exact tie.  A border point never joins two clusters
+ *     and never links two.  This is a stated rule that does not depend on any order; Open3D's and sklearn's DBSCAN give a border point to
+ *     whichever cluster's expansion visits it first, so their border labels depend on the order of the input and may differ from these
+ *     (the core points, their partition and the noise set are the same).
+ *   Noise: every other point; its label is -1.
+ *   Size filter: the size of a cluster counts its core and its border points.  A cluster smaller than min_cluster_size, or larger than
+ *     max_cluster_size where that is not 0, is dissolved: its points get the label -1.
+ *   Numbering: the surviving clusters are numbered 0 .. *n_clusters - 1 by ascending smallest CORE member index, in the caller's order.
+ *     The output therefore does not depend on scheduling, on the cell size of the call's grid or on its curve order.
+ *   Outputs: labels[i] is the cluster of point i or -1; *n_clusters the number of surviving clusters; cluster_sizes[c], for
+ *     c < min(*n_clusters, cluster_cap), the size of cluster c (entries beyond are not written).  grouped_index holds the labelled points
+ *     (label >= 0) sorted by (label, index) -- the members of cluster 0 in ascending index, then those of cluster 1, ... -- and *n_grouped
+ *     is their number (capacity n).  The members of cluster c start at the running sum of cluster_sizes[0 .. c - 1]: the offsets are that
+ *     sum, and there is no output for them.  Asking for fewer optional outputs moves no bit of the rest.
+ *   Cost: a point's work is proportional to the number of points in its ball (and its cell's neighbourhood), so a radius that holds a
+ *     large share of the cloud makes the call quadratic.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with "mi_cluster_dbscan" and names the cause and, for a bad point, its index (the
+ *     lowest); NOTHING the caller passed has been written -- for a NULL ctx, cloud_xyz, params, labels or n_clusters; n < 1; a radius that
+ *     is NaN, infinite or <= 0, or whose square is not finite; min_points < 1; min_cluster_size < 1; max_cluster_size < 0, or
+ *     0 < max_cluster_size < min_cluster_size; cluster_sizes given with cluster_cap < 1; grouped_index without n_grouped; an unknown
+ *     dist_mode; a non-finite coordinate or one above 1e18 in magnitude.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls keep: it works in buffers of its own.
+ *   Synchronous, host in and host out. */
+int mi_cluster_dbscan(mi_ctx* ctx, const float* cloud_xyz, int n, const mi_cluster_params* params,
+                      int* labels,               /* non-NULL; n */
+                      int* n_clusters,           /* non-NULL */
+                      int* cluster_sizes,        /* may be NULL; the first min(*n_clusters, cluster_cap) sizes */
+                      int cluster_cap,           /* >= 1 where cluster_sizes is given; ignored otherwise */
+                      unsigned char* is_core,    /* may be NULL; n */
+                      int* grouped_index,        /* may be NULL; capacity n: the labelled points by (label, index) */
+                      int* n_grouped);           /* non-NULL where grouped_index is given; may be given alone */
+
+/* Where the last mi_cluster_dbscan of this context spent its host wall time, in ms (measurement hook, tools/cluster_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA, input check, bounding box, its read-back
+ *   out[2] cell grid over the cloud, curve order    out[3] the core count (K15's count kernel; 0 with min_points = 1)
+ *   out[4] the link kernel (K34)                    out[5] the resolve kernel (K35)
+ *   out[6] sizes, filter, numbering, labels, the grouping and the downloads     out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage, and out[4] is the
+ * launch's own HIP-event time instead of host wall time). */
+#define MI_CLUSTER_STAGES 8
+int mi_cluster_dbscan_times(mi_ctx* ctx, double out_ms[MI_CLUSTER_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Point-to-plane ICP (no reference counterpart: the reference's ICP is point-to-point): the registration the normals are for
  * (plane registration).  It minimises sum (n_j . (R b_i + t - a_j))^2 over the matched pairs, linearised about the
  * current pose, and does not stall on surfaces that slide along themselves.  A sibling of mi_icp_register with buffers, state and
