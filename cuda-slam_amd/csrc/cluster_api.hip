@@ -23,7 +23,6 @@ extern "C" void mi_cluster_params_default(mi_cluster_params* p)
     p->dist_mode = MI_DIST_CPU_ROUNDING;
 }
 static_assert(sizeof(mi_cluster_params) == 64, "mi_cluster_params is 64 bytes (mi_slam.h)");
-static_assert(2 * sizeof(OutlierState) <= 64 * sizeof(float), "two OutlierStates must fit the context's pinned scratch");
 
 extern "C" int mi_cluster_dbscan(mi_ctx* c, const float* cloud_xyz, int n, const mi_cluster_params* p, int* labels, int* n_clusters, int* cluster_sizes,
                                  int cluster_cap, unsigned char* is_core, int* grouped_index, int* n_grouped)
@@ -54,16 +53,17 @@ extern "C" int mi_cluster_dbscan(mi_ctx* c, const float* cloud_xyz, int n, const
     const int tiles = outlier_scan_tiles(n);
     const bool counted = min_points > 1;                                           // min_points = 1: every point is core, nothing to count
     const int sizes_cap = cluster_sizes ? std::min(cluster_cap, n) : 0;
+    CallBuffers bufs;                  // (cluster_sizes and grouped_index go once their lengths are known)
     MI_TRY(search_front_reserve(b.front, np, np, true));
-    MI_TRY(b.ostate.reserve(2));
-    if (counted) MI_TRY(b.count.reserve(np));
-    MI_TRY(b.parent.reserve(np)); MI_TRY(b.root_of.reserve(np)); MI_TRY(b.size.reserve(np)); MI_TRY(b.rank.reserve(np)); MI_TRY(b.roots.reserve(np));
-    MI_TRY(b.labels.reserve(np)); MI_TRY(b.keep.reserve(np)); MI_TRY(b.core.reserve(np)); MI_TRY(b.tile_counts.reserve((size_t)tiles));
-    if (cluster_sizes) MI_TRY(b.sizes_out.reserve((size_t)sizes_cap));
-    if (n_grouped) MI_TRY(b.labelled.reserve(np));
+    MI_TRY(bufs.need(b.ostate, 2));
+    if (counted) MI_TRY(bufs.need(b.count, np));
+    MI_TRY(bufs.need(b.parent, np)); MI_TRY(bufs.need(b.root_of, np)); MI_TRY(bufs.need(b.size, np)); MI_TRY(bufs.need(b.rank, np)); MI_TRY(bufs.need(b.roots, np));
+    MI_TRY(bufs.need(b.labels, np, labels)); MI_TRY(bufs.need(b.keep, np)); MI_TRY(bufs.need(b.core, np, is_core)); MI_TRY(bufs.need(b.tile_counts, (size_t)tiles));
+    if (cluster_sizes) MI_TRY(bufs.need(b.sizes_out, (size_t)sizes_cap));
+    if (n_grouped) MI_TRY(bufs.need(b.labelled, np));
     if (grouped_index) {
-        MI_TRY(b.keys_a.reserve(np)); MI_TRY(b.keys_b.reserve(np)); MI_TRY(b.group_a.reserve(np)); MI_TRY(b.group_b.reserve(np));
-        MI_TRY(b.sort_temp.reserve(radix_sort_temp_bytes(n) + 16));
+        MI_TRY(bufs.need(b.keys_a, np)); MI_TRY(bufs.need(b.keys_b, np)); MI_TRY(bufs.need(b.group_a, np)); MI_TRY(bufs.need(b.group_b, np));
+        MI_TRY(bufs.need(b.sort_temp, radix_sort_temp_bytes(n) + 16));
     }
     MI_TRY(clock.mark(0));
 
@@ -75,10 +75,7 @@ extern "C" int mi_cluster_dbscan(mi_ctx* c, const float* cloud_xyz, int n, const
     MI_TRY(search_front_index_and_order(c, b.front, clock, "mi_cluster_dbscan", ppc, &f));
 
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (!search_front_fits(b.front, f) || (counted && b.count.cap < np) || b.parent.cap < np || b.root_of.cap < np || b.size.cap < np || b.rank.cap < np ||
-        b.roots.cap < np || b.labels.cap < np || b.keep.cap < np || b.core.cap < np || b.tile_counts.cap < (size_t)tiles || b.ostate.cap < 2 ||
-        (cluster_sizes && b.sizes_out.cap < (size_t)sizes_cap) || (n_grouped && b.labelled.cap < np) ||
-        (grouped_index && (b.keys_a.cap < np || b.keys_b.cap < np || b.group_a.cap < np || b.group_b.cap < np))) {
+    if (!search_front_fits(b.front, f) || !bufs.fits()) {
         set_error("internal: mi_cluster_dbscan buffers shorter than the launch");
         return MI_ERR_STATE;
     }
@@ -128,11 +125,11 @@ extern "C" int mi_cluster_dbscan(mi_ctx* c, const float* cloud_xyz, int n, const
     }
 
     // both counts once; nothing of the caller's has been written yet
-    OutlierState* os = reinterpret_cast<OutlierState*>(c->h_scratch);
-    MI_HIP(hipMemcpyAsync(os, b.ostate.p, 2 * sizeof(OutlierState), hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(compact_read_state(c, b.ostate.p, 2));
     MI_HIP(hipStreamSynchronize(c->stream));
-    const long long found = os[0].kept, grouped = n_grouped ? os[1].kept : 0;
-    if (found < 0 || found > (long long)n || grouped < 0 || grouped > (long long)n || (n_grouped && (found == 0) != (grouped == 0))) {
+    long long found, grouped = 0;
+    const bool found_ok = compact_kept(c, 0, n, &found), grouped_ok = !n_grouped || compact_kept(c, 1, n, &grouped);
+    if (!found_ok || !grouped_ok || (n_grouped && (found == 0) != (grouped == 0))) {
         set_error("internal: mi_cluster_dbscan counted %lld clusters and %lld labelled points among %d points", found, grouped, n);
         return MI_ERR_STATE;
     }
@@ -151,8 +148,7 @@ extern "C" int mi_cluster_dbscan(mi_ctx* c, const float* cloud_xyz, int n, const
             sorted = b.group_a.p;
         }
     }
-    MI_HIP(hipMemcpyAsync(labels, b.labels.p, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
-    if (is_core) MI_HIP(hipMemcpyAsync(is_core, b.core.p, np, hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(bufs.download(c->stream));
     const size_t nsizes = (size_t)std::min<long long>(found, sizes_cap);
     if (cluster_sizes && nsizes > 0) MI_HIP(hipMemcpyAsync(cluster_sizes, b.sizes_out.p, sizeof(int) * nsizes, hipMemcpyDeviceToHost, c->stream));
     if (grouped_index && grouped > 0) MI_HIP(hipMemcpyAsync(grouped_index, sorted, sizeof(int) * (size_t)grouped, hipMemcpyDeviceToHost, c->stream));
@@ -165,9 +161,4 @@ extern "C" int mi_cluster_dbscan(mi_ctx* c, const float* cloud_xyz, int n, const
     return MI_OK;
 }
 
-extern "C" int mi_cluster_dbscan_times(mi_ctx* c, double out_ms[MI_CLUSTER_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_cluster_dbscan_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_CLUSTER_STAGES; i++) out_ms[i] = c->cluster.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_cluster_dbscan_times(mi_ctx* c, double out_ms[MI_CLUSTER_STAGES]) { return stage_times("mi_cluster_dbscan_times", c ? c->cluster.ms : nullptr, out_ms); }

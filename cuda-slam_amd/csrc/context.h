@@ -12,6 +12,7 @@
 
 #include "../../include/mi_slam.h"
 #include "cpd_kernels.h"
+#include "call_buffers.hpp"
 #include "devbuf.h"
 #include "kernels.h"
 #include "nn_grid.h"
@@ -447,6 +448,13 @@ struct StageClock {
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
 static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+// The body of every *_times entry point: the eight slots a StageClock left in the context.  ms: null for a null context.
+static inline int stage_times(const char* who, const double* ms, double* out_ms)
+{
+    if (!ms || !out_ms) { set_error("%s: null argument", who); return MI_ERR_INVALID_ARG; }
+    for (int i = 0; i < 8; i++) out_ms[i] = ms[i];
+    return MI_OK;
+}
 
 // ---- the voxel filter's front end (voxel_api.hip), for mi_voxel_downsample and mi_ndt_voxels: the reserves, the upload, the range pass and its
 // read-back with everything that can refuse the cloud (nothing has been written to a caller's array then), the keys, the sort, the rows and the
@@ -503,6 +511,41 @@ static inline int search_front_timed_launch(mi_ctx* c, SearchFrontBuffers& b, St
         MI_HIP(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
         clock.ms[5] = (double)ms;
     }
+    return MI_OK;
+}
+
+// ---- the tail of a call that compacts flags over its cloud (outlier_compact, kernels.h: mi_remove_outliers, mi_iss_keypoints; the two counts
+// of mi_cluster_dbscan are read the same way).  compact_enqueue gathers the flagged rows of the cloud as uploaded (front.staging) and their
+// indices, where asked for, and counts them into *state.  compact_read_state puts `blocks` state blocks on their way into the context's pinned
+// scratch: a driver calls it once, with its per-point results, in front of their synchronisation; behind it compact_host_state is what came,
+// compact_kept block i's count (false unless within [0, n]: the driver refuses in its own words) and compact_download the kept rows.
+static_assert(2 * sizeof(OutlierState) <= 64 * sizeof(float), "two OutlierStates must fit the context's pinned scratch");
+static inline int compact_enqueue(mi_ctx* c, const SearchFrontBuffers& front, const unsigned char* keep, int n, int* tile_counts, int* out_index,
+                                  float* out_xyz, OutlierState* state)
+{
+    OutlierCompactArgs a{};
+    a.keep = keep; a.xyz = front.staging.p; a.n = n; a.tile_counts = tile_counts;
+    a.out_index = out_index; a.out_xyz = out_xyz; a.state = state;
+    MI_HIP(outlier_compact(a, c->stream));
+    return MI_OK;
+}
+static inline int compact_read_state(mi_ctx* c, const OutlierState* state, int blocks)
+{
+    MI_HIP(hipMemcpyAsync(c->h_scratch, state, (size_t)blocks * sizeof(OutlierState), hipMemcpyDeviceToHost, c->stream));
+    return MI_OK;
+}
+static inline const OutlierState* compact_host_state(const mi_ctx* c) { return reinterpret_cast<const OutlierState*>(c->h_scratch); }
+static inline bool compact_kept(const mi_ctx* c, int i, int n, long long* kept)
+{
+    *kept = compact_host_state(c)[i].kept;
+    return *kept >= 0 && *kept <= (long long)n;
+}
+static inline int compact_download(mi_ctx* c, long long kept, float* out_xyz, const float* d_xyz, int* out_index, const int* d_index)
+{
+    if (kept <= 0) return MI_OK;
+    if (out_xyz) MI_HIP(hipMemcpyAsync(out_xyz, d_xyz, sizeof(float) * 3 * (size_t)kept, hipMemcpyDeviceToHost, c->stream));
+    if (out_index) MI_HIP(hipMemcpyAsync(out_index, d_index, sizeof(int) * (size_t)kept, hipMemcpyDeviceToHost, c->stream));
+    if (out_xyz || out_index) MI_HIP(hipStreamSynchronize(c->stream));
     return MI_OK;
 }
 

@@ -27,12 +27,11 @@ extern "C" int mi_fpfh_features(mi_ctx* c, const float* cloud_xyz, const float* 
     StageClock clock(c, b.ms);         // mi_fpfh_features_times
 
     const size_t np = (size_t)n, rows = np * (size_t)k;
+    CallBuffers bufs;
     MI_TRY(search_front_reserve(b.front, np, np, true));
-    MI_TRY(b.nx.reserve(np)); MI_TRY(b.ny.reserve(np)); MI_TRY(b.nz.reserve(np)); MI_TRY(b.nstate.reserve(1));
-    MI_TRY(b.keys.reserve(rows)); MI_TRY(b.packed.reserve(FPFH_WORDS * np));
-    MI_TRY(b.out_fpfh.reserve(FPFH_DIM * np));
-    if (spfh_counts33) MI_TRY(b.out_counts.reserve(FPFH_DIM * np));
-    if (count) MI_TRY(b.out_count.reserve(np));
+    MI_TRY(bufs.need(b.nx, np)); MI_TRY(bufs.need(b.ny, np)); MI_TRY(bufs.need(b.nz, np)); MI_TRY(bufs.need(b.nstate, 1));
+    MI_TRY(bufs.need(b.keys, rows)); MI_TRY(bufs.need(b.packed, FPFH_WORDS * np));
+    MI_TRY(bufs.result(b.out_fpfh, FPFH_DIM * np, fpfh33)); MI_TRY(bufs.result(b.out_counts, FPFH_DIM * np, spfh_counts33)); MI_TRY(bufs.result(b.out_count, np, count));
     MI_TRY(clock.mark(0));
 
     MI_TRY(search_front_enqueue_normals(c, b.front, normals_xyz, n, b.nx.p, b.ny.p, b.nz.p, nullptr, b.nstate.p));
@@ -53,8 +52,7 @@ extern "C" int mi_fpfh_features(mi_ctx* c, const float* cloud_xyz, const float* 
     sa.n = n; sa.k = k;
     sa.fpfh = b.out_fpfh.p; sa.counts = spfh_counts33 ? b.out_counts.p : nullptr;
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (!search_front_fits(b.front, f) || b.nx.cap < np || b.ny.cap < np || b.nz.cap < np || b.keys.cap < rows || b.packed.cap < FPFH_WORDS * np ||
-        b.out_fpfh.cap < FPFH_DIM * np || (spfh_counts33 && b.out_counts.cap < FPFH_DIM * np) || (count && b.out_count.cap < np)) {
+    if (!search_front_fits(b.front, f) || !bufs.fits()) {
         set_error("internal: %s buffers shorter than the launch", who);
         return MI_ERR_STATE;
     }
@@ -69,18 +67,11 @@ extern "C" int mi_fpfh_features(mi_ctx* c, const float* cloud_xyz, const float* 
         return fpfh_sum(sa, c->stream);
     }));
 
-    MI_HIP(hipMemcpyAsync(fpfh33, b.out_fpfh.p, sizeof(float) * FPFH_DIM * np, hipMemcpyDeviceToHost, c->stream));
-    if (spfh_counts33) MI_HIP(hipMemcpyAsync(spfh_counts33, b.out_counts.p, FPFH_DIM * np, hipMemcpyDeviceToHost, c->stream));
-    if (count) MI_HIP(hipMemcpyAsync(count, b.out_count.p, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(bufs.download(c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
     MI_TRY(clock.mark(6));
     clock.finish();
     return MI_OK;
 }
 
-extern "C" int mi_fpfh_features_times(mi_ctx* c, double out_ms[MI_FPFH_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_fpfh_features_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_FPFH_STAGES; i++) out_ms[i] = c->fpfh.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_fpfh_features_times(mi_ctx* c, double out_ms[MI_FPFH_STAGES]) { return stage_times("mi_fpfh_features_times", c ? c->fpfh.ms : nullptr, out_ms); }

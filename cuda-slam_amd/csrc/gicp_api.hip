@@ -30,9 +30,9 @@ extern "C" int mi_estimate_covariances(mi_ctx* c, const float* cloud_xyz, int n,
     StageClock clock(c, b.ms);
 
     const size_t np = (size_t)n;
+    CallBuffers bufs;
     MI_TRY(search_front_reserve(b.front, np, np, true));
-    MI_TRY(b.out_cov.reserve(6 * np));
-    if (count) MI_TRY(b.out_count.reserve(np));
+    MI_TRY(bufs.result(b.out_cov, 6 * np, cov6)); MI_TRY(bufs.result(b.out_count, np, count));
     MI_TRY(clock.mark(0));
 
     SearchFront f;
@@ -51,14 +51,13 @@ extern "C" int mi_estimate_covariances(mi_ctx* c, const float* cloud_xyz, int n,
     a.epsilon = a.plane ? (double)epsilon : 0.0;
     a.cov6 = b.out_cov.p; a.count = count ? b.out_count.p : nullptr;
     // host-side shape checks before the hand-written kernel runs: every array it indexes is as long as the launch assumes
-    if (!search_front_fits(b.front, f) || b.out_cov.cap < 6 * np || (count && b.out_count.cap < np)) {
+    if (!search_front_fits(b.front, f) || !bufs.fits()) {
         set_error("internal: %s buffers shorter than the launch", who);
         return MI_ERR_STATE;
     }
     MI_TRY(search_front_timed_launch(c, b.front, clock, [&] { return knn_covariances(f.g, a, dist_mode == MI_DIST_FMA, c->stream); }));
 
-    MI_HIP(hipMemcpyAsync(cov6, b.out_cov.p, sizeof(float) * 6 * np, hipMemcpyDeviceToHost, c->stream));
-    if (count) MI_HIP(hipMemcpyAsync(count, b.out_count.p, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(bufs.download(c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
     MI_TRY(clock.mark(6));
     clock.finish();
@@ -85,9 +84,10 @@ int gicp_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* bef
 {
     mi_ctx::GicpBuffers& b = c->gicp;
     const size_t np = (size_t)n, mp = (size_t)m;
+    CallBuffers bufs;
     MI_TRY(search_front_reserve(b.front, np, mp, false));
-    MI_TRY(b.cov_staging.reserve(6 * std::max(np, mp)));
-    MI_TRY(b.cov_a.reserve(2 * mp)); MI_TRY(b.cov_b_in.reserve(2 * np)); MI_TRY(b.cov_b.reserve(2 * np)); MI_TRY(b.cov_bad.reserve(2));
+    MI_TRY(bufs.need(b.cov_staging, 6 * std::max(np, mp)));
+    MI_TRY(bufs.need(b.cov_a, 2 * mp)); MI_TRY(bufs.need(b.cov_b_in, 2 * np)); MI_TRY(bufs.need(b.cov_b, 2 * np)); MI_TRY(bufs.need(b.cov_bad, 2));
     MI_TRY(pose_loop_reserve(b.loop, n, want_idx));
     MI_TRY(clock.mark(0));
 
@@ -128,7 +128,7 @@ int gicp_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* bef
     a->rows = b.loop.rows.p;
     a->idx = want_idx ? b.loop.out_idx.p : nullptr;
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (!search_front_fits(b.front, *f) || b.cov_a.cap < 2 * mp || b.cov_b.cap < 2 * np || !pose_loop_fits(b.loop, n, want_idx)) {
+    if (!search_front_fits(b.front, *f) || !bufs.fits() || !pose_loop_fits(b.loop, n, want_idx)) {
         set_error("internal: %s buffers shorter than the launch", who);
         return MI_ERR_STATE;
     }
@@ -181,9 +181,4 @@ extern "C" int mi_gicp_system(mi_ctx* c, const float* before_xyz, const float* b
     return pose_loop_system_finish(c, clock, h, out_sums, out_centre);
 }
 
-extern "C" int mi_icp_gicp_times(mi_ctx* c, double out_ms[MI_GICP_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_icp_gicp_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_GICP_STAGES; i++) out_ms[i] = c->gicp.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_icp_gicp_times(mi_ctx* c, double out_ms[MI_GICP_STAGES]) { return stage_times("mi_icp_gicp_times", c ? c->gicp.ms : nullptr, out_ms); }

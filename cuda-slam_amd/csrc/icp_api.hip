@@ -261,12 +261,7 @@ extern "C" int mi_icp_load(mi_ctx* c, const float* before_xyz, int n_before, con
     return MI_OK;
 }
 
-extern "C" int mi_icp_load_times(mi_ctx* c, double out_ms[MI_LOAD_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_icp_load_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_LOAD_STAGES; i++) out_ms[i] = c->prob.load_ms[i];
-    return MI_OK;
-}
+extern "C" int mi_icp_load_times(mi_ctx* c, double out_ms[MI_LOAD_STAGES]) { return stage_times("mi_icp_load_times", c ? c->prob.load_ms : nullptr, out_ms); }
 
 // The one place an IcpRules is filled: the loaded problem's, the batch call's, mi_kabsch's (svd_ieee: the context's MISLAM_SVD_IEEE switch)
 static IcpRules icp_rules(const mi_icp_params& p, int m_total, int svd_ieee)

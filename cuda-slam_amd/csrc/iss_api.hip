@@ -47,13 +47,14 @@ extern "C" int mi_iss_keypoints(mi_ctx* c, const float* cloud_xyz, int n, const 
 
     const size_t np = (size_t)n;
     const int tiles = outlier_scan_tiles(n);
+    CallBuffers bufs;                  // (in the order of the download)
     MI_TRY(search_front_reserve(b.front, np, np, true));
-    MI_TRY(b.ostate.reserve(1));
-    MI_TRY(b.saliency.reserve(np)); MI_TRY(b.flag.reserve(np)); MI_TRY(b.tile_counts.reserve((size_t)tiles));
-    if (eigenvalues) MI_TRY(b.eigenvalues.reserve(3 * np));
-    if (neighbours) MI_TRY(b.neighbours.reserve(np));
-    if (out_xyz) MI_TRY(b.out_xyz.reserve(3 * np));
-    if (out_index) MI_TRY(b.out_index.reserve(np));
+    MI_TRY(bufs.watch(b.front.staging, 3 * np));                                   // the front end's; what the compaction gathers from
+    MI_TRY(bufs.need(b.ostate, 1));
+    MI_TRY(bufs.need(b.flag, np, is_keypoint)); MI_TRY(bufs.need(b.saliency, np, saliency)); MI_TRY(bufs.need(b.tile_counts, (size_t)tiles));
+    MI_TRY(bufs.result(b.eigenvalues, 3 * np, eigenvalues)); MI_TRY(bufs.result(b.neighbours, np, neighbours));
+    if (out_xyz) MI_TRY(bufs.need(b.out_xyz, 3 * np));                            // (their rows go once their number is known)
+    if (out_index) MI_TRY(bufs.need(b.out_index, np));
     MI_TRY(clock.mark(0));
 
     SearchFront f;
@@ -65,9 +66,7 @@ extern "C" int mi_iss_keypoints(mi_ctx* c, const float* cloud_xyz, int n, const 
     MI_TRY(search_front_index_and_order(c, b.front, clock, "mi_iss_keypoints", ppc, &f));
 
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (!search_front_fits(b.front, f) || b.front.staging.cap < 3 * np || b.saliency.cap < np || b.flag.cap < np || b.tile_counts.cap < (size_t)tiles ||
-        (eigenvalues && b.eigenvalues.cap < 3 * np) || (neighbours && b.neighbours.cap < np) || (out_xyz && b.out_xyz.cap < 3 * np) ||
-        (out_index && b.out_index.cap < np)) {
+    if (!search_front_fits(b.front, f) || !bufs.fits()) {
         set_error("internal: mi_iss_keypoints buffers shorter than the launch");
         return MI_ERR_STATE;
     }
@@ -89,35 +88,19 @@ extern "C" int mi_iss_keypoints(mi_ctx* c, const float* cloud_xyz, int n, const 
     MI_HIP(iss_suppress(f.g, sa, fma, c->stream));
 
     MI_HIP(hipMemsetAsync(b.ostate.p, 0, sizeof(OutlierState), c->stream));
-    OutlierCompactArgs ca{};
-    ca.keep = b.flag.p; ca.xyz = b.front.staging.p; ca.n = n; ca.tile_counts = b.tile_counts.p;
-    ca.out_index = out_index ? b.out_index.p : nullptr; ca.out_xyz = out_xyz ? b.out_xyz.p : nullptr; ca.state = b.ostate.p;
-    MI_HIP(outlier_compact(ca, c->stream));
+    MI_TRY(compact_enqueue(c, b.front, b.flag.p, n, b.tile_counts.p, out_index ? b.out_index.p : nullptr, out_xyz ? b.out_xyz.p : nullptr, b.ostate.p));
 
     // the state once, with the per-point results; then the keypoints' rows, whose number the state has brought
-    OutlierState* os = reinterpret_cast<OutlierState*>(c->h_scratch);
-    MI_HIP(hipMemcpyAsync(os, b.ostate.p, sizeof(OutlierState), hipMemcpyDeviceToHost, c->stream));
-    if (is_keypoint) MI_HIP(hipMemcpyAsync(is_keypoint, b.flag.p, np, hipMemcpyDeviceToHost, c->stream));
-    if (saliency) MI_HIP(hipMemcpyAsync(saliency, b.saliency.p, sizeof(float) * np, hipMemcpyDeviceToHost, c->stream));
-    if (eigenvalues) MI_HIP(hipMemcpyAsync(eigenvalues, b.eigenvalues.p, sizeof(float) * 3 * np, hipMemcpyDeviceToHost, c->stream));
-    if (neighbours) MI_HIP(hipMemcpyAsync(neighbours, b.neighbours.p, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(compact_read_state(c, b.ostate.p, 1));
+    MI_TRY(bufs.download(c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
-    const long long found = os->kept;
-    if (found < 0 || found > (long long)n) { set_error("internal: mi_iss_keypoints counted %lld keypoints among %d points", found, n); return MI_ERR_STATE; }
-    if (found > 0) {
-        if (out_xyz) MI_HIP(hipMemcpyAsync(out_xyz, b.out_xyz.p, sizeof(float) * 3 * (size_t)found, hipMemcpyDeviceToHost, c->stream));
-        if (out_index) MI_HIP(hipMemcpyAsync(out_index, b.out_index.p, sizeof(int) * (size_t)found, hipMemcpyDeviceToHost, c->stream));
-        if (out_xyz || out_index) MI_HIP(hipStreamSynchronize(c->stream));
-    }
+    long long found;
+    if (!compact_kept(c, 0, n, &found)) { set_error("internal: mi_iss_keypoints counted %lld keypoints among %d points", found, n); return MI_ERR_STATE; }
+    MI_TRY(compact_download(c, found, out_xyz, b.out_xyz.p, out_index, b.out_index.p));
     *out_n = (int)found;
     MI_TRY(clock.mark(6));
     clock.finish();
     return MI_OK;
 }
 
-extern "C" int mi_iss_keypoints_times(mi_ctx* c, double out_ms[MI_ISS_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_iss_keypoints_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_ISS_STAGES; i++) out_ms[i] = c->iss.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_iss_keypoints_times(mi_ctx* c, double out_ms[MI_ISS_STAGES]) { return stage_times("mi_iss_keypoints_times", c ? c->iss.ms : nullptr, out_ms); }

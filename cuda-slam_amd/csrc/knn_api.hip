@@ -26,10 +26,9 @@ extern "C" int mi_knn_search(mi_ctx* c, const float* query_xyz, int n, const flo
     StageClock clock(c, b.ms);         // mi_knn_search_times
 
     const size_t np = (size_t)n, rows = np * (size_t)k;
+    CallBuffers bufs;
     MI_TRY(search_front_reserve(b.front, np, (size_t)m, self));
-    MI_TRY(b.out_idx.reserve(rows));
-    if (d2) MI_TRY(b.out_d2.reserve(rows));
-    if (count) MI_TRY(b.out_count.reserve(np));
+    MI_TRY(bufs.result(b.out_idx, rows, idx)); MI_TRY(bufs.result(b.out_d2, rows, d2)); MI_TRY(bufs.result(b.out_count, np, count));
     MI_TRY(clock.mark(0));
 
     SearchFront f;
@@ -44,24 +43,17 @@ extern "C" int mi_knn_search(mi_ctx* c, const float* query_xyz, int n, const flo
     for (int i = 0; i < 3; i++) a.hi[i] = q.hi[i];
     a.idx = b.out_idx.p; a.d2 = d2 ? b.out_d2.p : nullptr; a.count = count ? b.out_count.p : nullptr;
     // host-side shape checks before the hand-written kernel runs: every array it indexes is as long as the launch assumes
-    if (!search_front_fits(b.front, f) || b.out_idx.cap < rows || (d2 && b.out_d2.cap < rows) || (count && b.out_count.cap < np)) {
+    if (!search_front_fits(b.front, f) || !bufs.fits()) {
         set_error("internal: mi_knn_search buffers shorter than the launch");
         return MI_ERR_STATE;
     }
     MI_TRY(search_front_timed_launch(c, b.front, clock, [&] { return knn_search(f.g, a, dist_mode == MI_DIST_FMA, c->stream); }));
 
-    MI_HIP(hipMemcpyAsync(idx, b.out_idx.p, sizeof(int) * rows, hipMemcpyDeviceToHost, c->stream));
-    if (d2) MI_HIP(hipMemcpyAsync(d2, b.out_d2.p, sizeof(float) * rows, hipMemcpyDeviceToHost, c->stream));
-    if (count) MI_HIP(hipMemcpyAsync(count, b.out_count.p, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(bufs.download(c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
     MI_TRY(clock.mark(6));
     clock.finish();
     return MI_OK;
 }
 
-extern "C" int mi_knn_search_times(mi_ctx* c, double out_ms[MI_KNN_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_knn_search_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_KNN_STAGES; i++) out_ms[i] = c->knn.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_knn_search_times(mi_ctx* c, double out_ms[MI_KNN_STAGES]) { return stage_times("mi_knn_search_times", c ? c->knn.ms : nullptr, out_ms); }

@@ -24,10 +24,11 @@ extern "C" int mi_feature_match(mi_ctx* c, const float* query_feat, int n, const
     StageClock clock(c, b.ms);         // mi_feature_match_times
 
     const size_t nq = (size_t)n, nt = (size_t)m, d = (size_t)dim;
-    MI_TRY(b.query.reserve(nq * d)); MI_TRY(b.target.reserve(nt * d)); MI_TRY(b.qq.reserve(nq)); MI_TRY(b.tt.reserve(nt));
-    MI_TRY(b.bad.reserve(2)); MI_TRY(b.keys.reserve(nq)); MI_TRY(b.out_idx.reserve(nq));
-    if (mutual) MI_TRY(b.rev_keys.reserve(nt));
-    if (d2) MI_TRY(b.out_d2.reserve(nq));
+    CallBuffers bufs;
+    MI_TRY(bufs.need(b.query, nq * d)); MI_TRY(bufs.need(b.target, nt * d)); MI_TRY(bufs.need(b.qq, nq)); MI_TRY(bufs.need(b.tt, nt));
+    MI_TRY(bufs.need(b.bad, 2)); MI_TRY(bufs.need(b.keys, nq)); MI_TRY(bufs.result(b.out_idx, nq, idx));
+    if (mutual) MI_TRY(bufs.need(b.rev_keys, nt));
+    MI_TRY(bufs.result(b.out_d2, nq, d2));
     MI_TRY(clock.mark(0));
 
     MI_TRY(host_to_device(c, b.query.p, query_feat, sizeof(float) * nq * d));
@@ -57,8 +58,7 @@ extern "C" int mi_feature_match(mi_ctx* c, const float* query_feat, int n, const
     fa.query = b.query.p; fa.target = b.target.p; fa.n = n; fa.m = m; fa.dim = dim;
     fa.keys = b.keys.p; fa.rev_keys = mutual ? b.rev_keys.p : nullptr; fa.idx = b.out_idx.p; fa.d2 = d2 ? b.out_d2.p : nullptr;
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (b.query.cap < nq * d || b.target.cap < nt * d || b.qq.cap < nq || b.tt.cap < nt || b.keys.cap < nq || b.out_idx.cap < nq ||
-        (mutual && b.rev_keys.cap < nt) || (d2 && b.out_d2.cap < nq)) {
+    if (!bufs.fits()) {
         set_error("internal: %s buffers shorter than the launch", who);
         return MI_ERR_STATE;
     }
@@ -73,17 +73,11 @@ extern "C" int mi_feature_match(mi_ctx* c, const float* query_feat, int n, const
     MI_HIP(match_finish(fa, c->stream));
     MI_TRY(clock.mark(5));
 
-    MI_HIP(hipMemcpyAsync(idx, b.out_idx.p, sizeof(int) * nq, hipMemcpyDeviceToHost, c->stream));
-    if (d2) MI_HIP(hipMemcpyAsync(d2, b.out_d2.p, sizeof(float) * nq, hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(bufs.download(c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
     MI_TRY(clock.mark(6));
     clock.finish();
     return MI_OK;
 }
 
-extern "C" int mi_feature_match_times(mi_ctx* c, double out_ms[MI_MATCH_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_feature_match_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_MATCH_STAGES; i++) out_ms[i] = c->match.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_feature_match_times(mi_ctx* c, double out_ms[MI_MATCH_STAGES]) { return stage_times("mi_feature_match_times", c ? c->match.ms : nullptr, out_ms); }

@@ -54,9 +54,12 @@ extern "C" int mi_ndt_voxels(mi_ctx* c, const float* xyz, int n, float voxel_siz
 
     const size_t np = (size_t)n;
     const size_t sum_tiles = (np + VOX_SUM_TILE - 1) / VOX_SUM_TILE;
-    MI_TRY(b.q6.reserve(6 * np)); MI_TRY(b.front.reserve(6 * sum_tiles)); MI_TRY(b.back.reserve(6 * sum_tiles)); MI_TRY(b.fix.reserve(sum_tiles));
-    MI_TRY(b.icov.reserve(6 * np));
-    if (out_cov6) MI_TRY(b.cov.reserve(6 * np));
+    CallBuffers bufs;                  // (every result goes once the number of rows is known)
+    MI_TRY(bufs.need(b.q6, 6 * np)); MI_TRY(bufs.need(b.front, 6 * sum_tiles)); MI_TRY(bufs.need(b.back, 6 * sum_tiles)); MI_TRY(bufs.need(b.fix, sum_tiles));
+    MI_TRY(bufs.need(b.icov, 6 * np));
+    if (out_cov6) MI_TRY(bufs.need(b.cov, 6 * np));
+    // the voxel front end's, as the scatter and the finish read them
+    MI_TRY(bufs.watch(b.vox.out_xyz, 3 * np)); MI_TRY(bufs.watch(b.vox.out_count, np)); MI_TRY(bufs.watch(b.vox.row_of, np)); MI_TRY(bufs.watch(b.vox.run_start, np + 1));
     NdtScatterArgs a{};
     VoxState* st = nullptr;
     MI_TRY(voxel_front_run(c, who, b.vox, clock, xyz, n, voxel_size, origin3, &a.v, &st));
@@ -64,8 +67,7 @@ extern "C" int mi_ndt_voxels(mi_ctx* c, const float* xyz, int n, float voxel_siz
 
     a.front = b.front.p; a.back = b.back.p; a.fix = b.fix.p; a.q6 = b.q6.p;
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (b.q6.cap < 6 * np || b.front.cap < 6 * sum_tiles || b.back.cap < 6 * sum_tiles || b.fix.cap < sum_tiles || b.icov.cap < 6 * np ||
-        (out_cov6 && b.cov.cap < 6 * np) || b.vox.out_xyz.cap < 3 * np || b.vox.out_count.cap < np || b.vox.row_of.cap < np || b.vox.run_start.cap < np + 1) {
+    if (!bufs.fits()) {
         set_error("internal: %s buffers shorter than the launch", who);
         return MI_ERR_STATE;
     }
@@ -120,9 +122,10 @@ int check_arguments(const char* who, mi_ctx* c, const float* before_xyz, int n, 
 }
 
 // Stages 0 - 4 of either call and the state block at pose T: after it the step kernel's arguments are complete and checked against the buffers.
+// bufs: the call's list, which brings out_terms (null: not asked for) to the caller behind the step.
 int ndt_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* before_xyz, int n, const int* vox_coord, const float* vox_mean,
-                const float* vox_icov6, int nv, float voxel_size, const float* origin3, float outlier_ratio, const float* T, bool want_idx, bool want_terms,
-                NdtStepArgs* a, PlaneState* h)
+                const float* vox_icov6, int nv, float voxel_size, const float* origin3, float outlier_ratio, const float* T, bool want_idx,
+                unsigned char* out_terms, CallBuffers& bufs, NdtStepArgs* a, PlaneState* h)
 {
     mi_ctx::NdtBuffers& b = c->ndt;
     const size_t np = (size_t)n, vp = (size_t)nv;
@@ -133,13 +136,13 @@ int ndt_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* befo
     for (int i = 0; i < 4; i++)
         if (!std::isfinite(constants[i])) { set_error("%s: voxel_size %g and outlier_ratio %g leave fp64", who, (double)voxel_size, (double)outlier_ratio); return MI_ERR_INVALID_ARG; }
 
-    MI_TRY(b.staging.reserve(3 * np));
-    MI_TRY(b.ux.reserve(np)); MI_TRY(b.uy.reserve(np)); MI_TRY(b.uz.reserve(np)); MI_TRY(b.qx.reserve(np)); MI_TRY(b.qy.reserve(np)); MI_TRY(b.qz.reserve(np));
-    MI_TRY(b.range_lo_hi.reserve(2 * 6 * KNN_RANGE_BLOCKS)); MI_TRY(b.range_bad.reserve(2 * KNN_RANGE_BLOCKS)); MI_TRY(b.kstate.reserve(1)); MI_TRY(b.order.reserve(np));
-    MI_TRY(b.vcoord.reserve(3 * vp)); MI_TRY(b.vmean.reserve(3 * vp)); MI_TRY(b.vicov.reserve(6 * vp)); MI_TRY(b.mean4.reserve(vp)); MI_TRY(b.icov4.reserve(2 * vp));
-    MI_TRY(b.mstate.reserve(1)); MI_TRY(b.hkeys.reserve((size_t)capacity)); MI_TRY(b.hvals.reserve((size_t)capacity));
+    MI_TRY(bufs.need(b.staging, 3 * np));
+    MI_TRY(bufs.need(b.ux, np)); MI_TRY(bufs.need(b.uy, np)); MI_TRY(bufs.need(b.uz, np)); MI_TRY(bufs.need(b.qx, np)); MI_TRY(bufs.need(b.qy, np)); MI_TRY(bufs.need(b.qz, np));
+    MI_TRY(bufs.need(b.range_lo_hi, 2 * 6 * KNN_RANGE_BLOCKS)); MI_TRY(bufs.need(b.range_bad, 2 * KNN_RANGE_BLOCKS)); MI_TRY(bufs.need(b.kstate, 1)); MI_TRY(bufs.need(b.order, np));
+    MI_TRY(bufs.need(b.vcoord, 3 * vp)); MI_TRY(bufs.need(b.vmean, 3 * vp)); MI_TRY(bufs.need(b.vicov, 6 * vp)); MI_TRY(bufs.need(b.mean4, vp)); MI_TRY(bufs.need(b.icov4, 2 * vp));
+    MI_TRY(bufs.need(b.mstate, 1)); MI_TRY(bufs.need(b.hkeys, (size_t)capacity)); MI_TRY(bufs.need(b.hvals, (size_t)capacity));
     MI_TRY(pose_loop_reserve(b.loop, n, want_idx));
-    if (want_terms) MI_TRY(b.out_terms.reserve(np));
+    MI_TRY(bufs.result(b.out_terms, np, out_terms));
     MortonArgs ma{};
     MI_TRY(morton_args(b.morton, b.ux.p, b.uy.p, b.uz.p, n, b.order.p, &ma));
     MI_TRY(clock.mark(0));
@@ -193,7 +196,7 @@ int ndt_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* befo
     for (int k = 0; k < 3 && any; k++) centre[k] = 0.5f * (ndt_key_float(hs->lo[k]) + ndt_key_float(hs->hi[k]));
 
     MI_HIP(hipMemsetAsync(b.hkeys.p, 0xff, sizeof(unsigned long long) * (size_t)capacity, c->stream));      // every slot NDT_KEY_EMPTY
-    if (b.hkeys.cap < capacity || b.hvals.cap < capacity || b.vcoord.cap < 3 * vp || b.icov4.cap < 2 * vp || b.mean4.cap < vp) {
+    if (!bufs.fits()) {
         set_error("internal: %s buffers shorter than the launch", who);
         return MI_ERR_STATE;
     }
@@ -217,10 +220,9 @@ int ndt_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* befo
     a->h = constants[2]; a->k = constants[3];
     a->rows = b.loop.rows.p;
     a->idx = want_idx ? b.loop.out_idx.p : nullptr;
-    a->terms = want_terms ? b.out_terms.p : nullptr;
+    a->terms = out_terms ? b.out_terms.p : nullptr;
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (b.qx.cap < np || b.qy.cap < np || b.qz.cap < np || b.order.cap < np || !pose_loop_fits(b.loop, n, want_idx) ||
-        (want_terms && b.out_terms.cap < np)) {
+    if (!bufs.fits() || !pose_loop_fits(b.loop, n, want_idx)) {
         set_error("internal: %s buffers shorter than the launch", who);
         return MI_ERR_STATE;
     }
@@ -245,7 +247,8 @@ extern "C" int mi_ndt_register(mi_ctx* c, const float* before_xyz, int n, const 
 
     NdtStepArgs a;
     PlaneState h;
-    MI_TRY(ndt_prepare(c, who, clock, before_xyz, n, vox_coord, vox_mean, vox_icov6, nv, voxel_size, origin3, p->outlier_ratio, init_T, false, false, &a, &h));
+    CallBuffers bufs;
+    MI_TRY(ndt_prepare(c, who, clock, before_xyz, n, vox_coord, vox_mean, vox_icov6, nv, voxel_size, origin3, p->outlier_ratio, init_T, false, nullptr, bufs, &a, &h));
 
     MI_TRY(pose_loop_run(c, b.loop, clock, who, n, loop, &h, [&] { return ndt_step(a, p->neighbourhood, c->stream); }));
     return pose_loop_results(clock, h, out_T, iterations, score, stop_reason);
@@ -265,17 +268,13 @@ extern "C" int mi_ndt_system(mi_ctx* c, const float* before_xyz, int n, const in
 
     NdtStepArgs a;
     PlaneState h;
-    MI_TRY(ndt_prepare(c, who, clock, before_xyz, n, vox_coord, vox_mean, vox_icov6, nv, voxel_size, origin3, outlier_ratio, T, out_idx != nullptr,
-                       out_terms != nullptr, &a, &h));
+    CallBuffers bufs;
+    MI_TRY(ndt_prepare(c, who, clock, before_xyz, n, vox_coord, vox_mean, vox_icov6, nv, voxel_size, origin3, outlier_ratio, T, out_idx != nullptr, out_terms,
+                       bufs, &a, &h));
 
     MI_TRY(pose_loop_system_run(c, b.loop, clock, n, &h, out_idx, [&] { return ndt_step(a, neighbourhood, c->stream); }));
-    if (out_terms) MI_HIP(hipMemcpyAsync(out_terms, b.out_terms.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(bufs.download(c->stream));
     return pose_loop_system_finish(c, clock, h, out_sums, out_centre);
 }
 
-extern "C" int mi_ndt_times(mi_ctx* c, double out_ms[MI_NDT_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_ndt_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_NDT_STAGES; i++) out_ms[i] = c->ndt.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_ndt_times(mi_ctx* c, double out_ms[MI_NDT_STAGES]) { return stage_times("mi_ndt_times", c ? c->ndt.ms : nullptr, out_ms); }

@@ -28,10 +28,9 @@ extern "C" int mi_estimate_normals(mi_ctx* c, const float* cloud_xyz, int n, int
     StageClock clock(c, b.ms);         // mi_estimate_normals_times
 
     const size_t np = (size_t)n;
+    CallBuffers bufs;
     MI_TRY(search_front_reserve(b.front, np, np, true));
-    MI_TRY(b.out_normals.reserve(3 * np));
-    if (curvature) MI_TRY(b.out_curvature.reserve(np));
-    if (count) MI_TRY(b.out_count.reserve(np));
+    MI_TRY(bufs.result(b.out_normals, 3 * np, normals_xyz)); MI_TRY(bufs.result(b.out_curvature, np, curvature)); MI_TRY(bufs.result(b.out_count, np, count));
     MI_TRY(clock.mark(0));
 
     SearchFront f;
@@ -47,24 +46,17 @@ extern "C" int mi_estimate_normals(mi_ctx* c, const float* cloud_xyz, int n, int
     for (int i = 0; i < 3; i++) a.view[i] = viewpoint3 ? (double)viewpoint3[i] : 0.0;
     a.normals = b.out_normals.p; a.curvature = curvature ? b.out_curvature.p : nullptr; a.count = count ? b.out_count.p : nullptr;
     // host-side shape checks before the hand-written kernel runs: every array it indexes is as long as the launch assumes
-    if (!search_front_fits(b.front, f) || b.out_normals.cap < 3 * np || (curvature && b.out_curvature.cap < np) || (count && b.out_count.cap < np)) {
+    if (!search_front_fits(b.front, f) || !bufs.fits()) {
         set_error("internal: mi_estimate_normals buffers shorter than the launch");
         return MI_ERR_STATE;
     }
     MI_TRY(search_front_timed_launch(c, b.front, clock, [&] { return knn_normals(f.g, a, dist_mode == MI_DIST_FMA, c->stream); }));
 
-    MI_HIP(hipMemcpyAsync(normals_xyz, b.out_normals.p, sizeof(float) * 3 * np, hipMemcpyDeviceToHost, c->stream));
-    if (curvature) MI_HIP(hipMemcpyAsync(curvature, b.out_curvature.p, sizeof(float) * np, hipMemcpyDeviceToHost, c->stream));
-    if (count) MI_HIP(hipMemcpyAsync(count, b.out_count.p, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(bufs.download(c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
     MI_TRY(clock.mark(6));
     clock.finish();
     return MI_OK;
 }
 
-extern "C" int mi_estimate_normals_times(mi_ctx* c, double out_ms[MI_NORMALS_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_estimate_normals_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_NORMALS_STAGES; i++) out_ms[i] = c->normals.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_estimate_normals_times(mi_ctx* c, double out_ms[MI_NORMALS_STAGES]) { return stage_times("mi_estimate_normals_times", c ? c->normals.ms : nullptr, out_ms); }

@@ -49,14 +49,15 @@ extern "C" int mi_remove_outliers(mi_ctx* c, const float* cloud_xyz, int n, cons
 
     const size_t np = (size_t)n;
     const int tiles = outlier_scan_tiles(n), stat_blocks = outlier_stat_blocks(n);
+    CallBuffers bufs;                  // (in the order of the download)
     MI_TRY(search_front_reserve(b.front, np, np, true));
-    MI_TRY(b.ostate.reserve(1));
-    MI_TRY(b.keep.reserve(np)); MI_TRY(b.tile_counts.reserve((size_t)tiles));
-    if (statistical) { MI_TRY(b.score.reserve(np)); MI_TRY(b.partials.reserve((size_t)stat_blocks)); }
-    if (!statistical || neighbours) MI_TRY(b.count.reserve(np));
-    if (statistical && mean_distance) MI_TRY(b.out_mean.reserve(np));
-    if (out_xyz) MI_TRY(b.out_xyz.reserve(3 * np));
-    if (out_index) MI_TRY(b.out_index.reserve(np));
+    MI_TRY(bufs.watch(b.front.staging, 3 * np));                                   // the front end's; what the compaction gathers from
+    MI_TRY(bufs.need(b.ostate, 1));
+    MI_TRY(bufs.need(b.keep, np, keep)); MI_TRY(bufs.need(b.tile_counts, (size_t)tiles));
+    if (statistical) { MI_TRY(bufs.need(b.score, np)); MI_TRY(bufs.need(b.partials, (size_t)stat_blocks)); MI_TRY(bufs.result(b.out_mean, np, mean_distance)); }
+    if (!statistical || neighbours) MI_TRY(bufs.need(b.count, np, neighbours));
+    if (out_xyz) MI_TRY(bufs.need(b.out_xyz, 3 * np));                            // (their rows go once their number is known)
+    if (out_index) MI_TRY(bufs.need(b.out_index, np));
     MI_TRY(clock.mark(0));
 
     SearchFront f;
@@ -67,9 +68,7 @@ extern "C" int mi_remove_outliers(mi_ctx* c, const float* cloud_xyz, int n, cons
     MI_TRY(search_front_index_and_order(c, b.front, clock, "mi_remove_outliers", ppc, &f));
 
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (!search_front_fits(b.front, f) || b.front.staging.cap < 3 * np || b.keep.cap < np || b.tile_counts.cap < (size_t)tiles ||
-        (statistical && (b.score.cap < np || b.partials.cap < (size_t)stat_blocks)) || ((!statistical || neighbours) && b.count.cap < np) ||
-        (statistical && mean_distance && b.out_mean.cap < np) || (out_xyz && b.out_xyz.cap < 3 * np) || (out_index && b.out_index.cap < np)) {
+    if (!search_front_fits(b.front, f) || !bufs.fits()) {
         set_error("internal: mi_remove_outliers buffers shorter than the launch");
         return MI_ERR_STATE;
     }
@@ -96,21 +95,15 @@ extern "C" int mi_remove_outliers(mi_ctx* c, const float* cloud_xyz, int n, cons
         MI_HIP(hipMemsetAsync(b.ostate.p, 0, sizeof(OutlierState), c->stream));    // (mean, stddev, threshold: the host states them below)
         MI_HIP(outlier_flags_radius(b.count.p, n, min_nb, b.keep.p, c->stream));
     }
-    OutlierCompactArgs ca{};
-    ca.keep = b.keep.p; ca.xyz = b.front.staging.p; ca.n = n; ca.tile_counts = b.tile_counts.p;
-    ca.out_index = out_index ? b.out_index.p : nullptr; ca.out_xyz = out_xyz ? b.out_xyz.p : nullptr; ca.state = b.ostate.p;
-    MI_HIP(outlier_compact(ca, c->stream));
+    MI_TRY(compact_enqueue(c, b.front, b.keep.p, n, b.tile_counts.p, out_index ? b.out_index.p : nullptr, out_xyz ? b.out_xyz.p : nullptr, b.ostate.p));
 
     // the state once, with the per-point results; then the kept rows, whose number the state has brought
-    OutlierState* os = reinterpret_cast<OutlierState*>(c->h_scratch);
-    static_assert(sizeof(OutlierState) <= 64 * sizeof(float), "OutlierState must fit the context's pinned scratch");
-    MI_HIP(hipMemcpyAsync(os, b.ostate.p, sizeof(OutlierState), hipMemcpyDeviceToHost, c->stream));
-    if (keep) MI_HIP(hipMemcpyAsync(keep, b.keep.p, np, hipMemcpyDeviceToHost, c->stream));
-    if (statistical && mean_distance) MI_HIP(hipMemcpyAsync(mean_distance, b.out_mean.p, sizeof(float) * np, hipMemcpyDeviceToHost, c->stream));
-    if (neighbours) MI_HIP(hipMemcpyAsync(neighbours, b.count.p, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(compact_read_state(c, b.ostate.p, 1));
+    MI_TRY(bufs.download(c->stream));
     MI_HIP(hipStreamSynchronize(c->stream));
-    const long long kept = os->kept;
-    if (kept < 0 || kept > (long long)n) { set_error("internal: mi_remove_outliers kept %lld of %d points", kept, n); return MI_ERR_STATE; }
+    const OutlierState* os = compact_host_state(c);
+    long long kept;
+    if (!compact_kept(c, 0, n, &kept)) { set_error("internal: mi_remove_outliers kept %lld of %d points", kept, n); return MI_ERR_STATE; }
     if (stats) {
         *stats = mi_outlier_stats{};
         stats->mean = statistical ? os->mean : 0.0;
@@ -118,20 +111,11 @@ extern "C" int mi_remove_outliers(mi_ctx* c, const float* cloud_xyz, int n, cons
         stats->threshold = statistical ? os->threshold : (double)min_nb;
         stats->kept = kept;
     }
-    if (kept > 0) {
-        if (out_xyz) MI_HIP(hipMemcpyAsync(out_xyz, b.out_xyz.p, sizeof(float) * 3 * (size_t)kept, hipMemcpyDeviceToHost, c->stream));
-        if (out_index) MI_HIP(hipMemcpyAsync(out_index, b.out_index.p, sizeof(int) * (size_t)kept, hipMemcpyDeviceToHost, c->stream));
-        if (out_xyz || out_index) MI_HIP(hipStreamSynchronize(c->stream));
-    }
+    MI_TRY(compact_download(c, kept, out_xyz, b.out_xyz.p, out_index, b.out_index.p));
     *out_n = (int)kept;
     MI_TRY(clock.mark(6));
     clock.finish();
     return MI_OK;
 }
 
-extern "C" int mi_remove_outliers_times(mi_ctx* c, double out_ms[MI_OUTLIER_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_remove_outliers_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_OUTLIER_STAGES; i++) out_ms[i] = c->outlier.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_remove_outliers_times(mi_ctx* c, double out_ms[MI_OUTLIER_STAGES]) { return stage_times("mi_remove_outliers_times", c ? c->outlier.ms : nullptr, out_ms); }

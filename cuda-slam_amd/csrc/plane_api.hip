@@ -44,8 +44,9 @@ int plane_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* be
 {
     mi_ctx::PlaneBuffers& b = c->plane;
     const size_t np = (size_t)n, mp = (size_t)m;
+    CallBuffers bufs;
     MI_TRY(search_front_reserve(b.front, np, mp, false));
-    MI_TRY(b.nx.reserve(mp)); MI_TRY(b.ny.reserve(mp)); MI_TRY(b.nz.reserve(mp)); MI_TRY(b.normals.reserve(mp)); MI_TRY(b.nstate.reserve(1));
+    MI_TRY(bufs.need(b.nx, mp)); MI_TRY(bufs.need(b.ny, mp)); MI_TRY(bufs.need(b.nz, mp)); MI_TRY(bufs.need(b.normals, mp)); MI_TRY(bufs.need(b.nstate, 1));
     MI_TRY(pose_loop_reserve(b.loop, n, want_idx));
     MI_TRY(clock.mark(0));
 
@@ -68,7 +69,7 @@ int plane_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* be
     a->rows = b.loop.rows.p;
     a->idx = want_idx ? b.loop.out_idx.p : nullptr;
     // host-side shape checks before the hand-written kernels run: every array they index is as long as the launches assume
-    if (!search_front_fits(b.front, *f) || b.normals.cap < mp || !pose_loop_fits(b.loop, n, want_idx)) {
+    if (!search_front_fits(b.front, *f) || !bufs.fits() || !pose_loop_fits(b.loop, n, want_idx)) {
         set_error("internal: %s buffers shorter than the launch", who);
         return MI_ERR_STATE;
     }
@@ -121,9 +122,4 @@ extern "C" int mi_plane_system(mi_ctx* c, const float* before_xyz, int n, const 
     return pose_loop_system_finish(c, clock, h, out_sums, out_centre);
 }
 
-extern "C" int mi_icp_plane_times(mi_ctx* c, double out_ms[MI_PLANE_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_icp_plane_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_PLANE_STAGES; i++) out_ms[i] = c->plane.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_icp_plane_times(mi_ctx* c, double out_ms[MI_PLANE_STAGES]) { return stage_times("mi_icp_plane_times", c ? c->plane.ms : nullptr, out_ms); }

@@ -217,9 +217,4 @@ extern "C" int mi_ransac_register(mi_ctx* c, const float* src_xyz, int n, const 
     return MI_OK;
 }
 
-extern "C" int mi_ransac_register_times(mi_ctx* c, double out_ms[MI_RANSAC_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_ransac_register_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_RANSAC_STAGES; i++) out_ms[i] = c->ransac.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_ransac_register_times(mi_ctx* c, double out_ms[MI_RANSAC_STAGES]) { return stage_times("mi_ransac_register_times", c ? c->ransac.ms : nullptr, out_ms); }

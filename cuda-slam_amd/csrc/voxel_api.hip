@@ -147,9 +147,4 @@ extern "C" int mi_voxel_downsample(mi_ctx* c, const float* xyz, int n, float vox
     return MI_OK;
 }
 
-extern "C" int mi_voxel_downsample_times(mi_ctx* c, double out_ms[MI_VOXEL_STAGES])
-{
-    if (!c || !out_ms) { set_error("mi_voxel_downsample_times: null argument"); return MI_ERR_INVALID_ARG; }
-    for (int i = 0; i < MI_VOXEL_STAGES; i++) out_ms[i] = c->vox.ms[i];
-    return MI_OK;
-}
+extern "C" int mi_voxel_downsample_times(mi_ctx* c, double out_ms[MI_VOXEL_STAGES]) { return stage_times("mi_voxel_downsample_times", c ? c->vox.ms : nullptr, out_ms); }
