@@ -88,7 +88,7 @@ struct ProfileSpan {
     hipEvent_t e0, e1;
 };
 
-struct CpdWorkspace;   // cpd_api.hip
+struct CpdWorkspace;   // cpd_workspace.h
 struct PrepState;      // prepare_api.hip
 
 }  // namespace mislam

@@ -12,7 +12,7 @@ constexpr int FGT_GRID_SWEEP_MIN_POINTS = 65536;   // above this the K-centre sw
 constexpr int FGT_GRID_SWEEP_BLOCKS = 1024;
 constexpr size_t FGT_SWEEP_SCRATCH_BYTES = (size_t)(FGT_GRID_SWEEP_BLOCKS + 1) * 20;   // current centre + per-workgroup arg-max records
 
-// Monomial tables of one truncation order p, device resident (built on the host, cpd_api.hip).  Index t is the reference's
+// Monomial tables of one truncation order p, device resident (built on the host, cpd_plan.hpp).  Index t is the reference's
 // graded order (fgt.cpp:124-137): degree by degree, x-power descending, then y-power descending.
 struct FgtTables {
     const unsigned int* mono;   // [pd]  a | b << 8 | c << 16

@@ -154,7 +154,7 @@ def main():
     exact = ((b64[:, None, :] - A64[None, :, :]) ** 2).sum()
     assert abs(total - exact) < 1e-9 * exact
 
-    # C3 (round 6) -- the FGT / hybrid CPD modes with their E-step's QUERIES sharded (cpd_api.hip cpd_estep_fgt_enqueue): both clouds whole on every rank, the
+    # C3 (round 6) -- the FGT / hybrid CPD modes with their E-step's QUERIES sharded (cpd_fgt_api.hip cpd_estep_fgt_enqueue): both clouds whole on every rank, the
     # coefficient tables replicated; rank r evaluates the first transform at fixed points mi_shard_range(n), writes THEIR weights (1/den, x/den: a float4 per point),
     # fills the rest with all-ones and the ranks take an element-wise UNSIGNED minimum -- which must hand every rank every weight bit for bit, whatever the
     # pattern (NaN payloads, -0, denormals, infinities: a sum with zeros would not) -- then evaluates the second transform at moving points mi_shard_range(m);

@@ -34,7 +34,7 @@ WEIGHTS = (1e-6, 0.3, 1.0 - 1e-6)
 PATHS = ("valu", "mfma", "culled", "every_pair")
 
 
-# ---- the plan (cpd_api.hip plan_chunks, cpd_load) ----
+# ---- the plan (cpd_plan.hpp plan_chunks, cpd_chunk_plan; tests/test_cpd_plan.py holds the two together) ----
 def plan_chunks(owners, owner_r, stream_len, cu_count=CU_COUNT):
     owner_blocks = max(1, (owners + 256 * owner_r - 1) // (256 * owner_r))
     ch = (cu_count * 8 + owner_blocks - 1) // owner_blocks

@@ -43,7 +43,7 @@ CONTEXTS = {"default": None, "splits0": ("MISLAM_FGT_MODEL_SPLITS", "0"), "lists
 f32 = np.float32
 
 
-# ---- the plan (cpd_api.hip cpd_estep_fgt_enqueue, cpd_fgt.hip) ----
+# ---- the plan (cpd_plan.hpp, cpd_fgt_api.hip cpd_estep_fgt_enqueue, cpd_fgt.hip; tests/test_cpd_plan.py holds the first to these) ----
 def cluster_count(m, n, sigma2, sigma2_init):
     """fgt_cluster_count: (int) std::round(min(n, m, 50 + s2i / s2)) in float."""
     k = min(f32(n), f32(m), f32(50.0) + f32(sigma2_init) / f32(sigma2))
