@@ -2,10 +2,12 @@
 
 This module is plumbing for the Python-side callers in this repository (tests, bench.py, __graft_entry__): it passes host
 numpy buffers straight through to the C entry points and adds nothing of its own.  There is deliberately no fallback: if
-the shared library is missing, or no HIP device is usable, the calls raise.
+the shared library is missing, or no HIP device is usable, the calls raise.  The header is the only statement of the C interface:
+lib() parses it and gives every function its argument and return types at load, and nothing else in this module types a call.
 """
 import ctypes as C
 import os
+import re as _re                     # under a private name: the module's public names are its interface
 
 import numpy as np
 
@@ -32,28 +34,6 @@ CPD_APPROX_NONE, CPD_APPROX_FULL, CPD_APPROX_HYBRID = 0, 1, 2
 UNIQUE_ID_BYTES = 128
 EXCHANGE_MIN_U64, EXCHANGE_SUM_F64 = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)      # mi_exchange_fn
-
-# every symbol include/mi_slam.h declares (tests check that the library exports each of them)
-EXPORTS = [
-    "mi_abi_version", "mi_last_error", "mi_device_count", "mi_ctx_create", "mi_dist_unique_id", "mi_ctx_create_dist",
-    "mi_ctx_create_exchange", "mi_runtime_info", "mi_ctx_preload", "mi_ctx_rank", "mi_dist_info", "mi_shard_range", "mi_source_share", "mi_pack_key", "mi_unpack_key", "mi_ctx_destroy", "mi_ctx_synchronize", "mi_icp_params_default", "mi_icp_params_cuda_slam",
-    "mi_icp_register", "mi_icp_load", "mi_icp_reset", "mi_icp_run", "mi_icp_auto_batch", "mi_icp_result", "mi_icp_batch_route", "mi_icp_register_batch", "mi_nn_search", "mi_nn_search_ex", "mi_cross_moments", "mi_kabsch",
-    "mi_transform_mse", "mi_cpd_params_default", "mi_cpd_register", "mi_cpd_batch_route", "mi_cpd_register_batch", "mi_cpd_sigma_squared", "mi_cpd_sigma_squared_mode", "mi_cpd_estep",
-    "mi_cpd_estep_truncated", "mi_cpd_estep_fgt", "mi_fgt_kcenter", "mi_fgt_kcenter_guided", "mi_fgt_tables", "mi_nicp_params_default", "mi_nicp_register",
-    "mi_prepare_params_default", "mi_prepare_cloud", "mi_voxel_index", "mi_voxel_downsample", "mi_voxel_downsample_times",
-    "mi_knn_search", "mi_knn_search_times", "mi_estimate_normals", "mi_estimate_normals_times",
-    "mi_outlier_params_default", "mi_remove_outliers", "mi_remove_outliers_times",
-    "mi_iss_params_default", "mi_iss_keypoints", "mi_iss_keypoints_times",
-    "mi_cluster_params_default", "mi_cluster_dbscan", "mi_cluster_dbscan_times",
-    "mi_plane_params_default", "mi_icp_plane_register", "mi_plane_system", "mi_icp_plane_times",
-    "mi_estimate_covariances", "mi_icp_gicp_register", "mi_gicp_system", "mi_icp_gicp_times",
-    "mi_fpfh_features", "mi_fpfh_features_times",
-    "mi_feature_match", "mi_feature_match_times",
-    "mi_ransac_params_default", "mi_ransac_register", "mi_ransac_hypotheses", "mi_ransac_register_times",
-    "mi_ndt_constants", "mi_ndt_voxels", "mi_ndt_params_default", "mi_ndt_register", "mi_ndt_system", "mi_ndt_times",
-    "mi_cpd_mstep", "mi_profile_enable", "mi_profile_select", "mi_profile_reset", "mi_profile_get", "mi_icp_load_times", "mi_profile_search_stats", "mi_profile_search_phases", "mi_selftest_sort_pairs", "mi_selftest_cloud_range", "mi_selftest_fail_loads", "mi_selftest_live_buffers", "mi_selftest_icp_schedule", "mi_selftest_cpd_last", "mi_selftest_nicp_candidates", "mi_nn_kernel_name",
-]
-
 
 class IcpParams(C.Structure):
     _fields_ = [("eps", C.c_float), ("max_iterations", C.c_int), ("max_distance_squared", C.c_float),
@@ -113,28 +93,68 @@ class MiSlamError(RuntimeError):
 
 
 _lib = None
-_f = C.POINTER(C.c_float)
-_i = C.POINTER(C.c_int)
-_u8 = C.POINTER(C.c_ubyte)
+
+
+# ---- the loader: the header is the only statement of the C interface; every prototype below is read from it
+_HEADER = os.path.join(os.path.dirname(_HERE), "include", "mi_slam.h")       # the tree's header, also when MISLAM_LIB names a variant build
+_SCALARS = {"int": C.c_int, "float": C.c_float, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong, "unsigned int": C.c_uint}
+_ARGUMENTS = dict(_SCALARS, mi_exchange_fn=EXCHANGE_FN)
+_RETURNS = dict(_SCALARS, **{"void": None, "const char*": C.c_char_p})
+
+
+def _parse_header(text):
+    """[(name, return text, [argument texts], restype, [argtypes])] of every mi_* prototype of a header's text.  An argument with a '*' or
+    a '[' is a c_void_p; what is left is the vocabulary above.  Anything else raises and names the declaration: no ctypes default is used."""
+    text = _re.sub(r"/\*.*?\*/", " ", text, flags=_re.S)
+    text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
+    out = []
+    for decl in text.split(";"):
+        if not _re.search(r"\bmi_\w+\s*\(", decl):
+            continue
+        decl = " ".join(decl.split())
+        m = _re.fullmatch(r"([\w\s*]+?)\s*\b(mi_\w+)\s*\(([^()]*)\)", decl)
+        if not m:
+            raise MiSlamError("mi_slam.h: cannot parse the declaration `%s`" % decl)
+        ret, name, args = _re.sub(r"\s*\*", "*", m.group(1)), m.group(2), [a.strip() for a in m.group(3).split(",")]
+        args = [] if args == ["void"] else args
+        if ret not in _RETURNS:
+            raise MiSlamError("mi_slam.h: return type `%s` is outside the binding's vocabulary in `%s`" % (ret, decl))
+        argtypes = []
+        for a in args:
+            scalar = _re.fullmatch(r"(.+?)\s*\b\w+", a)          # the type in front of the parameter's name
+            if "*" in a or "[" in a:
+                argtypes.append(C.c_void_p)
+            elif scalar and scalar.group(1) in _ARGUMENTS:
+                argtypes.append(_ARGUMENTS[scalar.group(1)])
+            else:
+                raise MiSlamError("mi_slam.h: argument `%s` is outside the binding's vocabulary in `%s`" % (a, decl))
+        out.append((name, ret, args, _RETURNS[ret], argtypes))
+    return out
+
+
+try:
+    with open(_HEADER) as _fh:
+        _PROTOTYPES = _parse_header(_fh.read())
+except OSError:
+    _PROTOTYPES = []                                          # lib() raises
+EXPORTS = [p[0] for p in _PROTOTYPES]                         # every symbol include/mi_slam.h declares
 
 
 def lib():
-    """Load libmislam.so (raises if it has not been built -- run __graft_entry__.build())."""
+    """Load libmislam.so (raises if it has not been built -- run __graft_entry__.build()) and give every function its header's types."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise MiSlamError("libmislam.so not built at %s: run `python -c 'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
-        _lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        _lib.mi_last_error.restype = C.c_char_p
-        _lib.mi_ctx_destroy.restype = None
-        _lib.mi_icp_params_default.restype = None
-        _lib.mi_icp_params_cuda_slam.restype = None
-        _lib.mi_cpd_params_default.restype = None
-        _lib.mi_prepare_params_default.restype = None
-        _lib.mi_pack_key.restype = C.c_ulonglong
-        _lib.mi_pack_key.argtypes = [C.c_float, C.c_int]
-        _lib.mi_unpack_key.restype = None
-        _lib.mi_unpack_key.argtypes = [C.c_ulonglong, _f, _i]
+        if not _PROTOTYPES:
+            raise MiSlamError("no mi_* prototype read from %s (is the header there?): the binding takes every type from it" % _HEADER)
+        loaded = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
+        for name, _, _, restype, argtypes in _PROTOTYPES:
+            if not hasattr(loaded, name):
+                raise MiSlamError("%s lacks %s, which mi_slam.h declares" % (LIB_PATH, name))
+            f = getattr(loaded, name)
+            f.restype, f.argtypes = restype, argtypes
+        _lib = loaded
     return _lib
 
 
@@ -143,8 +163,24 @@ def _check(rc):
         raise MiSlamError("libmislam error %d: %s" % (rc, lib().mi_last_error().decode()))
 
 
-def _fp(a):
-    return a.ctypes.data_as(_f)
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _raw(name):
+    """mi_<name> as the header types it, with pointers as Python ints, ctypes objects or None: returns the error code, raises nothing."""
+    return lambda *args: getattr(lib(), name)(*args)
+
+
+def _params(cls, default, kw):
+    """A parameter struct at the library's defaults (the function named `default`) with the fields of kw set."""
+    p = cls()
+    getattr(lib(), default)(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
 
 
 def _cloud(a):
@@ -161,44 +197,23 @@ def device_count():
 
 
 def icp_params(cuda_slam=False, **kw):
-    p = IcpParams()
-    (lib().mi_icp_params_cuda_slam if cuda_slam else lib().mi_icp_params_default)(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(IcpParams, "mi_icp_params_cuda_slam" if cuda_slam else "mi_icp_params_default", kw)
 
 
 def cpd_params(**kw):
-    p = CpdParams()
-    lib().mi_cpd_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(CpdParams, "mi_cpd_params_default", kw)
 
 
 def nicp_params(**kw):
-    p = NicpParams()
-    lib().mi_nicp_params_default.restype = None
-    lib().mi_nicp_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(NicpParams, "mi_nicp_params_default", kw)
 
 
 def fgt_tables(order):
     """Host-only: exponents (a, b, c) per monomial in the reference's graded order, C_k and the Horner slot (mi_fgt_tables)."""
     pd = C.c_int(0)
     _check(lib().mi_fgt_tables(int(order), None, None, None, C.byref(pd)))
-    mono = np.empty(pd.value, np.uint32)
-    ck = np.empty(pd.value, np.float32)
-    slot = np.empty(pd.value, np.int32)
-    _check(lib().mi_fgt_tables(int(order), mono.ctypes.data_as(C.POINTER(C.c_uint)), _fp(ck), slot.ctypes.data_as(_i), C.byref(pd)))
+    mono, ck, slot = np.empty(pd.value, np.uint32), np.empty(pd.value, np.float32), np.empty(pd.value, np.int32)
+    _check(lib().mi_fgt_tables(int(order), _ptr(mono), _ptr(ck), _ptr(slot), C.byref(pd)))
     exps = np.stack([mono & 0xff, (mono >> 8) & 0xff, (mono >> 16) & 0xff], axis=1).astype(np.int32)
     return exps, ck, slot
 
@@ -215,19 +230,10 @@ class IcpBatchInfo(C.Structure):
 
 def icp_batch_route(n_before, n_after, params):
     """1 if mi_icp_register_batch carries a problem of these sizes under these rules on the batched kernel, 0 if it takes the existing path."""
-    f = lib().mi_icp_batch_route
-    f.argtypes = [C.c_int, C.c_int, C.POINTER(IcpParams)]
-    f.restype = C.c_int
-    return f(int(n_before), int(n_after), C.byref(params))
+    return lib().mi_icp_batch_route(int(n_before), int(n_after), C.byref(params))
 
 
-def icp_register_batch_raw(handle, n_problems, before, before_range, after, after_range, params, out_T, iterations, error, stop_reason, info):
-    """mi_icp_register_batch with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_icp_register_batch
-    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                  C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f(handle, n_problems, before, before_range, after, after_range, params, out_T, iterations, error, stop_reason, info)
+icp_register_batch_raw = _raw("mi_icp_register_batch")
 
 
 class CpdBatchInfo(C.Structure):
@@ -236,19 +242,10 @@ class CpdBatchInfo(C.Structure):
 
 def cpd_batch_route(m_before, n_after, params):
     """1 if mi_cpd_register_batch carries a problem of these sizes under these rules on the batched kernel, 0 if it takes the existing path."""
-    f = lib().mi_cpd_batch_route
-    f.argtypes = [C.c_int, C.c_int, C.POINTER(CpdParams)]
-    f.restype = C.c_int
-    return f(int(m_before), int(n_after), C.byref(params))
+    return lib().mi_cpd_batch_route(int(m_before), int(n_after), C.byref(params))
 
 
-def cpd_register_batch_raw(handle, n_problems, before, before_range, after, after_range, params, out_sR_t, out_scale, iterations, error, stop_reason,
-                           info):
-    """mi_cpd_register_batch with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_cpd_register_batch
-    f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 11
-    f.restype = C.c_int
-    return f(handle, n_problems, before, before_range, after, after_range, params, out_sR_t, out_scale, iterations, error, stop_reason, info)
+cpd_register_batch_raw = _raw("mi_cpd_register_batch")
 
 
 def _batch_arrays(befores, afters, before_range, after_range):
@@ -275,12 +272,20 @@ def _batch_arrays(befores, afters, before_range, after_range):
     return before, br, after, ar
 
 
-def voxel_index_raw(p, origin, voxel, out):
-    """mi_voxel_index with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_voxel_index
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
-    f.restype = C.c_int
-    return f(p, origin, voxel, out)
+def _batch_call(befores, afters, before_range, after_range):
+    """What both batched calls start from: the four input arrays, the number of problems B and the per-problem outputs T [B, 16],
+    iterations, error and stop_reason [B]."""
+    arrays = _batch_arrays(befores, afters, before_range, after_range)
+    B = len(arrays[1])
+    return arrays, B, np.zeros((B, 16), np.float32), np.zeros(B, np.int32), np.zeros(B, np.float32), np.zeros(B, np.int32)
+
+
+def _batch_Rt(T):
+    M = T.reshape(-1, 4, 4).transpose(0, 2, 1)        # column-major 4x4 -> [row, col]
+    return M[:, :3, :3].copy(), M[:, :3, 3].copy()
+
+
+voxel_index_raw = _raw("mi_voxel_index")
 
 
 def voxel_index(p, origin, voxel):
@@ -292,31 +297,14 @@ def voxel_index(p, origin, voxel):
     return out
 
 
-def voxel_downsample_raw(handle, xyz, n, voxel, origin, out_xyz, out_n, out_count, out_coord, voxel_of_point):
-    """mi_voxel_downsample with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_voxel_downsample
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 6
-    f.restype = C.c_int
-    return f(handle, xyz, n, voxel, origin, out_xyz, out_n, out_count, out_coord, voxel_of_point)
+voxel_downsample_raw = _raw("mi_voxel_downsample")
 
 
 KNN_MAX_K = 32                      # MI_KNN_MAX_K
 
 
-def knn_search_raw(handle, query, n, cloud, m, k, dist_mode, max_d2, idx, d2, count):
-    """mi_knn_search with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_knn_search
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f(handle, query, n, cloud, m, k, dist_mode, max_d2, idx, d2, count)
-
-
-def estimate_normals_raw(handle, cloud, n, k, dist_mode, max_d2, viewpoint, normals, curvature, count):
-    """mi_estimate_normals with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_estimate_normals
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f(handle, cloud, n, k, dist_mode, max_d2, viewpoint, normals, curvature, count)
+knn_search_raw = _raw("mi_knn_search")
+estimate_normals_raw = _raw("mi_estimate_normals")
 
 
 OUTLIER_STATISTICAL, OUTLIER_RADIUS = 0, 1     # MI_OUTLIER_*
@@ -324,143 +312,52 @@ OUTLIER_STATISTICAL, OUTLIER_RADIUS = 0, 1     # MI_OUTLIER_*
 
 def outlier_params(**kw):
     """mi_outlier_params at its defaults (statistical, k = 16, std_ratio = 2, CPU rounding) with the given fields set."""
-    p = OutlierParams()
-    lib().mi_outlier_params_default.restype = None
-    lib().mi_outlier_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(OutlierParams, "mi_outlier_params_default", kw)
 
 
-def remove_outliers_raw(handle, cloud, n, params, out_xyz, out_index, out_n, keep, mean_distance, neighbours, stats):
-    """mi_remove_outliers with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_remove_outliers
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
-    f.restype = C.c_int
-    return f(handle, cloud, n, params, out_xyz, out_index, out_n, keep, mean_distance, neighbours, stats)
+remove_outliers_raw = _raw("mi_remove_outliers")
 
 
 def iss_params(**kw):
     """mi_iss_params at its defaults (gamma 0.975 and 0.975, min_neighbours 5, CPU rounding; both radii 0: set them) with the given fields set."""
-    p = IssParams()
-    lib().mi_iss_params_default.restype = None
-    lib().mi_iss_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(IssParams, "mi_iss_params_default", kw)
 
 
-def iss_keypoints_raw(handle, cloud, n, params, out_xyz, out_index, out_n, is_keypoint, saliency, eigenvalues, neighbours):
-    """mi_iss_keypoints with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_iss_keypoints
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
-    f.restype = C.c_int
-    return f(handle, cloud, n, params, out_xyz, out_index, out_n, is_keypoint, saliency, eigenvalues, neighbours)
+iss_keypoints_raw = _raw("mi_iss_keypoints")
 
 
 def cluster_params(**kw):
     """mi_cluster_params at its defaults (min_points 1, min_cluster_size 1, no upper limit, CPU rounding; radius 0: set it) with the given fields set."""
-    p = ClusterParams()
-    lib().mi_cluster_params_default.restype = None
-    lib().mi_cluster_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(ClusterParams, "mi_cluster_params_default", kw)
 
 
-def cluster_dbscan_raw(handle, cloud, n, params, labels, n_clusters, cluster_sizes, cluster_cap, is_core, grouped_index, n_grouped):
-    """mi_cluster_dbscan with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_cluster_dbscan
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3
-    f.restype = C.c_int
-    return f(handle, cloud, n, params, labels, n_clusters, cluster_sizes, cluster_cap, is_core, grouped_index, n_grouped)
+cluster_dbscan_raw = _raw("mi_cluster_dbscan")
 
 
 def plane_params(**kw):
     """mi_plane_params at its defaults (eps 1e-6 and 1e-6, 50 iterations, no distance limit, CPU rounding) with the given fields set."""
-    p = PlaneParams()
-    lib().mi_plane_params_default.restype = None
-    lib().mi_plane_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(PlaneParams, "mi_plane_params_default", kw)
 
 
-def icp_plane_register_raw(handle, before, n, after, normals, m, params, init_T, out_T, iterations, error, stop_reason):
-    """mi_icp_plane_register with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_icp_plane_register
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6
-    f.restype = C.c_int
-    return f(handle, before, n, after, normals, m, params, init_T, out_T, iterations, error, stop_reason)
-
-
-def plane_system_raw(handle, before, n, after, normals, m, T, dist_mode, max_d2, out_sums, out_centre, out_idx):
-    """mi_plane_system with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_plane_system
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f(handle, before, n, after, normals, m, T, dist_mode, max_d2, out_sums, out_centre, out_idx)
+icp_plane_register_raw = _raw("mi_icp_plane_register")
+plane_system_raw = _raw("mi_plane_system")
 
 
 COV_RAW, COV_PLANE = 0, 1     # MI_COV_*
 
 
-def estimate_covariances_raw(handle, cloud, n, k, dist_mode, max_d2, mode, epsilon, cov6, count):
-    """mi_estimate_covariances with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_estimate_covariances
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f(handle, cloud, n, k, dist_mode, max_d2, mode, epsilon, cov6, count)
-
-
-def icp_gicp_register_raw(handle, before, before_cov, n, after, after_cov, m, params, init_T, out_T, iterations, error, stop_reason):
-    """mi_icp_gicp_register with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_icp_gicp_register
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6
-    f.restype = C.c_int
-    return f(handle, before, before_cov, n, after, after_cov, m, params, init_T, out_T, iterations, error, stop_reason)
-
-
-def gicp_system_raw(handle, before, before_cov, n, after, after_cov, m, T, dist_mode, max_d2, out_sums, out_centre, out_idx):
-    """mi_gicp_system with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_gicp_system
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f(handle, before, before_cov, n, after, after_cov, m, T, dist_mode, max_d2, out_sums, out_centre, out_idx)
-
-
-def icp_gicp_times_raw(handle, out_ms):
-    """mi_icp_gicp_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_icp_gicp_times
-    f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
-    return f(handle, out_ms)
+estimate_covariances_raw = _raw("mi_estimate_covariances")
+icp_gicp_register_raw = _raw("mi_icp_gicp_register")
+gicp_system_raw = _raw("mi_gicp_system")
+icp_gicp_times_raw = _raw("mi_icp_gicp_times")
 
 
 def ndt_params(**kw):
     """mi_ndt_params with the library's defaults, then the given fields"""
-    p = NdtParams()
-    lib().mi_ndt_params_default.restype = None
-    lib().mi_ndt_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(NdtParams, "mi_ndt_params_default", kw)
 
 
-def ndt_constants_raw(voxel, outlier_ratio, out):
-    """mi_ndt_constants with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_ndt_constants
-    f.argtypes, f.restype = [C.c_float, C.c_float, C.c_void_p], C.c_int
-    return f(voxel, outlier_ratio, out)
+ndt_constants_raw = _raw("mi_ndt_constants")
 
 
 def ndt_constants(voxel, outlier_ratio=0.55):
@@ -470,71 +367,24 @@ def ndt_constants(voxel, outlier_ratio=0.55):
     return out
 
 
-def ndt_voxels_raw(handle, xyz, n, voxel, origin, min_points, eig_ratio, out_coord, out_mean, out_icov, out_n, out_count, out_cov, out_origin):
-    """mi_ndt_voxels with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_ndt_voxels
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 7
-    f.restype = C.c_int
-    return f(handle, xyz, n, voxel, origin, min_points, eig_ratio, out_coord, out_mean, out_icov, out_n, out_count, out_cov, out_origin)
-
-
-def ndt_register_raw(handle, before, n, coord, mean, icov, nv, voxel, origin, params, init_T, out_T, iterations, score, stop_reason):
-    """mi_ndt_register with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_ndt_register
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 7
-    f.restype = C.c_int
-    return f(handle, before, n, coord, mean, icov, nv, voxel, origin, params, init_T, out_T, iterations, score, stop_reason)
-
-
-def ndt_system_raw(handle, before, n, coord, mean, icov, nv, voxel, origin, T, neighbourhood, outlier_ratio, out_sums, out_centre, out_idx, out_terms):
-    """mi_ndt_system with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_ndt_system
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 4
-    f.restype = C.c_int
-    return f(handle, before, n, coord, mean, icov, nv, voxel, origin, T, neighbourhood, outlier_ratio, out_sums, out_centre, out_idx, out_terms)
-
-
-def ndt_times_raw(handle, out_ms):
-    """mi_ndt_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_ndt_times
-    f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
-    return f(handle, out_ms)
+ndt_voxels_raw = _raw("mi_ndt_voxels")
+ndt_register_raw = _raw("mi_ndt_register")
+ndt_system_raw = _raw("mi_ndt_system")
+ndt_times_raw = _raw("mi_ndt_times")
 
 
 FPFH_BINS, FPFH_DIM = 11, 33     # MI_FPFH_BINS, MI_FPFH_DIM
 
 
-def fpfh_features_raw(handle, cloud, normals, n, k, dist_mode, max_d2, fpfh, counts, count):
-    """mi_fpfh_features with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_fpfh_features
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f(handle, cloud, normals, n, k, dist_mode, max_d2, fpfh, counts, count)
-
-
-def fpfh_features_times_raw(handle, out_ms):
-    """mi_fpfh_features_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_fpfh_features_times
-    f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
-    return f(handle, out_ms)
+fpfh_features_raw = _raw("mi_fpfh_features")
+fpfh_features_times_raw = _raw("mi_fpfh_features_times")
 
 
 FEATURE_MAX_DIM = 64             # MI_FEATURE_MAX_DIM
 
 
-def feature_match_raw(handle, query, n, target, m, dim, mutual, idx, d2):
-    """mi_feature_match with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_feature_match
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f(handle, query, n, target, m, dim, mutual, idx, d2)
-
-
-def feature_match_times_raw(handle, out_ms):
-    """mi_feature_match_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_feature_match_times
-    f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
-    return f(handle, out_ms)
+feature_match_raw = _raw("mi_feature_match")
+feature_match_times_raw = _raw("mi_feature_match_times")
 
 
 class RansacParams(C.Structure):
@@ -544,39 +394,15 @@ class RansacParams(C.Structure):
 
 def ransac_params(max_distance, **kw):
     """mi_ransac_params_default with max_distance and any other field set: hypotheses, seed, edge_similarity, refine_iterations."""
-    p = RansacParams()
-    f = lib().mi_ransac_params_default
-    f.argtypes, f.restype = [C.c_void_p], None
-    f(C.byref(p))
-    p.max_distance = max_distance
-    for k, v in kw.items():
+    for k in kw:
         if k not in ("hypotheses", "seed", "edge_similarity", "refine_iterations"):
             raise TypeError("mi_ransac_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(RansacParams, "mi_ransac_params_default", dict(kw, max_distance=max_distance))
 
 
-def ransac_register_raw(handle, src, n, tgt, m, idx, params, R9, t3, inliers, rmse, best, nvalid, mask):
-    """mi_ransac_register with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_ransac_register
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 9
-    f.restype = C.c_int
-    return f(handle, src, n, tgt, m, idx, params, R9, t3, inliers, rmse, best, nvalid, mask)
-
-
-def ransac_hypotheses_raw(handle, src, n, tgt, m, idx, params, first, count, triples, valid, pose12, inlier_count):
-    """mi_ransac_hypotheses with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_ransac_hypotheses
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
-    f.restype = C.c_int
-    return f(handle, src, n, tgt, m, idx, params, first, count, triples, valid, pose12, inlier_count)
-
-
-def ransac_register_times_raw(handle, out_ms):
-    """mi_ransac_register_times with ctypes pointers (or None) as given: returns the error code, raises nothing."""
-    f = lib().mi_ransac_register_times
-    f.argtypes, f.restype = [C.c_void_p, C.c_void_p], C.c_int
-    return f(handle, out_ms)
+ransac_register_raw = _raw("mi_ransac_register")
+ransac_hypotheses_raw = _raw("mi_ransac_hypotheses")
+ransac_register_times_raw = _raw("mi_ransac_register_times")
 
 
 def _cov6(a, points):
@@ -598,9 +424,7 @@ def _T16(T):
 
 def icp_auto_batch(n_moving_total, m_fixed_total, world, source_sharded, every_pair_search):
     """Iterations mi_icp_run enqueues between host checks with sync_every = 0: a function of global sizes only."""
-    f = lib().mi_icp_auto_batch
-    f.argtypes = [C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int]
-    return int(f(n_moving_total, m_fixed_total, world, 1 if source_sharded else 0, 1 if every_pair_search else 0))
+    return int(lib().mi_icp_auto_batch(n_moving_total, m_fixed_total, world, 1 if source_sharded else 0, 1 if every_pair_search else 0))
 
 
 def source_share(n_total, rank, world):
@@ -620,12 +444,7 @@ def unpack_key(key):
     return d2.value, idx.value
 
 
-def selftest_cloud_range_raw(ctx, xyz, n, check, out_lo_hi, out_first_bad):
-    """mi_selftest_cloud_range with raw pointers -> its return code."""
-    f = lib().mi_selftest_cloud_range
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f(ctx, xyz, n, check, out_lo_hi, out_first_bad)
+selftest_cloud_range_raw = _raw("mi_selftest_cloud_range")
 
 
 def selftest_live_buffers():
@@ -653,6 +472,13 @@ def runtime_info():
 def _T_to_Rt(T):
     M = np.array(T, dtype=np.float32).reshape(4, 4).T   # column-major -> M[row, col]
     return M[:3, :3].copy(), M[:3, 3].copy()
+
+
+# the C type of every Structure above (tests/test_capi_prototypes.py has the compiler check each layout against the header's)
+_C_TYPES = {IcpParams: "mi_icp_params", CpdParams: "mi_cpd_params", NicpParams: "mi_nicp_params", PrepareParams: "mi_prepare_params",
+            OutlierParams: "mi_outlier_params", OutlierStats: "mi_outlier_stats", IssParams: "mi_iss_params", ClusterParams: "mi_cluster_params",
+            PlaneParams: "mi_plane_params", NdtParams: "mi_ndt_params", RansacParams: "mi_ransac_params", IcpBatchInfo: "mi_icp_batch_info",
+            CpdBatchInfo: "mi_cpd_batch_info"}
 
 
 class Context:
@@ -715,51 +541,60 @@ class Context:
         _check(lib().mi_dist_info(self._h, C.byref(n), C.byref(r), C.byref(seen)))
         return n.value, r.value, int(seen.value)
 
+    # ---- ms per stage of the last call of each kind: mi_<key>_times fills eight doubles, these are their labels
+    _TIMES = {
+        "voxel_downsample": ("workspace", "upload", "range", "sort", "sums", "download", "unused", "total"),
+        "knn_search": ("workspace", "upload", "check", "grid", "order", "search", "download", "total"),
+        "estimate_normals": ("workspace", "upload", "check", "grid", "order", "fused", "download", "total"),
+        "remove_outliers": ("workspace", "upload", "check", "grid", "order", "kernel", "finish", "total"),
+        "iss_keypoints": ("workspace", "upload", "check", "grid", "order", "saliency", "finish", "total"),
+        "cluster_dbscan": ("workspace", "upload", "grid", "count", "link", "resolve", "finish", "total"),
+        "icp_plane": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
+        "icp_gicp": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
+        "ndt": ("workspace", "upload", "check", "table", "order", "iterations", "download", "total"),
+        "fpfh_features": ("workspace", "upload", "check", "grid", "order", "kernels", "download", "total"),
+        "feature_match": ("workspace", "upload", "check", "unused3", "unused4", "kernels", "download", "total"),
+        "ransac_register": ("workspace", "upload", "hypotheses", "count", "argmax", "refine", "unused6", "total"),
+        "icp_load": ("workspace", "upload_moving", "order_moving", "upload_fixed", "hierarchy", "grid", "reset", "total"),
+    }
+
+    def _times(self, name):
+        out = (C.c_double * 8)()
+        _check(getattr(lib(), "mi_%s_times" % name)(self._h, out))
+        return dict(zip(self._TIMES[name], list(out)))
+
     # ---- ICP
     def icp_register(self, before, after, params):
         before, after = _cloud(before), _cloud(after)
         T = (C.c_float * 16)()
         it, err = C.c_int(0), C.c_float(0)
-        _check(lib().mi_icp_register(self._h, _fp(before), before.shape[0], _fp(after), after.shape[0], C.byref(params), T,
+        _check(lib().mi_icp_register(self._h, _ptr(before), before.shape[0], _ptr(after), after.shape[0], C.byref(params), T,
                                      C.byref(it), C.byref(err)))
-        R, t = _T_to_Rt(T)
-        return R, t, it.value, err.value
+        return _T_to_Rt(T) + (it.value, err.value)
 
     def icp_register_batch(self, befores, afters, params, before_range=None, after_range=None):
         """B registrations under one set of rules (mi_icp_register_batch).  befores / afters: two lists of (n, 3) arrays -- or two
         (N, 3) arrays plus before_range / after_range, (B, 2) integer arrays of (first point, count).  Returns (R [B,3,3], t [B,3],
         iterations [B], error [B], stop_reason [B], info)."""
-        before, br, after, ar = _batch_arrays(befores, afters, before_range, after_range)
-        B = len(br)
-        T = np.zeros((B, 16), np.float32)
-        it, why = np.zeros(B, np.int32), np.zeros(B, np.int32)
-        err = np.zeros(B, np.float32)
+        clouds, B, T, it, err, why = _batch_call(befores, afters, before_range, after_range)
         info = IcpBatchInfo()
-        _check(icp_register_batch_raw(self._h, B, before.ctypes.data, br.ctypes.data, after.ctypes.data, ar.ctypes.data,
-                                      C.addressof(params), T.ctypes.data, it.ctypes.data, err.ctypes.data, why.ctypes.data,
+        _check(icp_register_batch_raw(self._h, B, *map(_ptr, clouds), C.addressof(params), T.ctypes.data, it.ctypes.data, err.ctypes.data, why.ctypes.data,
                                       C.addressof(info)))
-        M = T.reshape(B, 4, 4).transpose(0, 2, 1)        # column-major 4x4 -> [row, col]
-        return M[:, :3, :3].copy(), M[:, :3, 3].copy(), it, err, why, info
+        return _batch_Rt(T) + (it, err, why, info)
 
     def cpd_register_batch(self, befores, afters, params, before_range=None, after_range=None):
         """B CPD registrations under one set of rules (mi_cpd_register_batch).  befores / afters: two lists of (n, 3) arrays -- or two
         (N, 3) arrays plus before_range / after_range, (B, 2) integer arrays of (first point, count).  Returns (sR [B,3,3], t [B,3],
         scale [B], iterations [B], error [B], stop_reason [B], info)."""
-        before, br, after, ar = _batch_arrays(befores, afters, before_range, after_range)
-        B = len(br)
-        T = np.zeros((B, 16), np.float32)
-        it, why = np.zeros(B, np.int32), np.zeros(B, np.int32)
-        err, scale = np.zeros(B, np.float32), np.zeros(B, np.float32)
-        info = CpdBatchInfo()
-        _check(cpd_register_batch_raw(self._h, B, before.ctypes.data, br.ctypes.data, after.ctypes.data, ar.ctypes.data,
-                                      C.addressof(params), T.ctypes.data, scale.ctypes.data, it.ctypes.data, err.ctypes.data,
+        clouds, B, T, it, err, why = _batch_call(befores, afters, before_range, after_range)
+        scale, info = np.zeros(B, np.float32), CpdBatchInfo()
+        _check(cpd_register_batch_raw(self._h, B, *map(_ptr, clouds), C.addressof(params), T.ctypes.data, scale.ctypes.data, it.ctypes.data, err.ctypes.data,
                                       why.ctypes.data, C.addressof(info)))
-        M = T.reshape(B, 4, 4).transpose(0, 2, 1)        # column-major 4x4 -> [row, col]
-        return M[:, :3, :3].copy(), M[:, :3, 3].copy(), scale, it, err, why, info
+        return _batch_Rt(T) + (scale, it, err, why, info)
 
     def icp_load(self, before, after, params):
         before, after = _cloud(before), _cloud(after)
-        _check(lib().mi_icp_load(self._h, _fp(before), before.shape[0], _fp(after), after.shape[0], C.byref(params)))
+        _check(lib().mi_icp_load(self._h, _ptr(before), before.shape[0], _ptr(after), after.shape[0], C.byref(params)))
 
     def icp_reset(self):
         _check(lib().mi_icp_reset(self._h))
@@ -773,43 +608,31 @@ class Context:
         T = (C.c_float * 16)()
         it, err, why = C.c_int(0), C.c_float(0), C.c_int(0)
         _check(lib().mi_icp_result(self._h, T, C.byref(it), C.byref(err), C.byref(why)))
-        R, t = _T_to_Rt(T)
-        return R, t, it.value, err.value, why.value
+        return _T_to_Rt(T) + (it.value, err.value, why.value)
 
     # ---- primitives
     def nn_search(self, src, tgt, dist_mode=DIST_CPU_ROUNDING, nn_mode=NN_AUTO):
         src, tgt = _cloud(src), _cloud(tgt)
         n = src.shape[0]
-        idx = np.empty(n, np.int32)
-        d2 = np.empty(n, np.float32)
-        _check(lib().mi_nn_search_ex(self._h, _fp(src), n, _fp(tgt), tgt.shape[0], dist_mode, nn_mode,
-                                     idx.ctypes.data_as(_i), _fp(d2)))
+        idx, d2 = np.empty(n, np.int32), np.empty(n, np.float32)
+        _check(lib().mi_nn_search_ex(self._h, _ptr(src), n, _ptr(tgt), tgt.shape[0], dist_mode, nn_mode, _ptr(idx), _ptr(d2)))
         return idx, d2
 
     def kabsch(self, src, tgt, idx, keep=None):
         src, tgt = _cloud(src), _cloud(tgt)
         idx = np.ascontiguousarray(idx, np.int32)
-        kp = None
-        if keep is not None:
-            keep = np.ascontiguousarray(keep, np.uint8)
-            kp = keep.ctypes.data_as(_u8)
-        R9 = (C.c_float * 9)()
-        t3 = (C.c_float * 3)()
-        used = C.c_int(0)
-        _check(lib().mi_kabsch(self._h, _fp(src), src.shape[0], _fp(tgt), tgt.shape[0], idx.ctypes.data_as(_i), kp, R9, t3,
-                               C.byref(used)))
+        keep = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        R9, t3, used = (C.c_float * 9)(), (C.c_float * 3)(), C.c_int(0)
+        _check(lib().mi_kabsch(self._h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(idx), _ptr(keep), R9, t3, C.byref(used)))
         return np.array(R9, np.float32).reshape(3, 3).T.copy(), np.array(t3, np.float32), used.value
 
     def cross_moments(self, src, tgt, idx, keep=None):
         """{pairs, sum src, sum tgt, sum tgt_r src_c} over the kept pairs (src[i], tgt[idx[i]]), fp64."""
         src, tgt = _cloud(src), _cloud(tgt)
         idx = np.ascontiguousarray(idx, np.int32)
-        kp = None
-        if keep is not None:
-            keep = np.ascontiguousarray(keep, np.uint8)
-            kp = keep.ctypes.data_as(_u8)
+        keep = None if keep is None else np.ascontiguousarray(keep, np.uint8)
         out = (C.c_double * 16)()
-        _check(lib().mi_cross_moments(self._h, _fp(src), src.shape[0], _fp(tgt), tgt.shape[0], idx.ctypes.data_as(_i), kp, out))
+        _check(lib().mi_cross_moments(self._h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(idx), _ptr(keep), out))
         return np.array(out, np.float64)
 
     def transform_mse(self, src, R, t, tgt=None, idx=None, keep=None, divide_by_pairs=True, want_cloud=True):
@@ -817,19 +640,14 @@ class Context:
         n = src.shape[0]
         R9 = np.ascontiguousarray(np.asarray(R, np.float32).T).reshape(9)
         t3 = np.ascontiguousarray(t, np.float32)
-        out = np.empty((n, 3), np.float32) if want_cloud else None
-        mse = C.c_float(0)
-        tp, m, ip, kp = None, 0, None, None
-        if tgt is not None:
-            tgt = _cloud(tgt)
-            tp, m = _fp(tgt), tgt.shape[0]
-            idx = np.ascontiguousarray(idx, np.int32)
-            ip = idx.ctypes.data_as(_i)
-            if keep is not None:
-                keep = np.ascontiguousarray(keep, np.uint8)
-                kp = keep.ctypes.data_as(_u8)
-        _check(lib().mi_transform_mse(self._h, _fp(src), n, _fp(R9), _fp(t3), tp, m, ip, kp, 1 if divide_by_pairs else 0,
-                                      _fp(out) if want_cloud else None, C.byref(mse) if tgt is not None else None))
+        out, mse = (np.empty((n, 3), np.float32) if want_cloud else None), C.c_float(0)
+        if tgt is None:
+            idx = keep = None
+        else:
+            tgt, idx = _cloud(tgt), np.ascontiguousarray(idx, np.int32)
+            keep = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        _check(lib().mi_transform_mse(self._h, _ptr(src), n, _ptr(R9), _ptr(t3), _ptr(tgt), 0 if tgt is None else tgt.shape[0], _ptr(idx), _ptr(keep),
+                                      1 if divide_by_pairs else 0, _ptr(out), C.byref(mse) if tgt is not None else None))
         return out, (mse.value if tgt is not None else None)
 
     # ---- CPD
@@ -837,73 +655,60 @@ class Context:
         before, after = _cloud(before), _cloud(after)
         T = (C.c_float * 16)()
         it, err, sc = C.c_int(0), C.c_float(0), C.c_float(0)
-        _check(lib().mi_cpd_register(self._h, _fp(before), before.shape[0], _fp(after), after.shape[0], C.byref(params), T,
+        _check(lib().mi_cpd_register(self._h, _ptr(before), before.shape[0], _ptr(after), after.shape[0], C.byref(params), T,
                                      C.byref(sc), C.byref(it), C.byref(err)))
-        sR, t = _T_to_Rt(T)
-        return sR, t, sc.value, it.value, err.value
+        return _T_to_Rt(T) + (sc.value, it.value, err.value)
 
     def cpd_sigma_squared(self, before, after, mode=SIGMA2_EXACT):
         before, after = _cloud(before), _cloud(after)
         s = C.c_float(0)
-        _check(lib().mi_cpd_sigma_squared_mode(self._h, _fp(before), before.shape[0], _fp(after), after.shape[0], mode, C.byref(s)))
+        _check(lib().mi_cpd_sigma_squared_mode(self._h, _ptr(before), before.shape[0], _ptr(after), after.shape[0], mode, C.byref(s)))
         return s.value
 
     def cpd_estep(self, y, x, constant, sigma2):
         y, x = _cloud(y), _cloud(x)
         m, n = y.shape[0], x.shape[0]
-        p1 = np.empty(m, np.float32)
-        pt1 = np.empty(n, np.float32)
-        px = np.empty((m, 3), np.float32)
-        L = C.c_float(0)
-        _check(lib().mi_cpd_estep(self._h, _fp(y), m, _fp(x), n, C.c_float(constant), C.c_float(sigma2), _fp(p1), _fp(pt1),
-                                  _fp(px), C.byref(L)))
+        p1, pt1, px, L = np.empty(m, np.float32), np.empty(n, np.float32), np.empty((m, 3), np.float32), C.c_float(0)
+        _check(lib().mi_cpd_estep(self._h, _ptr(y), m, _ptr(x), n, constant, sigma2, _ptr(p1), _ptr(pt1), _ptr(px), C.byref(L)))
         return p1, pt1, px, L.value
 
     def cpd_estep_truncated(self, y, x, constant, sigma2, truncate=1e-3):
         y, x = _cloud(y), _cloud(x)
         m, n = y.shape[0], x.shape[0]
         p1, pt1, px, L = np.empty(m, np.float32), np.empty(n, np.float32), np.empty((m, 3), np.float32), C.c_float(0)
-        _check(lib().mi_cpd_estep_truncated(self._h, _fp(y), m, _fp(x), n, C.c_float(constant), C.c_float(sigma2),
-                                            C.c_float(truncate), _fp(p1), _fp(pt1), _fp(px), C.byref(L)))
+        _check(lib().mi_cpd_estep_truncated(self._h, _ptr(y), m, _ptr(x), n, constant, sigma2, truncate, _ptr(p1), _ptr(pt1), _ptr(px), C.byref(L)))
         return p1, pt1, px, L.value
 
     def cpd_estep_fgt(self, y, x, weight, sigma2, sigma2_init, ratio_of_far_field=10.0, order_of_truncation=8):
         y, x = _cloud(y), _cloud(x)
         m, n = y.shape[0], x.shape[0]
         p1, pt1, px, L = np.empty(m, np.float32), np.empty(n, np.float32), np.empty((m, 3), np.float32), C.c_float(0)
-        _check(lib().mi_cpd_estep_fgt(self._h, _fp(y), m, _fp(x), n, C.c_float(weight), C.c_float(sigma2), C.c_float(sigma2_init),
-                                      C.c_float(ratio_of_far_field), int(order_of_truncation), _fp(p1), _fp(pt1), _fp(px),
-                                      C.byref(L)))
+        _check(lib().mi_cpd_estep_fgt(self._h, _ptr(y), m, _ptr(x), n, weight, sigma2, sigma2_init, ratio_of_far_field,
+                                      int(order_of_truncation), _ptr(p1), _ptr(pt1), _ptr(px), C.byref(L)))
         return p1, pt1, px, L.value
 
     def fgt_kcenter(self, cloud, K):
         cloud = _cloud(cloud)
-        centers = np.empty((K, 3), np.float32)
-        cluster = np.empty(cloud.shape[0], np.int32)
-        _check(lib().mi_fgt_kcenter(self._h, _fp(cloud), cloud.shape[0], int(K), _fp(centers), cluster.ctypes.data_as(_i)))
+        centers, cluster = np.empty((K, 3), np.float32), np.empty(cloud.shape[0], np.int32)
+        _check(lib().mi_fgt_kcenter(self._h, _ptr(cloud), cloud.shape[0], int(K), _ptr(centers), _ptr(cluster)))
         return centers, cluster
 
     def fgt_kcenter_guided(self, cloud, K, guess):
         """-> centers, cluster, picked (the sweep's choices), verified (leading entries of `guess` that were the sweep's own; -1: no replay)"""
         cloud = _cloud(cloud)
         guess = np.ascontiguousarray(guess, np.int32)
-        centers = np.empty((K, 3), np.float32)
-        cluster = np.empty(cloud.shape[0], np.int32)
-        picked = np.empty(K, np.int32)
-        verified = C.c_int(-2)
-        _check(lib().mi_fgt_kcenter_guided(self._h, _fp(cloud), cloud.shape[0], int(K), guess.ctypes.data_as(_i), int(guess.shape[0]), _fp(centers),
-                                           cluster.ctypes.data_as(_i), picked.ctypes.data_as(_i), C.byref(verified)))
+        centers, cluster = np.empty((K, 3), np.float32), np.empty(cloud.shape[0], np.int32)
+        picked, verified = np.empty(K, np.int32), C.c_int(-2)
+        _check(lib().mi_fgt_kcenter_guided(self._h, _ptr(cloud), cloud.shape[0], int(K), _ptr(guess), int(guess.shape[0]), _ptr(centers),
+                                           _ptr(cluster), _ptr(picked), C.byref(verified)))
         return centers, cluster, picked, verified.value
 
     def cpd_mstep(self, before, after, p1, pt1, px, const_scale, scale=1.0, sigma2=0.0):
         before, after = _cloud(before), _cloud(after)
-        p1 = np.ascontiguousarray(p1, np.float32)
-        pt1 = np.ascontiguousarray(pt1, np.float32)
-        px = np.ascontiguousarray(px, np.float32)
-        R9 = (C.c_float * 9)()
-        t3 = (C.c_float * 3)()
+        p1, pt1, px = (np.ascontiguousarray(a, np.float32) for a in (p1, pt1, px))
+        R9, t3 = (C.c_float * 9)(), (C.c_float * 3)()
         s, s2 = C.c_float(scale), C.c_float(sigma2)
-        _check(lib().mi_cpd_mstep(self._h, _fp(before), before.shape[0], _fp(after), after.shape[0], _fp(p1), _fp(pt1), _fp(px),
+        _check(lib().mi_cpd_mstep(self._h, _ptr(before), before.shape[0], _ptr(after), after.shape[0], _ptr(p1), _ptr(pt1), _ptr(px),
                                   1 if const_scale else 0, R9, t3, C.byref(s), C.byref(s2)))
         return np.array(R9, np.float32).reshape(3, 3).T.copy(), np.array(t3, np.float32), s.value, s2.value
 
@@ -920,11 +725,9 @@ class Context:
         sn = before.shape[0] if subcloud_idx is None else len(subcloud_idx)
         T = (C.c_float * 16)()
         it, err = C.c_int(0), C.c_float(0)
-        _check(lib().mi_nicp_register(self._h, _fp(before), before.shape[0], _fp(after), after.shape[0], C.byref(params),
-                                      heads.ctypes.data_as(_i), subcloud_idx.ctypes.data_as(_i) if subcloud_idx is not None else None,
-                                      sn, T, C.byref(it), C.byref(err)))
-        R, t = _T_to_Rt(T)
-        return R, t, it.value, err.value
+        _check(lib().mi_nicp_register(self._h, _ptr(before), before.shape[0], _ptr(after), after.shape[0], C.byref(params),
+                                      _ptr(heads), _ptr(subcloud_idx), sn, T, C.byref(it), C.byref(err)))
+        return _T_to_Rt(T) + (it.value, err.value)
 
     # ---- input stage
     def prepare_cloud(self, raw, subcloud_idx=None, shuffle_idx=None, noise_rows=None, noise_unit=None, noise_intensity=0.0,
@@ -951,12 +754,9 @@ class Context:
             p.has_transform = 1
             p.rotation[:] = np.asarray(R, np.float32).T.reshape(9).tolist()        # column-major
             p.translation[:] = np.asarray(t, np.float32).tolist()
-        out = np.empty((n + n_out, 3), np.float32)
-        got = C.c_int(0)
-        ip = lambda a: None if a is None else a.ctypes.data_as(_i)
-        fp = lambda a: None if a is None else _fp(a)
-        _check(lib().mi_prepare_cloud(self._h, _fp(raw), raw.shape[0], ip(sub), n, ip(shuf), ip(rows), fp(nu), n_noise, fp(ou), n_out,
-                                      C.byref(p), _fp(out), C.byref(got)))
+        out, got = np.empty((n + n_out, 3), np.float32), C.c_int(0)
+        _check(lib().mi_prepare_cloud(self._h, _ptr(raw), raw.shape[0], _ptr(sub), n, _ptr(shuf), _ptr(rows), _ptr(nu), n_noise, _ptr(ou), n_out,
+                                      C.byref(p), _ptr(out), C.byref(got)))
         assert got.value == n + n_out
         return out
 
@@ -967,18 +767,14 @@ class Context:
         of every input point [n]."""
         xyz = _cloud(xyz)
         n = xyz.shape[0]
-        op = None
-        if origin is not None:
-            origin = np.ascontiguousarray(origin, np.float32).reshape(3)
-            op = origin.ctypes.data
+        origin = None if origin is None else np.ascontiguousarray(origin, np.float32).reshape(3)
         out = np.empty((n, 3), np.float32)
         counts = np.empty(n, np.int32) if want_counts else None
         coords = np.empty((n, 3), np.int32) if want_coords else None
         vmap = np.empty(n, np.int32) if want_map else None
         rows = C.c_int(0)
-        ptr = lambda a: None if a is None else a.ctypes.data
-        _check(voxel_downsample_raw(self._h, xyz.ctypes.data, n, float(voxel), op, out.ctypes.data, C.addressof(rows), ptr(counts), ptr(coords),
-                                    ptr(vmap)))
+        _check(voxel_downsample_raw(self._h, xyz.ctypes.data, n, float(voxel), _ptr(origin), out.ctypes.data, C.addressof(rows), _ptr(counts), _ptr(coords),
+                                    _ptr(vmap)))
         res = [out[:rows.value].copy()]
         if want_counts:
             res.append(counts[:rows.value].copy())
@@ -990,9 +786,7 @@ class Context:
 
     def voxel_downsample_times(self):
         """ms per stage of the last voxel_downsample: workspace, upload, range, sort, sums, download, total (mi_voxel_downsample_times)."""
-        out = (C.c_double * 8)()
-        _check(lib().mi_voxel_downsample_times(self._h, out))
-        return dict(zip(("workspace", "upload", "range", "sort", "sums", "download", "unused", "total"), list(out)))
+        return self._times("voxel_downsample")
 
     # ---- k nearest neighbours
     def knn_search(self, query, cloud, k, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_d2=True, want_count=False):
@@ -1009,16 +803,13 @@ class Context:
         idx = np.empty((n, int(k)), np.int32)
         d2 = np.empty((n, int(k)), np.float32) if want_d2 else None
         count = np.empty(n, np.int32) if want_count else None
-        ptr = lambda a: None if a is None else a.ctypes.data
-        _check(knn_search_raw(self._h, qp, n, cloud.ctypes.data, m, int(k), int(dist_mode), float(max_d2), idx.ctypes.data, ptr(d2), ptr(count)))
+        _check(knn_search_raw(self._h, qp, n, cloud.ctypes.data, m, int(k), int(dist_mode), float(max_d2), idx.ctypes.data, _ptr(d2), _ptr(count)))
         res = [idx] + ([d2] if want_d2 else []) + ([count] if want_count else [])
         return res[0] if len(res) == 1 else tuple(res)
 
     def knn_search_times(self):
         """ms per stage of the last knn_search: workspace, upload, check, grid, order, search, download, total (mi_knn_search_times)."""
-        out = (C.c_double * 8)()
-        _check(lib().mi_knn_search_times(self._h, out))
-        return dict(zip(("workspace", "upload", "check", "grid", "order", "search", "download", "total"), list(out)))
+        return self._times("knn_search")
 
     # ---- surface normals
     def estimate_normals(self, cloud, k, viewpoint=None, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_curvature=False, want_count=False):
@@ -1031,16 +822,13 @@ class Context:
         normals = np.empty((n, 3), np.float32)
         curvature = np.empty(n, np.float32) if want_curvature else None
         count = np.empty(n, np.int32) if want_count else None
-        ptr = lambda a: None if a is None else a.ctypes.data
-        _check(estimate_normals_raw(self._h, cloud.ctypes.data, n, int(k), int(dist_mode), float(max_d2), ptr(view), normals.ctypes.data, ptr(curvature), ptr(count)))
+        _check(estimate_normals_raw(self._h, cloud.ctypes.data, n, int(k), int(dist_mode), float(max_d2), _ptr(view), normals.ctypes.data, _ptr(curvature), _ptr(count)))
         res = [normals] + ([curvature] if want_curvature else []) + ([count] if want_count else [])
         return res[0] if len(res) == 1 else tuple(res)
 
     def estimate_normals_times(self):
         """ms per stage of the last estimate_normals: workspace, upload, check, grid, order, fused, download, total (mi_estimate_normals_times)."""
-        out = (C.c_double * 8)()
-        _check(lib().mi_estimate_normals_times(self._h, out))
-        return dict(zip(("workspace", "upload", "check", "grid", "order", "fused", "download", "total"), list(out)))
+        return self._times("estimate_normals")
 
     # ---- outlier removal
     def remove_outliers(self, cloud, params, want_keep=False, want_mean_distance=False, want_neighbours=False, want_stats=False):
@@ -1056,18 +844,15 @@ class Context:
         mean_distance = np.empty(n, np.float32) if want_mean_distance else None
         neighbours = np.empty(n, np.int32) if want_neighbours else None
         stats = OutlierStats() if want_stats else None
-        ptr = lambda a: None if a is None else a.ctypes.data
         _check(remove_outliers_raw(self._h, cloud.ctypes.data, n, C.addressof(params), out_xyz.ctypes.data, out_index.ctypes.data, C.addressof(out_n),
-                                   ptr(keep), ptr(mean_distance), ptr(neighbours), None if stats is None else C.addressof(stats)))
+                                   _ptr(keep), _ptr(mean_distance), _ptr(neighbours), None if stats is None else C.addressof(stats)))
         res = [out_xyz[:out_n.value].copy(), out_index[:out_n.value].copy()]
         res += [a for a in (keep, mean_distance, neighbours, stats) if a is not None]
         return tuple(res)
 
     def remove_outliers_times(self):
         """ms per stage of the last remove_outliers: workspace, upload, check, grid, order, kernel, finish, total (mi_remove_outliers_times)."""
-        out = (C.c_double * 8)()
-        _check(lib().mi_remove_outliers_times(self._h, out))
-        return dict(zip(("workspace", "upload", "check", "grid", "order", "kernel", "finish", "total"), list(out)))
+        return self._times("remove_outliers")
 
     # ---- ISS keypoints
     def iss_keypoints(self, cloud, params, want_is_keypoint=False, want_saliency=False, want_eigenvalues=False, want_neighbours=False):
@@ -1081,18 +866,15 @@ class Context:
         saliency = np.empty(n, np.float32) if want_saliency else None
         eigenvalues = np.empty((n, 3), np.float32) if want_eigenvalues else None
         neighbours = np.empty(n, np.int32) if want_neighbours else None
-        ptr = lambda a: None if a is None else a.ctypes.data
         _check(iss_keypoints_raw(self._h, cloud.ctypes.data, n, C.addressof(params), out_xyz.ctypes.data, out_index.ctypes.data, C.addressof(out_n),
-                                 ptr(is_keypoint), ptr(saliency), ptr(eigenvalues), ptr(neighbours)))
+                                 _ptr(is_keypoint), _ptr(saliency), _ptr(eigenvalues), _ptr(neighbours)))
         res = [out_xyz[:out_n.value].copy(), out_index[:out_n.value].copy()]
         res += [a for a in (is_keypoint, saliency, eigenvalues, neighbours) if a is not None]
         return tuple(res)
 
     def iss_keypoints_times(self):
         """ms per stage of the last iss_keypoints: workspace, upload, check, grid, order, saliency, finish, total (mi_iss_keypoints_times)."""
-        out = (C.c_double * 8)()
-        _check(lib().mi_iss_keypoints_times(self._h, out))
-        return dict(zip(("workspace", "upload", "check", "grid", "order", "saliency", "finish", "total"), list(out)))
+        return self._times("iss_keypoints")
 
     # ---- density-based clustering
     def cluster_dbscan(self, cloud, params, want_sizes=False, want_core=False, want_grouped=False):
@@ -1105,18 +887,15 @@ class Context:
         sizes = np.empty(n, np.int32) if want_sizes else None
         core = np.empty(n, np.uint8) if want_core else None
         grouped = np.empty(n, np.int32) if want_grouped else None
-        ptr = lambda a: None if a is None else a.ctypes.data
-        _check(cluster_dbscan_raw(self._h, cloud.ctypes.data, n, C.addressof(params), labels.ctypes.data, C.addressof(n_clusters), ptr(sizes), n, ptr(core),
-                                  ptr(grouped), C.addressof(n_grouped) if want_grouped else None))
+        _check(cluster_dbscan_raw(self._h, cloud.ctypes.data, n, C.addressof(params), labels.ctypes.data, C.addressof(n_clusters), _ptr(sizes), n, _ptr(core),
+                                  _ptr(grouped), C.addressof(n_grouped) if want_grouped else None))
         res = [labels, n_clusters.value]
         res += ([sizes[:n_clusters.value].copy()] if want_sizes else []) + ([core] if want_core else []) + ([grouped[:n_grouped.value].copy()] if want_grouped else [])
         return tuple(res)
 
     def cluster_dbscan_times(self):
         """ms per stage of the last cluster_dbscan: workspace, upload (with the check), grid (with the order), count, link, resolve, finish, total (mi_cluster_dbscan_times)."""
-        out = (C.c_double * 8)()
-        _check(lib().mi_cluster_dbscan_times(self._h, out))
-        return dict(zip(("workspace", "upload", "grid", "count", "link", "resolve", "finish", "total"), list(out)))
+        return self._times("cluster_dbscan")
 
     # ---- point-to-plane ICP
     def icp_plane_register(self, before, after, after_normals, params, init=None):
@@ -1129,10 +908,9 @@ class Context:
         T = np.zeros(16, np.float32)
         it, err, why = C.c_int(0), C.c_float(0), C.c_int(0)
         _check(icp_plane_register_raw(self._h, before.ctypes.data, before.shape[0], after.ctypes.data, normals.ctypes.data, after.shape[0],
-                                      C.addressof(params), None if T0 is None else T0.ctypes.data, T.ctypes.data, C.addressof(it), C.addressof(err),
+                                      C.addressof(params), _ptr(T0), T.ctypes.data, C.addressof(it), C.addressof(err),
                                       C.addressof(why)))
-        R, t = _T_to_Rt(T)
-        return R, t, it.value, err.value, why.value
+        return _T_to_Rt(T) + (it.value, err.value, why.value)
 
     def plane_system(self, before, after, after_normals, T=None, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_idx=True):
         """One point-to-plane linearisation at transform T (mi_plane_system) -> (sums float64 [32], centre float32 [3], idx int32 [n] if asked
@@ -1145,16 +923,14 @@ class Context:
         sums, centre = np.zeros(32, np.float64), np.zeros(3, np.float32)
         idx = np.empty(n, np.int32) if want_idx else None
         _check(plane_system_raw(self._h, before.ctypes.data, n, after.ctypes.data, normals.ctypes.data, after.shape[0],
-                                None if T0 is None else T0.ctypes.data, int(dist_mode), float(max_d2), sums.ctypes.data, centre.ctypes.data,
-                                None if idx is None else idx.ctypes.data))
+                                _ptr(T0), int(dist_mode), float(max_d2), sums.ctypes.data, centre.ctypes.data,
+                                _ptr(idx)))
         return (sums, centre, idx) if want_idx else (sums, centre)
 
     def icp_plane_times(self):
         """ms per stage of the last icp_plane_register / plane_system: workspace, upload, check, grid, order, iterations, download, total
         (mi_icp_plane_times)."""
-        out = (C.c_double * 8)()
-        _check(lib().mi_icp_plane_times(self._h, out))
-        return dict(zip(("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"), list(out)))
+        return self._times("icp_plane")
 
     # ---- generalized ICP
     def estimate_covariances(self, cloud, k, mode=COV_PLANE, epsilon=1e-3, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_count=False):
@@ -1166,7 +942,7 @@ class Context:
         cov = np.empty((n, 6), np.float32)
         count = np.empty(n, np.int32) if want_count else None
         _check(estimate_covariances_raw(self._h, cloud.ctypes.data, n, int(k), int(dist_mode), float(max_d2), int(mode), float(epsilon), cov.ctypes.data,
-                                        None if count is None else count.ctypes.data))
+                                        _ptr(count)))
         return (cov, count) if want_count else cov
 
     def icp_gicp_register(self, before, before_cov, after, after_cov, params, init=None):
@@ -1179,10 +955,9 @@ class Context:
         T = np.zeros(16, np.float32)
         it, err, why = C.c_int(0), C.c_float(0), C.c_int(0)
         _check(icp_gicp_register_raw(self._h, before.ctypes.data, cb.ctypes.data, before.shape[0], after.ctypes.data, ca.ctypes.data, after.shape[0],
-                                     C.addressof(params), None if T0 is None else T0.ctypes.data, T.ctypes.data, C.addressof(it), C.addressof(err),
+                                     C.addressof(params), _ptr(T0), T.ctypes.data, C.addressof(it), C.addressof(err),
                                      C.addressof(why)))
-        R, t = _T_to_Rt(T)
-        return R, t, it.value, err.value, why.value
+        return _T_to_Rt(T) + (it.value, err.value, why.value)
 
     def gicp_system(self, before, before_cov, after, after_cov, T=None, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_idx=True):
         """One generalized-ICP linearisation at transform T (mi_gicp_system) -> (sums float64 [32], centre float32 [3], idx int32 [n] if asked
@@ -1194,16 +969,14 @@ class Context:
         sums, centre = np.zeros(32, np.float64), np.zeros(3, np.float32)
         idx = np.empty(n, np.int32) if want_idx else None
         _check(gicp_system_raw(self._h, before.ctypes.data, cb.ctypes.data, n, after.ctypes.data, ca.ctypes.data, after.shape[0],
-                               None if T0 is None else T0.ctypes.data, int(dist_mode), float(max_d2), sums.ctypes.data, centre.ctypes.data,
-                               None if idx is None else idx.ctypes.data))
+                               _ptr(T0), int(dist_mode), float(max_d2), sums.ctypes.data, centre.ctypes.data,
+                               _ptr(idx)))
         return (sums, centre, idx) if want_idx else (sums, centre)
 
     def icp_gicp_times(self):
         """ms per stage of the last icp_gicp_register / gicp_system: workspace, upload, check, grid, order, iterations, download, total
         (mi_icp_gicp_times)."""
-        out = (C.c_double * 8)()
-        _check(icp_gicp_times_raw(self._h, out))
-        return dict(zip(("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"), list(out)))
+        return self._times("icp_gicp")
 
     # ---- registration against a voxel map
     def ndt_voxels(self, xyz, voxel, origin=None, min_points=6, eig_ratio=0.01, want_cov=False):
@@ -1216,9 +989,9 @@ class Context:
         coord, mean, icov = np.empty((n, 3), np.int32), np.empty((n, 3), np.float32), np.empty((n, 6), np.float32)
         count, cov, used = np.empty(n, np.int32), (np.empty((n, 6), np.float32) if want_cov else None), np.zeros(3, np.float32)
         rows = C.c_int(0)
-        _check(ndt_voxels_raw(self._h, xyz.ctypes.data, n, float(voxel), None if o is None else o.ctypes.data, int(min_points), float(eig_ratio),
+        _check(ndt_voxels_raw(self._h, xyz.ctypes.data, n, float(voxel), _ptr(o), int(min_points), float(eig_ratio),
                               coord.ctypes.data, mean.ctypes.data, icov.ctypes.data, C.addressof(rows), count.ctypes.data,
-                              None if cov is None else cov.ctypes.data, used.ctypes.data))
+                              _ptr(cov), used.ctypes.data))
         r = rows.value
         out = dict(coord=coord[:r].copy(), mean=mean[:r].copy(), icov=icov[:r].copy(), count=count[:r].copy(), origin=used, voxel=float(voxel))
         if want_cov:
@@ -1243,10 +1016,9 @@ class Context:
         T = np.zeros(16, np.float32)
         it, score, why = C.c_int(0), C.c_float(0), C.c_int(0)
         _check(ndt_register_raw(self._h, before.ctypes.data, before.shape[0], coord.ctypes.data, mean.ctypes.data, icov.ctypes.data, coord.shape[0], voxel,
-                                origin.ctypes.data, C.addressof(params), None if T0 is None else T0.ctypes.data, T.ctypes.data, C.addressof(it),
+                                origin.ctypes.data, C.addressof(params), _ptr(T0), T.ctypes.data, C.addressof(it),
                                 C.addressof(score), C.addressof(why)))
-        R, t = _T_to_Rt(T)
-        return R, t, it.value, score.value, why.value
+        return _T_to_Rt(T) + (it.value, score.value, why.value)
 
     def ndt_system(self, before, vox, T=None, neighbourhood=7, outlier_ratio=0.55):
         """One NDT linearisation at transform T (mi_ndt_system) -> (sums float64 [32], centre float32 [3], idx int32 [n]: the row of every
@@ -1257,15 +1029,13 @@ class Context:
         n = before.shape[0]
         sums, centre, idx, terms = np.zeros(32, np.float64), np.zeros(3, np.float32), np.empty(n, np.int32), np.empty(n, np.uint8)
         _check(ndt_system_raw(self._h, before.ctypes.data, n, coord.ctypes.data, mean.ctypes.data, icov.ctypes.data, coord.shape[0], voxel, origin.ctypes.data,
-                              None if T0 is None else T0.ctypes.data, int(neighbourhood), float(outlier_ratio), sums.ctypes.data, centre.ctypes.data,
+                              _ptr(T0), int(neighbourhood), float(outlier_ratio), sums.ctypes.data, centre.ctypes.data,
                               idx.ctypes.data, terms.ctypes.data))
         return sums, centre, idx, terms
 
     def ndt_times(self):
         """ms per stage of the last ndt_register / ndt_system: workspace, upload, check, table, order, iterations, download, total (mi_ndt_times)."""
-        out = (C.c_double * 8)()
-        _check(ndt_times_raw(self._h, out))
-        return dict(zip(("workspace", "upload", "check", "table", "order", "iterations", "download", "total"), list(out)))
+        return self._times("ndt")
 
     # ---- local descriptors
     def fpfh_features(self, cloud, normals, k, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_counts=False, want_count=False):
@@ -1279,16 +1049,13 @@ class Context:
         fpfh = np.empty((n, FPFH_DIM), np.float32)
         counts = np.empty((n, FPFH_DIM), np.uint8) if want_counts else None
         count = np.empty(n, np.int32) if want_count else None
-        ptr = lambda a: None if a is None else a.ctypes.data
-        _check(fpfh_features_raw(self._h, cloud.ctypes.data, normals.ctypes.data, n, int(k), int(dist_mode), float(max_d2), fpfh.ctypes.data, ptr(counts), ptr(count)))
+        _check(fpfh_features_raw(self._h, cloud.ctypes.data, normals.ctypes.data, n, int(k), int(dist_mode), float(max_d2), fpfh.ctypes.data, _ptr(counts), _ptr(count)))
         res = [fpfh] + ([counts] if want_counts else []) + ([count] if want_count else [])
         return res[0] if len(res) == 1 else tuple(res)
 
     def fpfh_features_times(self):
         """ms per stage of the last fpfh_features: workspace, upload, check, grid, order, kernels, download, total (mi_fpfh_features_times)."""
-        out = (C.c_double * 8)()
-        _check(fpfh_features_times_raw(self._h, out))
-        return dict(zip(("workspace", "upload", "check", "grid", "order", "kernels", "download", "total"), list(out)))
+        return self._times("fpfh_features")
 
     def feature_match(self, query, target, mutual=False, want_d2=False):
         """The nearest row of target [m, dim] for every row of query [n, dim] in descriptor space, every pair looked at (mi_feature_match):
@@ -1300,14 +1067,12 @@ class Context:
         idx = np.empty(n, np.int32)
         d2 = np.empty(n, np.float32) if want_d2 else None
         _check(feature_match_raw(self._h, query.ctypes.data, n, target.ctypes.data, m, dim, 1 if mutual else 0, idx.ctypes.data,
-                                 None if d2 is None else d2.ctypes.data))
+                                 _ptr(d2)))
         return (idx, d2) if want_d2 else idx
 
     def feature_match_times(self):
         """ms per stage of the last feature_match: workspace, upload, check, -, -, kernels, download, total (mi_feature_match_times)."""
-        out = (C.c_double * 8)()
-        _check(feature_match_times_raw(self._h, out))
-        return dict(zip(("workspace", "upload", "check", "unused3", "unused4", "kernels", "download", "total"), list(out)))
+        return self._times("feature_match")
 
     def ransac_register(self, src, tgt, idx, params, want_mask=False):
         """A pose from correspondences src[i] <-> tgt[idx[i]] (idx -1: none) by hypothesise and verify (mi_ransac_register):
@@ -1320,7 +1085,7 @@ class Context:
         inl, best, nvalid, rmse = C.c_int(0), C.c_int(0), C.c_int(0), C.c_float(0)
         mask = np.empty(src.shape[0], np.uint8) if want_mask else None
         _check(ransac_register_raw(self._h, src.ctypes.data, src.shape[0], tgt.ctypes.data, tgt.shape[0], idx.ctypes.data, C.addressof(params), R9.ctypes.data,
-                                   t3.ctypes.data, C.addressof(inl), C.addressof(rmse), C.addressof(best), C.addressof(nvalid), None if mask is None else mask.ctypes.data))
+                                   t3.ctypes.data, C.addressof(inl), C.addressof(rmse), C.addressof(best), C.addressof(nvalid), _ptr(mask)))
         out = (R9.reshape(3, 3).T.copy(), t3, inl.value, np.float32(rmse.value), best.value, nvalid.value)
         return out + (mask,) if want_mask else out
 
@@ -1341,9 +1106,7 @@ class Context:
 
     def ransac_register_times(self):
         """ms per stage of the last ransac_register: workspace, upload, hypotheses, count, argmax, refine, -, total (mi_ransac_register_times)."""
-        out = (C.c_double * 8)()
-        _check(ransac_register_times_raw(self._h, out))
-        return dict(zip(("workspace", "upload", "hypotheses", "count", "argmax", "refine", "unused6", "total"), list(out)))
+        return self._times("ransac_register")
 
     # ---- profiling
     def profile_enable(self, on=True):
@@ -1375,7 +1138,7 @@ class Context:
         k = np.ascontiguousarray(keys, dtype=np.uint32).copy()
         v = np.ascontiguousarray(values, dtype=np.int32).copy()
         assert k.shape == v.shape and k.ndim == 1
-        _check(lib().mi_selftest_sort_pairs(self._h, k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), int(k.size), int(bits)))
+        _check(lib().mi_selftest_sort_pairs(self._h, _ptr(k), _ptr(v), int(k.size), int(bits)))
         return k, v
 
     def selftest_cloud_range(self, xyz, check=0):
@@ -1383,8 +1146,7 @@ class Context:
         check 0: refuse nothing; 1: non-finite points; 2: those and |coordinate| > 1e18 (mi_selftest_cloud_range)."""
         p = np.ascontiguousarray(xyz, dtype=np.float32)
         assert p.ndim == 2 and p.shape[1] == 3
-        lo_hi = np.zeros(6, np.float32)
-        bad = C.c_int(-1)
+        lo_hi, bad = np.zeros(6, np.float32), C.c_int(-1)
         _check(selftest_cloud_range_raw(self._h, p.ctypes.data, int(p.shape[0]), int(check), lo_hi.ctypes.data, C.byref(bad)))
         return lo_hi, int(bad.value)
 
@@ -1392,8 +1154,6 @@ class Context:
         """What the last ICP step left on the device: dict(order int32[rows], far uint8[rows], cursors int32[4], ticket, sums float64[18]
         = the 16 moments and 2 error sums the last solve read) (mi_selftest_icp_schedule)."""
         f = lib().mi_selftest_icp_schedule
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        f.restype = C.c_int
         rows, ticket = C.c_int(0), C.c_int(-1)
         cursors, sums = np.zeros(4, np.int32), np.zeros(18, np.float64)
         _check(f(self._h, 0, None, None, C.byref(rows), cursors.ctypes.data, C.byref(ticket), sums.ctypes.data))
@@ -1406,18 +1166,14 @@ class Context:
         pt1 [n], px [m,3], y [m,3] -- with arrays=False these four are left out --, xs float64[5], ks float64[14], R [3,3], t [3], scale, sigma2,
         sigma2_init, constant, route, fused, rows_x, rows_k, reduced, iterations, stop_reason)."""
         f = lib().mi_selftest_cpd_last
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 13
-        f.restype = C.c_int
         m, n = int(m), int(n)
         out = {}
         if arrays:
             out.update(p1=np.zeros(m, np.float32), pt1=np.zeros(n, np.float32), px=np.zeros((m, 3), np.float32), y=np.zeros((m, 3), np.float32))
         xs, ks, R9, t3 = np.zeros(5, np.float64), np.zeros(14, np.float64), np.zeros(9, np.float32), np.zeros(3, np.float32)
-        sc = [C.c_float(0) for _ in range(4)]
-        info = np.zeros(8, np.int32)
-        ptr = [out[k].ctypes.data if arrays else None for k in ("p1", "pt1", "px", "y")]
-        _check(f(self._h, m, n, *ptr, xs.ctypes.data, ks.ctypes.data, R9.ctypes.data, t3.ctypes.data,
-                 *[C.cast(C.byref(v), C.c_void_p) for v in sc], info.ctypes.data))
+        sc, info = [C.c_float(0) for _ in range(4)], np.zeros(8, np.int32)
+        _check(f(self._h, m, n, *[_ptr(out.get(k)) for k in ("p1", "pt1", "px", "y")], xs.ctypes.data, ks.ctypes.data, R9.ctypes.data, t3.ctypes.data,
+                 *map(C.byref, sc), info.ctypes.data))
         out.update(xs=xs, ks=ks, R=R9.reshape(3, 3).T.copy(), t=t3, scale=np.float32(sc[0].value), sigma2=np.float32(sc[1].value),
                    sigma2_init=np.float32(sc[2].value), constant=np.float32(sc[3].value))
         out.update(zip(("route", "fused", "rows_x", "rows_k", "reduced", "iterations", "stop_reason"), (int(v) for v in info[:7])))
@@ -1426,18 +1182,13 @@ class Context:
     def selftest_nicp_candidates(self, before, after, order_heads):
         """The moments stage and the candidates of nicp_register without its driver (mi_selftest_nicp_candidates): (raw float64[32] -- the sums of the
         clouds taken about their first points --, R [reps, 3, 3], t [reps, 3], approx [reps]) for order_heads [reps, 3]."""
-        f = lib().mi_selftest_nicp_candidates
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        f.restype = C.c_int
         before, after = _cloud(before), _cloud(after)
         heads = np.ascontiguousarray(order_heads, np.int32).reshape(-1, 3)
         raw, out = np.zeros(32, np.float64), np.zeros((len(heads), 13), np.float32)
-        _check(f(self._h, before.ctypes.data, before.shape[0], after.ctypes.data, after.shape[0], heads.ctypes.data, len(heads), raw.ctypes.data,
-                 out.ctypes.data))
+        _check(lib().mi_selftest_nicp_candidates(self._h, _ptr(before), before.shape[0], _ptr(after), after.shape[0], _ptr(heads), len(heads), _ptr(raw), _ptr(out)))
         return raw, out[:, :9].reshape(-1, 3, 3).copy(), out[:, 9:12].copy(), out[:, 12].copy()
 
     def nn_kernel_name(self, n_moving, m_fixed_local, nn_mode=NN_AUTO):
-        lib().mi_nn_kernel_name.restype = C.c_char_p
         return lib().mi_nn_kernel_name(self._h, n_moving, m_fixed_local, nn_mode).decode()
 
     def profile_select(self, kernels=None):
@@ -1450,9 +1201,7 @@ class Context:
 
     def icp_load_times(self):
         """ms per stage of the last icp_load: workspace, moving upload, moving order, fixed upload, hierarchy, grid, reset, total."""
-        out = (C.c_double * 8)()
-        _check(lib().mi_icp_load_times(self._h, out))
-        return dict(zip(("workspace", "upload_moving", "order_moving", "upload_fixed", "hierarchy", "grid", "reset", "total"), list(out)))
+        return self._times("icp_load")
 
     def profile_get(self, kernel):
         ms, n = C.c_double(0), C.c_longlong(0)
