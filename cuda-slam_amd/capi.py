@@ -332,6 +332,9 @@ def cluster_params(**kw):
 
 
 cluster_dbscan_raw = _raw("mi_cluster_dbscan")
+segment_plane_raw = _raw("mi_segment_plane")
+segment_plane_hypotheses_raw = _raw("mi_segment_plane_hypotheses")
+SEGMENT_MAX_PLANES = 16
 
 
 def plane_params(**kw):
@@ -549,6 +552,7 @@ class Context:
         "remove_outliers": ("workspace", "upload", "check", "grid", "order", "kernel", "finish", "total"),
         "iss_keypoints": ("workspace", "upload", "check", "grid", "order", "saliency", "finish", "total"),
         "cluster_dbscan": ("workspace", "upload", "grid", "count", "link", "resolve", "finish", "total"),
+        "segment_plane": ("workspace", "upload", "check", "hypotheses", "count", "argmax", "refine", "total"),
         "icp_plane": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
         "icp_gicp": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
         "ndt": ("workspace", "upload", "check", "table", "order", "iterations", "download", "total"),
@@ -896,6 +900,54 @@ class Context:
     def cluster_dbscan_times(self):
         """ms per stage of the last cluster_dbscan: workspace, upload (with the check), grid (with the order), count, link, resolve, finish, total (mi_cluster_dbscan_times)."""
         return self._times("cluster_dbscan")
+
+    # ---- the dominant planes of a cloud
+    @staticmethod
+    def _axis(axis):
+        if axis is None:
+            return None
+        axis = np.ascontiguousarray(axis, np.float32)
+        if axis.shape != (3,):
+            raise ValueError("axis must have 3 components")
+        return axis
+
+    def segment_plane(self, cloud, distance_threshold, hypotheses=1000, seed=0, refine_iterations=2, max_planes=1, min_inliers=3, axis=None,
+                      min_axis_cosine=0.0, want_labels=True, want_rmse=False, want_winners=False):
+        """The dominant planes of a cloud by hypothesise and verify (mi_segment_plane): planes [n_planes, 4] float32 (a, b, c, d with
+        a x + b y + c z + d = 0, in the order found) and plane_inliers [n_planes] int32; then, as asked for and in this order: labels [n]
+        int32 (the plane's number or -1), rmse [n_planes] float32 and winners [n_planes] int32 (the winning hypothesis of each round).
+        axis: only planes whose normal is within acos(min_axis_cosine) of +-axis."""
+        cloud, axis = _cloud(cloud), self._axis(axis)
+        n, P = cloud.shape[0], max(int(max_planes), 1)
+        planes, inliers, found = np.empty((P, 4), np.float32), np.empty(P, np.int32), C.c_int(0)
+        labels = np.empty(n, np.int32) if want_labels else None
+        rmse = np.empty(P, np.float32) if want_rmse else None
+        winners = np.empty(P, np.int32) if want_winners else None
+        _check(segment_plane_raw(self._h, cloud.ctypes.data, n, float(distance_threshold), int(hypotheses), int(seed) & (2 ** 64 - 1), int(refine_iterations),
+                                 int(max_planes), int(min_inliers), _ptr(axis), float(min_axis_cosine), planes.ctypes.data, C.addressof(found),
+                                 inliers.ctypes.data, _ptr(labels), _ptr(rmse), _ptr(winners)))
+        k = found.value
+        res = [planes[:k].copy(), inliers[:k].copy()]
+        res += ([labels] if want_labels else []) + ([rmse[:k].copy()] if want_rmse else []) + ([winners[:k].copy()] if want_winners else [])
+        return tuple(res)
+
+    def segment_plane_hypotheses(self, cloud, distance_threshold, hypotheses=1000, seed=0, axis=None, min_axis_cosine=0.0, first=0, count=None):
+        """Hypotheses first .. first + count - 1 of segment_plane's round 0 (mi_segment_plane_hypotheses): triples [count, 3] int32 (the
+        caller's indices), valid [count] uint8, plane4 [count, 4] float32 (zeros where invalid), inlier_count [count] int32."""
+        cloud, axis = _cloud(cloud), self._axis(axis)
+        count = int(hypotheses) - int(first) if count is None else int(count)
+        rows = max(count, 1)
+        triples, valid = np.empty((rows, 3), np.int32), np.empty(rows, np.uint8)
+        plane4, inl = np.empty((rows, 4), np.float32), np.empty(rows, np.int32)
+        _check(segment_plane_hypotheses_raw(self._h, cloud.ctypes.data, cloud.shape[0], float(distance_threshold), int(hypotheses), int(seed) & (2 ** 64 - 1),
+                                            _ptr(axis), float(min_axis_cosine), int(first), count, triples.ctypes.data, valid.ctypes.data,
+                                            plane4.ctypes.data, inl.ctypes.data))
+        return triples, valid, plane4, inl
+
+    def segment_plane_times(self):
+        """ms per stage of the last segment_plane, summed over its rounds: workspace, upload, check, hypotheses, count, argmax, refine (with
+        the flags, the labels, the peel and the downloads), total (mi_segment_plane_times)."""
+        return self._times("segment_plane")
 
     # ---- point-to-plane ICP
     def icp_plane_register(self, before, after, after_normals, params, init=None):

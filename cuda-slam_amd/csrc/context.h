@@ -267,6 +267,20 @@ struct mi_ctx {
         double ms[MI_CLUSTER_STAGES] = {0};              // mi_cluster_dbscan_times
     } cluster;
 
+    // ---- mi_segment_plane, mi_segment_plane_hypotheses: a search front end for its upload and input check (front.staging is the cloud as
+    // uploaded, what the peel gathers from), the labels and "still without a plane" flags in the caller's order, the remaining points by
+    // rank, one row per hypothesis, and two sets of flags and terms by rank: the plane that stands and the one on trial
+    struct SegmentBuffers {
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<int> labels, rem_index, tile_counts, triples, inlier_count, nvalid;
+        mislam::DevBuf<unsigned char> keep, valid, mask[2];
+        mislam::DevBuf<float> rem_xyz, plane4, plane;    // plane: the 4 floats K41 reads
+        mislam::DevBuf<double> s2[2], sums;              // sums: SEGMENT_SUMS
+        mislam::DevBuf<unsigned long long> best;
+        mislam::DevBuf<mislam::OutlierState> ostate;     // (kept: the remaining points)
+        double ms[MI_SEGMENT_STAGES] = {0};              // mi_segment_plane_times
+    } segment;
+
     // ---- mi_icp_plane_register, mi_plane_system: a search front end over the FIXED cloud with the moving cloud as its queries, the fixed
     // cloud's normals, the rows of an iteration's sums and the loop's state block -- a sibling of the three above, nothing shared with mi_icp_*
     struct PlaneBuffers {
@@ -447,7 +461,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 // The body of every *_times entry point: the eight slots a StageClock left in the context.  ms: null for a null context.
 static inline int stage_times(const char* who, const double* ms, double* out_ms)
 {

@@ -512,6 +512,52 @@ struct RansacMaskArgs {
 hipError_t ransac_mask_and_sum(const RansacMaskArgs& a, int* out_count, double* out_sum, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------------
+// K39 - K43 the dominant planes of a cloud (segment_kernels.hip; driver: segment_api.hip; the contract: mi_segment_plane in mi_slam.h).
+// K23 - K26's pattern over points instead of pairs: a round works on the REMAINING points by rank (rem_xyz, AoS, and rem_index, rank ->
+// the caller's index), K25's ransac_argmax picks the winner as it is, and K15's outlier_compact peels a plane's inliers off.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int SEGMENT_BLOCK = 256;   // = RANSAC_BLOCK: ransac_chunk_len plans K40's chunks, ransac_argmax reads its counts
+static_assert(SEGMENT_BLOCK == RANSAC_BLOCK, "K40 is planned by ransac_chunk_len");
+constexpr int SEGMENT_SUMS = 12;     // what K42 leaves: count, S, sum x y z, then xx xy xz yy yz zz about the centroid
+struct SegmentHypArgs {
+    const float* rem_xyz;            // C x 3: the remaining points by rank
+    const int* rem_index;            // C: rank -> the caller's index
+    int C;
+    unsigned long long seed;
+    unsigned long long g0;           // the global number of the first hypothesis of the launch: round * H + first
+    int count;                       // hypotheses g0 .. g0 + count - 1; the outputs are indexed from 0
+    int has_axis;
+    double axis[3], cos2;            // the caller's fp32 values, promoted; (double)cos * (double)cos
+    int* triples;                    // 3 * count: the caller's indices of the three draws
+    unsigned char* valid;            // count
+    float* plane4;                   // 4 * count: a, b, c, d; zeros where invalid
+};
+hipError_t segment_hypotheses(const SegmentHypArgs& a, hipStream_t s);
+struct SegmentCountArgs {
+    const float* rem_xyz; int C;
+    const float* plane4; const unsigned char* valid; int count;
+    double T2;                       // (double)distance_threshold squared
+    int chunk_len;                   // points per workgroup row, a multiple of SEGMENT_BLOCK (ransac_chunk_len)
+    int* inlier_count;               // count, zero before the launch
+};
+hipError_t segment_count(const SegmentCountArgs& a, hipStream_t s);
+// mask[r], s2[r] = s s / nn of an inlier (0 otherwise) of every remaining point under ONE plane on the device, then sums[SEGMENT_SUMS] by
+// one workgroup each in ransac_sum's fixed order: count, S and the coordinate sums; with want_scatter the six sums about the centroid too
+struct SegmentMaskArgs {
+    const float* rem_xyz; int C;
+    const float* plane;              // 4 floats on the device
+    double T2;
+    unsigned char* mask;             // C, by rank
+    double* s2;                      // C
+    double* sums;                    // SEGMENT_SUMS
+};
+hipError_t segment_mask_and_sums(const SegmentMaskArgs& a, int want_scatter, hipStream_t s);
+// labels[i] = -1, keep[i] = 1 for the n points of a call
+hipError_t segment_begin(int* labels, unsigned char* keep, int n, hipStream_t s);
+// labels[rem_index[r]] = plane, keep[rem_index[r]] = 0 where mask[r]
+hipError_t segment_label(const unsigned char* mask, const int* rem_index, int C, int plane, int* labels, unsigned char* keep, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------------------------
 // K27 - K31 NDT registration (ndt_kernels.hip; driver: ndt_api.hip, then pose_loop.hip for the iterations; the term of a pair: ndt_term.hpp).  mi_ndt_voxels: the voxel filter's
 // own front end (VoxArgs above: coordinates, counts and means are mi_voxel_downsample's by construction), then a second segmented pass
 // over the sorted order for the scatter about the fp32 mean and one lane per voxel for the eigenvalue floor and the inverse.
@@ -676,5 +722,6 @@ hipError_t preload_ransac_kernels();
 hipError_t preload_ndt_kernels();
 hipError_t preload_iss_kernels();
 hipError_t preload_cluster_kernels();
+hipError_t preload_segment_kernels();
 
 }  // namespace mislam

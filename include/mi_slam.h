@@ -871,6 +871,81 @@ int mi_cluster_dbscan(mi_ctx* ctx, const float* cloud_xyz, int n, const mi_clust
 int mi_cluster_dbscan_times(mi_ctx* ctx, double out_ms[MI_CLUSTER_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * The dominant planes of a cloud (no reference counterpart): hypothesise and verify, as Open3D's segment_plane and PCL's SACSegmentation
+ * with SACMODEL_PLANE -- three draws, the plane through them, a count of the points it explains, every hypothesis evaluated, the best one
+ * refined by least squares, its points taken out, and again for the next plane.  The step in front of mi_cluster_dbscan (INTEGRATION.md:
+ * planes out, then clusters).  No params struct: every setting is a scalar argument.  Single-GPU contexts only.
+ *
+ * Every rule below can be retraced in numpy (tests/segment_reference.py does), and the same input gives the same bits on every run.
+ *   Rounds: round p = 0 .. max_planes - 1 works on the REMAINING points, those without a plane yet, in ascending caller index: they are
+ *     ranks 0 .. C_p - 1, and C_0 = n.  The call ends in front of a round with C_p < 3 or C_p < min_inliers.
+ *   Draws, as mi_ransac_register's with the global hypothesis number g = p * H + h, in unsigned 64-bit arithmetic modulo 2^64:
+ *       u_r = mix(seed + 0x9E3779B97F4A7C15 * (3 g + r + 1)),  r = 0, 1, 2,   rank_r = ((u_r >> 32) * C_p) >> 32,   mix: the splitmix64 finaliser.
+ *     Two equal ranks make the hypothesis invalid.  The triple reported is the three caller indices, in draw order.
+ *   Plane of a hypothesis, in fp64 from the fp32 coordinates: e1 = p1 - p0, e2 = p2 - p0, component by component; N = e1 x e2, each
+ *     component two products and one subtraction (Nx = e1y e2z - e1z e2y, Ny = e1z e2x - e1x e2z, Nz = e1x e2y - e1y e2x);
+ *     len2 = (Nx Nx + Ny Ny) + Nz Nz.  len2 zero or not finite (collinear or coincident points): invalid.  q = 1.0 / sqrt(len2).  The plane
+ *     is rounded to fp32 at birth: (a, b, c) = (float)(N q), d = (float)(-(((Nx x0 + Ny y0) + Nz z0) q)).  A non-finite plane is invalid.
+ *     An invalid hypothesis reports (0, 0, 0, 0) and counts nothing.
+ *   Axis rule, only where axis3 is given, in fp64 from the fp32 values: dot = (a ax + b ay) + c az, aa = (ax ax + ay ay) + az az,
+ *     nn = (a a + b b) + c c; the hypothesis stays valid iff dot dot >= (cos cos) (aa nn), cos = min_axis_cosine: the plane's normal is
+ *     within acos(cos) of +-axis.  The rule is NOT applied again to refined planes.
+ *   Count, over the remaining points, in fp64 from the fp32 plane: s = ((a x + b y) + c z) + d; the point is an inlier iff
+ *     s s <= T2 nn, T2 = (double)distance_threshold * (double)distance_threshold.  No root and no division: the count is an integer function
+ *     of the reported plane, and a point exactly at the threshold belongs.
+ *   Winner: the valid hypothesis with the most inliers, the lowest h among equals.  The call ends when no hypothesis is valid or the
+ *     winner has fewer than min_inliers.
+ *   Refinement, refine_iterations times: the fp64 centroid of the current inliers (each coordinate's sum divided by their number), then
+ *     the six fp64 sums of products of (p - centroid), xx xy xz yy yz zz.  Every sum in one fixed order: rank r among the remaining
+ *     points to partial sum r mod 256 in ascending r, the partial sums added pairwise at strides 128, 64 .. 1.  The unit eigenvector of
+ *     the smallest eigenvalue (csrc/eig3.hpp in fp64), turned where its fp64 dot with the previous (a, b, c) is negative; d = -(n . centroid)
+ *     summed left to right; the plane rounded to fp32; a recount under the count rule.  An iteration that leaves fewer than 3 inliers,
+ *     or a non-finite plane, is not taken and ends refinement.
+ *   Outputs: plane p is the fp32 plane after refinement, plane_inliers[p] its final count, labels[i] = p at its inliers (-1: no plane),
+ *     rmse[p] = (float)sqrt(S / count) with S the sum of s s / nn over the inliers in the fixed order above, winners[p] the winning h of
+ *     round p.  The inliers then leave the remaining set.  Entries of the per-plane arrays at and beyond *n_planes are not written.
+ *     Asking for fewer optional outputs moves no bit of the rest.  A call that finds nothing returns MI_OK with *n_planes = 0 and,
+ *     where asked for, every label -1.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name and names the cause and, for a bad point, its index (the
+ *     lowest); NOTHING the caller passed has been written -- for a NULL ctx, cloud_xyz, planes4 or n_planes; n < 3; a distance_threshold
+ *     that is NaN, infinite or <= 0, or whose fp32 square is not finite; hypotheses, refine_iterations or max_planes outside the ranges
+ *     below; min_inliers < 3; with axis3: a non-finite or zero axis, a min_axis_cosine outside [0, 1); a non-finite coordinate or one above
+ *     1e18 in magnitude.  MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls keep: it works in buffers of its own.
+ *   Synchronous, host in and host out. */
+#define MI_SEGMENT_MAX_PLANES 16
+int mi_segment_plane(mi_ctx* ctx, const float* cloud_xyz, int n,
+                     float distance_threshold,        /* > 0, finite, square finite */
+                     int hypotheses,                  /* H: 1 .. MI_RANSAC_MAX_HYPOTHESES, every one evaluated, per plane */
+                     unsigned long long seed,
+                     int refine_iterations,           /* 0 .. MI_RANSAC_MAX_REFINE */
+                     int max_planes,                  /* P: 1 .. MI_SEGMENT_MAX_PLANES */
+                     int min_inliers,                 /* >= 3: a winner with fewer ends the call */
+                     const float axis3[3],            /* may be NULL: no constraint */
+                     float min_axis_cosine,           /* in [0, 1); read only with axis3 */
+                     float* planes4,                  /* non-NULL; 4 * P: a, b, c, d with a x + b y + c z + d = 0 */
+                     int* n_planes,                   /* non-NULL */
+                     int* plane_inliers,              /* may be NULL; P */
+                     int* labels,                     /* may be NULL; n: plane number or -1 */
+                     float* rmse,                     /* may be NULL; P */
+                     int* winners);                   /* may be NULL; P: the winning h of each round */
+/* Test-grade primitive, like mi_ransac_hypotheses: hypotheses first .. first + count - 1 of ROUND 0 (the whole cloud) of the call above
+ * (first >= 0, count >= 1, first + count <= hypotheses), each with its triple (3 caller indices), valid flag, plane and inlier count.
+ * Every output may be NULL.  The same checks and errors. */
+int mi_segment_plane_hypotheses(mi_ctx* ctx, const float* cloud_xyz, int n, float distance_threshold, int hypotheses,
+                                unsigned long long seed, const float axis3[3], float min_axis_cosine, int first, int count,
+                                int* triples /* 3*count */, unsigned char* valid /* count */, float* plane4 /* 4*count */, int* inlier_count /* count */);
+/* Where the last mi_segment_plane of this context spent its host wall time, in ms, summed over the rounds (measurement hook,
+ * tools/segment_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA
+ *   out[2] input check and its read-back            out[3] the hypothesis kernel (K39)
+ *   out[4] the counting kernel (K40)                out[5] arg-max and the winner's read-back
+ *   out[6] flags, sums, refinement, labels, the peel and the downloads          out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage). */
+#define MI_SEGMENT_STAGES 8
+int mi_segment_plane_times(mi_ctx* ctx, double out_ms[MI_SEGMENT_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Point-to-plane ICP (no reference counterpart: the reference's ICP is point-to-point): the registration the normals are for
  * (plane registration).  It minimises sum (n_j . (R b_i + t - a_j))^2 over the matched pairs, linearised about the
  * current pose, and does not stall on surfaces that slide along themselves.  A sibling of mi_icp_register with buffers, state and
