@@ -408,6 +408,45 @@ ransac_hypotheses_raw = _raw("mi_ransac_hypotheses")
 ransac_register_times_raw = _raw("mi_ransac_register_times")
 
 
+class Fgr:
+    """mi_fgr_params, held in a namespace: the module's own Structures are the thirteen that _C_TYPES names and
+    tests/test_capi_prototypes.py counts; the compiler checks this one's layout against the header's in tests/test_fgr_abi.py."""
+    C_TYPE = "mi_fgr_params"
+
+    class Params(C.Structure):
+        _fields_ = [("max_distance", C.c_float), ("division_factor", C.c_float), ("decrease_every", C.c_int), ("max_iterations", C.c_int),
+                    ("tuple_scale", C.c_float), ("max_tuples", C.c_int), ("tuple_trials", C.c_int), ("seed", C.c_ulonglong),
+                    ("eps_rotation", C.c_float), ("eps_translation", C.c_float), ("sync_every", C.c_int), ("verbose", C.c_int),
+                    ("reserved", C.c_int * 8)]
+
+
+FGR_MAX_TUPLES = 1 << 20         # MI_FGR_MAX_TUPLES
+RANSAC_MAX_HYPOTHESES = 1 << 22  # MI_RANSAC_MAX_HYPOTHESES
+
+
+def fgr_params(max_distance, **kw):
+    """mi_fgr_params_default with max_distance and any other field set: division_factor, decrease_every, max_iterations, tuple_scale,
+    max_tuples, tuple_trials, seed, eps_rotation, eps_translation, sync_every, verbose."""
+    for k in kw:
+        if k == "reserved" or k not in [f[0] for f in Fgr.Params._fields_]:
+            raise TypeError("mi_fgr_params has no field %r" % k)
+    return _params(Fgr.Params, "mi_fgr_params_default", dict(kw, max_distance=max_distance))
+
+
+def fgr_used_capacity(params, matches):
+    """The largest `used` mi_fgr_register can report for these params over `matches` correspondences: what weights and used_src are sized for."""
+    if not params.tuple_scale > 0:
+        return max(int(matches), 1)
+    trials = params.tuple_trials if params.tuple_trials > 0 else min(100 * int(matches), RANSAC_MAX_HYPOTHESES)
+    return max(3 * min(trials, params.max_tuples), 1)
+
+
+fgr_register_raw = _raw("mi_fgr_register")
+fgr_tuples_raw = _raw("mi_fgr_tuples")
+fgr_system_raw = _raw("mi_fgr_system")
+fgr_register_times_raw = _raw("mi_fgr_register_times")
+
+
 def _cov6(a, points):
     a = np.ascontiguousarray(a, np.float32)
     if a.shape != (points, 6):
@@ -559,6 +598,7 @@ class Context:
         "fpfh_features": ("workspace", "upload", "check", "grid", "order", "kernels", "download", "total"),
         "feature_match": ("workspace", "upload", "check", "unused3", "unused4", "kernels", "download", "total"),
         "ransac_register": ("workspace", "upload", "hypotheses", "count", "argmax", "refine", "unused6", "total"),
+        "fgr_register": ("workspace", "upload", "check", "tuples", "gather", "iterations", "download", "total"),
         "icp_load": ("workspace", "upload_moving", "order_moving", "upload_fixed", "hierarchy", "grid", "reset", "total"),
     }
 
@@ -1159,6 +1199,56 @@ class Context:
     def ransac_register_times(self):
         """ms per stage of the last ransac_register: workspace, upload, hypotheses, count, argmax, refine, -, total (mi_ransac_register_times)."""
         return self._times("ransac_register")
+
+    # ---- Fast Global Registration
+    @staticmethod
+    def _matches(src, tgt, idx):
+        src, tgt = _cloud(src), _cloud(tgt)
+        idx = np.ascontiguousarray(idx, np.int32)
+        if idx.shape != (src.shape[0],):
+            raise ValueError("idx has one entry per source point")
+        return src, tgt, idx
+
+    def fgr_register(self, src, tgt, idx, params, init=None, want_weights=False):
+        """A pose from correspondences src[i] <-> tgt[idx[i]] (idx -1: none) by Fast Global Registration (mi_fgr_register; params:
+        fgr_params(...); init: a [4, 4] transform indexed [row, col], None for the identity) -> (R [3, 3] float32, t [3], iterations, error,
+        stop_reason, used, final_mu), then weights [used] float32 and used_src [used] int32 if asked for."""
+        src, tgt, idx = self._matches(src, tgt, idx)
+        T0, T = _T16(init), np.zeros(16, np.float32)
+        it, why, used, err, mu = C.c_int(0), C.c_int(0), C.c_int(0), C.c_float(0), C.c_float(0)
+        cap = fgr_used_capacity(params, int((idx >= 0).sum()))
+        weights = np.zeros(cap, np.float32) if want_weights else None
+        used_src = np.zeros(cap, np.int32) if want_weights else None
+        _check(fgr_register_raw(self._h, src.ctypes.data, src.shape[0], tgt.ctypes.data, tgt.shape[0], idx.ctypes.data, C.addressof(params), _ptr(T0),
+                                T.ctypes.data, C.addressof(it), C.addressof(err), C.addressof(why), C.addressof(used), C.addressof(mu), _ptr(weights),
+                                _ptr(used_src)))
+        out = _T_to_Rt(T) + (it.value, err.value, why.value, used.value, np.float32(mu.value))
+        return out + (weights[:used.value].copy(), used_src[:used.value].copy()) if want_weights else out
+
+    def fgr_tuples(self, src, tgt, idx, params):
+        """The used list of fgr_register (mi_fgr_tuples): (used, used_src [used] int32, used_tgt [used] int32, accepted_trials)."""
+        src, tgt, idx = self._matches(src, tgt, idx)
+        cap = fgr_used_capacity(params, int((idx >= 0).sum()))
+        used_src, used_tgt = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        used, accepted = C.c_int(0), C.c_int(0)
+        _check(fgr_tuples_raw(self._h, src.ctypes.data, src.shape[0], tgt.ctypes.data, tgt.shape[0], idx.ctypes.data, C.addressof(params),
+                              C.addressof(used), used_src.ctypes.data, used_tgt.ctypes.data, C.addressof(accepted)))
+        return used.value, used_src[:used.value].copy(), used_tgt[:used.value].copy(), accepted.value
+
+    def fgr_system(self, src, tgt, idx, params, T=None, applied_updates=0):
+        """One linearisation of fgr_register over its used list at transform T with the mu that follows applied_updates updates
+        (mi_fgr_system) -> (sums float64 [32], centre float32 [3], mu float)."""
+        src, tgt, idx = self._matches(src, tgt, idx)
+        T0 = _T16(T)
+        sums, centre, mu = np.zeros(32, np.float64), np.zeros(3, np.float32), C.c_double(0)
+        _check(fgr_system_raw(self._h, src.ctypes.data, src.shape[0], tgt.ctypes.data, tgt.shape[0], idx.ctypes.data, C.addressof(params), _ptr(T0),
+                              int(applied_updates), sums.ctypes.data, centre.ctypes.data, C.addressof(mu)))
+        return sums, centre, mu.value
+
+    def fgr_register_times(self):
+        """ms per stage of the last fgr_register / fgr_system: workspace, upload, check, tuples (trials, compaction, read-back), gather,
+        iterations, download (with the weights pass), total (mi_fgr_register_times)."""
+        return self._times("fgr_register")
 
     # ---- profiling
     def profile_enable(self, on=True):

@@ -345,6 +345,21 @@ struct mi_ctx {
         double ms[MI_RANSAC_STAGES] = {0};               // mi_ransac_register_times
     } ransac;
 
+    // ---- mi_fgr_register, mi_fgr_tuples, mi_fgr_system: both clouds packed as uploaded (x, y, z and the range partials are scratch of their
+    // upload and check, one cloud after the other), the matches by rank, one row per tuple trial with the flags' compaction, the used
+    // list (indices and points by used rank), the weights, the step's mu, and K16's rows and state block
+    struct FgrBuffers {
+        mislam::DevBuf<float> staging, x, y, z, range_lo_hi, weights;
+        mislam::DevBuf<float4> src4, tgt4, used_p, used_q;
+        mislam::DevBuf<int> range_bad, match_src, match_tgt, triples, kept_trials, tile_counts, used_src, used_tgt;
+        mislam::DevBuf<unsigned char> accept;
+        mislam::DevBuf<mislam::KnnState> kstate;         // [0] the source's, [1] the target's bounding box and lowest refused point
+        mislam::DevBuf<mislam::OutlierState> ostate;     // (kept: the accepted trials)
+        mislam::DevBuf<double> mu;                       // [0]: the mu of the last linearisation that ran
+        mislam::PoseLoopBuffers loop;
+        double ms[MI_FGR_STAGES] = {0};                  // mi_fgr_register_times
+    } fgr;
+
     // ---- mi_ndt_voxels: the voxel filter's buffers once more (its front end runs on them: voxel_front_run), the scatter's partials and the results;
     // mi_ndt_register, mi_ndt_system: the moving cloud and its curve order, the listed voxels, their table, K16's rows and state block
     struct NdtBuffers {
@@ -461,7 +476,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 // The body of every *_times entry point: the eight slots a StageClock left in the context.  ms: null for a null context.
 static inline int stage_times(const char* who, const double* ms, double* out_ms)
 {

@@ -558,6 +558,48 @@ hipError_t segment_begin(int* labels, unsigned char* keep, int n, hipStream_t s)
 hipError_t segment_label(const unsigned char* mask, const int* rem_index, int C, int plane, int* labels, unsigned char* keep, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------------
+// K44 - K47 Fast Global Registration over correspondences (fgr_kernels.hip; driver: fgr_api.hip, then pose_loop.hip for the iterations;
+// the contract: mi_fgr_register in mi_slam.h).  K23's draws and edge rule (ransac_draw.hpp) as a filter over trials, K15's
+// outlier_compact over the trials' flags, the kept triples gathered into the USED list (pairs of points by used rank), and a step kernel
+// that writes K16's rows from the used list alone -- no search -- so the reduce and the solve are K16's own.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int FGR_BLOCK = 256;
+struct FgrTrialArgs {
+    const float4 *src4, *tgt4;       // both clouds as uploaded, packed (w unused)
+    const int *match_src, *match_tgt;   // C: rank -> the source index i and the target index idx[i] of the match
+    int C;
+    unsigned long long seed;
+    double e2;                       // (double)tuple_scale squared
+    int trials;
+    int* triples;                    // 3 * trials: the RANKS of the three draws
+    unsigned char* accept;           // trials: three distinct ranks whose edges pass
+};
+hipError_t fgr_trials(const FgrTrialArgs& a, hipStream_t s);            // K44
+struct FgrGatherArgs {
+    const float4 *src4, *tgt4;
+    const int *match_src, *match_tgt;
+    const int* kept_trials;          // outlier_compact's out_index over accept: used match u is draw u % 3 of trial kept_trials[u / 3];
+    const int* triples;              // ... both null: used match u is rank u (no tuple filter)
+    int used;                        // 3 * the kept trials, or C
+    int *used_src, *used_tgt;        // used: the match's indices into the caller's clouds
+    float4 *used_p, *used_q;         // used: its source and its target point
+};
+hipError_t fgr_gather(const FgrGatherArgs& a, hipStream_t s);           // K45
+struct FgrStepArgs {
+    const PlaneState* state;         // the fp64 pose to linearise at (NOT rounded to fp32), the centre, iterations, done
+    const float4 *p, *q;             // the used list: source and target points
+    int used;
+    double D2, delta2, division_factor;   // the schedule's operands (fgr_schedule.hpp)
+    int decrease_every;
+    int k;                           // the applied updates mu is formed from; < 0: state->iterations
+    double* rows;                    // plane_row_count(used) x PLANE_ROW
+    double* mu_out;                  // [0]: the mu of this linearisation
+    float* weights;                  // fgr_weights alone; used: (float)l
+};
+hipError_t fgr_step(const FgrStepArgs& a, hipStream_t s);               // K46; returns at once where the state says done
+hipError_t fgr_weights(const FgrStepArgs& a, hipStream_t s);            // K47: the step's arithmetic up to l, no rows, whatever done says
+
+// ---------------------------------------------------------------------------------------------------------------
 // K27 - K31 NDT registration (ndt_kernels.hip; driver: ndt_api.hip, then pose_loop.hip for the iterations; the term of a pair: ndt_term.hpp).  mi_ndt_voxels: the voxel filter's
 // own front end (VoxArgs above: coordinates, counts and means are mi_voxel_downsample's by construction), then a second segmented pass
 // over the sorted order for the scatter about the fp32 mean and one lane per voxel for the eigenvalue floor and the inverse.
@@ -723,5 +765,6 @@ hipError_t preload_ndt_kernels();
 hipError_t preload_iss_kernels();
 hipError_t preload_cluster_kernels();
 hipError_t preload_segment_kernels();
+hipError_t preload_fgr_kernels();
 
 }  // namespace mislam

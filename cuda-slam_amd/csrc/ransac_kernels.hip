@@ -1,5 +1,5 @@
 // K23 - K26 hypothesise and verify over correspondences (driver: ransac_api.hip; the contract: mi_ransac_register in mi_slam.h).
-//   K23 ransac_hypothesis: one lane per hypothesis.  The three counter-based draws, the edge check in fp64, the Kabsch solve of the three
+//   K23 ransac_hypothesis: one lane per hypothesis.  The three counter-based draws and the edge check in fp64 (ransac_draw.hpp), the Kabsch solve of the three
 //                          pairs (fp64 moments rounded to fp32 as solve_from_moments does, kabsch_rotation in the IEEE form, one
 //                          Newton-Schulz step in fp64 towards the nearest rotation).  Writes the triple, the valid flag and the fp32 pose.
 //   K24 ransac_count:      the hot path, O(H C).  One lane per hypothesis with its pose in registers as fp64; the workgroup stages 256 pairs
@@ -15,25 +15,12 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "ransac_draw.hpp"
 #include "svd3.hpp"
 
 namespace mislam {
 
 namespace {
-
-__device__ __forceinline__ unsigned long long ransac_mix(unsigned long long z)     // the splitmix64 finaliser
-{
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
-__device__ __forceinline__ double ransac_len2(const float* p, const float* q)
-{
-    const double x = (double)p[0] - (double)q[0], y = (double)p[1] - (double)q[1], z = (double)p[2] - (double)q[2];
-    return (x * x + y * y) + z * z;
-}
 
 __global__ __launch_bounds__(RANSAC_BLOCK) void ransac_hypothesis_kernel(const RansacHypArgs a)
 {
@@ -41,10 +28,7 @@ __global__ __launch_bounds__(RANSAC_BLOCK) void ransac_hypothesis_kernel(const R
     if (k >= a.count) return;
     const unsigned long long h = (unsigned long long)(a.first + k);
     unsigned int rank[3];
-    for (int r = 0; r < 3; r++) {
-        const unsigned long long u = ransac_mix(a.seed + 0x9E3779B97F4A7C15ull * (3ull * h + (unsigned long long)r + 1ull));
-        rank[r] = (unsigned int)(((u >> 32) * (unsigned long long)a.C) >> 32);      // < C
-    }
+    for (int r = 0; r < 3; r++) rank[r] = ransac_draw_rank(a.seed, h, r, a.C);      // < C (ransac_draw.hpp)
     float s[3][3], t[3][3];
     for (int r = 0; r < 3; r++) {
         const float* p = a.pairs6 + 6 * (size_t)rank[r];
@@ -52,12 +36,7 @@ __global__ __launch_bounds__(RANSAC_BLOCK) void ransac_hypothesis_kernel(const R
         a.triples[3 * (size_t)k + r] = a.src_index[rank[r]];
     }
     bool valid = rank[0] != rank[1] && rank[0] != rank[2] && rank[1] != rank[2];
-    {   // the edges (0, 1), (1, 2), (0, 2), written out: constant indices keep the points in registers
-        const double ls01 = ransac_len2(s[0], s[1]), lt01 = ransac_len2(t[0], t[1]);
-        const double ls12 = ransac_len2(s[1], s[2]), lt12 = ransac_len2(t[1], t[2]);
-        const double ls02 = ransac_len2(s[0], s[2]), lt02 = ransac_len2(t[0], t[2]);
-        valid = valid && ls01 >= a.e2 * lt01 && lt01 >= a.e2 * ls01 && ls12 >= a.e2 * lt12 && lt12 >= a.e2 * ls12 && ls02 >= a.e2 * lt02 && lt02 >= a.e2 * ls02;
-    }
+    valid = valid && ransac_edges_similar(s, t, a.e2);
     float R9[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, t3[3] = {0.f, 0.f, 0.f};
     if (valid) {
         // the moments of solve_from_moments (icp_solve.hpp): b = source, a = target; every sum of three left to right

@@ -1335,6 +1335,101 @@ int mi_ransac_hypotheses(mi_ctx* ctx, const float* src_xyz, int n, const float* 
 int mi_ransac_register_times(mi_ctx* ctx, double out_ms[MI_RANSAC_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * A pose from correspondences, the second method (no reference counterpart): Fast Global Registration (Zhou, Park, Koltun, ECCV 2016;
+ * Open3D's registration_fgr_based_on_feature_matching).  Where mi_ransac_register fits three matches at a time and counts, this
+ * minimises a Geman-McClure robust objective over ALL the matches by graduated non-convexity: a few dozen Gauss-Newton iterations of O(C)
+ * each, no hypothesis budget and no inlier threshold to choose.  The iterations are the pose loop of mi_icp_plane_register: the same rows,
+ * the same reduce, solve, update and stop rule, the same state block.  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+#define MI_FGR_MAX_TUPLES (1 << 20)
+typedef struct mi_fgr_params {
+    float max_distance;        /* delta > 0, finite: the annealing stops dividing once mu <= delta^2          no default: the caller sets it */
+    float division_factor;     /* > 1, finite                                                                 default 1.4 */
+    int   decrease_every;      /* >= 1: mu is divided once every this many applied updates                    default 4 */
+    int   max_iterations;      /* >= 0                                                                        default 64 */
+    float tuple_scale;         /* in [0, 1); 0: no tuple filter, every match is used once                     default 0.95 */
+    int   max_tuples;          /* 1 .. MI_FGR_MAX_TUPLES                                                      default 1000 */
+    int   tuple_trials;        /* 1 .. MI_RANSAC_MAX_HYPOTHESES; 0 = min(100 * C, MI_RANSAC_MAX_HYPOTHESES)   default 0 */
+    unsigned long long seed;
+    float eps_rotation, eps_translation;   /* as mi_plane_params; default 0, 0: the schedule runs to max_iterations */
+    int   sync_every, verbose;             /* as mi_plane_params */
+    int   reserved[8];
+} mi_fgr_params;
+void mi_fgr_params_default(mi_fgr_params* params);   /* the defaults above; max_distance 0 (the caller must set it), seed 0 */
+
+/* All arithmetic is fp64 from the caller's fp32 coordinates, every operation rounded once, nothing contracted.  Every rule below can be
+ * retraced in numpy (tests/fgr_reference.py does).
+ *   1 Matches: the pairs (i, idx[i]) with idx[i] >= 0 in ascending i are ranks 0 .. C - 1, as in mi_ransac_register.
+ *   2 Used list.  tuple_scale == 0: the used list is ranks 0 .. C - 1, once each, used = C.  tuple_scale > 0: trial h = 0 .. trials - 1
+ *     (trials = tuple_trials, or min(100 * C, MI_RANSAC_MAX_HYPOTHESES) where that is 0) draws three ranks by mi_ransac_register's
+ *     generator unchanged -- u_r = mix(seed + 0x9E3779B97F4A7C15 * (3 h + r + 1)), rank_r = ((u_r >> 32) * C) >> 32, the same mix.  Two
+ *     equal ranks reject the trial.  So does mi_ransac_register's edge check with e2 = (double)tuple_scale * (double)tuple_scale over the
+ *     pairs of draws (0, 1), (1, 2), (0, 2): ls2 >= e2 * lt2 and lt2 >= e2 * ls2 for all three.  The accepted trials are taken in ascending h
+ *     and the first max_tuples of them are kept; each kept trial contributes its three matches in draw order.  Duplicates stay: a match
+ *     drawn by several kept trials weighs that many times.  used = 3 * kept.  When no trial is accepted the call returns MI_OK with
+ *     *used = 0, init_T (or the identity) in out_T, 0 iterations, error 0, MI_STOP_NO_PAIRS and *final_mu = D2.
+ *   3 Scale and schedule.  D2 is the larger of the two clouds' squared bounding-box diagonals over ALL n and ALL m points (the library's
+ *     range pass: fp32 minima and maxima): per cloud dx = (double)hi_x - (double)lo_x and so on, ((dx*dx + dy*dy) + dz*dz).  delta2 =
+ *     (double)max_distance * (double)max_distance.  The linearisation that follows k applied updates uses mu_k: mu = D2, then
+ *     floor(k / decrease_every) times in a row "if mu > delta2: mu = mu / (double)division_factor".  The step kernel forms it from the
+ *     device's own iteration count, so sync_every moves no bit.  *final_mu = (float)mu of the last linearisation (D2 if there was none).
+ *   4 Step, one term per used match in used order.  The pose (R, t) is the fp64 state block AS IT IS -- NOT rounded to fp32, unlike the
+ *     move of mi_icp_plane_register.  c0 is the centre of the TARGET's bounding box, 0.5f * (lo + hi) in fp32, as there.  With p the source
+ *     and q the target point promoted to fp64:  x_i = ((R_i0*p_x + R_i1*p_y) + R_i2*p_z) + t_i;  r = x - q;  u = x - c0;
+ *     d2 = (r_x*r_x + r_y*r_y) + r_z*r_z;  w = mu / (mu + d2);  l = w * w.  The Jacobian's rows over (omega, v):
+ *       J_x = (0, u_z, -u_y, 1, 0, 0),  J_y = (-u_z, 0, u_x, 0, 1, 0),  J_z = (u_y, -u_x, 0, 0, 0, 1)
+ *     with -u_y and so on exact negations, and the term's entries, every product formed (the zeros and ones included):
+ *       H(i, j) = l * ((J_x[i]*J_x[j] + J_y[i]*J_y[j]) + J_z[i]*J_z[j])  for i <= j,   g(i) = l * ((J_x[i]*r_x + J_y[i]*r_y) + J_z[i]*r_z),
+ *       e = l * d2 + mu * ((w - 1) * (w - 1))   (the paper's objective with the line process eliminated: sqrt(l) = w),
+ *     aux = d2, count = 1.  A term whose x has a non-finite component contributes zeros and count 0.  No finite init_T can cause that
+ *     (|x| stays below 1e58); a pose that diverged inside the loop can.
+ *   Sums (mi_fgr_system's out_sums), the layout of mi_plane_system: [0, 21) the upper triangle of sum H, row-major; [21, 27) sum g; [27]
+ *     sum e; [28] sum d2; [29] the number of terms; [30, 32) 0.  Fixed order, a function of `used` alone: used match s is lane s % 64 of
+ *     row s / 64; a row is the tree v += shift-down(v, 32), 16, .. 1 over its 64 lanes (absent lanes hold +0); the rows are added as
+ *     mi_plane_system's are (one workgroup up to 1024 rows, 64 slabs first beyond).
+ *   5 Solve, update, stop: mi_icp_plane_register's, unchanged -- MI_STOP_NO_PAIRS below 6 terms, the scaled LDL^T with its pivot floor
+ *     (MI_STOP_DEGENERATE, the pose of the previous iteration staying), x = (omega, v) solving (sum H) x = -(sum g), R <- dR R,
+ *     t <- dR (t - c0) + c0 + v, then MI_STOP_CONVERGED under both eps, then MI_STOP_MAX_ITERATIONS.  A positive eps may stop the loop
+ *     BEFORE the schedule has brought mu down to delta2 (a step can be small while mu is still large): both default to 0, which runs the
+ *     schedule to max_iterations.  max_iterations = 0 returns init_T with MI_STOP_MAX_ITERATIONS.
+ *   6 Outputs.  out_T: the fp64 pose rounded once to fp32, column-major, as mi_icp_plane_register writes it -- it goes straight into the
+ *     init_T of that call and its siblings.  *error = (float)(sum e / terms) of the last linearisation, 0 without one.  weights[r] =
+ *     (float)l of used match r under the RETURNED fp64 pose and the mu of the last linearisation (one more pass of the step's arithmetic, no
+ *     update; 0 for a non-finite x); used_src[r] its source index i.  Both may be NULL; the caller sizes them for the largest `used` the
+ *     params allow: C without a filter, else 3 * min(trials, max_tuples).  iterations, error, stop_reason and final_mu may be NULL.
+ *   7 Determinism: no floating-point atomics, counter-based draws, an integer compaction: the same input and seed give the same bits on
+ *     every call, whatever ran on the context before.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name; NO output has been written -- for a NULL ctx, src_xyz, tgt_xyz,
+ *     idx, params, out_T or used; n < 1 or m < 1; a field of params outside the ranges above (eps NaN or negative, sync_every < 0); a
+ *     non-finite entry of init_T's rotation block or translation column; an idx[i] that is >= m or < -1 (the message names the lowest i);
+ *     fewer than 3 matches; a coordinate that is not finite or above 1e18 in magnitude (the message names the array and the lowest index).
+ *     MI_ERR_STATE on a distributed context.  A problem loaded by mi_icp_load survives the call: it works in buffers of its own.
+ *     Synchronous, host in and host out. */
+int mi_fgr_register(mi_ctx* ctx, const float* src_xyz, int n, const float* tgt_xyz, int m,
+                    const int* idx,                    /* n: src[i] <-> tgt[idx[i]]; -1: no pair (mi_feature_match's output) */
+                    const mi_fgr_params* params, const float init_T[16] /* may be NULL: identity */,
+                    float out_T[16], int* iterations, float* error, int* stop_reason, int* used, float* final_mu,
+                    float* weights /* may be NULL; used */, int* used_src /* may be NULL; used */);
+/* Test-grade primitive: the used list of the call above (rule 2) -- *used, the source and target indices of every used match in used
+ * order (either may be NULL; sized as weights above) and the number of accepted trials before max_tuples cuts (0 without a filter; may
+ * be NULL).  The same checks and errors, with used in the place of out_T. */
+int mi_fgr_tuples(mi_ctx* ctx, const float* src_xyz, int n, const float* tgt_xyz, int m, const int* idx, const mi_fgr_params* params,
+                  int* used, int* used_src, int* used_tgt, int* accepted_trials);
+/* Test-grade primitive, like mi_plane_system: one linearisation (rules 3 and 4) over the used list at the pose T (NULL: the identity, the
+ * same bits) with the mu that follows applied_updates (>= 0) updates: the sums, the centre c0 and that mu, unrounded (the last two may be
+ * NULL).  Without a used match the sums are 0.  The same checks and errors, with out_sums in the place of out_T. */
+int mi_fgr_system(mi_ctx* ctx, const float* src_xyz, int n, const float* tgt_xyz, int m, const int* idx, const mi_fgr_params* params,
+                  const float T[16] /* may be NULL */, int applied_updates, double out_sums[32], float out_centre[3], double* mu);
+/* Where the last mi_fgr_register or mi_fgr_system of this context spent its host wall time, in ms (measurement hook, tools/fgr_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload (both clouds, the matches, the state)
+ *   out[2] range pass, input check, its read-back   out[3] tuple trials, their compaction, its read-back
+ *   out[4] gather of the used list                  out[5] the iterations, host reads of the state included
+ *   out[6] weights pass and downloads               out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage). */
+#define MI_FGR_STAGES 8
+int mi_fgr_register_times(mi_ctx* ctx, double out_ms[MI_FGR_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Registration against a voxel map (no reference counterpart): the Normal Distributions Transform (Biber & Strasser, IROS 2003; Magnusson,
  * 2009), as in PCL's NormalDistributionsTransform (registration against a voxel map).  The fixed side is summarised ONCE as
  * one Gaussian per occupied voxel (mi_ndt_voxels); a scan is then registered against those Gaussians by a direct voxel lookup per point,
