@@ -355,6 +355,27 @@ gicp_system_raw = _raw("mi_gicp_system")
 icp_gicp_times_raw = _raw("mi_icp_gicp_times")
 
 
+estimate_color_gradients_raw = _raw("mi_estimate_color_gradients")
+icp_color_register_raw = _raw("mi_icp_color_register")
+color_system_raw = _raw("mi_color_system")
+icp_color_times_raw = _raw("mi_icp_color_times")
+
+
+def intensity_of_rgb(rgb):
+    """The intensity the colour calls take, one float32 per point, of colours [n, 3]: (r + g + b) / 3, in float32 and in that order."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    if rgb.ndim != 2 or rgb.shape[1] != 3:
+        raise ValueError("colours are [n, 3]: r, g, b per point")
+    return ((rgb[:, 0] + rgb[:, 1]) + rgb[:, 2]) / np.float32(3)
+
+
+def _intensity(a, points):
+    a = np.ascontiguousarray(a, np.float32)
+    if a.shape != (points,):
+        raise ValueError("intensities are [points]: one float per point")
+    return a
+
+
 def ndt_params(**kw):
     """mi_ndt_params with the library's defaults, then the given fields"""
     return _params(NdtParams, "mi_ndt_params_default", kw)
@@ -594,6 +615,7 @@ class Context:
         "segment_plane": ("workspace", "upload", "check", "hypotheses", "count", "argmax", "refine", "total"),
         "icp_plane": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
         "icp_gicp": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
+        "icp_color": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
         "ndt": ("workspace", "upload", "check", "table", "order", "iterations", "download", "total"),
         "fpfh_features": ("workspace", "upload", "check", "grid", "order", "kernels", "download", "total"),
         "feature_match": ("workspace", "upload", "check", "unused3", "unused4", "kernels", "download", "total"),
@@ -1069,6 +1091,65 @@ class Context:
         """ms per stage of the last icp_gicp_register / gicp_system: workspace, upload, check, grid, order, iterations, download, total
         (mi_icp_gicp_times)."""
         return self._times("icp_gicp")
+
+    # ---- colored ICP
+    def estimate_color_gradients(self, cloud, normals, intensity, k, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_count=False):
+        """Per-point colour gradients from every point's k nearest neighbours (mi_estimate_color_gradients): [n, 3] float32, the gradient of
+        the intensity over the point's tangent plane; (0, 0, 0) where a point has fewer than two neighbours, a zero normal or a singular
+        system; then count [n] if asked for."""
+        cloud, normals = _cloud(cloud), _cloud(normals)
+        n = cloud.shape[0]
+        if normals.shape != cloud.shape:
+            raise ValueError("normals must have one normal per point")
+        intensity = _intensity(intensity, n)
+        grad = np.empty((n, 3), np.float32)
+        count = np.empty(n, np.int32) if want_count else None
+        _check(estimate_color_gradients_raw(self._h, cloud.ctypes.data, normals.ctypes.data, intensity.ctypes.data, n, int(k), int(dist_mode), float(max_d2),
+                                            grad.ctypes.data, _ptr(count)))
+        return (grad, count) if want_count else grad
+
+    @staticmethod
+    def _color_fixed(after, after_normals, after_intensity, after_gradients):
+        after, normals, grad = _cloud(after), _cloud(after_normals), _cloud(after_gradients)
+        if normals.shape != after.shape or grad.shape != after.shape:
+            raise ValueError("after_normals and after_gradients must have one row per fixed point")
+        return after, normals, _intensity(after_intensity, after.shape[0]), grad
+
+    def icp_color_register(self, before, before_intensity, after, after_normals, after_intensity, after_gradients, params, lambda_geometric=0.968, init=None):
+        """Colored ICP of `before` with its intensities onto `after` with its normals, intensities and colour gradients
+        (mi_icp_color_register; params: plane_params(...); init: a [4, 4] transform indexed [row, col], None for the identity) ->
+        (R [3, 3], t [3], iterations, error, stop_reason)."""
+        before = _cloud(before)
+        ib = _intensity(before_intensity, before.shape[0])
+        after, normals, ia, grad = self._color_fixed(after, after_normals, after_intensity, after_gradients)
+        T0 = _T16(init)
+        T = np.zeros(16, np.float32)
+        it, err, why = C.c_int(0), C.c_float(0), C.c_int(0)
+        _check(icp_color_register_raw(self._h, before.ctypes.data, ib.ctypes.data, before.shape[0], after.ctypes.data, normals.ctypes.data, ia.ctypes.data,
+                                      grad.ctypes.data, after.shape[0], C.addressof(params), float(lambda_geometric), _ptr(T0), T.ctypes.data,
+                                      C.addressof(it), C.addressof(err), C.addressof(why)))
+        return _T_to_Rt(T) + (it.value, err.value, why.value)
+
+    def color_system(self, before, before_intensity, after, after_normals, after_intensity, after_gradients, T=None, dist_mode=DIST_CPU_ROUNDING,
+                     max_d2=np.inf, lambda_geometric=0.968, want_idx=True):
+        """One colored-ICP linearisation at transform T (mi_color_system) -> (sums float64 [32], centre float32 [3], idx int32 [n] if asked
+        for: the fixed index of every moving point's pair, -1 where it has none)."""
+        before = _cloud(before)
+        n = before.shape[0]
+        ib = _intensity(before_intensity, n)
+        after, normals, ia, grad = self._color_fixed(after, after_normals, after_intensity, after_gradients)
+        T0 = _T16(T)
+        sums, centre = np.zeros(32, np.float64), np.zeros(3, np.float32)
+        idx = np.empty(n, np.int32) if want_idx else None
+        _check(color_system_raw(self._h, before.ctypes.data, ib.ctypes.data, n, after.ctypes.data, normals.ctypes.data, ia.ctypes.data, grad.ctypes.data,
+                                after.shape[0], _ptr(T0), int(dist_mode), float(max_d2), float(lambda_geometric), sums.ctypes.data, centre.ctypes.data,
+                                _ptr(idx)))
+        return (sums, centre, idx) if want_idx else (sums, centre)
+
+    def icp_color_times(self):
+        """ms per stage of the last icp_color_register / color_system: workspace, upload, check, grid, order, iterations, download, total
+        (mi_icp_color_times)."""
+        return self._times("icp_color")
 
     # ---- registration against a voxel map
     def ndt_voxels(self, xyz, voxel, origin=None, min_points=6, eig_ratio=0.01, want_cov=False):

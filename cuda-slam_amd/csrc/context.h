@@ -312,6 +312,35 @@ struct mi_ctx {
         double ms[MI_GICP_STAGES] = {0};                 // mi_icp_gicp_times
     } gicp;
 
+    // ---- mi_estimate_color_gradients: mi_fpfh_features' front end -- self mode, the normals beside the cloud -- with the intensities beside
+    // them and three floats per point as its result
+    struct ColorGradientBuffers {
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<float> nx, ny, nz;                // the normals, SoA, the caller's order
+        mislam::DevBuf<mislam::KnnState> nstate;         // the normals' input check
+        mislam::DevBuf<float> intensity;                 // as uploaded, the caller's order
+        mislam::DevBuf<int> bad;                         // [0] the lowest refused intensity, or KNN_NO_POINT
+        mislam::DevBuf<float> out_gradients;
+        mislam::DevBuf<int> out_count;
+        double ms[MI_NORMALS_STAGES] = {0};              // (the stages of mi_estimate_normals_times; no entry point reads them yet)
+    } colorgrad;
+
+    // ---- mi_icp_color_register, mi_color_system: PlaneBuffers' sibling -- a search front end over the FIXED cloud with the moving cloud as its
+    // queries, the fixed cloud's normals, gradients and intensities, the moving cloud's intensities, the rows of an iteration's sums and the
+    // loop's state block (K16's layout: its reduce and solve run on them)
+    struct ColorBuffers {
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<float> nx, ny, nz;                // the normals, SoA, the caller's order (what their input check reads)
+        mislam::DevBuf<float4> normals;                  // the same, packed (what the step kernel gathers)
+        mislam::DevBuf<mislam::KnnState> nstate;         // the normals' input check
+        mislam::DevBuf<float> ia_in, grad_in;            // the fixed cloud's intensities and gradients as uploaded
+        mislam::DevBuf<float4> grad_i;                   // ... packed, (g_x, g_y, g_z, I), the caller's order (what the step kernel gathers)
+        mislam::DevBuf<float> ib_in, ib;                 // the moving cloud's intensities: the caller's order, and along the curve (what the step kernel streams)
+        mislam::DevBuf<int> bad;                         // [0] before_intensity, [1] after_intensity, [2] after_gradients_xyz: the lowest refused index, or KNN_NO_POINT
+        mislam::PoseLoopBuffers loop;
+        double ms[MI_COLOR_STAGES] = {0};                // mi_icp_color_times
+    } color;
+
     // ---- mi_fpfh_features: a search front end in self mode, the normals beside the cloud, what K18 leaves for K19 and the results
     struct FpfhBuffers {
         mislam::SearchFrontBuffers front;
@@ -476,7 +505,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 // The body of every *_times entry point: the eight slots a StageClock left in the context.  ms: null for a null context.
 static inline int stage_times(const char* who, const double* ms, double* out_ms)
 {

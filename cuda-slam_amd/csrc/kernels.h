@@ -741,6 +741,43 @@ hipError_t cluster_labels(const ClusterNumberArgs& a, hipStream_t s);     // K38
 // keys[k] = (unsigned)labels[index[k]] >> shift for k < count: the sort keys of the grouping
 hipError_t cluster_group_keys(const int* labels, const int* index, int count, int shift, unsigned int* keys, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K48 / K49 colored ICP (color_kernels.hip; driver: color_api.hip, then pose_loop.hip for the iterations; the arithmetic of a gradient and
+// of a pair: color_terms.hpp).  K48 is K14's shape -- K13's search in self mode and, with the keys still in registers, the sums of a
+// tangent-plane least squares and its 3 x 3 solve.  K49 is K16's step with a photometric residual beside the geometric one; it writes K16's
+// rows, so the reduce, the solve, the state block and the rules are K16's own: plane_reduce_solve, PlaneState, PlaneRules.
+// ---------------------------------------------------------------------------------------------------------------
+struct ColorGradientArgs {
+    SearchQueries q;                 // the cloud itself (self mode)
+    SearchCloud c;
+    const float *nx, *ny, *nz;       // the normals, as the cloud: SoA, the caller's order
+    const float* intensity;          // n, the caller's order
+    int k;
+    float max_d2;                    // candidates with d2 > this do not exist (+inf: no limit)
+    float* gradients;                // n * 3, AoS, the caller's order
+    int* count;                      // n, may be null
+};
+hipError_t color_gradients(const NnGridView& g, const ColorGradientArgs& a, int fma, hipStream_t s);
+struct ColorStepArgs {
+    const PlaneState* state;         // the pose to linearise at (rounded to fp32 by every lane), the centre, done
+    SearchQueries q;                 // the moving cloud
+    SearchCloud c;                   // the fixed cloud
+    const float4* normals;           // the fixed cloud's normals in the caller's order (w unused)
+    const float4* grad_i;            // the fixed cloud's colour gradients and intensities in the caller's order: (g_x, g_y, g_z, I)
+    const float* ib;                 // the moving cloud's intensities along its curve order: read at the lane's own slot
+    double lambda;                   // the caller's fp32 lambda_geometric, promoted
+    float max_d2;                    // a match with d2 > this is no pair (+inf: no limit)
+    double* rows;                    // plane_row_count(n) x PLANE_ROW
+    int* idx;                        // may be null; n, the caller's order: the matched fixed index of a pair, -1 otherwise
+};
+hipError_t color_step(const NnGridView& g, const ColorStepArgs& a, int fma, hipStream_t s);
+// *bad = min(*bad, the lowest index of v with a value that is not finite or above 1e18 in magnitude) -- the caller sets *bad to KNN_NO_POINT first
+hipError_t color_check_values(const float* v, int count, int* bad, hipStream_t s);
+// m gradients of three floats and m intensities as uploaded -> one float4 each; both arrays checked as above, each into its own word
+hipError_t color_pack_fixed(const float* grad3, const float* intensity, int m, float4* packed, int* bad_intensity, int* bad_gradient, hipStream_t s);
+// out[s] = in[order[s]]: the moving cloud's intensities along its curve
+hipError_t color_permute_intensity(const float* in, const int* order, int n, float* out, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -766,5 +803,6 @@ hipError_t preload_iss_kernels();
 hipError_t preload_cluster_kernels();
 hipError_t preload_segment_kernels();
 hipError_t preload_fgr_kernels();
+hipError_t preload_color_kernels();
 
 }  // namespace mislam

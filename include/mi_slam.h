@@ -1146,6 +1146,115 @@ int mi_gicp_system(mi_ctx* ctx, const float* before_xyz, const float* before_cov
 int mi_icp_gicp_times(mi_ctx* ctx, double out_ms[MI_GICP_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * Colored ICP (no reference counterpart): Park, Zhou, Koltun, Colored Point Cloud Registration Revisited, ICCV 2017 (INTEGRATION.md:
+ * colour registration).  Beside the point-to-plane residual every pair carries a photometric one: the fixed cloud's intensity, continued
+ * over its tangent plane by a per-point gradient, against the moving point's intensity.  On walls, floors and table tops the geometry
+ * leaves three motions of six open (mi_icp_plane_register stops with MI_STOP_DEGENERATE there); the texture fixes them.  Intensity is
+ * one float per point; a caller with colours converts them first ((r + g + b) / 3 is the usual choice).  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+
+/* Per-point colour gradients of a cloud with normals and intensities, computed on the device: three floats per point, the gradient of the
+ * intensity over the point's tangent plane.  Every rule can be retraced in numpy (tests/color_reference.py does).
+ *   Neighbourhood of point i: the neighbours that mi_knn_search(ctx, NULL, n, cloud_xyz, n, k, dist_mode, max_distance_squared, ...)
+ *     returns for row i -- the same set in the same order, bit for bit: self mode skips by index, and a duplicate of point i stored
+ *     elsewhere is a neighbour.  count[i] is that call's count[i].  A finite max_distance_squared makes it the "hybrid" k-and-radius
+ *     neighbourhood; INFINITY is no limit.
+ *   Sums, every operand promoted to fp64 first and every operation rounded; sums of three are formed left to right, (x + y) + z; the
+ *     neighbours j are taken in the order of mi_knn_search's row i, nearest first; n is the normal of point i, used as given:
+ *       e = p_j - p_i                                  s = (n_x e_x + n_y e_y) + n_z e_z
+ *       u = e - s n      u_a = e_a - s n_a  (the neighbour projected into the tangent plane)
+ *       delta = I_j - I_i
+ *       M += u u^T       M_ab += u_a u_b for a <= b: xx, xy, xz, yy, yz, zz (one product, one addition per entry and neighbour)
+ *       b += u delta     b_a += u_a delta
+ *   Constraint: behind the loop, with w = (double)count[i] and ww = w w, M_ab += (ww n_a) n_b for a <= b: the row d . n = 0 of the least
+ *     squares, weighted by the neighbour count.
+ *   Solve: d = M^-1 b by the adjugate and the determinant, mi_icp_gicp_register's cofactors with M in the place of Sigma:
+ *       c00 = M11 M22 - M12 M12   c01 = M02 M12 - M01 M22   c02 = M01 M12 - M02 M11
+ *       c11 = M00 M22 - M02 M02   c12 = M01 M02 - M00 M12   c22 = M00 M11 - M01 M01   (two products, one subtraction)
+ *       det = (M00 c00 + M01 c01) + M02 c02;   d_r = ((c_r0 b_0 + c_r1 b_1) + c_r2 b_2) / det, c symmetric
+ *     Each component is rounded once to fp32.
+ *   Zero gradient: d = (0, 0, 0) where count[i] < 2, where the normal of point i is exactly (0, 0, 0) (what mi_estimate_normals writes
+ *     for a point with fewer than three points), or where det is <= 0 or not finite.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name and names the cause and, for a bad point, normal or
+ *     intensity, its index (the lowest); NO output array has been written -- for a NULL ctx, cloud_xyz, normals_xyz, intensity or
+ *     gradients_xyz; n < 1; k outside [2, MI_KNN_MAX_K]; a dist_mode other than the two of mi_knn_search; max_distance_squared NaN or
+ *     negative; a non-finite coordinate, normal component or intensity, or one above 1e18 in magnitude.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls of this header keep: it works in buffers
+ *     of its own.  Synchronous, host in and host out. */
+int mi_estimate_color_gradients(mi_ctx* ctx,
+                                const float* cloud_xyz, const float* normals_xyz, const float* intensity, int n,
+                                int k, int dist_mode,            /* 2 <= k <= MI_KNN_MAX_K; MI_DIST_CPU_ROUNDING or MI_DIST_FMA */
+                                float max_distance_squared,      /* INFINITY: no limit; else neighbours with d2 > this do not exist */
+                                float* gradients_xyz,            /* n*3 */
+                                int* count);                     /* may be NULL; n: neighbours used for point i (<= k) */
+
+/* Registers the moving cloud `before` (n points with intensities) onto the fixed cloud `after` (m points with normals, intensities and
+ * colour gradients), on the device.  params is mi_plane_params, and every field means here what it means for mi_icp_plane_register.
+ * lambda_geometric in [0, 1] weighs the geometric residual, 1 - lambda_geometric the photometric one (0.968 is the authors' choice).
+ * Every rule below can be retraced in numpy (tests/color_reference.py does).
+ *   Transform, the pose's rounding to fp32, q, match, centre c0: exactly those of mi_icp_plane_register -- q = ((R00*b_x + R01*b_y) +
+ *     R02*b_z) + t_x in fp32 with the pose rounded once; the pair of moving point i is row i of mi_knn_search(ctx, q, n, after_xyz, m, 1,
+ *     dist_mode, max_distance_squared, ...), key for key; c0 = 0.5f * (lo + hi) of the fixed cloud's bounding box.  A query without a
+ *     candidate within the limit has no pair, and neither has one whose matched normal is exactly (0, 0, 0).  A matched gradient of
+ *     (0, 0, 0) is still a pair: its photometric residual is the plain intensity difference.
+ *   Pair terms, every operand promoted to fp64 first and every operation rounded; j the match of i, n, g and Ia the normal, gradient
+ *     and intensity of fixed point j, Ib the intensity of moving point i; sums of three are formed left to right; (P x y)_0 = P_y y_2 -
+ *     P_z y_1, (P x y)_1 = P_z y_0 - P_x y_2, (P x y)_2 = P_x y_1 - P_y y_0 (two products, one subtraction each):
+ *       dv = q - a_j             P = q - c0
+ *       rG = (n_x dv_x + n_y dv_y) + n_z dv_z                          JG = [P x n, n]      (mi_icp_plane_register's r and J)
+ *       qp = dv - rG n           qp_a = dv_a - rG n_a                  (q projected into the tangent plane of a_j, relative to a_j)
+ *       rC = (((g_x qp_x + g_y qp_y) + g_z qp_z) + Ia) - Ib
+ *       gn = (g_x n_x + g_y n_y) + g_z n_z       mvec = g - gn n       mvec_a = g_a - gn n_a
+ *       JC = [P x mvec, mvec]
+ *   Weights: lg = (double)lambda_geometric, lc = 1.0 - lg.  Per pair, with a <= b over the six entries of JG and JC:
+ *       H_ab = lg (JG_a JG_b) + lc (JC_a JC_b)       g_a = lg (JG_a rG) + lc (JC_a rC)       e = lg (rG rG) + lc (rC rC)
+ *     With lambda_geometric = 1 the colour terms are multiplied by +0: the sums are mi_plane_system's, except where a signed zero differs.
+ *   Sums (mi_color_system's out_sums), the layout of mi_plane_system: [0, 21) the upper triangle of sum H, row-major; [21, 27) sum g;
+ *     [27] sum e; [28] sum d2 (the matches' fp32 squared distances); [29] the number of pairs; [30, 32) 0.  The sums are added in a
+ *     fixed order that depends on n alone, with no floating-point atomics: the same input gives the same bits on every call, whatever
+ *     ran on the context before and whatever sync_every.
+ *   Solve, update, stop rule, outputs, sync_every, max_iterations = 0: those of mi_icp_plane_register, by the same code, with
+ *     x = (omega, v) solving (sum H) x = -(sum g): MI_STOP_NO_PAIRS below 6 pairs; MI_STOP_DEGENERATE on a diagonal entry that is <= 0
+ *     or not finite or a pivot of the scaled LDL^T below 1e-10 (the pose stays as it was); dR by Rodrigues' formula, R <- dR R,
+ *     t <- dR (t - c0) + c0 + v; MI_STOP_CONVERGED, then MI_STOP_MAX_ITERATIONS.  *error is sum e / pairs of the last linearisation,
+ *     rounded to fp32, 0 when it had no pair.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name and names the cause and, for a bad point, normal, intensity
+ *     or gradient, which array and which index (the lowest); NO output has been written -- for a NULL ctx, before_xyz, before_intensity,
+ *     after_xyz, after_normals_xyz, after_intensity, after_gradients_xyz, params or out_T; n < 1 or m < 1; a dist_mode other than the
+ *     two of mi_knn_search; max_distance_squared NaN or negative; lambda_geometric NaN or outside [0, 1]; eps_rotation or
+ *     eps_translation NaN or negative; max_iterations < 0; sync_every < 0; a non-finite entry of init_T's rotation block or translation
+ *     column; a non-finite coordinate, normal component, intensity or gradient component, or one above 1e18 in magnitude.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls of this header keep: it works in buffers
+ *     of its own.  Synchronous, host in and host out. */
+int mi_icp_color_register(mi_ctx* ctx, const float* before_xyz, const float* before_intensity, int n,
+                          const float* after_xyz, const float* after_normals_xyz, const float* after_intensity,
+                          const float* after_gradients_xyz, int m,
+                          const mi_plane_params* params, float lambda_geometric, const float init_T[16] /* may be NULL: identity */,
+                          float out_T[16], int* iterations, float* error, int* stop_reason);
+
+/* One linearisation at a given transform, as mi_plane_system: the sums above at the pose T (NULL: the identity, the same bits), the
+ * centre c0, and per moving point the fixed index of its pair, or -1 where it has none.  The same arguments are refused, with out_sums
+ * in the place of out_T; out_centre and out_idx may be NULL. */
+int mi_color_system(mi_ctx* ctx, const float* before_xyz, const float* before_intensity, int n,
+                    const float* after_xyz, const float* after_normals_xyz, const float* after_intensity,
+                    const float* after_gradients_xyz, int m,
+                    const float T[16] /* may be NULL */, int dist_mode, float max_distance_squared, float lambda_geometric,
+                    double out_sums[32], float out_centre[3], int* out_idx /* may be NULL; n: matched fixed index or -1 */);
+
+/* Where the last mi_icp_color_register or mi_color_system of this context spent its host wall time, in ms (measurement hook,
+ * tools/color_icp_bench.py).  The stages are those of mi_icp_plane_times, with the intensities and gradients beside the normals:
+ *   out[0] workspace (device allocations)           out[1] upload + repack (intensities, gradients, normals, both clouds, state)
+ *   out[2] input checks, bounding box, read-backs   out[3] cell grid over the fixed cloud
+ *   out[4] curve order of the moving cloud + permute (its intensities with it)
+ *   out[5] the iterations, host reads of the state included
+ *   out[6] download of the results                  out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage). */
+#define MI_COLOR_STAGES 8
+int mi_icp_color_times(mi_ctx* ctx, double out_ms[MI_COLOR_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Local descriptors (no reference counterpart): Fast Point Feature Histograms (Rusu, Blodow, Beetz, ICRA 2009) of a cloud with normals,
  * the descriptor a global registration matches to find the start that the local registrations above refine (INTEGRATION.md:
  * descriptors).  Matching the descriptors: mi_feature_match below (a start without odometry).  Single-GPU contexts only.
