@@ -37,6 +37,20 @@ def d2_matrix(query, cloud, dist_mode):
     return fma_sq_f32(dz, fma_sq_f32(dy, dx * dx))
 
 
+def d2_pairs(a, b, dist_mode):
+    """float32 [n]: |b[r] - a[r]|^2 over paired rows in the arithmetic of dist_mode -- d2_matrix's expression, operation for operation, so
+    d2_pairs(q[i], c[j]) is d2_matrix(q, c)[i, j] bit for bit (tests/test_cluster_scale_reference.py)."""
+    a = np.ascontiguousarray(a, np.float32)
+    b = np.ascontiguousarray(b, np.float32)
+    dx = b[:, 0] - a[:, 0]
+    dy = b[:, 1] - a[:, 1]
+    dz = b[:, 2] - a[:, 2]
+    if dist_mode == DIST_CPU_ROUNDING:
+        return (dx * dx + dy * dy) + dz * dz
+    assert dist_mode == DIST_FMA
+    return fma_sq_f32(dz, fma_sq_f32(dy, dx * dx))
+
+
 def sorted_keys(query, cloud, dist_mode, max_d2=np.inf, keep=32, block=256, only=None):
     """uint64 [n, keep]: every row's `keep` smallest keys, ascending, KEY_EMPTY where the candidates run out.  query None: self mode,
     the key of candidate i is void in row i (by index).  (Rows are worked `block` at a time: the matrix itself is never held whole.)
