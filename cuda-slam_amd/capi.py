@@ -326,6 +326,27 @@ def iss_params(**kw):
 iss_keypoints_raw = _raw("mi_iss_keypoints")
 
 
+class Mls:
+    """mi_mls_params, held in a namespace as Fgr's is; the compiler checks this one's layout against the header's in tests/test_mls_abi.py."""
+    C_TYPE = "mi_mls_params"
+    QUADRATIC, PLANE, UNTOUCHED = 0, 1, 2      # MI_MLS_*: out_status
+
+    class Params(C.Structure):
+        _fields_ = [("radius", C.c_float), ("gauss_scale", C.c_float), ("order", C.c_int), ("min_neighbours", C.c_int), ("dist_mode", C.c_int),
+                    ("reserved", C.c_int * 11)]
+
+
+def mls_params(**kw):
+    """mi_mls_params at its defaults (order 2, min_neighbours 3, CPU rounding, gauss_scale 0 = the radius; radius 0: set it) with the given fields set."""
+    for k in kw:
+        if k == "reserved" or k not in [f[0] for f in Mls.Params._fields_]:
+            raise TypeError("mi_mls_params has no field %r" % k)
+    return _params(Mls.Params, "mi_mls_params_default", kw)
+
+
+mls_smooth_raw = _raw("mi_mls_smooth")
+
+
 def cluster_params(**kw):
     """mi_cluster_params at its defaults (min_points 1, min_cluster_size 1, no upper limit, CPU rounding; radius 0: set it) with the given fields set."""
     return _params(ClusterParams, "mi_cluster_params_default", kw)
@@ -611,6 +632,7 @@ class Context:
         "estimate_normals": ("workspace", "upload", "check", "grid", "order", "fused", "download", "total"),
         "remove_outliers": ("workspace", "upload", "check", "grid", "order", "kernel", "finish", "total"),
         "iss_keypoints": ("workspace", "upload", "check", "grid", "order", "saliency", "finish", "total"),
+        "mls_smooth": ("workspace", "upload", "check", "grid", "order", "fit", "download", "total"),
         "cluster_dbscan": ("workspace", "upload", "grid", "count", "link", "resolve", "finish", "total"),
         "segment_plane": ("workspace", "upload", "check", "hypotheses", "count", "argmax", "refine", "total"),
         "icp_plane": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
@@ -941,6 +963,29 @@ class Context:
     def iss_keypoints_times(self):
         """ms per stage of the last iss_keypoints: workspace, upload, check, grid, order, saliency, finish, total (mi_iss_keypoints_times)."""
         return self._times("iss_keypoints")
+
+    # ---- moving-least-squares smoothing
+    def mls_smooth(self, cloud, params, queries=None, want_normals=False, want_curvature=False, want_neighbours=False, want_status=False):
+        """Moving-least-squares smoothing (mi_mls_smooth; params: mls_params(radius=...)): the queries (None: the cloud's own points)
+        projected onto the polynomial fitted to the cloud around them, [nq, 3] float32; then, as asked for and in this order: normals
+        [nq, 3] float32, curvature [nq] float32, neighbours [nq] int32 (the ball's count, the query's own copy included) and status
+        [nq] uint8 (Mls.QUADRATIC, Mls.PLANE, Mls.UNTOUCHED).  Alone, the smoothed queries are returned as an array, not a tuple."""
+        cloud = _cloud(cloud)
+        queries = None if queries is None else _cloud(queries)
+        nq = cloud.shape[0] if queries is None else queries.shape[0]
+        out_xyz = np.empty((nq, 3), np.float32)
+        normals = np.empty((nq, 3), np.float32) if want_normals else None
+        curvature = np.empty(nq, np.float32) if want_curvature else None
+        neighbours = np.empty(nq, np.int32) if want_neighbours else None
+        status = np.empty(nq, np.uint8) if want_status else None
+        _check(mls_smooth_raw(self._h, cloud.ctypes.data, cloud.shape[0], _ptr(queries), nq, C.addressof(params), out_xyz.ctypes.data, _ptr(normals),
+                              _ptr(curvature), _ptr(neighbours), _ptr(status)))
+        res = [out_xyz] + [a for a in (normals, curvature, neighbours, status) if a is not None]
+        return out_xyz if len(res) == 1 else tuple(res)
+
+    def mls_smooth_times(self):
+        """ms per stage of the last mls_smooth: workspace, upload, check, grid, order, fit, download, total (mi_mls_smooth_times)."""
+        return self._times("mls_smooth")
 
     # ---- density-based clustering
     def cluster_dbscan(self, cloud, params, want_sizes=False, want_core=False, want_grouped=False):

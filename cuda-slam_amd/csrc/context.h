@@ -254,6 +254,16 @@ struct mi_ctx {
         double ms[MI_ISS_STAGES] = {0};                  // mi_iss_keypoints_times
     } iss;
 
+    // ---- mi_mls_smooth: a search front end over the cloud with the queries beside it (the cloud itself, or a cloud of their own) and K50's
+    // per-query results
+    struct MlsBuffers {
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<float> out_xyz, out_normals, out_curvature;
+        mislam::DevBuf<int> out_neighbours;
+        mislam::DevBuf<unsigned char> out_status;
+        double ms[MI_MLS_STAGES] = {0};                  // mi_mls_smooth_times
+    } mls;
+
     // ---- mi_cluster_dbscan: a search front end in self mode, the core count, the union-find's parents, every point's root, the clusters' sizes,
     // the flags and scan tiles of the two compactions (the surviving roots; the labelled points) and the grouping's sort
     struct ClusterBuffers {
@@ -505,7 +515,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8 && MI_MLS_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 // The body of every *_times entry point: the eight slots a StageClock left in the context.  ms: null for a null context.
 static inline int stage_times(const char* who, const double* ms, double* out_ms)
 {

@@ -697,6 +697,27 @@ struct IssSuppressArgs {
 hipError_t iss_suppress(const NnGridView& g, const IssSuppressArgs& a, int fma, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------------
+// K50 moving-least-squares smoothing (mls_kernels.hip; driver: mls_api.hip; the arithmetic behind the walks: mls_fit.hpp): the fixed-radius
+// walk of K15 over one cell grid, twice per query and with nothing skipped.  The first walk takes K32's nine fp64 sums about the query, and
+// behind it come the plane (eig3.hpp), the query's foot on it and the frame; the second walk takes the 27 weighted sums of a full quadratic over
+// that plane, and behind it come plane_solve6 (plane_solve.hpp), the fall-back decision and the projection.  order == 1 is an instance without the
+// second walk.
+// ---------------------------------------------------------------------------------------------------------------
+struct MlsArgs {
+    SearchQueries q;                 // the queries: the cloud itself in self mode, or a cloud of their own along their own curve
+    SearchCloud c;
+    float r2;                        // a point with d2 <= r2 is in the ball, the query's own copy included
+    int min_neighbours;              // >= 3
+    double s2;                       // the square of the Gaussian's scale
+    float* xyz;                      // nq * 3, AoS, the caller's order: every row is written
+    float* normals;                  // nq * 3, may be null
+    float* curvature;                // nq, may be null
+    int* neighbours;                 // nq, may be null
+    unsigned char* status;           // nq, may be null
+};
+hipError_t mls_smooth(const NnGridView& g, const MlsArgs& a, int order, int fma, hipStream_t s);      // order 1 or 2
+
+// ---------------------------------------------------------------------------------------------------------------
 // K34 - K38 density-based clustering (cluster_kernels.hip; driver: cluster_api.hip): the core flags are K15's early radius count; K34 links
 // the core points of every ball in a lock-free union-find over the caller's indices (the argument: the head of cluster_kernels.hip); K35
 // resolves every point to the root of its cluster (a core point's own, a border point's nearest core neighbour's); K36 counts the clusters'
@@ -804,5 +825,6 @@ hipError_t preload_cluster_kernels();
 hipError_t preload_segment_kernels();
 hipError_t preload_fgr_kernels();
 hipError_t preload_color_kernels();
+hipError_t preload_mls_kernels();
 
 }  // namespace mislam

@@ -802,6 +802,81 @@ int mi_iss_keypoints(mi_ctx* ctx, const float* cloud_xyz, int n, const mi_iss_pa
 int mi_iss_keypoints_times(mi_ctx* ctx, double out_ms[MI_ISS_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * Moving-least-squares surface smoothing (Alexa et al. 2003; PCL's MovingLeastSquares without upsampling; no reference counterpart):
+ * moves every query back onto the surface its neighbourhood was sampled from and returns that surface's normal, to be taken between
+ * mi_remove_outliers and mi_estimate_normals (smoothing).  Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+typedef struct mi_mls_params {
+    float radius;          /* finite, > 0, square finite: the ball of every fit                           default 0: the caller must set it */
+    float gauss_scale;     /* finite, > 0, or 0 = radius (PCL's sqr_gauss_param = radius^2)                default 0 */
+    int   order;           /* 1: project onto the local plane; 2: onto the quadratic over it               default 2 */
+    int   min_neighbours;  /* >= 3: fewer points in the ball leave the query untouched                     default 3 */
+    int   dist_mode;       /* MI_DIST_CPU_ROUNDING / MI_DIST_FMA, as mi_knn_search                         default CPU_ROUNDING */
+    int   reserved[11];
+} mi_mls_params;           /* 64 bytes */
+void mi_mls_params_default(mi_mls_params* p);
+
+#define MI_MLS_QUADRATIC 0   /* out_status: the quadratic fit */
+#define MI_MLS_PLANE 1       /*             the plane alone */
+#define MI_MLS_UNTOUCHED 2   /*             fewer than min_neighbours points in the ball */
+
+/* The queries (query_xyz == NULL: the cloud's own points, nq == n) projected onto a polynomial fitted to the cloud's points around them,
+ * computed on the device.  Every rule below can be retraced in numpy (tests/mls_reference.py does); everything is fp64 unless said
+ * otherwise, one operation per written operator, products before sums, sums of three as (a + b) + c.
+ *   Ball of query q: N = { j : d2(q, p_j) <= r2 }, r2 = radius * radius in one IEEE fp32 multiplication, d2 in the dist_mode arithmetic
+ *     of mi_knn_search.  A point AT the radius belongs.  Nothing is skipped: with query_xyz == NULL point i is in its own ball, and so
+ *     are its duplicates.  out_neighbours[q] = c = |N|; in self mode that is the count mi_remove_outliers gives in radius mode at the
+ *     same radius with its neighbours output, plus one.
+ *   Untouched: c < min_neighbours: out_xyz = the query's input bits, normal (0, 0, 0), curvature 0, status MI_MLS_UNTOUCHED.
+ *   Plane (first walk over the ball): d = p_j - q (exact, or rounded at 2^-53); nine running sums S = sum d and Q = sum d d^T (upper
+ *     triangle), one product and one addition per entry and point; m = S / c, C_ab = Q_ab / c - m_a m_b: the covariance rule of
+ *     mi_estimate_covariances with the query in the place of the point.  lambda0 <= lambda1 <= lambda2 and the eigenvector of lambda0
+ *     by the fp64 cyclic Jacobi of mi_estimate_normals, normalised: the unit normal n.  Its sign is deterministic and otherwise
+ *     unspecified, as for mi_estimate_normals without a viewpoint.  Curvature = max(lambda0, 0) / ((lambda0 + lambda1) + lambda2), 0
+ *     where that sum is not positive.  The query's foot on the plane, relative to q: o = t n, t = (n_x m_x + n_y m_y) + n_z m_z.
+ *   Frame: k = the axis with the smallest |n_k|, the lowest k on ties; u = (e_k x n) / |e_k x n|, v = n x u.
+ *   Quadratic (second walk over the same ball; order == 2 and c >= 6 only): e = d - o; a = u . e, b = v . e, f = n . e;
+ *     w = exp(-((d_x d_x + d_y d_y) + d_z d_z) / (s s)) with s = (double)gauss_scale, or (double)radius where gauss_scale is 0;
+ *     phi = (1, a, b, a a, a b, b b); A_ij += (w phi_i) phi_j for i <= j (21 sums) and g_i += (w phi_i) f (6 sums).  A x = g by
+ *     the solve of mi_icp_plane_register: A scaled to a unit diagonal, LDL^T without pivoting, a diagonal entry that is not positive
+ *     and finite or a pivot below 1e-10 is degenerate.  A degenerate system falls back to the plane.
+ *   Outputs, each rounded once to fp32:
+ *     MI_MLS_QUADRATIC  out_xyz_k = (float)((q_k + o_k) + x_0 n_k); the normal (n_k - x_1 u_k) - x_2 v_k, divided by its length
+ *     MI_MLS_PLANE      (order == 1, c < 6, or a degenerate system)  out_xyz_k = (float)(q_k + o_k); the normal n
+ *     The curvature is the plane's in both.  An exact plane z = const gives lambda0 = 0, n = (0, 0, 1), o = 0 and every f = 0
+ *     exactly: out_xyz is the query's input bits.  A cloud of identical points gives MI_MLS_PLANE with o = 0.
+ *   Summation order: the walk's over the call's cell grid (cells about one radius long): a function of the cloud, the radius and
+ *     the context's tuning alone, not of the queries' number or order.
+ *   Deterministic: the same call gives the same bits whatever ran on the context before.  No floating-point atomics.  Asking for
+ *     fewer optional outputs moves no bit of the rest.
+ *   Cost: a query's work is proportional to the number of points in its ball (and its cell's neighbourhood), walked twice at order 2.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with "mi_mls_smooth" and names the cause and, for a bad point, its index (the
+ *     lowest); NO output has been written -- for a NULL ctx, cloud_xyz, params or out_xyz; n < 1 or nq < 1; query_xyz == NULL with
+ *     nq != n; an unknown dist_mode; a radius that is NaN, infinite or <= 0, or whose square is not finite; a gauss_scale that is
+ *     NaN, infinite or < 0; an order outside {1, 2}; min_neighbours < 3; a non-finite coordinate or one above 1e18 in magnitude.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls keep: it works in buffers of its own.
+ *   Synchronous, host in and host out. */
+int mi_mls_smooth(mi_ctx* ctx, const float* cloud_xyz, int n,
+                  const float* query_xyz,       /* NULL: the cloud itself (nq == n) */
+                  int nq, const mi_mls_params* params,
+                  float* out_xyz,               /* nq * 3, non-NULL */
+                  float* out_normals,           /* nq * 3, may be NULL */
+                  float* out_curvature,         /* nq, may be NULL */
+                  int* out_neighbours,          /* nq, may be NULL */
+                  unsigned char* out_status);   /* nq, may be NULL: MI_MLS_QUADRATIC / MI_MLS_PLANE / MI_MLS_UNTOUCHED */
+
+/* Where the last mi_mls_smooth of this context spent its host wall time, in ms (measurement hook, tools/mls_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA
+ *   out[2] input check, bounding box, its read-back out[3] cell grid over the cloud
+ *   out[4] curve order of the queries + permute     out[5] the fit kernel (K50)
+ *   out[6] download                                 out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage, and out[5] is the
+ * launch's own HIP-event time instead of host wall time). */
+#define MI_MLS_STAGES 8
+int mi_mls_smooth_times(mi_ctx* ctx, double out_ms[MI_MLS_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Density-based clustering (DBSCAN, Ester et al. 1996; with min_points = 1 Euclidean cluster extraction; no reference counterpart):
  * splits a scene into its objects, drops clutter by component size, and yields the per-object clouds that mi_icp_register_batch and
  * mi_cpd_register_batch take (clustering).  Single-GPU contexts only.
