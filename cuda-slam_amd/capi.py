@@ -347,6 +347,25 @@ def mls_params(**kw):
 mls_smooth_raw = _raw("mi_mls_smooth")
 
 
+RADIUS_MAX_TOTAL = 1 << 31          # MI_RADIUS_MAX_TOTAL
+
+
+def _kernel_constant(name):
+    """An integer constant of csrc/kernels.h, read from that file as the prototypes are read from the header: stated in one place."""
+    with open(os.path.join(_HERE, "csrc", "kernels.h")) as fh:
+        m = _re.search(r"^constexpr int %s = (\d+);" % name, fh.read(), flags=_re.M)
+    if not m:
+        raise MiSlamError("csrc/kernels.h states no integer constant %s" % name)
+    return int(m.group(1))
+
+
+RADIUS_WAVE_ROW = _kernel_constant("RADIUS_WAVE_ROW")          # the longest row the sort kernel ranks in registers ...
+RADIUS_SORT_CHUNK = _kernel_constant("RADIUS_SORT_CHUNK")      # ... and the keys of a longer row it holds in the LDS at a time: where its paths change
+
+
+radius_search_raw = _raw("mi_radius_search")
+
+
 def cluster_params(**kw):
     """mi_cluster_params at its defaults (min_points 1, min_cluster_size 1, no upper limit, CPU rounding; radius 0: set it) with the given fields set."""
     return _params(ClusterParams, "mi_cluster_params_default", kw)
@@ -633,6 +652,7 @@ class Context:
         "remove_outliers": ("workspace", "upload", "check", "grid", "order", "kernel", "finish", "total"),
         "iss_keypoints": ("workspace", "upload", "check", "grid", "order", "saliency", "finish", "total"),
         "mls_smooth": ("workspace", "upload", "check", "grid", "order", "fit", "download", "total"),
+        "radius_search": ("workspace", "front", "count", "scan", "fill", "sort", "download", "total"),
         "cluster_dbscan": ("workspace", "upload", "grid", "count", "link", "resolve", "finish", "total"),
         "segment_plane": ("workspace", "upload", "check", "hypotheses", "count", "argmax", "refine", "total"),
         "icp_plane": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
@@ -986,6 +1006,51 @@ class Context:
     def mls_smooth_times(self):
         """ms per stage of the last mls_smooth: workspace, upload, check, grid, order, fit, download, total (mi_mls_smooth_times)."""
         return self._times("mls_smooth")
+
+    # ---- every neighbour within a radius
+    def radius_count(self, cloud, radius, query=None, dist_mode=DIST_CPU_ROUNDING):
+        """The counts-only form of mi_radius_search: (offsets [n + 1] int64, total).  Row i holds offsets[i + 1] - offsets[i] cloud points
+        within `radius` of query i (query None: the cloud's own points, point i itself skipped by index); no list is built and the total
+        has no limit."""
+        cloud = _cloud(cloud)
+        query = None if query is None else _cloud(query)
+        n = cloud.shape[0] if query is None else query.shape[0]
+        offsets, total = np.empty(n + 1, np.int64), C.c_longlong(0)
+        _check(radius_search_raw(self._h, _ptr(query), n, cloud.ctypes.data, cloud.shape[0], float(radius), int(dist_mode), 1, offsets.ctypes.data,
+                                 None, None, 0, C.addressof(total)))
+        return offsets, total.value
+
+    def radius_search(self, cloud, radius, query=None, dist_mode=DIST_CPU_ROUNDING, sorted=True, want_d2=True, capacity=None):
+        """Every cloud point within `radius` of every query, as CSR lists (mi_radius_search): offsets [n + 1] int64, idx [total] int32 and,
+        if asked for, d2 [total] float32; row i is idx[offsets[i]:offsets[i + 1]].  query None: the cloud's own points, point i itself
+        skipped by index.  sorted: every row ascending by (d2 bits, index), so its head is mi_knn_search's row under the limit radius^2;
+        otherwise the order is unspecified but the same on every call.  capacity None: one call for the counts and one to fill arrays of
+        exactly that size -- this costs a second count pass; a caller who knows a bound passes it as capacity and pays one call, and gets
+        a MiSlamError naming the total if the bound was short."""
+        cloud = _cloud(cloud)
+        query = None if query is None else _cloud(query)
+        n = cloud.shape[0] if query is None else query.shape[0]
+        if capacity is None:
+            capacity = max(self.radius_count(cloud, radius, query, dist_mode)[1], 1)
+        offsets, total = np.empty(n + 1, np.int64), C.c_longlong(0)
+        idx = np.empty(int(capacity), np.int32)
+        d2 = np.empty(int(capacity), np.float32) if want_d2 else None
+        _check(radius_search_raw(self._h, _ptr(query), n, cloud.ctypes.data, cloud.shape[0], float(radius), int(dist_mode), 1 if sorted else 0,
+                                 offsets.ctypes.data, idx.ctypes.data, _ptr(d2), int(capacity), C.addressof(total)))
+        if total.value > capacity:
+            raise MiSlamError("mi_radius_search: %d neighbours in all, capacity %d: nothing was written" % (total.value, capacity))
+        res = [offsets, idx[:total.value]] + ([d2[:total.value]] if want_d2 else [])
+        return tuple(res)
+
+    def radius_grid(self):
+        """(nx, ny, nz) of the cell grid the last radius_search or radius_count walked (mi_selftest_radius_grid)."""
+        dims = (C.c_int * 3)()
+        _check(lib().mi_selftest_radius_grid(self._h, dims))
+        return tuple(dims)
+
+    def radius_search_times(self):
+        """ms per stage of the last radius_search or radius_count: workspace, front, count, scan, fill, sort, download, total (mi_radius_search_times)."""
+        return self._times("radius_search")
 
     # ---- density-based clustering
     def cluster_dbscan(self, cloud, params, want_sizes=False, want_core=False, want_grouped=False):

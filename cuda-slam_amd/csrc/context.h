@@ -264,6 +264,20 @@ struct mi_ctx {
         double ms[MI_MLS_STAGES] = {0};                  // mi_mls_smooth_times
     } mls;
 
+    // ---- mi_radius_search: MlsBuffers' sibling -- a search front end over the cloud with the queries beside it, the rows' lengths, the scan's
+    // tile sums, the 64-bit offsets and, once their length is known, the lists: packed keys, and what K54 unpacks them into
+    struct RadiusBuffers {
+        mislam::SearchFrontBuffers front;
+        mislam::DevBuf<int> count;                       // n, the caller's row order
+        mislam::DevBuf<long long> tile_sums, offsets;    // radius_scan_tiles(n); n + 1
+        mislam::DevBuf<unsigned long long> keys;         // offsets[n]
+        mislam::DevBuf<int> out_idx;
+        mislam::DevBuf<float> out_d2;
+        mislam::DevBuf<int> mismatch;                    // [0]: a fill walk disagreed with its count (RadiusFillArgs::mismatch)
+        int grid_dims[3] = {0, 0, 0};                    // the last call's cell grid (mi_selftest_radius_grid)
+        double ms[MI_RADIUS_STAGES] = {0};               // mi_radius_search_times
+    } radius;
+
     // ---- mi_cluster_dbscan: a search front end in self mode, the core count, the union-find's parents, every point's root, the clusters' sizes,
     // the flags and scan tiles of the two compactions (the surviving roots; the labelled points) and the grouping's sort
     struct ClusterBuffers {
@@ -515,7 +529,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8 && MI_MLS_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8 && MI_MLS_STAGES == 8 && MI_RADIUS_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 // The body of every *_times entry point: the eight slots a StageClock left in the context.  ms: null for a null context.
 static inline int stage_times(const char* who, const double* ms, double* out_ms)
 {

@@ -718,6 +718,39 @@ struct MlsArgs {
 hipError_t mls_smooth(const NnGridView& g, const MlsArgs& a, int order, int fma, hipStream_t s);      // order 1 or 2
 
 // ---------------------------------------------------------------------------------------------------------------
+// K51 - K54 every neighbour within a radius, as CSR lists (radius_kernels.hip; driver: radius_api.hip).  The lengths are K15's full radius
+// count; K51 scans them into 64-bit offsets in the caller's row order (three small launches, a fixed order, no atomics); K52 walks the ball
+// a second time with a sink that stores the packed keys (bits(d2) << 32) | j at keys[offsets[row] + found++] (RadiusFillSink, knn_scan.hpp);
+// K53 orders every row in place by key, one wave per row: a rank by counted smaller keys over the wave's lanes up to RADIUS_WAVE_ROW keys,
+// a bitonic network through LDS chunks of RADIUS_SORT_CHUNK keys beyond; K54 unpacks the keys into idx and d2.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int RADIUS_SCAN_TILE = 1024;       // counts per workgroup of the scan: 256 lanes x 4 consecutive counts
+constexpr int RADIUS_WAVE_ROW = 64;          // the longest row K53 ranks in registers: one key per lane of a wave
+constexpr int RADIUS_SORT_CHUNK = 512;       // keys of a longer row that K53 holds in the LDS at a time (a power of two, >= 2 * RADIUS_WAVE_ROW)
+
+int radius_scan_tiles(int n);        // tiles of the scan of n counts
+// offsets[i] = count[0] + ... + count[i - 1] for i = 0 .. n (offsets[n]: the total), all sums in 64 bits; tile_sums: radius_scan_tiles(n) words
+hipError_t radius_scan_offsets(const int* count, int n, long long* tile_sums, long long* offsets, hipStream_t s);
+
+struct RadiusFillArgs {
+    SearchQueries q;                 // the queries: the cloud itself in self mode, or a cloud of their own along their own curve
+    int self;                        // self mode: candidate order[s] is skipped, by index
+    float r2;                        // a point with d2 <= r2 belongs to the row
+    const long long* offsets;        // n + 1, the caller's row order
+    unsigned long long* keys;        // offsets[n] keys: row i is [offsets[i], offsets[i + 1]), in the order the walk met its members
+    int* mismatch;                   // one word the caller zeroed: set to 1 by a lane whose walk met another number of members than its row holds
+};
+// the count of a separate query set: radius_count (K15) skips index order[s] whatever the mode, so it serves self mode alone
+hipError_t radius_query_count(const NnGridView& g, const SearchQueries& q, float r2, int* count, int fma, hipStream_t s);
+hipError_t radius_fill(const NnGridView& g, const RadiusFillArgs& a, int fma, hipStream_t s);
+// every row [offsets[i], offsets[i + 1]) of keys ascending, in place
+hipError_t radius_sort_rows(const long long* offsets, long long rows, unsigned long long* keys, hipStream_t s);
+// the points of every cell of a grid ascending by index, in place: the build leaves them in the order its atomics made, and a walk that
+// writes what it meets (K52 without K53 behind it) must meet the same order on every call.  Leaves NnGridView::slot_of stale.
+hipError_t radius_order_cells(const unsigned int* cell_start, long long n_cells, float4* pts, hipStream_t s);
+hipError_t radius_unpack(const unsigned long long* keys, long long total, int* idx, float* d2, hipStream_t s);     // d2 may be null
+
+// ---------------------------------------------------------------------------------------------------------------
 // K34 - K38 density-based clustering (cluster_kernels.hip; driver: cluster_api.hip): the core flags are K15's early radius count; K34 links
 // the core points of every ball in a lock-free union-find over the caller's indices (the argument: the head of cluster_kernels.hip); K35
 // resolves every point to the root of its cluster (a core point's own, a border point's nearest core neighbour's); K36 counts the clusters'
@@ -826,5 +859,6 @@ hipError_t preload_segment_kernels();
 hipError_t preload_fgr_kernels();
 hipError_t preload_color_kernels();
 hipError_t preload_mls_kernels();
+hipError_t preload_radius_kernels();
 
 }  // namespace mislam

@@ -1,7 +1,7 @@
 // K13 / K14 / K15 / K16 -- the search body of the kernels that walk a cloud's cell grid, stated once: the walk over Chebyshev shells of cells with
 // its stop rule (shell_walk; the contract and the proof of the stop rule: the head of knn_kernels.hip), the sorted list of K keys in
 // registers that the exact k-NN kernels feed from it (knn_scan), the counter of the fixed-radius kernel (radius_scan) and the single key of
-// the plane ICP's match (NearestSink; plane_kernels.hip), and what the
+// the plane ICP's match (NearestSink; plane_kernels.hip), the writer of the radius search's lists (RadiusFillSink; radius_kernels.hip), and what the
 // kernels share around them: the lane's query (knn_lane) and the host's choice of an instantiation (knn_dispatch).
 // knn_search_kernel (knn_kernels.hip) writes the list out; knn_normals_kernel (normals_kernels.hip) and knn_outlier_score_kernel
 // (outlier_kernels.hip) go on with the keys still in registers.  One lane per query; no LDS, no scratch: every index into the list is static.
@@ -171,6 +171,28 @@ __device__ __forceinline__ int radius_scan(const NnGridView& g, const float (&q)
     shell_walk<FMA>(g, q, hi, sink);
     return found;
 }
+
+// a writer as a sink (K52's lists): RadiusCountSink's membership and stop rule, and every member's key (bits(d2) << 32) | j stored at
+// row[found++] in the order the walk offers them.  row: the row's first key, a 64-bit address formed once by the caller.  A second walk
+// over the same grid meets what the counting walk met, so found ends at the row's length; `room` is that length, and a key beyond it is
+// dropped, not stored -- a wrong count must not become a write outside the lists; the kernel reports found != room to the driver.
+struct RadiusFillSink {
+    static constexpr bool LEAVES = false;
+    unsigned int skip;
+    float r2;
+    unsigned long long* row;
+    int room;
+    int& found;
+    __device__ __forceinline__ bool take(float d2, unsigned int pj)
+    {
+        if (pj != skip && d2 <= r2) {
+            if (found < room) row[found] = ((unsigned long long)__float_as_uint(d2) << 32) | pj;
+            found++;
+        }
+        return false;
+    }
+    __device__ __forceinline__ bool stop(float bound) const { return bound > r2; }
+};
 
 // Host: launch(K, FMA, grid) with the list size of k (knn_list_size) and the distance arithmetic as integral constants, and the grid of one
 // lane per query in workgroups of KNN_BLOCK -- the one place that maps (k, fma) to an instantiation of a kernel template.

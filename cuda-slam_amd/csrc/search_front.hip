@@ -146,7 +146,7 @@ bool search_front_fits(const SearchFrontBuffers& b, const SearchFront& f)
 
 void search_front_destroy_events(mi_ctx* c)
 {
-    for (SearchFrontBuffers* b : {&c->knn.front, &c->normals.front, &c->outlier.front, &c->plane.front, &c->cov.front, &c->gicp.front, &c->fpfh.front, &c->iss.front, &c->cluster.front, &c->segment.front, &c->colorgrad.front, &c->color.front, &c->mls.front})
+    for (SearchFrontBuffers* b : {&c->knn.front, &c->normals.front, &c->outlier.front, &c->plane.front, &c->cov.front, &c->gicp.front, &c->fpfh.front, &c->iss.front, &c->cluster.front, &c->segment.front, &c->colorgrad.front, &c->color.front, &c->mls.front, &c->radius.front})
         for (hipEvent_t e : b->ev) if (e) (void)hipEventDestroy(e);
 }
 

@@ -615,6 +615,60 @@ int mi_knn_search(mi_ctx* ctx,
 #define MI_KNN_STAGES 8
 int mi_knn_search_times(mi_ctx* ctx, double out_ms[MI_KNN_STAGES]);
 
+/* Every cloud point within a radius of every query, as CSR lists, computed on the device (Open3D's search_radius_vector_3d, PCL's
+ * radiusSearch): what mi_knn_search cannot give once a ball holds more than MI_KNN_MAX_K points, and what mi_remove_outliers counts but
+ * does not name (neighbourhoods).
+ *   Membership: r2 = radius * radius, one IEEE fp32 multiplication (mi_remove_outliers' radius method forms the same number).  Candidate j
+ *     belongs to row i if and only if d2(i, j) <= r2, d2 in the dist_mode arithmetic of mi_knn_search on the fp32 differences; a point
+ *     exactly AT r2 belongs.  Self mode, query_xyz == NULL: the queries are the cloud's own points (n must equal m) and candidate j == i is
+ *     skipped BY INDEX -- a duplicate of point i stored elsewhere belongs, at d2 = +0 -- so a row's length is mi_remove_outliers'
+ *     neighbours[i] at the same radius and dist_mode, bit for bit.
+ *   Layout: row i is entries [offsets[i], offsets[i + 1]) of idx and d2; offsets[0] = 0, offsets[n] = *total.  An empty row repeats its
+ *     offset.  The offsets are 64-bit: a counts-only call has no limit on *total.
+ *   Order: sorted = 1: every row ascends by the key (bits(d2) << 32) | j, the smaller distance first, equal distance bits to the lower
+ *     index -- for any k <= MI_KNN_MAX_K the first min(k, length) entries of row i are row i of mi_knn_search(ctx, query_xyz, n, cloud_xyz,
+ *     m, k, dist_mode, r2, ...), index and distance bits alike.  sorted = 0: the same set in an order that is not specified; the same
+ *     input still gives the same bits on every call, whatever ran on the context before.
+ *   Two modes, and the capacity protocol (in the manner of snprintf):
+ *     idx == NULL  counts only: capacity must be 0, d2 must be NULL; offsets and *total are written and no list is built.
+ *     idx != NULL  0 < capacity <= MI_RADIUS_MAX_TOTAL entries of idx (and of d2, unless NULL).  offsets and *total are ALWAYS written.
+ *                  idx and d2 are written if and only if *total <= capacity, entries [0, *total) of them and nothing behind; otherwise
+ *                  they are left untouched, no device memory is taken for the lists, and the call STILL returns MI_OK: the caller
+ *                  compares *total with capacity and, if it was short, calls again with arrays of *total entries.
+ *   Cost: two walks of every query's ball (one counts, one writes), each proportional to the points in the ball AND in the cells it
+ *     touches; with lists, 16 bytes of device memory per entry; with sorted = 1 a rank per row that is quadratic in the row's length
+ *     up to 64 entries and L log^2 L beyond.  A radius that holds much of the cloud makes the whole call quadratic in the cloud: this is
+ *     a search of small balls.  Exact for every query position and cloud shape, as mi_knn_search is.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with "mi_radius_search" and names the cause and, for a bad point, which array and which
+ *     index; NOTHING has been written -- for a NULL ctx, cloud_xyz, offsets or total; n < 1 or m < 1; self mode with n != m; a dist_mode
+ *     other than the two of mi_knn_search; sorted outside {0, 1}; radius NaN, infinite or <= 0, or radius * radius not finite; d2 given
+ *     without idx; idx == NULL with capacity != 0; idx != NULL with capacity outside [1, MI_RADIUS_MAX_TOTAL]; a non-finite coordinate
+ *     in either array, or one of magnitude above 1e18.
+ *   MI_ERR_STATE on a distributed context.  A device allocation that fails (the lists': 16 bytes per entry) is MI_ERR_HIP; the context
+ *     stays usable, and the output arrays' contents are then unspecified.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other searches keep: it works in buffers of its own.
+ *   Synchronous, host in and host out. */
+#define MI_RADIUS_MAX_TOTAL (1LL << 31)
+int mi_radius_search(mi_ctx* ctx,
+                     const float* query_xyz, int n,   /* NULL: the queries are the cloud's own points (n must equal m); neighbour j == i is skipped by index */
+                     const float* cloud_xyz, int m,
+                     float radius, int dist_mode,     /* finite, > 0; MI_DIST_CPU_ROUNDING or MI_DIST_FMA */
+                     int sorted,                      /* 1: every row ascending by key; 0: order unspecified but the same on every call */
+                     long long* offsets,              /* n + 1: row i is [offsets[i], offsets[i + 1]); offsets[0] = 0, offsets[n] = *total */
+                     int* idx, float* d2,             /* capacity entries each; d2 may be NULL; idx NULL: counts only */
+                     long long capacity,              /* 0 with idx NULL; else 1 .. MI_RADIUS_MAX_TOTAL */
+                     long long* total);               /* the members of all rows, whether the lists were written or not */
+
+/* Where the last mi_radius_search of this context spent its host wall time, in ms (measurement hook, tools/radius_bench.py):
+ *   out[0] workspace (device allocations, the lists' included)   out[1] upload, input check, cell grid, curve order (unsorted: + the cells' order)
+ *   out[2] the count kernel                                      out[3] the scan and the read-back of the total
+ *   out[4] the fill kernel (unsorted: the cells' order in out[1]) out[5] the sort kernel (0 with sorted = 0)
+ *   out[6] unpack + download of the results                      out[7] the whole call
+ * As with mi_knn_search_times, the parts are attributable only while profiling is enabled (the stream is then drained after every
+ * stage, and out[2], out[4] and out[5] are the launches' own HIP-event times instead of host wall time). */
+#define MI_RADIUS_STAGES 8
+int mi_radius_search_times(mi_ctx* ctx, double out_ms[MI_RADIUS_STAGES]);
+
 /* ----------------------------------------------------------------------------------------------------------------
  * Surface normals and curvature (no reference counterpart: the reference has no normals anywhere): the first consumer of the k-NN
  * lists, which here never leave the device (normals).  Single-GPU contexts only.
@@ -1799,6 +1853,9 @@ int mi_selftest_fail_loads(mi_ctx* ctx, int n);
  * until it is really freed (behind the next drain of its context's stream).  Creating a context, using it and destroying it leaves the count where
  * it was: what the library's own tests check.  Needs no context. */
 int mi_selftest_live_buffers(long long* count);
+/* The cells per axis of the grid that the last mi_radius_search of this context walked (0, 0, 0 before the first): how a test tells that
+ * MISLAM_OUTLIER_RADIUS_CELL or MISLAM_KNN_POINTS_PER_CELL was taken and gave the regime it was meant to give. */
+int mi_selftest_radius_grid(mi_ctx* ctx, int dims[3]);
 /* What the last ICP step of the loaded problem left on the device besides its result: rows = the moving cloud's 64-point chunks; the first
  * min(cap_rows, rows) entries of the work order dealt for the next search (a permutation of the chunks, walking ones first) and of the chunks' flags
  * (non-zero: its wave walked the box hierarchy); the four range cursors of the dealing (two pairs: a step deals on the pair of its parity and leaves the
