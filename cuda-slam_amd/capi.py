@@ -384,6 +384,7 @@ def plane_params(**kw):
 
 icp_plane_register_raw = _raw("mi_icp_plane_register")
 plane_system_raw = _raw("mi_plane_system")
+evaluate_registration_raw = _raw("mi_evaluate_registration")
 
 
 COV_RAW, COV_PLANE = 0, 1     # MI_COV_*
@@ -657,6 +658,7 @@ class Context:
         "segment_plane": ("workspace", "upload", "check", "hypotheses", "count", "argmax", "refine", "total"),
         "icp_plane": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
         "icp_gicp": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
+        "evaluate_registration": ("workspace", "upload", "check", "grid", "order", "step", "download", "total"),
         "icp_color": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
         "ndt": ("workspace", "upload", "check", "table", "order", "iterations", "download", "total"),
         "fpfh_features": ("workspace", "upload", "check", "grid", "order", "kernels", "download", "total"),
@@ -1155,6 +1157,35 @@ class Context:
         """ms per stage of the last icp_plane_register / plane_system: workspace, upload, check, grid, order, iterations, download, total
         (mi_icp_plane_times)."""
         return self._times("icp_plane")
+
+    # ---- the quality of a pose
+    def evaluate_registration(self, before, after, T=None, pairs=None, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_sums=False, want_information=True,
+                              want_idx=False, want_d2=False):
+        """Fitness and inlier RMSE of `before` under the [4, 4] transform T (indexed [row, col]; None: the identity) against `after`
+        (mi_evaluate_registration).  pairs None: every moving point's nearest fixed point within max_d2; else int32 [n], -1 or the fixed
+        index to pair moving point i with (feature matches under a RANSAC or FGR pose).  Returns (fitness, inlier_rmse) and then, each if
+        asked for, sums float64 [32], information float64 [6, 6] (rotation first, about the origin: a pose-graph edge's weight), idx
+        int32 [n] (-1: no pair) and d2 float32 [n] (+inf: no pair)."""
+        before, after = _cloud(before), _cloud(after)
+        n = before.shape[0]
+        T0 = _T16(T)
+        if pairs is not None:
+            pairs = np.ascontiguousarray(pairs, np.int32)
+            if pairs.shape != (n,):
+                raise ValueError("pairs must hold one fixed index (or -1) per moving point")
+        fitness, rmse = C.c_double(0), C.c_double(0)
+        sums = np.zeros(32, np.float64) if want_sums else None
+        info = np.zeros((6, 6), np.float64) if want_information else None
+        idx = np.empty(n, np.int32) if want_idx else None
+        d2 = np.empty(n, np.float32) if want_d2 else None
+        _check(evaluate_registration_raw(self._h, before.ctypes.data, n, after.ctypes.data, after.shape[0], _ptr(T0), _ptr(pairs), int(dist_mode),
+                                         float(max_d2), C.addressof(fitness), C.addressof(rmse), _ptr(sums), _ptr(info), _ptr(idx), _ptr(d2)))
+        return (fitness.value, rmse.value) + tuple(x for x in (sums, info, idx, d2) if x is not None)
+
+    def evaluate_registration_times(self):
+        """ms per stage of the last evaluate_registration: workspace, upload, check, grid (0 with pairs given), order, step, download, total
+        (mi_evaluate_registration_times)."""
+        return self._times("evaluate_registration")
 
     # ---- generalized ICP
     def estimate_covariances(self, cloud, k, mode=COV_PLANE, epsilon=1e-3, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_count=False):

@@ -316,6 +316,18 @@ struct mi_ctx {
         double ms[MI_PLANE_STAGES] = {0};                // mi_icp_plane_times
     } plane;
 
+    // ---- mi_evaluate_registration: PlaneBuffers' sibling without normals -- a search front end over the FIXED cloud with the moving cloud as
+    // its queries, the rows of the one linearisation and the state block, the pairs' distances, and with the pairs given the caller's
+    // pair_idx and the lowest refused entry
+    struct EvalBuffers {
+        mislam::SearchFrontBuffers front;
+        mislam::PoseLoopBuffers loop;
+        mislam::DevBuf<float> out_d2;
+        mislam::DevBuf<int> pair_idx;                    // as uploaded, the caller's order
+        mislam::DevBuf<int> pair_bad;                    // [0] the lowest index of an entry outside {-1} and [0, m), or KNN_NO_POINT
+        double ms[MI_EVAL_STAGES] = {0};                 // mi_evaluate_registration_times
+    } eval;
+
     // ---- mi_estimate_covariances: mi_estimate_normals' sibling with six floats per point as its result, in buffers of its own
     struct CovarianceBuffers {
         mislam::SearchFrontBuffers front;
@@ -529,7 +541,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8 && MI_MLS_STAGES == 8 && MI_RADIUS_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8 && MI_MLS_STAGES == 8 && MI_RADIUS_STAGES == 8 && MI_EVAL_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 // The body of every *_times entry point: the eight slots a StageClock left in the context.  ms: null for a null context.
 static inline int stage_times(const char* who, const double* ms, double* out_ms)
 {
@@ -562,6 +574,9 @@ int search_front_upload_and_check(mi_ctx* c, SearchFrontBuffers& b, StageClock& 
                                   const float* query_xyz, int n, SearchFront* f, const char* cloud_name = "cloud_xyz",
                                   const char* query_name = "query_xyz");
 int search_front_index_and_order(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, const char* who, float points_per_cell, SearchFront* f);
+// its second half alone, stage 4: the queries along their curve and no grid (mi_evaluate_registration with the pairs given: f->g stays empty,
+// search_front_fits does not hold, and the driver checks q*, order and c* itself)
+int search_front_order(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, SearchFront* f);
 // What a search kernel is handed beside the grid f.g.  No driver reads these buffers for a launch itself, so search_front_fits, the host-side
 // shape check of what every search kernel indexes (q*, order, c*, the grid's offsets and points), checks what was handed out.
 SearchQueries search_front_queries(const SearchFrontBuffers& b, const SearchFront& f);

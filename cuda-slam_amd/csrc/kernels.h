@@ -832,6 +832,27 @@ hipError_t color_pack_fixed(const float* grad3, const float* intensity, int m, f
 // out[s] = in[order[s]]: the moving cloud's intensities along its curve
 hipError_t color_permute_intensity(const float* in, const int* order, int n, float* out, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K55 the quality of a pose (eval_kernels.hip; driver: eval_api.hip; the host arithmetic behind the sums: eval_block.hpp): K16's move and
+// match, or the caller's pairs, and the point-to-point terms about the origin in K16's row -- so the rows reduce, the state block and the
+// read-back are K16's own: plane_reduce_solve with solve = 0, PlaneState.
+// ---------------------------------------------------------------------------------------------------------------
+struct EvalStepArgs {
+    const PlaneState* state;         // the pose to evaluate at (rounded to fp32 by every lane)
+    SearchQueries q;                 // the moving cloud along its curve order, in both modes
+    SearchCloud c;                   // the fixed cloud
+    const int* pair_idx;             // null: the pair is the nearest fixed point (the grid is walked); else n entries in the caller's
+                                     // order, -1 or a fixed index in [0, m) (eval_check_pairs), and the grid is not touched
+    int m;                           // fixed points (what a given index is held against once more)
+    float max_d2;                    // a pair with d2 > this, or with a d2 that is not finite, is no pair (+inf: no limit)
+    double* rows;                    // plane_row_count(n) x PLANE_ROW
+    int* idx;                        // may be null; n, the caller's order: the fixed index of a pair, -1 otherwise
+    float* d2;                       // may be null; n, the caller's order: the pair's fp32 squared distance, +inf otherwise
+};
+hipError_t eval_step(const NnGridView& g, const EvalStepArgs& a, int fma, hipStream_t s);
+// *bad = min(*bad, the lowest i with pair_idx[i] outside {-1} and [0, m)) -- the caller sets *bad to KNN_NO_POINT first
+hipError_t eval_check_pairs(const int* pair_idx, int n, int m, int* bad, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -860,5 +881,6 @@ hipError_t preload_fgr_kernels();
 hipError_t preload_color_kernels();
 hipError_t preload_mls_kernels();
 hipError_t preload_radius_kernels();
+hipError_t preload_eval_kernels();
 
 }  // namespace mislam

@@ -94,7 +94,11 @@ int search_front_index_and_order(mi_ctx* c, SearchFrontBuffers& b, StageClock& c
     f->n_cells = (size_t)g.nx * g.ny * g.nz;
     MI_TRY(grid_build_into(b.cells, g, b.cx.p, b.cy.p, b.cz.p, f->m, c->stream));
     MI_TRY(clock.mark(3));
+    return search_front_order(c, b, clock, f);
+}
 
+int search_front_order(mi_ctx* c, SearchFrontBuffers& b, StageClock& clock, SearchFront* f)
+{
     // the queries along their curve: order[s] = the caller's index of sorted slot s
     MortonArgs ma{};
     MI_TRY(morton_args(b.morton, f->ux, f->uy, f->uz, f->n, b.order.p, &ma));
@@ -146,7 +150,7 @@ bool search_front_fits(const SearchFrontBuffers& b, const SearchFront& f)
 
 void search_front_destroy_events(mi_ctx* c)
 {
-    for (SearchFrontBuffers* b : {&c->knn.front, &c->normals.front, &c->outlier.front, &c->plane.front, &c->cov.front, &c->gicp.front, &c->fpfh.front, &c->iss.front, &c->cluster.front, &c->segment.front, &c->colorgrad.front, &c->color.front, &c->mls.front, &c->radius.front})
+    for (SearchFrontBuffers* b : {&c->knn.front, &c->normals.front, &c->outlier.front, &c->plane.front, &c->cov.front, &c->gicp.front, &c->fpfh.front, &c->iss.front, &c->cluster.front, &c->segment.front, &c->colorgrad.front, &c->color.front, &c->mls.front, &c->radius.front, &c->eval.front})
         for (hipEvent_t e : b->ev) if (e) (void)hipEventDestroy(e);
 }
 

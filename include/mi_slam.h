@@ -1790,6 +1790,70 @@ int mi_ndt_system(mi_ctx* ctx, const float* before_xyz, int n,
 int mi_ndt_times(mi_ctx* ctx, double out_ms[MI_NDT_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * The quality of a pose (no reference counterpart): what Open3D's evaluate_registration and get_information_matrix_from_point_clouds
+ * and PCL's getFitnessScore give -- the fitness, the inlier RMSE, the correspondence set and the 6 x 6 information matrix a pose-graph
+ * edge carries -- behind any of the registrations above, whose `error` means something else in each.  One search launch and the rows
+ * reduce of mi_plane_system; single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+/* Evaluates the pose T of the moving cloud `before` (n points) against the fixed cloud `after` (m points), on the device.  Every rule
+ * below can be retraced in numpy (tests/eval_reference.py does).
+ *   Transform: T is column-major 4 x 4 like every transform of this library, T[4 * col + row]; only the rotation block and the
+ *     translation column are read, as given.  Move: the move of mi_icp_plane_register, by the same code -- every read entry of T is
+ *     promoted to fp64 and rounded once to fp32 (the same bits), and with every operation rounded to fp32, in this order,
+ *     q_x = ((R00*b_x + R01*b_y) + R02*b_z) + t_x, and likewise q_y and q_z.  A NULL T gives the identity's bits.
+ *   Pair, search mode (pair_idx NULL): the pair of moving point i is row i of mi_knn_search(ctx, q, n, after_xyz, m, 1, dist_mode,
+ *     max_distance_squared, ...), key for key: the same distance arithmetic on the fp32 differences a_j - q_i, equal distance bits going
+ *     to the lower index.  A query without a candidate within the limit has no pair.
+ *   Pair, given mode (pair_idx non-NULL, n entries): j = pair_idx[i]; -1 means no pair.  Otherwise d2 is the fp32 squared distance of
+ *     q_i and a_j in dist_mode's arithmetic, on the differences a_j - q_i: (dx*dx + dy*dy) + dz*dz for MI_DIST_CPU_ROUNDING,
+ *     fma(dz, dz, fma(dy, dy, dx*dx)) for MI_DIST_FMA -- what mi_knn_search computes for that pair.  The pair counts when
+ *     d2 <= max_distance_squared and d2 is finite.  No cell grid is built in this mode: it evaluates feature matches (mi_feature_match's
+ *     idx) under the pose of mi_ransac_register or mi_fgr_register.
+ *   Terms, every operand promoted to fp64 first: a = a_j, d = q - a, and the three rows of G = [ -[a]x | I ],
+ *       G0 = (0, a_z, -a_y, 1, 0, 0)      G1 = (-a_z, 0, a_x, 0, 1, 0)      G2 = (a_y, -a_x, 0, 0, 0, 1)
+ *     -- Open3D's convention: the fixed point, about the origin, the rotation's entries first.
+ *   Sums (out_sums, the layout of mi_plane_system): [0, 21) the upper triangle of Lambda = sum G^T G, row-major, a pair's entry (i, j)
+ *     being (G0i*G0j + G1i*G1j) + G2i*G2j; [21, 27) g = sum G^T d, a pair's entry i being (G0i*d_x + G1i*d_y) + G2i*d_z; [27] the sum
+ *     of (d_x^2 + d_y^2) + d_z^2; [28] the sum of (double)d2, the pairs' fp32 squared distances; [29] the number of pairs; [30, 32) 0.
+ *     So Lambda x = -g is one point-to-point Gauss-Newton step about the origin, x = (omega, v).  The device forms only the products
+ *     that are not 0 or 1 whatever the point, with the bits of the expressions above.  The sums are added in a fixed order that depends
+ *     on n alone, with no floating-point atomics, and a moving point's place in that order is the same in both modes: the same input
+ *     gives the same bits on every call, whatever ran on the context before, and given mode handed search mode's own out_idx repeats
+ *     every output of search mode bit for bit.
+ *   Outputs: *out_fitness = pairs / n, one fp64 division.  *out_inlier_rmse = sqrt(sums[27] / pairs), one fp64 division and one root,
+ *     or 0 with no pair.  out_information (row-major 6 x 6) is the symmetric expansion of sums[0, 21), the same bits, and all zeros with
+ *     no pair.  out_idx[i] is the fixed index of moving point i's pair or -1; out_d2[i] the pair's fp32 d2, or +INFINITY where there is
+ *     no pair.  out_sums, out_information, out_idx and out_d2 may be NULL.  No pair at all is a valid answer: MI_OK, fitness 0, RMSE 0,
+ *     every sum +0.
+ *   The search is exact for any pose; the speed is only claimed for a pose that brings the moving cloud within a few cells of the fixed
+ *     one, as mi_knn_search says of itself.  A finite max_distance_squared bounds every walk.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name and names the cause and, for a bad point or pair, which
+ *     array and which index (the lowest); NO output has been written -- for a NULL ctx, before_xyz, after_xyz, out_fitness or
+ *     out_inlier_rmse; n < 1 or m < 1; a dist_mode other than the two of mi_knn_search; max_distance_squared NaN or negative; a
+ *     non-finite entry of T's rotation block or translation column; a non-finite coordinate, or one above 1e18 in magnitude; a pair_idx
+ *     entry that is neither -1 nor in [0, m) (found on the device, read back with the coordinates' check).
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the searches and the registrations keep: it works in
+ *     buffers of its own.
+ *   Synchronous, host in and host out. */
+int mi_evaluate_registration(mi_ctx* ctx, const float* before_xyz, int n, const float* after_xyz, int m,
+                             const float T[16] /* may be NULL: identity */,
+                             const int* pair_idx /* may be NULL: search; else n entries, -1 or a fixed index in [0, m) */,
+                             int dist_mode, float max_distance_squared, double* out_fitness, double* out_inlier_rmse,
+                             double out_sums[32] /* may be NULL */, double out_information[36] /* may be NULL; row-major, symmetric */,
+                             int* out_idx /* may be NULL; n */, float* out_d2 /* may be NULL; n */);
+
+/* Where the last mi_evaluate_registration of this context spent its host wall time, in ms (measurement hook, tools/eval_bench.py), laid
+ * out as mi_icp_plane_times:
+ *   out[0] workspace (device allocations)           out[1] upload + AoS -> SoA (pair_idx, fixed cloud, moving cloud, state)
+ *   out[2] input checks, bounding box, read-backs   out[3] cell grid over the fixed cloud (0 with the pairs given)
+ *   out[4] curve order of the moving cloud + permute out[5] the step, the rows reduce and the host read of the state
+ *   out[6] download of the results                  out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage). */
+#define MI_EVAL_STAGES 8
+int mi_evaluate_registration_times(mi_ctx* ctx, double out_ms[MI_EVAL_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
  * -------------------------------------------------------------------------------------------------------------- */
 enum {
