@@ -385,6 +385,37 @@ def plane_params(**kw):
 icp_plane_register_raw = _raw("mi_icp_plane_register")
 plane_system_raw = _raw("mi_plane_system")
 evaluate_registration_raw = _raw("mi_evaluate_registration")
+pose_graph_optimize_raw = _raw("mi_pose_graph_optimize")
+pose_graph_system_raw = _raw("mi_pose_graph_system")
+
+
+class PoseGraph:
+    """mi_pose_graph_params, held in a namespace as Fgr holds its own: the compiler checks this one's layout against the header's in
+    tests/test_pose_graph_abi.py."""
+    C_TYPE = "mi_pose_graph_params"
+
+    class Params(C.Structure):
+        _fields_ = [("max_iterations", C.c_int), ("max_pcg_iterations", C.c_int), ("reference_node", C.c_int), ("pcg_tolerance", C.c_double),
+                    ("relative_decrease", C.c_double), ("absolute_cost", C.c_double), ("lambda0", C.c_double), ("line_process_mu", C.c_double)]
+
+
+def pose_graph_params(**kw):
+    """mi_pose_graph_params at its defaults (50 linearisations, 200 inner iterations, reference node 0, tolerances 1e-8, 1e-9 and 0,
+    lambda0 1e-6, no line process) with the given fields set."""
+    return _params(PoseGraph.Params, "mi_pose_graph_default_params", kw)
+
+
+def _pose_graph_arrays(poses, edge_source, edge_target, edge_T, edge_information, edge_uncertain):
+    """The graph as the ABI takes it: [V, 4, 4] and [E, 4, 4] transforms indexed [row, col] become column-major 16s."""
+    poses = np.ascontiguousarray(np.swapaxes(np.asarray(poses, np.float64).reshape(-1, 4, 4), 1, 2)).reshape(-1, 16)
+    src, tgt = np.ascontiguousarray(edge_source, np.int32).reshape(-1), np.ascontiguousarray(edge_target, np.int32).reshape(-1)
+    E = len(src)
+    Z = np.ascontiguousarray(np.swapaxes(np.asarray(edge_T, np.float64).reshape(-1, 4, 4), 1, 2)).reshape(-1, 16)
+    info = np.ascontiguousarray(edge_information, np.float64).reshape(-1, 36)
+    unc = None if edge_uncertain is None else np.ascontiguousarray(edge_uncertain, np.uint8).reshape(-1)
+    if len(tgt) != E or len(Z) != E or len(info) != E or (unc is not None and len(unc) != E):
+        raise ValueError("edge arrays must hold one entry per edge")
+    return poses, src, tgt, Z, info, unc, E
 
 
 COV_RAW, COV_PLANE = 0, 1     # MI_COV_*
@@ -659,6 +690,7 @@ class Context:
         "icp_plane": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
         "icp_gicp": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
         "evaluate_registration": ("workspace", "upload", "check", "grid", "order", "step", "download", "total"),
+        "pose_graph": ("workspace", "upload", "lists", "linearise", "solve", "candidate", "download", "total"),
         "icp_color": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
         "ndt": ("workspace", "upload", "check", "table", "order", "iterations", "download", "total"),
         "fpfh_features": ("workspace", "upload", "check", "grid", "order", "kernels", "download", "total"),
@@ -1186,6 +1218,48 @@ class Context:
         """ms per stage of the last evaluate_registration: workspace, upload, check, grid (0 with pairs given), order, step, download, total
         (mi_evaluate_registration_times)."""
         return self._times("evaluate_registration")
+
+    # ---- pose-graph optimisation
+    def pose_graph_optimize(self, poses, edge_source, edge_target, edge_T, edge_information, edge_uncertain=None, params=None):
+        """Optimises the [V, 4, 4] poses (indexed [row, col], scan frame to world) of a graph whose edge e aligns scan edge_source[e] to scan
+        edge_target[e] by edge_T[e] with the [6, 6] weight edge_information[e] (mi_pose_graph_optimize; evaluate_registration's T and
+        information).  Returns poses [V, 4, 4], weights [E], chi2 [E] and the report: a dict of initial_cost, final_cost, linearisations,
+        accepted, pcg_iterations, lambda, stop_reason and pcg_residual."""
+        P, src, tgt, Z, info, unc, E = _pose_graph_arrays(poses, edge_source, edge_target, edge_T, edge_information, edge_uncertain)
+        params = params if params is not None else pose_graph_params()
+        out, w, chi2, report = np.empty_like(P), np.empty(E, np.float64), np.empty(E, np.float64), np.zeros(8, np.float64)
+        _check(pose_graph_optimize_raw(self._h, P.ctypes.data, len(P), _ptr(src), _ptr(tgt), _ptr(Z), _ptr(info), _ptr(unc), E, C.addressof(params),
+                                       out.ctypes.data, w.ctypes.data, chi2.ctypes.data, report.ctypes.data))
+        names = ("initial_cost", "final_cost", "linearisations", "accepted", "pcg_iterations", "lambda", "stop_reason", "pcg_residual")
+        rep = {k: (int(v) if k in ("linearisations", "accepted", "pcg_iterations", "stop_reason") else float(v)) for k, v in zip(names, report)}
+        return np.swapaxes(out.reshape(-1, 4, 4), 1, 2).copy(), w, chi2, rep
+
+    def pose_graph_system(self, poses, edge_source, edge_target, edge_T, edge_information, edge_uncertain=None, params=None, p=None, solve=False):
+        """One linearisation at the given poses and lambda = params.lambda0 (mi_pose_graph_system).  Returns a dict: r [E, 6], chi2 [E],
+        w [E], M [E, 21], h [E, 6], diag [V, 21], g [V, 6], cost, and Hp [V, 6] for a given p [V, 6], and with solve x [V, 6],
+        pcg_iterations and pcg_residual."""
+        P, src, tgt, Z, info, unc, E = _pose_graph_arrays(poses, edge_source, edge_target, edge_T, edge_information, edge_uncertain)
+        params = params if params is not None else pose_graph_params()
+        V = len(P)
+        o = dict(r=np.zeros((E, 6)), chi2=np.zeros(E), w=np.zeros(E), M=np.zeros((E, 21)), h=np.zeros((E, 6)), diag=np.zeros((V, 21)), g=np.zeros((V, 6)))
+        pv = None if p is None else np.ascontiguousarray(p, np.float64).reshape(V, 6)
+        hp = np.zeros((V, 6)) if pv is not None else None
+        x = np.zeros((V, 6)) if solve else None
+        pcg, cost = np.zeros(2), C.c_double(0)
+        _check(pose_graph_system_raw(self._h, P.ctypes.data, V, _ptr(src), _ptr(tgt), _ptr(Z), _ptr(info), _ptr(unc), E, C.addressof(params), _ptr(pv),
+                                     int(bool(solve)), o["r"].ctypes.data, o["chi2"].ctypes.data, o["w"].ctypes.data, o["M"].ctypes.data, o["h"].ctypes.data,
+                                     o["diag"].ctypes.data, o["g"].ctypes.data, _ptr(hp), _ptr(x), pcg.ctypes.data, C.addressof(cost)))
+        o["cost"] = cost.value
+        if hp is not None:
+            o["Hp"] = hp
+        if solve:
+            o.update(x=x, pcg_iterations=int(pcg[0]), pcg_residual=float(pcg[1]))
+        return o
+
+    def pose_graph_times(self):
+        """ms per stage of the last pose_graph_optimize or pose_graph_system: workspace, upload, lists, linearise, solve, candidate, download,
+        total (mi_pose_graph_times)."""
+        return self._times("pose_graph")
 
     # ---- generalized ICP
     def estimate_covariances(self, cloud, k, mode=COV_PLANE, epsilon=1e-3, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_count=False):

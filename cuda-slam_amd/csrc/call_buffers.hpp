@@ -14,7 +14,7 @@
 namespace mislam {
 
 struct CallBuffers {
-    static constexpr int CAPACITY = 24;                  // the longest driver (ndt_prepare, ndt_api.hip) records 20
+    static constexpr int CAPACITY = 40;                  // the longest driver (pose_graph_api.hip) records 35
     struct Entry {
         const void* p;                                   // the DevBuf's own fields, read again by fits() and download(): &buf.p ...
         const size_t* cap;                               // ... and &buf.cap

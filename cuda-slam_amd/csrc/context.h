@@ -328,6 +328,25 @@ struct mi_ctx {
         double ms[MI_EVAL_STAGES] = {0};                 // mi_evaluate_registration_times
     } eval;
 
+    // ---- mi_pose_graph_optimize, mi_pose_graph_system: the graph as uploaded (poses of 12 numbers, the edges' endpoints, flags, measurements
+    // and information triangles), the incidence lists and their sort, the edge terms of the linearisation and the weights of the candidate,
+    // the nodes' diagonal blocks and gradients, the inner solve's vectors and partial sums, and the state block
+    struct PoseGraphBuffers {
+        mislam::DevBuf<double> poses, candidate;         // 12 V each
+        mislam::DevBuf<int> src, tgt, list, list_tmp, offsets, long_nodes;
+        mislam::DevBuf<unsigned char> uncertain;
+        mislam::DevBuf<double> Z, L;                     // [12][E], [21][E]
+        mislam::DevBuf<unsigned int> keys_a, keys_b;
+        mislam::DevBuf<unsigned char> sort_temp;
+        mislam::DevBuf<double> r, chi2, w, M, h;         // the edge terms (PgTerms)
+        mislam::DevBuf<double> chi2_c, w_c;              // ... of the candidate pass
+        mislam::DevBuf<double> cost_parts;
+        mislam::DevBuf<double> diag, grad;               // [21][V], [6][V]
+        mislam::DevBuf<double> x, pr, pz, pp, pq, pq_node, parts, user_p, hp;
+        mislam::DevBuf<mislam::PgState> state;
+        double ms[MI_POSE_GRAPH_STAGES] = {0};           // mi_pose_graph_times
+    } pose_graph;
+
     // ---- mi_estimate_covariances: mi_estimate_normals' sibling with six floats per point as its result, in buffers of its own
     struct CovarianceBuffers {
         mislam::SearchFrontBuffers front;
@@ -541,7 +560,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8 && MI_MLS_STAGES == 8 && MI_RADIUS_STAGES == 8 && MI_EVAL_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8 && MI_MLS_STAGES == 8 && MI_RADIUS_STAGES == 8 && MI_EVAL_STAGES == 8 && MI_POSE_GRAPH_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 // The body of every *_times entry point: the eight slots a StageClock left in the context.  ms: null for a null context.
 static inline int stage_times(const char* who, const double* ms, double* out_ms)
 {

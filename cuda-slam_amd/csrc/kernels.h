@@ -853,6 +853,58 @@ hipError_t eval_step(const NnGridView& g, const EvalStepArgs& a, int fma, hipStr
 // *bad = min(*bad, the lowest i with pair_idx[i] outside {-1} and [0, m)) -- the caller sets *bad to KNN_NO_POINT first
 hipError_t eval_check_pairs(const int* pair_idx, int n, int m, int* bad, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K56-K63 pose-graph optimisation (pose_graph_kernels.hip; driver: pose_graph_api.hip; the edge's arithmetic: pose_graph_terms.hpp).
+// Everything fp64.  Per edge and per node arrays are structure-of-arrays: component c of item i at [c * count + i].  Every sum over a node's
+// incidence list follows one rule, whichever kernel forms it: lane l of 64 adds the list's entries l, l + 64, ... in ascending order, and
+// the 64 partial sums are added one by one from lane 0 on -- for a list of at most 64 entries that is the list's own order, which one lane
+// retraces alone; longer lists (PG_LONG_LIST) take one wave per node.  Every sum over the nodes or the edges goes through reduce.hpp.
+// ---------------------------------------------------------------------------------------------------------------
+struct PgGraph {
+    int V, E, reference;
+    const int *src, *tgt;            // E each
+    const unsigned char* uncertain;  // E, or null: no edge is
+    const double* Z;                 // [12][E]: the measurements as given, R row-major then t
+    const double* L;                 // [21][E]: the upper triangles of the information matrices
+    const int* list;                 // 2 E entries 2 * edge + side, by node, ascending within a node
+    const int* offsets;              // V + 1
+    const int* long_nodes;           // the nodes whose list is longer than PG_LONG_LIST, ascending
+    int n_long;
+    double mu;                       // line_process_mu
+};
+struct PgTerms {
+    double *r, *chi2, *w, *M, *h;    // [6][E], E, E, [21][E], [6][E]
+};
+struct PgState {                     // the device-resident scalars of the inner solve and the costs
+    double rz, pq, alpha, beta, gg, rr;
+    double cost[2];                  // [0] at the linearisation, [1] of the candidate
+    double tolerance;
+    int done, iterations, max_iterations, breakdown;
+};
+static_assert(sizeof(PgState) <= 64 * sizeof(float), "a PgState must fit the context's pinned scratch");
+struct PgVectors {
+    double *x, *r, *z, *p, *q;       // [6][V] each
+    double* pq_node;                 // V: a long node's p . q, from the wave that formed it
+    double* parts;                   // pg_node_blocks(V) x 2: the partial rows of the dots
+};
+static inline int pg_blocks(int count) { return (count + 255) / 256; }
+// K56: keys[i] = (the node of list entry vals_in[i]) >> shift; with vals_in null the entries are 0 .. n2 - 1 themselves and vals_out receives them
+hipError_t pg_incidence_keys(const int* src, const int* tgt, const int* vals_in, int n2, int shift, unsigned int* keys, int* vals_out, hipStream_t s);
+hipError_t pg_build_offsets(const PgGraph& g, int* offsets, hipStream_t s);                       // K56 (g.list filled, g.offsets not read)
+// K57: one lane per edge; with system = 0 only chi2 and w are written (the candidate pass).  cost_parts: pg_blocks(E) partial sums.
+hipError_t pg_edge_terms_launch(const PgGraph& g, const double* poses, const PgTerms& t, int system, double* cost_parts, hipStream_t s);
+hipError_t pg_cost_finish(const double* cost_parts, int nparts, PgState* st, int slot, hipStream_t s);   // K58
+hipError_t pg_node_gather(const PgGraph& g, const PgTerms& t, double* diag /*[21][V]*/, double* grad /*[6][V]*/, hipStream_t s);   // K59
+// K60: q = (H + lambda diag H) p and the partial sums of p . q; honours st->done unless st is null
+hipError_t pg_product(const PgGraph& g, const PgTerms& t, const double* diag, double lambda, const double* p, double* q, double* pq_node, double* parts,
+                      const PgState* st, hipStream_t s);
+// K61, K62: the inner solve.  pg_pcg_begin resets the state and forms r = -g, z, p; pg_pcg_iterations enqueues `count` iterations, each of
+// which returns at once where the state says done.
+hipError_t pg_pcg_begin(const PgGraph& g, const double* diag, const double* grad, double lambda, double tolerance, int max_iterations, const PgVectors& v,
+                        PgState* st, hipStream_t s);
+hipError_t pg_pcg_iterations(const PgGraph& g, const PgTerms& t, const double* diag, double lambda, const PgVectors& v, PgState* st, int count, hipStream_t s);
+hipError_t pg_apply_step(const PgGraph& g, const double* poses, const double* x, double* out_poses, hipStream_t s);   // K63
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -882,5 +934,6 @@ hipError_t preload_color_kernels();
 hipError_t preload_mls_kernels();
 hipError_t preload_radius_kernels();
 hipError_t preload_eval_kernels();
+hipError_t preload_pose_graph_kernels();
 
 }  // namespace mislam

@@ -1854,6 +1854,100 @@ int mi_evaluate_registration(mi_ctx* ctx, const float* before_xyz, int n, const 
 int mi_evaluate_registration_times(mi_ctx* ctx, double out_ms[MI_EVAL_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * Pose-graph optimisation (no reference counterpart): what Open3D's global_optimization does for multiway registration and g2o or
+ * GTSAM do for a SLAM back end -- many pairwise poses, each weighted by the information matrix mi_evaluate_registration returns, turned
+ * into one consistent set of scan poses.  Levenberg-Marquardt outside, preconditioned conjugate gradients on the block-sparse system
+ * inside, everything fp64 and on the device; single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+typedef struct mi_pose_graph_params {
+    int max_iterations;        /* linearisations at most */
+    int max_pcg_iterations;    /* conjugate-gradient iterations per solve at most */
+    int reference_node;        /* the node that never moves */
+    double pcg_tolerance;      /* a solve stops at |r_k|_2 <= pcg_tolerance |g|_2 */
+    double relative_decrease;  /* MI_STOP_CONVERGED when an accepted step lowers the cost by this fraction or less */
+    double absolute_cost;      /* MI_STOP_CONVERGED when the cost is this or less */
+    double lambda0;            /* the damping the outer loop starts with; mi_pose_graph_system's lambda */
+    double line_process_mu;    /* > 0: the edges flagged uncertain are weighted by the line process; 0: every weight is 1 */
+} mi_pose_graph_params;
+/* 50, 200, 0, 1e-8, 1e-9, 0, 1e-6, 0 */
+void mi_pose_graph_default_params(mi_pose_graph_params* p);
+
+/* Optimises the poses of a graph of V nodes and E edges.  Every rule below can be retraced in numpy (tests/pose_graph_reference.py does).
+ *   Graph: node k has a pose T_k = (R_k, t_k), scan frame to world, column-major 4 x 4 like every transform of this library,
+ *     T[4 * col + row]; only the rotation block and the translation column are read.  Edge e = (s, t) = (edge_source[e], edge_target[e])
+ *     has a measurement Z_e (edge_T, the same layout) that aligns the source scan to the target scan -- exactly the T of
+ *     mi_evaluate_registration(before = source, after = target, T) -- and an information matrix Lambda_e, row-major 6 x 6 with the
+ *     rotation first: that call's out_information.  Only its upper triangle is read.
+ *   Error of an edge: E_e = T_t^-1 T_s Z_e^-1.  Z_e is inverted in the edge kernel, from the measurement as given.
+ *   Residual: r_e = (omega, v), omega = log_SO3(R_E) -- half the antisymmetric part s of R_E, scaled by theta / |s| with
+ *     theta = atan2(|s|, (trace - 1) / 2); below |s| = 1e-8, s itself -- and v = t_E (not the SE(3) logarithm's translation).  The left
+ *     error in the target's frame: the perturbation mi_evaluate_registration's Lambda weights.
+ *   Update of a node: T_k <- exp(delta_k) T_k, delta = (omega, v): R <- dR R, t <- dR t + v with Rodrigues' dR of
+ *     mi_icp_plane_register (centre 0).  A node whose step is all zeros keeps its pose's bits.
+ *   Jacobians (the Gauss-Newton approximation, stated and not refined): d r_e / d delta_s = A_e = Ad(T_t^-1) =
+ *     [[R_t^T, 0], [[t']x R_t^T, R_t^T]], t' = -R_t^T t_t, and d r_e / d delta_t = -A_e.
+ *   Terms: chi2_e = r_e^T Lambda_e r_e; M_e = w_e A_e^T Lambda_e A_e (symmetric, its upper triangle's 21 numbers row-major);
+ *     h_e = w_e A_e^T Lambda_e r_e.  H_ss += M_e, H_tt += M_e, H_st = H_ts^T -= M_e, g_s += h_e, g_t -= h_e: a graph Laplacian with
+ *     6 x 6 block weights, (H p)_s += M_e (p_s - p_t), (H p)_t -= M_e (p_s - p_t).
+ *   Line process (switchable loop closures as Geman-McClure): an edge with edge_uncertain[e] != 0, under mu = line_process_mu > 0,
+ *     has w_e = (mu / (mu + chi2_e))^2 and the share mu chi2_e / (mu + chi2_e) of the cost F; every other edge w_e = 1 and the share
+ *     chi2_e.  Weights are recomputed at every linearisation; the final ones are an output, and the caller prunes the edges whose
+ *     weight is below its own threshold (0.25 in Open3D).
+ *   Gauge: reference_node never moves; its rows and columns are left out (p_ref = 0).  A node without edges keeps its pose.  A
+ *     component without the reference node is determined only up to a common motion; the damping keeps the system solvable.
+ *   Sums: a node's diagonal block, gradient and row of H p are sums over its incidence list, ascending in the edge index, an edge's
+ *     source side before its target side: 64 partial sums over the entries l, l + 64, ... each, added from l = 0 on (for a list of at
+ *     most 64 entries: the list's own order).  Lists above 64 entries are summed by one wave, shorter ones by one lane, to the same bits.
+ *     Every dot product, norm and cost is summed in a fixed order that depends on V or E alone.  No floating-point atomics: the same
+ *     input gives the same bits on every call, whatever ran on the context before.
+ *   Inner solve: (H + lambda diag(H)) x = -g by preconditioned conjugate gradients from x = 0.  The preconditioner is, per node, the
+ *     inverse of the damped 6 x 6 diagonal block, applied by mi_icp_plane_register's scaled LDL^T afresh at every use (no inverse is
+ *     stored); a block that solve calls degenerate is preconditioned by the identity.  It stops at |r_k|_2 <= pcg_tolerance |g|_2 or at
+ *     max_pcg_iterations; the step reached at the cap is still tried.  alpha, beta, the norms and the done flag live on the device;
+ *     the host reads them every 16 iterations and once per solve, never per iteration.
+ *   Outer loop (Levenberg-Marquardt, Marquardt's scaling): linearise, F = the cost; F <= absolute_cost returns the input poses with
+ *     MI_STOP_CONVERGED.  lambda = lambda0.  Solve, form the candidate poses and their cost F_new on the device.  F_new < F: accept,
+ *     lambda <- max(lambda / 10, 1e-12); then MI_STOP_CONVERGED when (F - F_new) / F <= relative_decrease or F_new <= absolute_cost,
+ *     MI_STOP_MAX_ITERATIONS when max_iterations linearisations have been made, else linearise again.  Otherwise lambda <- 10 lambda
+ *     and the solve is repeated on the same linearisation; eight rejections in a row stop with MI_STOP_ERROR_INCREASED.
+ *   Outputs: out_poses in the layout of poses, every entry outside the rotation block and the translation column copied from poses;
+ *     out_weights[e] and out_chi2[e] at the returned poses; out_report = initial cost, final cost, linearisations, accepted steps,
+ *     conjugate-gradient iterations in total, final lambda, stop reason, the last solve's |r|_2 / |g|_2.  E = 0 returns the poses as given.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name and names the array and the lowest offending index; NO output
+ *     has been written -- for a NULL ctx, poses, params, out_poses or out_report, or NULL edge arrays with E > 0; V < 1 or E < 0;
+ *     reference_node outside [0, V); an edge endpoint outside [0, V) or source == target; a non-finite entry of a pose, a measurement
+ *     or an information matrix (upper triangle); a rotation block with max |R^T R - I| > 1e-3; a negative diagonal entry of an
+ *     information matrix; pcg_tolerance, relative_decrease, absolute_cost or line_process_mu NaN or negative; lambda0 <= 0 or NaN.
+ *     E >= 2^30 is refused too (V < 2^31 by its type).
+ *   MI_ERR_STATE on a distributed context.  A problem loaded by mi_icp_load survives the call: it works in buffers of its own.
+ *   Synchronous, host in and host out. */
+int mi_pose_graph_optimize(mi_ctx* ctx, const double* poses /* V x 16 */, int V,
+                           const int* edge_source, const int* edge_target, const double* edge_T /* E x 16 */,
+                           const double* edge_information /* E x 36 */, const unsigned char* edge_uncertain /* may be NULL; E */, int E,
+                           const mi_pose_graph_params* params, double* out_poses /* V x 16 */,
+                           double* out_weights /* may be NULL; E */, double* out_chi2 /* may be NULL; E */, double out_report[8]);
+
+/* One linearisation at the given poses with lambda = params->lambda0, stage by stage (the counterpart of mi_plane_system): per edge
+ * out_r (E x 6), out_chi2 (E), out_w (E), out_M (E x 21) and out_h (E x 6); per node out_diag (V x 21, the upper triangle of the
+ * diagonal block) and out_g (V x 6); for the caller's p (V x 6, may be NULL; the reference node's row is taken as 0) out_Hp (V x 6) =
+ * (H + lambda diag H) p with the reference node's row 0; with solve != 0 the inner solve's step out_x (V x 6) and its
+ * out_pcg[2] = iterations, |r|_2 / |g|_2.  Every output may be NULL; *out_cost (may be NULL) is F.  Same checks, same refusals. */
+int mi_pose_graph_system(mi_ctx* ctx, const double* poses, int V, const int* edge_source, const int* edge_target, const double* edge_T,
+                         const double* edge_information, const unsigned char* edge_uncertain, int E, const mi_pose_graph_params* params,
+                         const double* p, int solve, double* out_r, double* out_chi2, double* out_w, double* out_M, double* out_h,
+                         double* out_diag, double* out_g, double* out_Hp, double* out_x, double* out_pcg, double* out_cost);
+
+/* Where the last mi_pose_graph_optimize or mi_pose_graph_system of this context spent its host wall time, in ms (measurement hook,
+ * tools/pose_graph_bench.py):
+ *   out[0] workspace (device allocations)           out[1] input checks on the host, AoS -> SoA, upload
+ *   out[2] incidence lists (sort, offsets)          out[3] linearisations (edge terms, node gather, the cost's read-back)
+ *   out[4] inner solves, host reads included        out[5] candidate poses and their cost
+ *   out[6] download of the results                  out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage). */
+#define MI_POSE_GRAPH_STAGES 8
+int mi_pose_graph_times(mi_ctx* ctx, double out_ms[MI_POSE_GRAPH_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
  * -------------------------------------------------------------------------------------------------------------- */
 enum {
