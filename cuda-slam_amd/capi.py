@@ -483,6 +483,42 @@ feature_match_raw = _raw("mi_feature_match")
 feature_match_times_raw = _raw("mi_feature_match_times")
 
 
+class ScanContext:
+    """mi_scan_context_params, held in a namespace as PoseGraph holds its own: the compiler checks this one's layout against the header's in
+    tests/test_scan_context_abi.py."""
+    C_TYPE = "mi_scan_context_params"
+
+    class Params(C.Structure):
+        _fields_ = [("rings", C.c_int), ("sectors", C.c_int), ("max_radius", C.c_float), ("z_offset", C.c_float), ("reserved", C.c_int * 12)]
+
+
+SCAN_CONTEXT_MAX_RINGS, SCAN_CONTEXT_MAX_SECTORS, SCAN_CONTEXT_MAX_ROWS = 32, 64, 1 << 26      # MI_SCAN_CONTEXT_MAX_*
+SC_SEARCH_CHUNK = _kernel_constant("SC_SEARCH_CHUNK")          # database rows per workgroup of the search kernel: a multiple of this
+SC_SEARCH_WAVES = _kernel_constant("SC_SEARCH_WAVES")
+SC_SLICE = _kernel_constant("SC_SLICE")                        # points of a scan per workgroup of the binning kernel
+
+
+def scan_context_params(**kw):
+    """mi_scan_context_params at its defaults (20 rings, 60 sectors, max_radius 80, z_offset 2) with the given fields set."""
+    return _params(ScanContext.Params, "mi_scan_context_params_default", kw)
+
+
+def scan_context_tables(params=None):
+    """Host-only: the squared ring edges [rings + 1] and the sectors' boundary directions [sectors, 2] (cos, sin), float64, exactly as
+    mi_scan_context bins with them (mi_scan_context_tables)."""
+    params = params if params is not None else scan_context_params()
+    edge2 = np.empty(max(int(params.rings), 0) + 1, np.float64)
+    dirs = np.empty((max(int(params.sectors), 0), 2), np.float64)
+    if not (1 <= params.rings <= SCAN_CONTEXT_MAX_RINGS and 1 <= params.sectors <= SCAN_CONTEXT_MAX_SECTORS):
+        edge2, dirs = np.empty(SCAN_CONTEXT_MAX_RINGS + 1), np.empty((SCAN_CONTEXT_MAX_SECTORS, 2))     # the call refuses; nothing is written
+    _check(lib().mi_scan_context_tables(C.byref(params), edge2.ctypes.data, dirs.ctypes.data))
+    return edge2, dirs
+
+
+scan_context_raw = _raw("mi_scan_context")
+scan_context_search_raw = _raw("mi_scan_context_search")
+
+
 class RansacParams(C.Structure):
     _fields_ = [("hypotheses", C.c_int), ("seed", C.c_ulonglong), ("max_distance", C.c_float), ("edge_similarity", C.c_float),
                 ("refine_iterations", C.c_int), ("reserved", C.c_int * 8)]
@@ -694,6 +730,7 @@ class Context:
         "icp_color": ("workspace", "upload", "check", "grid", "order", "iterations", "download", "total"),
         "ndt": ("workspace", "upload", "check", "table", "order", "iterations", "download", "total"),
         "fpfh_features": ("workspace", "upload", "check", "grid", "order", "kernels", "download", "total"),
+        "scan_context": ("workspace", "upload", "check", "unused3", "unused4", "kernels", "download", "total"),
         "feature_match": ("workspace", "upload", "check", "unused3", "unused4", "kernels", "download", "total"),
         "ransac_register": ("workspace", "upload", "hypotheses", "count", "argmax", "refine", "unused6", "total"),
         "fgr_register": ("workspace", "upload", "check", "tuples", "gather", "iterations", "download", "total"),
@@ -1260,6 +1297,58 @@ class Context:
         """ms per stage of the last pose_graph_optimize or pose_graph_system: workspace, upload, lists, linearise, solve, candidate, download,
         total (mi_pose_graph_times)."""
         return self._times("pose_graph")
+
+    # ---- place recognition
+    def scan_context(self, clouds_or_xyz, offsets=None, centres=None, params=None):
+        """Scan Context descriptors [n_scans, rings, sectors] float32 of many scans in one call (mi_scan_context).  clouds_or_xyz: a list of
+        [n_s, 3] clouds, or with offsets [n_scans + 1] one [n, 3] array that holds them all; centres [n_scans, 3]: the sensors' positions
+        (None: the origin); z is up."""
+        if offsets is None:
+            clouds = [_cloud(c) for c in clouds_or_xyz]
+            offsets = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int32)
+            xyz = np.concatenate(clouds) if clouds else np.zeros((0, 3), np.float32)
+        else:
+            xyz, offsets = _cloud(clouds_or_xyz), np.ascontiguousarray(offsets, np.int32).reshape(-1)
+            if len(offsets) and offsets[-1] > len(xyz):
+                raise ValueError("offsets reach past the points")
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        n_scans = len(offsets) - 1
+        params = params if params is not None else scan_context_params()
+        if centres is not None:
+            centres = np.ascontiguousarray(centres, np.float32)
+            if centres.shape != (n_scans, 3):
+                raise ValueError("centres is [n_scans, 3]")
+        if xyz.shape[0] == 0:
+            xyz = np.zeros((1, 3), np.float32)               # a pointer to pass; no offset reaches it
+        desc = np.empty((max(n_scans, 0), max(int(params.rings), 0), max(int(params.sectors), 0)), np.float32)
+        _check(scan_context_raw(self._h, xyz.ctypes.data, offsets.ctypes.data, n_scans, _ptr(centres), C.addressof(params), desc.ctypes.data))
+        return desc
+
+    def scan_context_search(self, query, db, limit=None, params=None, want_second=False):
+        """The best row of db [nd, rings, sectors] for every descriptor of query [nq, rings, sectors], every pair at every shift
+        (mi_scan_context_search): idx [nq] int32, dist [nq] float32, shift [nq] int32 -- turning the query scan counter-clockwise about z by
+        shift * 2 pi / sectors aligns it with scan idx -- then the runner-up's distance [nq] if asked for.  limit [nq]: query i sees the
+        rows below limit[i] (<= 0: idx -1, dist inf, shift 0)."""
+        params = params if params is not None else scan_context_params()
+        shape = (int(params.rings), int(params.sectors))
+        query, db = np.ascontiguousarray(query, np.float32), np.ascontiguousarray(db, np.float32)
+        if query.ndim != 3 or db.ndim != 3 or query.shape[1:] != shape or db.shape[1:] != shape:
+            raise ValueError("query and db are [rows, rings, sectors] with the params' rings and sectors")
+        nq, nd = query.shape[0], db.shape[0]
+        if limit is not None:
+            limit = np.ascontiguousarray(limit, np.int32)
+            if limit.shape != (nq,):
+                raise ValueError("limit has one entry per query")
+        idx, dist, shift = np.empty(nq, np.int32), np.empty(nq, np.float32), np.empty(nq, np.int32)
+        second = np.empty(nq, np.float32) if want_second else None
+        _check(scan_context_search_raw(self._h, query.ctypes.data, nq, db.ctypes.data, nd, _ptr(limit), C.addressof(params), idx.ctypes.data,
+                                       dist.ctypes.data, shift.ctypes.data, _ptr(second)))
+        return (idx, dist, shift, second) if want_second else (idx, dist, shift)
+
+    def scan_context_times(self):
+        """ms per stage of the last scan_context or scan_context_search: workspace, upload, check, -, -, kernels, download, total
+        (mi_scan_context_times)."""
+        return self._times("scan_context")
 
     # ---- generalized ICP
     def estimate_covariances(self, cloud, k, mode=COV_PLANE, epsilon=1e-3, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_count=False):

@@ -347,6 +347,21 @@ struct mi_ctx {
         double ms[MI_POSE_GRAPH_STAGES] = {0};           // mi_pose_graph_times
     } pose_graph;
 
+    // ---- mi_scan_context, mi_scan_context_search: the points, offsets and centres of the scans with the two tables and the descriptors; the
+    // two descriptor arrays of a search, their unit columns and masks, the limits, the packed winners (and runners-up) and the outputs
+    struct ScanContextBuffers {
+        mislam::DevBuf<float> xyz, centres, out_desc;
+        mislam::DevBuf<int> offsets;
+        mislam::DevBuf<double> tables;                   // rings + 1 squared ring edges, then 2 * sectors boundary directions
+        mislam::DevBuf<float> query, db, q_unit, d_unit;
+        mislam::DevBuf<unsigned long long> q_mask, d_mask, keys, keys2;
+        mislam::DevBuf<int> limit;
+        mislam::DevBuf<int> bad;                         // [0] the points' or the queries', [1] the database's lowest refused index, or SC_NO_INDEX
+        mislam::DevBuf<int> out_idx, out_shift;
+        mislam::DevBuf<float> out_dist, out_second;
+        double ms[MI_SCAN_CONTEXT_STAGES] = {0};         // mi_scan_context_times
+    } scan_context;
+
     // ---- mi_estimate_covariances: mi_estimate_normals' sibling with six floats per point as its result, in buffers of its own
     struct CovarianceBuffers {
         mislam::SearchFrontBuffers front;
@@ -560,7 +575,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8 && MI_MLS_STAGES == 8 && MI_RADIUS_STAGES == 8 && MI_EVAL_STAGES == 8 && MI_POSE_GRAPH_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8 && MI_MLS_STAGES == 8 && MI_RADIUS_STAGES == 8 && MI_EVAL_STAGES == 8 && MI_POSE_GRAPH_STAGES == 8 && MI_SCAN_CONTEXT_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 // The body of every *_times entry point: the eight slots a StageClock left in the context.  ms: null for a null context.
 static inline int stage_times(const char* who, const double* ms, double* out_ms)
 {

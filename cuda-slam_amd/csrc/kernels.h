@@ -905,6 +905,54 @@ hipError_t pg_pcg_begin(const PgGraph& g, const double* diag, const double* grad
 hipError_t pg_pcg_iterations(const PgGraph& g, const PgTerms& t, const double* diag, double lambda, const PgVectors& v, PgState* st, int count, hipStream_t s);
 hipError_t pg_apply_step(const PgGraph& g, const double* poses, const double* x, double* out_poses, hipStream_t s);   // K63
 
+// ---------------------------------------------------------------------------------------------------------------
+// K64-K67 Scan Context: place recognition for loop closures (scan_context_kernels.hip; driver: scan_context_api.hip; the binning's
+// arithmetic: scan_context_bin.hpp; the contract: mi_scan_context and mi_scan_context_search in mi_slam.h).
+//   K64 sc_bins:      one workgroup per slice of SC_SLICE points of one scan: the descriptor of the slice in the LDS as the bits of the bins'
+//                     positive fp32 maxima (which order as unsigned integers), merged into the scan's descriptor by atomicMax; the input
+//                     check (lowest refused point by atomicMin) in the same pass.
+//   K65 sc_normalise: one wave per descriptor, one lane per sector: the column's fp64 norm in ring order, the fp32 unit column, the
+//                     64-bit mask of the non-empty columns, the input check.
+//   K66 sc_search:    one workgroup of SC_SEARCH_WAVES waves per (query, chunk of SC_SEARCH_CHUNK-row multiples); a wave forms one
+//                     candidate's sectors x sectors cosines on the matrix pipe (v_mfma_f32_32x32x2_f32, the query's unit columns resident
+//                     in registers as the A operand), parks them in its own LDS tile, and lane s sums the wrapped diagonal of shift s in
+//                     fp64; every lane keeps the running minimum of its shift, merged at the end by atomicMin on
+//                     (ordered(distance) << 32 | row << 6 | shift).
+//   K67 sc_finish:    one lane per query: the key unpacked into idx, dist, shift (and the runner-up's distance).
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int SC_SLICE = 4096;               // points of a scan per workgroup of K64, at least (a longer scan than 65 535 slices: longer slices)
+constexpr int SC_SEARCH_WAVES = 2;           // waves of a K66 workgroup; each takes every SC_SEARCH_WAVES-th row of the chunk
+constexpr int SC_SEARCH_CHUNK = 64;          // database rows of a K66 workgroup: a multiple of this (sc_chunk_len)
+constexpr int SC_ROW_BITS = 26;              // of the packed key: rows below 2^26 (MI_SCAN_CONTEXT_MAX_ROWS), 6 bits of shift
+constexpr int SC_NO_INDEX = 0x7fffffff;      // *bad while nothing has been refused
+struct ScBinArgs {
+    const float* xyz;                // all points, AoS
+    const int* offsets;              // n_scans + 1
+    const float* centres;            // 3 per scan, or null: the origin
+    int n_scans, rings, sectors, slice;
+    float z_offset;
+    const double* ring_edge2;        // rings + 1 (mi_scan_context_tables)
+    const double* sector_dir;        // 2 * sectors
+    unsigned int* desc;              // n_scans * rings * sectors, zero before the launch: the bits of the fp32 descriptor
+    int* bad;                        // SC_NO_INDEX before the launch: the lowest point with a coordinate that is not finite or above SC_MAX_ABS
+};
+hipError_t sc_bins(const ScBinArgs& a, int longest_scan, hipStream_t s);
+// unit[row] = the descriptor with every column scaled to length 1 (an empty column stays +0), mask[row] bit j = column j is not empty;
+// *bad = min(*bad, the lowest row with a negative or non-finite value)
+hipError_t sc_normalise(const float* desc, int rows, int rings, int sectors, float* unit, unsigned long long* mask, int* bad, hipStream_t s);
+struct ScSearchArgs {
+    const float* q_unit; const unsigned long long* q_mask; int nq;
+    const float* d_unit; const unsigned long long* d_mask; int nd;
+    const int* limit;                // nq, or null: every query sees all nd rows
+    const int* exclude;              // nq, or null: a row that query i does not see (the runner-up pass: the winner)
+    int rings, sectors, chunk_len;
+    unsigned long long* keys;        // nq, all ones before the launch
+};
+int sc_chunk_len(int nq, int nd, int cu_count);
+hipError_t sc_search(const ScSearchArgs& a, hipStream_t s);
+// idx / dist / shift from keys (all ones: -1, +inf, 0); second (may be null) from keys2 alone
+hipError_t sc_finish(const unsigned long long* keys, const unsigned long long* keys2, int nq, int* idx, float* dist, int* shift, float* second, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -935,5 +983,6 @@ hipError_t preload_mls_kernels();
 hipError_t preload_radius_kernels();
 hipError_t preload_eval_kernels();
 hipError_t preload_pose_graph_kernels();
+hipError_t preload_scan_context_kernels();
 
 }  // namespace mislam

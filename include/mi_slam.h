@@ -1948,6 +1948,115 @@ int mi_pose_graph_system(mi_ctx* ctx, const double* poses, int V, const int* edg
 int mi_pose_graph_times(mi_ctx* ctx, double out_ms[MI_POSE_GRAPH_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * Place recognition (no reference counterpart): which earlier scan a new scan should be tried against -- the loop-closure candidates the
+ * pose graph weighs.  Scan Context (Kim and Kim, IROS 2018): a small polar height map per scan and a comparison that is invariant to
+ * a rotation about the up axis, whose best column shift is also a yaw estimate: the init_T of the local registrations (INTEGRATION.md:
+ * which tile to try).  The search is exact: every query is compared with every stored descriptor at every shift; no ring key, no pruning.
+ * Single-GPU contexts only.
+ * -------------------------------------------------------------------------------------------------------------- */
+#define MI_SCAN_CONTEXT_MAX_RINGS 32
+#define MI_SCAN_CONTEXT_MAX_SECTORS 64
+#define MI_SCAN_CONTEXT_MAX_ROWS (1 << 26)
+typedef struct mi_scan_context_params {
+    int rings;           /* 1 .. MI_SCAN_CONTEXT_MAX_RINGS: equal steps of the planar distance from the centre */
+    int sectors;         /* 1 .. MI_SCAN_CONTEXT_MAX_SECTORS: equal steps of the angle about z, counter-clockwise from +x */
+    float max_radius;    /* > 0: points at or beyond it in the xy-plane belong to no bin */
+    float z_offset;      /* added to every height, so that the ground is positive (the sensor's height above it) */
+    int reserved[12];
+} mi_scan_context_params;
+/* 20, 60, 80, 2 */
+void mi_scan_context_params_default(mi_scan_context_params* p);
+
+/* The two tables of the binning, written by the host alone: ring_edge2[rings + 1], the squared ring edges (max_radius r / rings)^2 in
+ * fp64, r = 0 .. rings, the last one max_radius^2 itself; sector_dir[2 * sectors], the unit directions (cos, sin)(2 pi j / sectors) of the
+ * boundary at which sector j begins, the four axes exact and, for an even number of sectors, direction j + sectors / 2 the exact negative
+ * of direction j.  mi_scan_context bins with exactly these doubles, and so does the restatement (tests/scan_context_reference.py), which
+ * reads them through this call.  MI_ERR_INVALID_ARG for a NULL argument or params out of range (as below).  Needs no context. */
+int mi_scan_context_tables(const mi_scan_context_params* params, double* ring_edge2, double* sector_dir);
+
+/* The descriptors of n_scans scans in one call: desc[n_scans][rings][sectors], fp32.  Scan s is the points [offsets[s], offsets[s + 1]) of
+ * xyz (offsets has n_scans + 1 ascending entries from 0; an empty scan is allowed and gives an all-zero descriptor) seen from
+ * centres[3 s ..] (the sensor's position; centres NULL: the origin).  z is the up axis: the caller supplies gravity-aligned scans.
+ * Every rule below can be retraced in numpy (tests/scan_context_reference.py does, bit for bit).
+ *   A bin holds the largest z + z_offset -- one fp32 addition -- over the scan's points that fall into it; a bin without points holds +0,
+ *     and so does a bin whose largest value is <= 0.
+ *   The bin of a point: no transcendental function and no square root stands between a point and its bin.  dx = (double)x - (double)cx,
+ *     dy = (double)y - (double)cy, d2 = dx dx + dy dy: two fp64 products and one sum, every operation rounded once, none fused.
+ *     Ring: d2 >= ring_edge2[rings] belongs to no bin (a point exactly at max_radius is out); otherwise the ring is the number of inner
+ *       edges ring_edge2[1 .. rings - 1] that are <= d2: a point exactly on an edge belongs to the ring outside it.
+ *     Sector: the half-plane first -- upper for dy > 0, or dy == 0 and dx > 0; lower for dy < 0, or dy == 0 and dx < 0; the point exactly
+ *       at the centre goes to sector 0 (of ring 0).  The upper half-plane holds the boundaries j with 2 j < sectors, the lower one the
+ *       others.  The point has passed boundary j = (c_j, s_j) when c_j dy - s_j dx >= 0 (two fp64 products, one difference): a point
+ *       exactly on a boundary belongs to the sector that begins there.  With j0 the first boundary of the point's half-plane and p the
+ *       number of that half-plane's boundaries it has passed, the sector is j0 - 1 + p (in the upper half-plane boundary 0 is always
+ *       passed; in the lower one p = 0 leaves the point in the last sector that began above, which happens for odd `sectors`).
+ *   Determinism: the maximum is merged by integer atomics on the fp32 bits (a positive fp32 orders as its bits do); the same input gives
+ *     the same bits on every call, and a scan's descriptor does not depend on what else is in the batch.  No floating-point atomics.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name and names the cause and the lowest offending index; NO output
+ *     has been written -- for a NULL ctx, xyz, offsets, params or desc; n_scans < 1; offsets[0] != 0 or offsets that descend; rings or
+ *     sectors out of range; max_radius or z_offset not finite, or max_radius <= 0; a coordinate of a centre or of a point that is not
+ *     finite or above 1e18 in magnitude (checked in this order: offsets, centres, points).
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call, and so does everything the other calls of this header keep: it works in buffers
+ *     of its own.  Synchronous, host in and host out. */
+int mi_scan_context(mi_ctx* ctx,
+                    const float* xyz,          /* offsets[n_scans] * 3 */
+                    const int* offsets,        /* n_scans + 1 */
+                    int n_scans,
+                    const float* centres,      /* may be NULL; n_scans * 3 */
+                    const mi_scan_context_params* params,
+                    float* desc);              /* n_scans * rings * sectors */
+
+/* The best stored descriptor for every query, every pair looked at, at every shift: idx[i] = the winning row of db_desc, dist[i] its
+ * distance, shift[i] in [0, sectors) the column shift at which it was reached.  Both arrays have mi_scan_context's layout,
+ * [rows][rings][sectors]; params gives the shape (max_radius and z_offset are checked and otherwise unused).  Query i sees the rows
+ * [0, limit[i]) (limit NULL: all nd) -- an online caller passes i - 50 to skip the scans just behind it; limit[i] <= 0 gives idx = -1,
+ * dist = +INFINITY, shift = 0.  second_dist (may be NULL) receives the lowest distance among the rows query i sees other than idx[i]
+ * (+INFINITY if there is none): the runner-up of a ratio test.  Every rule below can be retraced in numpy (tests/scan_context_reference.py
+ * does, with the fp32 fmaf emulated exactly).
+ *   Normalised columns: column j of a descriptor is its `rings` values in sector j.  A column whose values are all zero is empty.
+ *     Otherwise u_j = column / |column|: the norm is the fp64 square root of the fp64 sum of squares, rings ascending, every product
+ *     exact and every sum rounded once; each component is divided in fp64 and rounded to fp32 once.
+ *   Cosine: G(j, k) = c_rings with c_0 = +0, c_(r+1) = fmaf(uq_j[r], uc_k[r], c_r), r ascending: all fp32, the bits the fp32-input
+ *     matrix instructions produce (see mi_feature_match).  Zero-padding rings to the instruction's K and sectors to its tile changes no
+ *     bit of any output: a zero step leaves the chain alone, and no padded column is ever on a diagonal.
+ *   Distance at shift s: with P_s the sectors j for which neither column j of the query nor column (j + s) mod sectors of the row is
+ *     empty, d_s = (float)(sum_(j in P_s) (1.0 - (double)G(j, (j + s) mod sectors)) / |P_s|): every term, the sum (j ascending, from +0)
+ *     and the quotient in fp64, rounded to fp32 once.  P_s empty: d_s = 1.
+ *   Winner: the minimum over s, the lowest s on ties; then the minimum over the rows, the lowest row on ties.  Chunks of rows are merged
+ *     by an integer atomicMin on (distance mapped to an order-preserving unsigned, row, shift); the same input gives the same bits on
+ *     every call.  No floating-point atomics.
+ *   Which way the shift turns: sector j is the angle [2 pi j / sectors, 2 pi (j + 1) / sectors) counter-clockwise from +x, so rotating
+ *     the QUERY scan about +z through its centre by shift[i] 2 pi / sectors aligns it with scan idx[i] (about that one's centre): the
+ *     init_T of a local registration of the query onto the stored scan is that rotation, moved from the query's centre to the stored
+ *     one's.  A query that is the stored scan turned counter-clockwise by k sectors comes back with shift = (sectors - k) mod sectors.
+ *     The estimate is good to within a sector's width.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with the entry point's name; NO output has been written -- for a NULL ctx, query_desc,
+ *     db_desc, params, idx, dist or shift; nq < 1 or nd < 1, or nd above MI_SCAN_CONTEXT_MAX_ROWS; params out of range as for
+ *     mi_scan_context; a limit[i] > nd (the lowest i); a negative or non-finite descriptor value: the message names the array and the
+ *     lowest row, query_desc first.
+ *   MI_ERR_STATE on a distributed context.
+ *   A problem loaded by mi_icp_load survives the call: it works in buffers of its own.  Synchronous, host in and host out. */
+int mi_scan_context_search(mi_ctx* ctx,
+                           const float* query_desc, int nq,   /* nq * rings * sectors */
+                           const float* db_desc, int nd,      /* nd * rings * sectors */
+                           const int* limit,                  /* may be NULL; nq */
+                           const mi_scan_context_params* params,
+                           int* idx, float* dist, int* shift, /* nq each */
+                           float* second_dist);               /* may be NULL; nq */
+
+/* Where the last mi_scan_context or mi_scan_context_search of this context spent its host wall time, in ms (measurement hook,
+ * tools/scan_context_bench.py):
+ *   out[0] workspace (device allocations)           out[1] upload (points, offsets, tables; or the two descriptor arrays)
+ *   out[2] the search's normalisation, the input check and its read-back (mi_scan_context: 0, its check runs inside the binning kernel)
+ *   out[3], out[4] unused (0)                       out[5] the kernels (binning and its check's read-back; or searches + finish)
+ *   out[6] download of the results                  out[7] the whole call
+ * The parts are attributable only while profiling is enabled (the stream is then drained after every stage; mi_profile_get then has
+ * the search launches' own HIP-event time under MI_KERNEL_NN and the binning kernel's under MI_KERNEL_MOMENTS). */
+#define MI_SCAN_CONTEXT_STAGES 8
+int mi_scan_context_times(mi_ctx* ctx, double out_ms[MI_SCAN_CONTEXT_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
  * -------------------------------------------------------------------------------------------------------------- */
 enum {
