@@ -519,6 +519,41 @@ scan_context_raw = _raw("mi_scan_context")
 scan_context_search_raw = _raw("mi_scan_context_search")
 
 
+class Tsdf:
+    """mi_tsdf_params, held in a namespace as ScanContext holds its own: the compiler checks this one's layout against the header's in
+    tests/test_tsdf_abi.py."""
+    C_TYPE = "mi_tsdf_params"
+
+    class Params(C.Structure):
+        _fields_ = [("voxel_size", C.c_float), ("truncation", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float),
+                    ("max_weight", C.c_float), ("reserved", C.c_int * 11)]
+
+
+TSDF_MAX_HALF_STEPS = 16                                        # MI_TSDF_MAX_HALF_STEPS
+TSDF_BLOCK = _kernel_constant("TSDF_BLOCK")                     # rays per workgroup of the sampling kernel
+
+
+def tsdf_params(**kw):
+    """mi_tsdf_params at its defaults (no range gate, no weight cap; voxel_size and truncation 0: set them) with the given fields set."""
+    return _params(Tsdf.Params, "mi_tsdf_params_default", kw)
+
+
+tsdf_integrate_raw = _raw("mi_tsdf_integrate")
+tsdf_extract_raw = _raw("mi_tsdf_extract")
+
+
+def _tsdf_map(m):
+    """(coord [nv, 3] int32, tsdf [nv] float32, weight [nv] float32) of a map given as such a triple, or of None: the empty map"""
+    if m is None:
+        return np.zeros((0, 3), np.int32), np.zeros(0, np.float32), np.zeros(0, np.float32)
+    coord, tsdf, weight = m
+    coord = np.ascontiguousarray(coord, np.int32).reshape(-1, 3)
+    tsdf, weight = np.ascontiguousarray(tsdf, np.float32).ravel(), np.ascontiguousarray(weight, np.float32).ravel()
+    if not (len(coord) == len(tsdf) == len(weight)):
+        raise ValueError("a map is coord [nv, 3], tsdf [nv] and weight [nv]")
+    return coord, tsdf, weight
+
+
 class RansacParams(C.Structure):
     _fields_ = [("hypotheses", C.c_int), ("seed", C.c_ulonglong), ("max_distance", C.c_float), ("edge_similarity", C.c_float),
                 ("refine_iterations", C.c_int), ("reserved", C.c_int * 8)]
@@ -731,6 +766,7 @@ class Context:
         "ndt": ("workspace", "upload", "check", "table", "order", "iterations", "download", "total"),
         "fpfh_features": ("workspace", "upload", "check", "grid", "order", "kernels", "download", "total"),
         "scan_context": ("workspace", "upload", "check", "unused3", "unused4", "kernels", "download", "total"),
+        "tsdf": ("workspace", "upload", "check", "sampling", "sort", "fusion", "download", "total"),
         "feature_match": ("workspace", "upload", "check", "unused3", "unused4", "kernels", "download", "total"),
         "ransac_register": ("workspace", "upload", "hypotheses", "count", "argmax", "refine", "unused6", "total"),
         "fgr_register": ("workspace", "upload", "check", "tuples", "gather", "iterations", "download", "total"),
@@ -1349,6 +1385,61 @@ class Context:
         """ms per stage of the last scan_context or scan_context_search: workspace, upload, check, -, -, kernels, download, total
         (mi_scan_context_times)."""
         return self._times("scan_context")
+
+    # ---- the map
+    def tsdf_integrate(self, scans, poses, origin, params, map=None):
+        """Posed scans fused into a sparse TSDF map (mi_tsdf_integrate): (coord [nv, 3] int32, tsdf [nv] float32, weight [nv] float32), the
+        rows ascending by (cz, cy, cx).  scans: a list of [n_s, 3] clouds in their sensors' frames; poses: [K, 4, 4] sensor to world (the
+        mathematical matrices, as icp_plane_register returns R and t), or None: identities; origin [3] and params (tsdf_params(voxel_size=..,
+        truncation=..)) fix the lattice and the band; map: such a triple to fuse onto, or None.  Two calls inside: one for the number of
+        voxels, one to fill arrays of exactly that size."""
+        clouds = [_cloud(s) for s in scans]
+        offsets = np.concatenate([[0], np.cumsum([len(s) for s in clouds])]).astype(np.int64)
+        xyz = np.ascontiguousarray(np.concatenate(clouds) if clouds else np.zeros((0, 3), np.float32), np.float32)
+        if xyz.shape[0] == 0:
+            xyz = np.zeros((1, 3), np.float32)               # a pointer to pass; no offset reaches it
+        T = None
+        if poses is not None:
+            poses = np.asarray(poses, np.float64)
+            if poses.shape != (len(clouds), 4, 4):
+                raise ValueError("poses is [K, 4, 4]")
+            T = np.ascontiguousarray(poses.transpose(0, 2, 1), np.float32)      # column-major, as the C interface takes them
+        origin = np.ascontiguousarray(origin, np.float32).reshape(3)
+        coord, tsdf, weight = _tsdf_map(map)
+        nv_in, nv = len(coord), C.c_longlong(0)
+        args = (self._h, xyz.ctypes.data, offsets.ctypes.data, len(clouds), _ptr(T), origin.ctypes.data, C.addressof(params),
+                coord.ctypes.data if nv_in else None, tsdf.ctypes.data if nv_in else None, weight.ctypes.data if nv_in else None, nv_in)
+        _check(tsdf_integrate_raw(*args, None, None, None, 0, C.addressof(nv)))
+        n = nv.value
+        out_coord, out_tsdf, out_weight = np.empty((n, 3), np.int32), np.empty(n, np.float32), np.empty(n, np.float32)
+        if n:
+            _check(tsdf_integrate_raw(*args, out_coord.ctypes.data, out_tsdf.ctypes.data, out_weight.ctypes.data, n, C.addressof(nv)))
+            if nv.value != n:
+                raise MiSlamError("mi_tsdf_integrate: %d voxels counted, then %d" % (n, nv.value))
+        return out_coord, out_tsdf, out_weight
+
+    def tsdf_extract(self, map, origin, voxel_size, min_weight=1, want_normals=True):
+        """The surface of a TSDF map as points with normals (mi_tsdf_extract): (xyz [n, 3] float32, normals [n, 3] float32 or None), by row,
+        then axis; the normals point to the observed side, a zero one where the field has no gradient.  Two calls inside, as above."""
+        coord, tsdf, weight = _tsdf_map(map)
+        origin = np.ascontiguousarray(origin, np.float32).reshape(3)
+        nv, found = len(coord), C.c_longlong(0)
+        args = (self._h, coord.ctypes.data if nv else None, tsdf.ctypes.data if nv else None, weight.ctypes.data if nv else None, nv,
+                origin.ctypes.data, float(voxel_size), float(min_weight))
+        _check(tsdf_extract_raw(*args, None, None, 0, C.addressof(found)))
+        n = found.value
+        xyz = np.empty((n, 3), np.float32)
+        normals = np.empty((n, 3), np.float32) if want_normals else None
+        if n:
+            _check(tsdf_extract_raw(*args, xyz.ctypes.data, _ptr(normals), n, C.addressof(found)))
+            if found.value != n:
+                raise MiSlamError("mi_tsdf_extract: %d points counted, then %d" % (n, found.value))
+        return xyz, normals
+
+    def tsdf_times(self):
+        """ms per stage of the last tsdf_integrate or tsdf_extract: workspace, upload, check, sampling (extraction: table), sort (count +
+        scan), fusion (fill), download, total (mi_tsdf_times)."""
+        return self._times("tsdf")
 
     # ---- generalized ICP
     def estimate_covariances(self, cloud, k, mode=COV_PLANE, epsilon=1e-3, dist_mode=DIST_CPU_ROUNDING, max_d2=np.inf, want_count=False):

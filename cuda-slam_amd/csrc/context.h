@@ -362,6 +362,27 @@ struct mi_ctx {
         double ms[MI_SCAN_CONTEXT_STAGES] = {0};         // mi_scan_context_times
     } scan_context;
 
+    // ---- mi_tsdf_integrate: the scans, offsets and poses as uploaded, the input map, the rays' counts and K51's scan of them, the entries'
+    // keys, values and the sort's ping and pong, the voxel filter's head-flag scan, and the fused rows; mi_tsdf_extract: the map as uploaded,
+    // the table of its observed voxels, the rows' counts and their scan, the points and normals
+    struct TsdfBuffers {
+        mislam::DevBuf<float> xyz, poses, in_tsdf, in_weight;
+        mislam::DevBuf<long long> offsets, tile_sums, sample_off;
+        mislam::DevBuf<int> in_coord, count;
+        mislam::DevBuf<mislam::TsdfState> state;
+        mislam::DevBuf<unsigned int> keys_a, keys_b, axis_keys;
+        mislam::DevBuf<int> vals_a, vals_b, block_heads, row_of, run_start;
+        mislam::DevBuf<unsigned char> sort_temp;
+        mislam::DevBuf<mislam::VoxState> vstate;         // (rows: the voxels of the output)
+        mislam::DevBuf<double> value;
+        mislam::DevBuf<int> out_coord;
+        mislam::DevBuf<float> out_tsdf, out_weight;
+        mislam::DevBuf<unsigned long long> hkeys;
+        mislam::DevBuf<int> hvals;
+        mislam::DevBuf<float> out_xyz, out_normals;
+        double ms[MI_TSDF_STAGES] = {0};                 // mi_tsdf_times
+    } tsdf;
+
     // ---- mi_estimate_covariances: mi_estimate_normals' sibling with six floats per point as its result, in buffers of its own
     struct CovarianceBuffers {
         mislam::SearchFrontBuffers front;
@@ -575,7 +596,7 @@ struct StageClock {
     }
     void finish() { ms[7] = wall_ms() - t_begin; }
 };
-static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8 && MI_MLS_STAGES == 8 && MI_RADIUS_STAGES == 8 && MI_EVAL_STAGES == 8 && MI_POSE_GRAPH_STAGES == 8 && MI_SCAN_CONTEXT_STAGES == 8, "StageClock: eight slots, the last one the whole call");
+static_assert(MI_LOAD_STAGES == 8 && MI_VOXEL_STAGES == 8 && MI_KNN_STAGES == 8 && MI_NORMALS_STAGES == 8 && MI_OUTLIER_STAGES == 8 && MI_PLANE_STAGES == 8 && MI_GICP_STAGES == 8 && MI_FPFH_STAGES == 8 && MI_MATCH_STAGES == 8 && MI_RANSAC_STAGES == 8 && MI_NDT_STAGES == 8 && MI_ISS_STAGES == 8 && MI_CLUSTER_STAGES == 8 && MI_SEGMENT_STAGES == 8 && MI_FGR_STAGES == 8 && MI_COLOR_STAGES == 8 && MI_MLS_STAGES == 8 && MI_RADIUS_STAGES == 8 && MI_EVAL_STAGES == 8 && MI_POSE_GRAPH_STAGES == 8 && MI_SCAN_CONTEXT_STAGES == 8 && MI_TSDF_STAGES == 8, "StageClock: eight slots, the last one the whole call");
 // The body of every *_times entry point: the eight slots a StageClock left in the context.  ms: null for a null context.
 static inline int stage_times(const char* who, const double* ms, double* out_ms)
 {

@@ -953,6 +953,80 @@ hipError_t sc_search(const ScSearchArgs& a, hipStream_t s);
 // idx / dist / shift from keys (all ones: -1, +inf, 0); second (may be null) from keys2 alone
 hipError_t sc_finish(const unsigned long long* keys, const unsigned long long* keys2, int nq, int* idx, float* dist, int* shift, float* second, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K68-K72 TSDF map: posed scans fused into a sparse truncated signed distance field, and its surface read back as points with normals
+// (tsdf_kernels.hip; driver: tsdf_api.hip; the arithmetic: tsdf_ray.hpp; the contract: mi_tsdf_integrate and mi_tsdf_extract in mi_slam.h).
+//   K68 tsdf_samples:  one lane per ray, twice: the count of its surviving samples (with the input check and the occupied range, folded over
+//                      the wave and merged by integer atomics), and behind K51's scan of the counts the fill: per sample the three axis keys
+//                      and the fp64 value, at the position (ray, k) gives it.  No LDS, no scratch.
+//   K69 tsdf_map_keys: one lane per row of the input map: its axis keys, in front of every sample.
+//       The voxel filter's stable radix sort (one per axis) and head-flag scan (vox_rows) order the entries and find the voxels' runs: a
+//       voxel's input row, then its samples in ascending (scan, point, k).
+//   K70 tsdf_fuse:     one lane per voxel: the fp64 sum of its run in that order, the count, the fused row.
+//   K71 tsdf_table:    one lane per row of a map: the observed voxels into an open-addressing table of packed coordinates (the layout of
+//                      the NDT map's table, NdtMapView).
+//   K72 tsdf_crossings: one lane per row, twice: the count of its crossings, and behind K51's scan the fill of points and normals.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int TSDF_BLOCK = 256;              // rays, rows or voxels per workgroup of K68-K72: one per lane
+constexpr int TSDF_NO_INDEX = 0x7fffffff;    // TsdfState's bad_* while nothing has been refused
+// Device-resident facts of one mi_tsdf_integrate; the host sets the starts and reads it back once, behind the count pass.
+struct TsdfState {
+    int bad_point;                   // the lowest point with a coordinate that is not finite or above 1e18 in magnitude
+    int bad_range;                   // the lowest point with a sample whose voxel coordinate is outside [-2^30, 2^30)
+    int cmin[3], cmax[3];            // the occupied range of the surviving samples (INT_MAX / INT_MIN: none)
+};
+struct TsdfSampleArgs {
+    const float* xyz;                // all points, AoS
+    const long long* offsets;        // n_scans + 1
+    const float* poses;              // 16 per scan, column-major, or null: identities
+    int n_scans, rays;
+    float origin[3], voxel, truncation, min_range, max_range;
+    int half_steps;                  // S
+    TsdfState* state;
+    int* count;                      // rays: the count pass writes, the fill reads nothing of it
+    // the fill alone:
+    const long long* sample_off;     // rays + 1: K51's scan of count
+    int base;                        // entries in front of the samples (the input map's rows)
+    size_t entries;                  // base + all samples: the stride of axis_keys
+    int cmin[3];                     // what the axis keys are taken from
+    unsigned int *keys, *axis_keys;  // entries; 3 x entries
+    int* vals;                       // entries: the identity
+    double* value;                   // all samples: f
+};
+hipError_t tsdf_samples(const TsdfSampleArgs& a, bool fill, hipStream_t s);
+hipError_t tsdf_map_keys(const int* coord, int nv, const int cmin[3], size_t entries, unsigned int* keys, unsigned int* axis_keys, int* vals, hipStream_t s);
+struct TsdfFuseArgs {
+    const int* sorted_idx;           // entries: the entry at every sorted position
+    const int* run_start;            // rows + 1
+    int rows, base;
+    size_t entries;
+    const unsigned int* axis_keys;
+    int cmin[3];
+    const double* value;
+    const float *in_tsdf, *in_weight;   // base
+    float max_weight;
+    int* out_coord;                  // rows x 3
+    float *out_tsdf, *out_weight;    // rows
+};
+hipError_t tsdf_fuse(const TsdfFuseArgs& a, hipStream_t s);
+struct TsdfTableView {
+    const unsigned long long* keys;  // capacity slots: the packed coordinate stored there, or all ones
+    const int* vals;                 // its row
+    unsigned long long mask;         // capacity - 1, capacity a power of two >= 2 nv
+    int cmin[3], ext[3];             // the key of (cx, cy, cz) is (cx - cmin_x) | (cy - cmin_y) << 20 | (cz - cmin_z) << 40, each in [0, ext) <= 2^20
+};
+// the rows with weight >= min_weight into the table (keys all ones before the launch)
+hipError_t tsdf_table(const int* coord, const float* weight, int nv, float min_weight, const TsdfTableView& t, unsigned long long* keys, int* vals, hipStream_t s);
+struct TsdfCrossArgs {
+    const int* coord; const float* tsdf; const float* weight; int nv;
+    float origin[3], voxel, min_weight;
+    TsdfTableView table;
+    int* count;                      // nv: the count pass writes
+    const long long* offsets;        // nv + 1 (the fill)
+    float *out_xyz, *out_normals;    // 3 per crossing; out_normals may be null
+};
+hipError_t tsdf_crossings(const TsdfCrossArgs& a, bool fill, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();
@@ -984,5 +1058,6 @@ hipError_t preload_radius_kernels();
 hipError_t preload_eval_kernels();
 hipError_t preload_pose_graph_kernels();
 hipError_t preload_scan_context_kernels();
+hipError_t preload_tsdf_kernels();
 
 }  // namespace mislam

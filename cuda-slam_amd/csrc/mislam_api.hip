@@ -179,7 +179,7 @@ extern "C" int mi_ctx_preload(mi_ctx* c)
     if (!c) { set_error("mi_ctx_preload: null context"); return MI_ERR_INVALID_ARG; }
     MI_ENTER(c);
     MI_HIP(preload_nn_kernel()); MI_HIP(preload_nn_tree()); MI_HIP(preload_nn_grid()); MI_HIP(preload_icp_kernels()); MI_HIP(preload_icp_batch()); MI_HIP(preload_cpd_kernels()); MI_HIP(preload_cpd_batch());
-    MI_HIP(preload_cpd_fgt()); MI_HIP(preload_nicp_api()); MI_HIP(preload_prepare_api()); MI_HIP(preload_voxel_kernels()); MI_HIP(preload_knn_kernels()); MI_HIP(preload_normals_kernels()); MI_HIP(preload_outlier_kernels()); MI_HIP(preload_plane_kernels()); MI_HIP(preload_gicp_kernels()); MI_HIP(preload_fpfh_kernels()); MI_HIP(preload_match_kernels()); MI_HIP(preload_ransac_kernels()); MI_HIP(preload_ndt_kernels()); MI_HIP(preload_iss_kernels()); MI_HIP(preload_cluster_kernels()); MI_HIP(preload_segment_kernels()); MI_HIP(preload_fgr_kernels()); MI_HIP(preload_color_kernels()); MI_HIP(preload_mls_kernels()); MI_HIP(preload_radius_kernels()); MI_HIP(preload_eval_kernels()); MI_HIP(preload_pose_graph_kernels()); MI_HIP(preload_scan_context_kernels());
+    MI_HIP(preload_cpd_fgt()); MI_HIP(preload_nicp_api()); MI_HIP(preload_prepare_api()); MI_HIP(preload_voxel_kernels()); MI_HIP(preload_knn_kernels()); MI_HIP(preload_normals_kernels()); MI_HIP(preload_outlier_kernels()); MI_HIP(preload_plane_kernels()); MI_HIP(preload_gicp_kernels()); MI_HIP(preload_fpfh_kernels()); MI_HIP(preload_match_kernels()); MI_HIP(preload_ransac_kernels()); MI_HIP(preload_ndt_kernels()); MI_HIP(preload_iss_kernels()); MI_HIP(preload_cluster_kernels()); MI_HIP(preload_segment_kernels()); MI_HIP(preload_fgr_kernels()); MI_HIP(preload_color_kernels()); MI_HIP(preload_mls_kernels()); MI_HIP(preload_radius_kernels()); MI_HIP(preload_eval_kernels()); MI_HIP(preload_pose_graph_kernels()); MI_HIP(preload_scan_context_kernels()); MI_HIP(preload_tsdf_kernels());
     return MI_OK;
 }
 

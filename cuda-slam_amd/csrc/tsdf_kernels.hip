@@ -1,0 +1,273 @@
+// K68-K72: the kernels of mi_tsdf_integrate and mi_tsdf_extract (kernels.h has the plan; tsdf_ray.hpp the arithmetic, which host and device
+// share word for word).  Every kernel is one lane per ray, row or voxel, in workgroups of TSDF_BLOCK; none uses LDS or scratch, none has a
+// floating-point atomic: the only atomics are integer minima and maxima (the same answer in any order) and the table's compare-and-swap on
+// keys that are all different.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+
+#include "kernels.h"
+#include "tsdf_ray.hpp"
+
+namespace mislam {
+
+// the scan of ray i: the last s with offsets[s] <= i (empty scans repeat an offset: the last one of them holds the ray)
+__device__ __forceinline__ int tsdf_scan_of(const long long* __restrict__ offsets, int n_scans, long long i)
+{
+    int lo = 0, hi = n_scans;                // offsets[lo] <= i < offsets[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ int wave_min_int(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_max_int(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// ---- K68
+template <bool FILL>
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_samples_kernel(TsdfSampleArgs a)
+{
+    const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
+    const bool live = i < a.rays;
+    int bad_point = TSDF_NO_INDEX, bad_range = TSDF_NO_INDEX;
+    int lo0 = INT_MAX, lo1 = INT_MAX, lo2 = INT_MAX, hi0 = INT_MIN, hi1 = INT_MIN, hi2 = INT_MIN;
+    int n = 0;
+    if (live) {
+        const float px = a.xyz[3 * (size_t)i], py = a.xyz[3 * (size_t)i + 1], pz = a.xyz[3 * (size_t)i + 2];
+        if (!(fabsf(px) <= TSDF_MAX_ABS && fabsf(py) <= TSDF_MAX_ABS && fabsf(pz) <= TSDF_MAX_ABS)) bad_point = i;
+        else {
+            const int scan = tsdf_scan_of(a.offsets, a.n_scans, (long long)i);
+            float w[3], o[3];
+            tsdf_move(a.poses ? a.poses + 16 * (size_t)scan : nullptr, px, py, pz, w, o);
+            TsdfRay r;
+            if (tsdf_ray(w, o, a.min_range, a.max_range, &r)) {
+                const float origin[3] = {a.origin[0], a.origin[1], a.origin[2]};
+                size_t at = 0, room = 0;             // (the fill is the count's own code on the same operands; it still never writes past its share)
+                if (FILL) { at = (size_t)a.base + (size_t)a.sample_off[i]; room = (size_t)(a.sample_off[i + 1] - a.sample_off[i]); }
+                const bool ok = tsdf_walk(r, a.half_steps, a.voxel, origin, a.truncation, [&](int, const int c[3], double f) {
+                    if (FILL && (size_t)n < room) {
+                        const unsigned int kx = (unsigned int)(c[0] - a.cmin[0]), ky = (unsigned int)(c[1] - a.cmin[1]), kz = (unsigned int)(c[2] - a.cmin[2]);
+                        const size_t e = at + (size_t)n;
+                        a.keys[e] = kx;
+                        a.axis_keys[e] = kx; a.axis_keys[a.entries + e] = ky; a.axis_keys[2 * a.entries + e] = kz;
+                        a.vals[e] = (int)e;
+                        a.value[e - (size_t)a.base] = f;
+                    } else {
+                        lo0 = min(lo0, c[0]); lo1 = min(lo1, c[1]); lo2 = min(lo2, c[2]);
+                        hi0 = max(hi0, c[0]); hi1 = max(hi1, c[1]); hi2 = max(hi2, c[2]);
+                    }
+                    n++;
+                });
+                if (!ok) bad_range = i;
+            }
+        }
+        if (!FILL) a.count[i] = n;
+    }
+    if (FILL) return;
+    // the facts of the wave, then one set of integer atomics per wave (a refused call's ranges are not read)
+    bad_point = wave_min_int(bad_point); bad_range = wave_min_int(bad_range);
+    lo0 = wave_min_int(lo0); lo1 = wave_min_int(lo1); lo2 = wave_min_int(lo2);
+    hi0 = wave_max_int(hi0); hi1 = wave_max_int(hi1); hi2 = wave_max_int(hi2);
+    if ((threadIdx.x & 63) == 0) {
+        if (bad_point != TSDF_NO_INDEX) atomicMin(&a.state->bad_point, bad_point);
+        if (bad_range != TSDF_NO_INDEX) atomicMin(&a.state->bad_range, bad_range);
+        if (lo0 <= hi0) {
+            atomicMin(&a.state->cmin[0], lo0); atomicMin(&a.state->cmin[1], lo1); atomicMin(&a.state->cmin[2], lo2);
+            atomicMax(&a.state->cmax[0], hi0); atomicMax(&a.state->cmax[1], hi1); atomicMax(&a.state->cmax[2], hi2);
+        }
+    }
+}
+
+hipError_t tsdf_samples(const TsdfSampleArgs& a, bool fill, hipStream_t s)
+{
+    if (a.rays < 1 || !a.xyz || !a.offsets || !a.state || !a.count || a.half_steps < 0 || a.half_steps > TSDF_MAX_HALF_STEPS) return hipErrorInvalidValue;
+    if (fill && (!a.sample_off || !a.keys || !a.axis_keys || !a.vals || !a.value)) return hipErrorInvalidValue;
+    const dim3 grid((a.rays - 1) / TSDF_BLOCK + 1), block(TSDF_BLOCK);
+    if (fill) hipLaunchKernelGGL(tsdf_samples_kernel<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(tsdf_samples_kernel<false>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- K69
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_map_keys_kernel(const int* __restrict__ coord, int nv, int c0, int c1, int c2, size_t entries,
+                                                                   unsigned int* __restrict__ keys, unsigned int* __restrict__ axis_keys, int* __restrict__ vals)
+{
+    const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
+    if (i >= nv) return;
+    const unsigned int kx = (unsigned int)(coord[3 * (size_t)i] - c0), ky = (unsigned int)(coord[3 * (size_t)i + 1] - c1), kz = (unsigned int)(coord[3 * (size_t)i + 2] - c2);
+    keys[i] = kx;
+    axis_keys[i] = kx; axis_keys[entries + i] = ky; axis_keys[2 * entries + i] = kz;
+    vals[i] = i;
+}
+
+hipError_t tsdf_map_keys(const int* coord, int nv, const int cmin[3], size_t entries, unsigned int* keys, unsigned int* axis_keys, int* vals, hipStream_t s)
+{
+    if (nv < 1 || (size_t)nv > entries || !coord || !keys || !axis_keys || !vals) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tsdf_map_keys_kernel, dim3((nv - 1) / TSDF_BLOCK + 1), dim3(TSDF_BLOCK), 0, s, coord, nv, cmin[0], cmin[1], cmin[2], entries, keys, axis_keys, vals);
+    return hipGetLastError();
+}
+
+// ---- K70.  The sort is stable and the entries were numbered (input row, then the samples by ray and k), so a voxel's run is its input row,
+// if it has one, and then its samples in ascending (scan, point, k): the lane sums them as they come.
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_fuse_kernel(TsdfFuseArgs a)
+{
+    const int row = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
+    if (row >= a.rows) return;
+    int j = a.run_start[row];
+    const int end = a.run_start[row + 1];
+    const int e0 = a.sorted_idx[j];
+    a.out_coord[3 * (size_t)row] = (int)a.axis_keys[e0] + a.cmin[0];
+    a.out_coord[3 * (size_t)row + 1] = (int)a.axis_keys[a.entries + e0] + a.cmin[1];
+    a.out_coord[3 * (size_t)row + 2] = (int)a.axis_keys[2 * a.entries + e0] + a.cmin[2];
+    const bool stored = e0 < a.base;
+    if (stored) j++;
+    if (stored && j == end) {                // no sample touched it: its bits
+        a.out_tsdf[row] = a.in_tsdf[e0];
+        a.out_weight[row] = a.in_weight[e0];
+        return;
+    }
+    const double D = stored ? (double)a.in_tsdf[e0] : 0.0, W = stored ? (double)a.in_weight[e0] : 0.0;
+    const double C = (double)(end - j);
+    double F = 0.0;
+    for (; j < end; j++) F += a.value[a.sorted_idx[j] - a.base];
+    const double total = W + C, cap = (double)a.max_weight;
+    a.out_tsdf[row] = (float)((W * D + F) / total);
+    a.out_weight[row] = (float)(total < cap ? total : cap);
+}
+
+hipError_t tsdf_fuse(const TsdfFuseArgs& a, hipStream_t s)
+{
+    if (a.rows < 1 || !a.sorted_idx || !a.run_start || !a.axis_keys || !a.value || !a.out_coord || !a.out_tsdf || !a.out_weight) return hipErrorInvalidValue;
+    if (a.base > 0 && (!a.in_tsdf || !a.in_weight)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tsdf_fuse_kernel, dim3((a.rows - 1) / TSDF_BLOCK + 1), dim3(TSDF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- K71, K72.  (the driver has checked the range: every coordinate minus its axis minimum is in [0, ext) with ext <= 2^20)
+constexpr unsigned long long TSDF_KEY_EMPTY = 0xffffffffffffffffull;
+__device__ __forceinline__ unsigned long long tsdf_hash(unsigned long long key)      // splitmix64's finaliser, as the NDT map's table
+{
+    key ^= key >> 30; key *= 0xbf58476d1ce4e5b9ull;
+    key ^= key >> 27; key *= 0x94d049bb133111ebull;
+    return key ^ (key >> 31);
+}
+
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_table_kernel(const int* __restrict__ coord, const float* __restrict__ weight, int nv, float min_weight,
+                                                                TsdfTableView t, unsigned long long* __restrict__ keys, int* __restrict__ vals)
+{
+    const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
+    if (i >= nv || !(weight[i] >= min_weight)) return;
+    const unsigned long long key = (unsigned long long)(coord[3 * (size_t)i] - t.cmin[0]) | (unsigned long long)(coord[3 * (size_t)i + 1] - t.cmin[1]) << 20 |
+                                   (unsigned long long)(coord[3 * (size_t)i + 2] - t.cmin[2]) << 40;
+    unsigned long long slot = tsdf_hash(key) & t.mask;
+    for (unsigned long long probe = 0; probe <= t.mask; probe++) {               // (at most nv of the >= 2 nv slots are ever taken)
+        const unsigned long long old = atomicCAS(&keys[slot], TSDF_KEY_EMPTY, key);
+        if (old == TSDF_KEY_EMPTY || old == key) { vals[slot] = i; return; }
+        slot = (slot + 1) & t.mask;
+    }
+}
+
+// the row of the observed voxel (cx, cy, cz), or -1
+__device__ __forceinline__ int tsdf_lookup(const TsdfTableView& t, int cx, int cy, int cz)
+{
+    const long long rx = (long long)cx - t.cmin[0], ry = (long long)cy - t.cmin[1], rz = (long long)cz - t.cmin[2];
+    if (rx < 0 || rx >= t.ext[0] || ry < 0 || ry >= t.ext[1] || rz < 0 || rz >= t.ext[2]) return -1;      // outside the listed box: no key is formed
+    const unsigned long long key = (unsigned long long)rx | (unsigned long long)ry << 20 | (unsigned long long)rz << 40;
+    unsigned long long slot = tsdf_hash(key) & t.mask;
+    for (unsigned long long probe = 0; probe <= t.mask; probe++) {
+        const unsigned long long k = t.keys[slot];
+        if (k == key) return t.vals[slot];
+        if (k == TSDF_KEY_EMPTY) return -1;
+        slot = (slot + 1) & t.mask;
+    }
+    return -1;
+}
+
+hipError_t tsdf_table(const int* coord, const float* weight, int nv, float min_weight, const TsdfTableView& t, unsigned long long* keys, int* vals, hipStream_t s)
+{
+    if (nv < 1 || t.mask + 1 < 2 * (unsigned long long)nv || (t.mask & (t.mask + 1)) != 0 || !coord || !weight || !keys || !vals) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tsdf_table_kernel, dim3((nv - 1) / TSDF_BLOCK + 1), dim3(TSDF_BLOCK), 0, s, coord, weight, nv, min_weight, t, keys, vals);
+    return hipGetLastError();
+}
+
+// the gradient at the observed voxel (cx, cy, cz) of value f
+__device__ __forceinline__ void tsdf_gradient_at(const TsdfCrossArgs& a, int cx, int cy, int cz, double f, double g[3])
+{
+#pragma unroll
+    for (int ax = 0; ax < 3; ax++) {
+        const int dx = ax == 0, dy = ax == 1, dz = ax == 2;
+        const int m = tsdf_lookup(a.table, cx - dx, cy - dy, cz - dz), p = tsdf_lookup(a.table, cx + dx, cy + dy, cz + dz);
+        g[ax] = tsdf_gradient(m >= 0, m >= 0 ? (double)a.tsdf[m] : 0.0, f, p >= 0, p >= 0 ? (double)a.tsdf[p] : 0.0);
+    }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_crossings_kernel(TsdfCrossArgs a)
+{
+    const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
+    if (i >= a.nv) return;
+    int n = 0;
+    if (a.weight[i] >= a.min_weight) {
+        const int cx = a.coord[3 * (size_t)i], cy = a.coord[3 * (size_t)i + 1], cz = a.coord[3 * (size_t)i + 2];
+        const double f0 = (double)a.tsdf[i];
+        bool have_gi = false;
+        double gi[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int ax = 0; ax < 3; ax++) {
+            const int dx = ax == 0, dy = ax == 1, dz = ax == 2;
+            const int j = tsdf_lookup(a.table, cx + dx, cy + dy, cz + dz);
+            if (j < 0) continue;
+            const double f1 = (double)a.tsdf[j];
+            double r;
+            if (!tsdf_crossing(f0, f1, &r)) continue;
+            if (FILL && (long long)n < a.offsets[i + 1] - a.offsets[i]) {       // (the count's own code again; never past the row's share)
+                const size_t at = 3 *((size_t)a.offsets[i] + (size_t)n);
+                a.out_xyz[at] = ax == 0 ? tsdf_crossing_coord(cx, a.origin[0], a.voxel, r) : (float)tsdf_centre(cx, a.origin[0], a.voxel);
+                a.out_xyz[at + 1] = ax == 1 ? tsdf_crossing_coord(cy, a.origin[1], a.voxel, r) : (float)tsdf_centre(cy, a.origin[1], a.voxel);
+                a.out_xyz[at + 2] = ax == 2 ? tsdf_crossing_coord(cz, a.origin[2], a.voxel, r) : (float)tsdf_centre(cz, a.origin[2], a.voxel);
+                if (a.out_normals) {
+                    if (!have_gi) { tsdf_gradient_at(a, cx, cy, cz, f0, gi); have_gi = true; }
+                    double gj[3];
+                    tsdf_gradient_at(a, cx + dx, cy + dy, cz + dz, f1, gj);
+                    float nrm[3];
+                    tsdf_normal(gi, gj, r, nrm);
+                    a.out_normals[at] = nrm[0]; a.out_normals[at + 1] = nrm[1]; a.out_normals[at + 2] = nrm[2];
+                }
+            }
+            n++;
+        }
+    }
+    if (!FILL) a.count[i] = n;
+}
+
+hipError_t tsdf_crossings(const TsdfCrossArgs& a, bool fill, hipStream_t s)
+{
+    if (a.nv < 1 || !a.coord || !a.tsdf || !a.weight || !a.table.keys || !a.table.vals || !a.count) return hipErrorInvalidValue;
+    if (fill && (!a.offsets || !a.out_xyz)) return hipErrorInvalidValue;
+    const dim3 grid((a.nv - 1) / TSDF_BLOCK + 1), block(TSDF_BLOCK);
+    if (fill) hipLaunchKernelGGL(tsdf_crossings_kernel<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(tsdf_crossings_kernel<false>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+// Loads this translation unit's code object (mi_ctx_preload).
+__global__ void preload_tsdf_kernels_kernel() {}
+hipError_t preload_tsdf_kernels()
+{
+    hipFuncAttributes attr;
+    return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(preload_tsdf_kernels_kernel));
+}
+
+}  // namespace mislam

@@ -2057,6 +2057,88 @@ int mi_scan_context_search(mi_ctx* ctx,
 int mi_scan_context_times(mi_ctx* ctx, double out_ms[MI_SCAN_CONTEXT_STAGES]);
 
 /* ----------------------------------------------------------------------------------------------------------------
+ * The map: posed scans fused into a sparse truncated signed distance field (TSDF; Curless and Levoy), and its surface read back as points
+ * with normals -- the tile and tile_normals of the next mi_icp_plane_register.  Single-GPU contexts, synchronous, host in and host out, in
+ * buffers of their own: a problem loaded by mi_icp_load and everything the searches and registrations keep survive both calls.  A map is
+ * three arrays of nv rows: coord (cx, cy, cz per row, the voxel of mi_voxel_index with the caller's origin and voxel_size), tsdf in [-1, 1]
+ * (the signed distance to the surface in truncations, positive on the sensor's side) and weight > 0 (the samples fused so far), the rows
+ * strictly ascending by (cz, cy, cx) as signed integers: the order mi_tsdf_integrate writes, and mi_voxel_downsample's.
+ *
+ * mi_tsdf_integrate -- every rule, so that it can be retraced in numpy (tests/tsdf_reference.py does):
+ *   Ray.  Point p of scan s (scan s holds the points scan_offsets[s] .. scan_offsets[s + 1] - 1) moves by the scan's pose T_s (16 floats,
+ *     column-major, sensor to world, as mi_icp_plane_register's out_T; scan_T NULL: identities, through the same arithmetic) in fp32, in
+ *     the order of mi_icp_plane_register's move: w = ((R0 p_x + R1 p_y) + R2 p_z) + t per row of R, every operation rounded.  The sensor
+ *     position o is the translation column.  Everything behind this is fp64 on promoted operands, every operation rounded once, none
+ *     fused: e = w - o; rho = sqrt((e_x^2 + e_y^2) + e_z^2); d = e / rho.  A ray with rho == 0, rho not finite, rho < min_range or
+ *     rho > max_range contributes nothing.
+ *   Samples.  h = voxel_size / 2; S = floor(truncation / h), refused above MI_TSDF_MAX_HALF_STEPS.  For k = -S .. S ascending the depth is
+ *     s_k = rho + k h (one product, one sum); a sample with s_k <= 0 does not exist.  Its position is x_k = o + s_k d, one product and one
+ *     sum per coordinate, rounded once to fp32; its voxel is mi_voxel_index(x_k, origin3, voxel_size).  A sample whose voxel is that of
+ *     sample k - 1 of the same ray (where that one exists) is dropped: a line meets a convex voxel in one interval, so every voxel is
+ *     sampled at most once per ray.  This is fixed-step sampling, not an exact traversal: a voxel the ray only clips at a corner, between
+ *     two samples, can be missed.
+ *   Value.  The voxel's centre is c = origin + (index + 0.5) voxel_size per axis; sdf = (d_x (w_x - c_x) + d_y (w_y - c_y)) + d_z (w_z - c_z).
+ *     A sample with sdf < -truncation is dropped; otherwise its value is f = min(1, sdf / truncation) and its weight 1.
+ *   Fusion, per voxel and per call.  F = the fp64 sum of the voxel's f in ascending (scan, point within the scan, k), C = their number.  With
+ *     the voxel's stored (D, W) of the input map, or (0, 0): D' = (W D + F) / (W + C) and W' = min(W + C, max_weight), each rounded once to
+ *     fp32.  An input voxel that no sample touches passes through with its bits.  No floating-point atomic occurs anywhere: the same input
+ *     gives the same bits on every call, whatever ran on the context before.  The cap binds per call, so K scans in one call and K calls
+ *     of one scan differ once it binds -- and by the fp32 rounding of (D, W) between calls.
+ *   Output.  The union of the input voxels and the touched ones, ascending by (cz, cy, cx).  The capacity protocol is mi_radius_search's, in
+ *     the manner of snprintf: *out_nv is always written; the three arrays are written if and only if 0 < *out_nv <= capacity; a short
+ *     capacity still returns MI_OK; capacity == 0 (the arrays may be NULL) is a counts-only call.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with "mi_tsdf_integrate" and names the cause and, for a bad element, the array and the
+ *     lowest index; NOTHING has been written, *out_nv included -- for: a NULL required argument; K < 1; scan_offsets not starting at 0,
+ *     descending, or ending at 0; a coordinate that is not finite or above 1e18 in magnitude; a non-finite pose entry or origin; params
+ *     outside what the struct states; S above MI_TSDF_MAX_HALF_STEPS; a voxel coordinate (of a sample or of the input map) outside
+ *     [-2^30, 2^30); an occupied extent (input map and samples together) above 2^20 voxels along an axis; an input map that is not strictly
+ *     ascending, or holds a weight that is not finite and positive or a value that is not finite and in [-1, 1]; nv_in < 0 or capacity < 0;
+ *     capacity > 0 with a NULL output array; rays (2 S + 1) + nv_in >= 2^31.  nv_in == 0 with NULL in_* arrays is the empty map.
+ *   MI_ERR_STATE on a distributed context.  A device allocation that fails is MI_ERR_HIP; the context stays usable.
+ * -------------------------------------------------------------------------------------------------------------- */
+#define MI_TSDF_MAX_HALF_STEPS 16
+typedef struct mi_tsdf_params {
+    float voxel_size;     /* > 0, finite */
+    float truncation;     /* tau; >= voxel_size / 2, finite */
+    float min_range;      /* >= 0; default 0 */
+    float max_range;      /* > min_range; default INFINITY */
+    float max_weight;     /* > 0; default INFINITY (no cap) */
+    int   reserved[11];
+} mi_tsdf_params;
+void mi_tsdf_params_default(mi_tsdf_params* p);   /* voxel_size and truncation 0: the caller must set them */
+int mi_tsdf_integrate(mi_ctx* ctx,
+                      const float* scans_xyz, const long long* scan_offsets /* K + 1 */, int K,
+                      const float* scan_T /* K x 16, sensor to world; NULL: identities */,
+                      const float origin3[3], const mi_tsdf_params* params,
+                      const int* in_coord, const float* in_tsdf, const float* in_weight, int nv_in /* may be 0 */,
+                      int* out_coord, float* out_tsdf, float* out_weight, long long capacity, long long* out_nv);
+/* mi_tsdf_extract -- the surface of a map as points with normals.  The map is held to the checks of mi_tsdf_integrate's input map (nv == 0
+ * is the empty map: *out_n = 0).  A voxel is OBSERVED when weight >= min_weight (> 0); lookups by coordinate go through a table of packed
+ * coordinates, so the map's occupied extent is at most 2^20 voxels along an axis.
+ *   Crossing.  For every observed voxel i in row order and for the axis a = x, y, z in that order, with the neighbour j = i + e_a where it is
+ *     observed: f0 = tsdf[i] and f1 = tsdf[j] promoted to fp64; there is a crossing when (f0 > 0) != (f1 > 0) and not both |f| >= 1.  Then
+ *     r = f0 / (f0 - f1), and the point is the centre of i (origin + (index + 0.5) voxel_size per axis, fp64) with r voxel_size added along
+ *     a (one product, one sum), every coordinate rounded once to fp32.
+ *   Normal.  The gradient g at a voxel, per axis and in voxels: the central difference (f+ - f-) / 2 where both neighbours are observed, the
+ *     one-sided difference (f+ - f, or f - f-) where one is, 0 where none is.  The normal is v = (1 - r) g(i) + r g(j) (two products and a sum
+ *     per axis) divided by sqrt((v_x^2 + v_y^2) + v_z^2), rounded once to fp32: it points to the observed side, towards the sensor.  A zero
+ *     vector stays (0, 0, 0), which mi_icp_plane_register reads as "no pair here".
+ *   Output.  By row, then axis; 3 floats per crossing in out_xyz and, unless NULL, out_normals.  The capacity protocol is the one above:
+ *     *out_n is always written, the arrays if and only if 0 < *out_n <= capacity, capacity == 0 is a counts-only call.
+ *   Refusals as above, the message starting with "mi_tsdf_extract"; the map's arrays are called coord, tsdf and weight. */
+int mi_tsdf_extract(mi_ctx* ctx, const int* coord, const float* tsdf, const float* weight, int nv,
+                    const float origin3[3], float voxel_size, float min_weight /* > 0 */,
+                    float* out_xyz, float* out_normals /* may be NULL */, long long capacity, long long* out_n);
+/* Where the last mi_tsdf_integrate or mi_tsdf_extract of this context spent its host wall time, in ms:
+ *   out[0] workspace (device allocations)   out[1] upload   out[2] checks and read-backs
+ *   out[3] sampling (extraction: the table)   out[4] sort and runs (extraction: count + scan)   out[5] fusion (extraction: fill)
+ *   out[6] download   out[7] the whole call
+ * While profiling is enabled the stream is drained after every stage, so the parts are attributable (mi_profile_get then also holds the
+ * sampling and crossing launches' own HIP-event time under MI_KERNEL_NN and the fusion kernel's under MI_KERNEL_MOMENTS). */
+#define MI_TSDF_STAGES 8
+int mi_tsdf_times(mi_ctx* ctx, double out_ms[MI_TSDF_STAGES]);
+
+/* ----------------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel HIP-event timing on the context's own stream.
  * -------------------------------------------------------------------------------------------------------------- */
 enum {
