@@ -554,6 +554,46 @@ def _tsdf_map(m):
     return coord, tsdf, weight
 
 
+class TsdfRaycast:
+    """mi_tsdf_raycast_params, in a namespace as Tsdf: the compiler checks the layout against the header's in tests/test_tsdf_raycast_abi.py."""
+    C_TYPE = "mi_tsdf_raycast_params"
+
+    class Params(C.Structure):
+        _fields_ = [("voxel_size", C.c_float), ("min_weight", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float),
+                    ("visit_every_sample", C.c_int), ("reserved", C.c_int * 11)]
+
+
+TSDF_RAYCAST_MAX_STEPS = 65536                                  # MI_TSDF_RAYCAST_MAX_STEPS
+
+
+def tsdf_raycast_params(**kw):
+    """mi_tsdf_raycast_params at its defaults (min_weight 1, min_range 0, skipping on; voxel_size and max_range 0: set them) with the given
+    fields set."""
+    return _params(TsdfRaycast.Params, "mi_tsdf_raycast_params_default", kw)
+
+
+tsdf_raycast_raw = _raw("mi_tsdf_raycast")
+
+
+def pinhole_directions(width, height, fx, fy, cx, cy):
+    """The rays of a pinhole camera that looks along +z, x to the right and y down: [height * width, 3] float32, row by row, pixel (u, v) at
+    row v * width + u with the direction ((u - cx) / fx, (v - cy) / fy, 1).  Not normalised: mi_tsdf_raycast takes any length, and its depth is
+    along the ray, not along z."""
+    u, v = np.meshgrid(np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64))
+    d = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], axis=-1)
+    return np.ascontiguousarray(d.reshape(-1, 3), np.float32)
+
+
+def spherical_directions(rows, cols, elevation_lo, elevation_hi):
+    """The beams of a spinning LiDAR: [rows * cols, 3] float32, ring by ring; ring r has the elevation elevation_lo + r (elevation_hi -
+    elevation_lo) / (rows - 1) (radians above the sensor's xy plane; one ring: elevation_lo), column c the azimuth 2 pi c / cols about +z."""
+    elev = np.linspace(elevation_lo, elevation_hi, rows) if rows > 1 else np.array([float(elevation_lo)])
+    azim = 2 * np.pi * np.arange(cols) / cols
+    e, a = np.meshgrid(elev, azim, indexing="ij")
+    d = np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], axis=-1)
+    return np.ascontiguousarray(d.reshape(-1, 3), np.float32)
+
+
 class RansacParams(C.Structure):
     _fields_ = [("hypotheses", C.c_int), ("seed", C.c_ulonglong), ("max_distance", C.c_float), ("edge_similarity", C.c_float),
                 ("refine_iterations", C.c_int), ("reserved", C.c_int * 8)]
@@ -1436,9 +1476,37 @@ class Context:
                 raise MiSlamError("mi_tsdf_extract: %d points counted, then %d" % (n, found.value))
         return xyz, normals
 
+    def tsdf_raycast(self, map, origin, params, pose, dirs, compact=False):
+        """The map's surface as seen from a pose (mi_tsdf_raycast): (depth [n] float32, xyz [n, 3] float32, normals [n, 3] float32), row i for
+        ray i, zeros where a ray misses (depth > 0 marks a hit).  map: a (coord, tsdf, weight) triple or None; origin [3]; params:
+        tsdf_raycast_params(voxel_size=.., max_range=..); pose: the 4 x 4 matrix sensor to world, or None: the identity; dirs [n, 3] in the
+        sensor's frame, any length (pinhole_directions, spherical_directions).  compact=True: the hit rows only, with their ray indices:
+        (depth, xyz, normals, index [hits] int64)."""
+        coord, tsdf, weight = _tsdf_map(map)
+        origin = np.ascontiguousarray(origin, np.float32).reshape(3)
+        dirs = _cloud(dirs)
+        T = None
+        if pose is not None:
+            pose = np.asarray(pose, np.float64)
+            if pose.shape != (4, 4):
+                raise ValueError("pose is [4, 4]")
+            T = np.ascontiguousarray(pose.T, np.float32)     # column-major, as the C interface takes it
+        nv, n, hits = len(coord), len(dirs), C.c_longlong(0)
+        depth, xyz, normals = np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+        _check(tsdf_raycast_raw(self._h, coord.ctypes.data if nv else None, tsdf.ctypes.data if nv else None, weight.ctypes.data if nv else None, nv,
+                                origin.ctypes.data, C.addressof(params), _ptr(T), dirs.ctypes.data, n, depth.ctypes.data, xyz.ctypes.data,
+                                normals.ctypes.data, C.addressof(hits)))
+        if not compact:
+            return depth, xyz, normals
+        index = np.nonzero(depth > 0)[0]
+        if len(index) != hits.value:
+            raise MiSlamError("mi_tsdf_raycast: %d hits counted, %d rows with a depth" % (hits.value, len(index)))
+        return depth[index], xyz[index], normals[index], index
+
     def tsdf_times(self):
-        """ms per stage of the last tsdf_integrate or tsdf_extract: workspace, upload, check, sampling (extraction: table), sort (count +
-        scan), fusion (fill), download, total (mi_tsdf_times)."""
+        """ms per stage of the last tsdf_integrate, tsdf_extract or tsdf_raycast: workspace, upload, check, sampling (extraction and ray cast:
+        table), sort (extraction: count + scan; ray cast: block table), fusion (extraction: fill; ray cast: cast), download, total
+        (mi_tsdf_times)."""
         return self._times("tsdf")
 
     # ---- generalized ICP

@@ -1027,6 +1027,37 @@ struct TsdfCrossArgs {
 };
 hipError_t tsdf_crossings(const TsdfCrossArgs& a, bool fill, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------
+// K73-K75 TSDF ray casting: the map's surface as seen from a pose, one depth, point and normal per ray (tsdf_kernels.hip; driver:
+// tsdf_api.hip; the arithmetic: tsdf_cast.hpp; the contract: mi_tsdf_raycast in mi_slam.h).  The observed voxels are in K71's table.
+//   K73 tsdf_blocks:        one lane per row of the map: the 8^3-voxel block of every observed voxel into a table of K71's packing and hash
+//                           (keys alone), the new ones counted by an integer atomic.
+//   K74 tsdf_blocks_dilate: one lane per slot of K73's table: a held block marks itself and its 26 neighbours in a second table, sized from
+//                           K73's count.  A block that is NOT in it has no observed voxel within 8 voxels of any of its own.
+//   K75 tsdf_cast_rays:     one lane per ray: the direction turned by the pose, the march over the samples with one look-up each -- and,
+//                           with skipping on, a look-up in K74's table where a sample is unobserved, 14 samples stepped over where the block
+//                           is unmarked -- then, for a hit, the trilinear refinement (16 look-ups) and the normal (12).  Hits are counted over
+//                           the wave and added once per wave.  No LDS, no scratch, no floating-point atomic.
+// ---------------------------------------------------------------------------------------------------------------
+// the blocks of the observed rows into the table t (keys all ones and *count 0 before the launch); t.cmin / t.ext are in blocks
+hipError_t tsdf_blocks(const int* coord, const float* weight, int nv, float min_weight, const TsdfTableView& t, unsigned long long* keys, int* count, hipStream_t s);
+// held: K73's table of `slots` slots with `blocks` keys; keys: mask + 1 >= 54 blocks slots, all ones before the launch, in the same frame
+hipError_t tsdf_blocks_dilate(const unsigned long long* held, unsigned long long slots, int blocks, unsigned long long* keys, unsigned long long mask, hipStream_t s);
+struct TsdfCastArgs {
+    const float* dirs; int n;        // n x 3, the sensor's frame
+    float pose[16]; int has_pose;    // column-major, sensor to world; has_pose 0: the identity
+    float origin[3], voxel, min_range;
+    int steps;                       // K
+    const float* tsdf;               // the map's values by row
+    TsdfTableView table;             // K71's
+    TsdfTableView blocks;            // K74's (vals null; cmin / ext in blocks); read while skip != 0
+    int skip;
+    float* out_depth;                // n
+    float *out_xyz, *out_normals;    // n x 3 each; either may be null
+    int* hits;                       // 0 before the launch
+};
+hipError_t tsdf_cast_rays(const TsdfCastArgs& a, hipStream_t s);
+
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();
 hipError_t preload_nn_tree();

@@ -1,17 +1,19 @@
-// mi_tsdf_integrate, mi_tsdf_extract and mi_tsdf_times behind the C ABI: argument checks, the host check of a listed map (tsdf_ray.hpp), the
-// reserves of the calls' own buffers in the context, the uploads, the launches with their read-backs (the count pass's facts and total; the
-// number of voxels) and the download.  The kernels: tsdf_kernels.hip.  Nothing is written to a caller's array before the last refusal.
+// mi_tsdf_integrate, mi_tsdf_extract, mi_tsdf_raycast and mi_tsdf_times behind the C ABI: argument checks, the host check of a listed map
+// (tsdf_ray.hpp), the reserves of the calls' own buffers in the context, the uploads, the launches with their read-backs (the count pass's facts
+// and total; the number of voxels; the blocks and the hits of a ray cast) and the download.  The kernels: tsdf_kernels.hip.  Nothing is written to a caller's array before the last refusal.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cmath>
 
 #include "context.h"
+#include "tsdf_cast.hpp"
 #include "tsdf_ray.hpp"
 
 using namespace mislam;
 
 static_assert(TSDF_MAX_HALF_STEPS == MI_TSDF_MAX_HALF_STEPS, "tsdf_ray.hpp mirrors the header's limit");
+static_assert(TSDF_RAYCAST_MAX_STEPS == MI_TSDF_RAYCAST_MAX_STEPS, "tsdf_cast.hpp mirrors the header's limit");
 static_assert(sizeof(TsdfState) + sizeof(long long) <= 64 * sizeof(float) && sizeof(TsdfState) % sizeof(long long) == 0,
               "the count pass's facts and total must fit the context's pinned scratch");
 
@@ -305,6 +307,133 @@ extern "C" int mi_tsdf_extract(mi_ctx* c, const int* coord, const float* tsdf, c
         MI_TRY(clock.mark(6));
     }
     *out_n = found;
+    clock.finish();
+    return MI_OK;
+}
+
+extern "C" void mi_tsdf_raycast_params_default(mi_tsdf_raycast_params* p)
+{
+    if (!p) return;
+    *p = mi_tsdf_raycast_params{};
+    p->min_weight = 1.f;
+}
+
+extern "C" int mi_tsdf_raycast(mi_ctx* c, const int* coord, const float* tsdf, const float* weight, int nv, const float origin3[3],
+                               const mi_tsdf_raycast_params* params, const float T[16], const float* dirs_xyz, int n, float* out_depth, float* out_xyz,
+                               float* out_normals, long long* out_hits)
+{
+    const char* who = "mi_tsdf_raycast";
+    if (!c) { set_error("%s: null context", who); return MI_ERR_INVALID_ARG; }
+    if (!origin3 || !params || !dirs_xyz || !out_depth) { set_error("%s: null origin3, params, dirs_xyz or out_depth", who); return MI_ERR_INVALID_ARG; }
+    if (n < 1) { set_error("%s: n = %d", who, n); return MI_ERR_INVALID_ARG; }
+    if (nv < 0) { set_error("%s: nv = %d", who, nv); return MI_ERR_INVALID_ARG; }
+    if (nv > 0 && (!coord || !tsdf || !weight)) { set_error("%s: null coord, tsdf or weight with nv = %d", who, nv); return MI_ERR_INVALID_ARG; }
+    const mi_tsdf_raycast_params& p = *params;
+    if (!std::isfinite(p.voxel_size) || !(p.voxel_size > 0.f)) { set_error("%s: params: voxel_size not finite or not positive", who); return MI_ERR_INVALID_ARG; }
+    if (!(p.min_weight > 0.f)) { set_error("%s: params: min_weight not positive", who); return MI_ERR_INVALID_ARG; }
+    if (!(p.min_range >= 0.f) || !std::isfinite(p.min_range)) { set_error("%s: params: min_range negative or not finite", who); return MI_ERR_INVALID_ARG; }
+    if (!(p.max_range > p.min_range) || !std::isfinite(p.max_range)) { set_error("%s: params: max_range not finite or not above min_range", who); return MI_ERR_INVALID_ARG; }
+    if (p.visit_every_sample != 0 && p.visit_every_sample != 1) { set_error("%s: params: visit_every_sample = %d, neither 0 nor 1", who, p.visit_every_sample); return MI_ERR_INVALID_ARG; }
+    const double steps = tsdf_cast_steps(p.voxel_size, p.min_range, p.max_range);
+    if (!(steps <= (double)MI_TSDF_RAYCAST_MAX_STEPS)) {
+        set_error("%s: params: the range is %.0f samples of half a voxel, above MI_TSDF_RAYCAST_MAX_STEPS = %d", who, steps, MI_TSDF_RAYCAST_MAX_STEPS);
+        return MI_ERR_INVALID_ARG;
+    }
+    if (!finite3(origin3)) { set_error("%s: origin3 not finite", who); return MI_ERR_INVALID_ARG; }
+    if (T)
+        for (int e = 0; e < 16; e++)
+            if (!std::isfinite(T[e])) { set_error("%s: T has a non-finite entry (entry %d)", who, e); return MI_ERR_INVALID_ARG; }
+    for (long long e = 0; e < 3LL * n; e++)
+        if (!(std::fabs(dirs_xyz[e]) <= TSDF_MAX_ABS)) {
+            set_error("%s: dirs_xyz ray %lld has a component that is not finite or above 1e18 in magnitude", who, e / 3);
+            return MI_ERR_INVALID_ARG;
+        }
+    if (c->distributed()) { set_error("%s: single-GPU contexts only", who); return MI_ERR_STATE; }
+    MI_ENTER(c);
+    mi_ctx::TsdfBuffers& b = c->tsdf;
+    StageClock clock(c, b.ms);         // mi_tsdf_times
+
+    int cmin[3] = {0, 0, 0}, cmax[3] = {0, 0, 0};
+    MI_TRY(tsdf_refuse_map(who, "coord", "tsdf", "weight", coord, tsdf, weight, nv, cmin, cmax));
+    if (nv > 0) MI_TRY(tsdf_refuse_extent(who, cmin, cmax));
+    MI_TRY(clock.mark(2));
+    const size_t nr = (size_t)n, nm = (size_t)nv;
+    auto every_ray_misses = [&]() {
+        for (size_t i = 0; i < nr; i++) out_depth[i] = 0.f;
+        for (size_t i = 0; i < 3 * nr; i++) { if (out_xyz) out_xyz[i] = 0.f; if (out_normals) out_normals[i] = 0.f; }
+        if (out_hits) *out_hits = 0;
+        clock.finish();
+        return MI_OK;
+    };
+    if (nv == 0) return every_ray_misses();  // the empty map
+
+    size_t slots = 2;
+    while (slots < 2 * nm) slots <<= 1;
+    const bool skip = p.visit_every_sample == 0 && tsdf_cast_skip_sound(T, origin3, p.voxel_size, p.max_range);
+    CallBuffers bufs;
+    MI_TRY(bufs.need(b.in_coord, 3 * nm)); MI_TRY(bufs.need(b.in_tsdf, nm)); MI_TRY(bufs.need(b.in_weight, nm));
+    MI_TRY(bufs.need(b.hkeys, slots)); MI_TRY(bufs.need(b.hvals, slots));
+    MI_TRY(bufs.need(b.xyz, 3 * nr)); MI_TRY(bufs.need(b.cast_counts, 2));
+    if (skip) MI_TRY(bufs.need(b.block_held, slots));
+    MI_TRY(bufs.need(b.out_depth, nr, out_depth)); MI_TRY(bufs.result(b.out_xyz, 3 * nr, out_xyz)); MI_TRY(bufs.result(b.out_normals, 3 * nr, out_normals));
+    MI_TRY(clock.mark(0));
+    MI_TRY(host_to_device(c, b.in_coord.p, coord, sizeof(int) * 3 * nm));
+    MI_TRY(host_to_device(c, b.in_tsdf.p, tsdf, sizeof(float) * nm));
+    MI_TRY(host_to_device(c, b.in_weight.p, weight, sizeof(float) * nm));
+    MI_TRY(host_to_device(c, b.xyz.p, dirs_xyz, sizeof(float) * 3 * nr));
+    MI_TRY(clock.mark(1));
+
+    if (!bufs.fits()) { set_error("internal: %s buffers shorter than the launch", who); return MI_ERR_STATE; }
+    TsdfCastArgs a{};
+    a.dirs = b.xyz.p; a.n = n; a.has_pose = T ? 1 : 0;
+    for (int k = 0; k < 16; k++) a.pose[k] = T ? T[k] : 0.f;
+    for (int k = 0; k < 3; k++) { a.origin[k] = origin3[k]; a.table.cmin[k] = cmin[k]; a.table.ext[k] = cmax[k] - cmin[k] + 1; }
+    a.voxel = p.voxel_size; a.min_range = p.min_range; a.steps = (int)steps; a.tsdf = b.in_tsdf.p;
+    a.table.keys = b.hkeys.p; a.table.vals = b.hvals.p; a.table.mask = (unsigned long long)slots - 1ull;
+    a.out_depth = b.out_depth.p; a.out_xyz = out_xyz ? b.out_xyz.p : nullptr; a.out_normals = out_normals ? b.out_normals.p : nullptr;
+    a.hits = b.cast_counts.p + 1;
+    MI_HIP(hipMemsetAsync(b.hkeys.p, 0xff, sizeof(unsigned long long) * slots, c->stream));       // every slot free
+    MI_HIP(hipMemsetAsync(b.cast_counts.p, 0, 2 * sizeof(int), c->stream));
+    MI_HIP(tsdf_table(b.in_coord.p, b.in_weight.p, nv, p.min_weight, a.table, b.hkeys.p, b.hvals.p, c->stream));
+    MI_TRY(clock.mark(3));
+
+    int* h_count = reinterpret_cast<int*>(c->h_scratch);
+    if (skip) {
+        // the blocks' frame: the map's range in blocks with one block to spare on every side, for the neighbours K74 marks
+        for (int k = 0; k < 3; k++) {
+            a.blocks.cmin[k] = (cmin[k] >> TSDF_SKIP_SHIFT) - 1;
+            a.blocks.ext[k] = (cmax[k] >> TSDF_SKIP_SHIFT) - (cmin[k] >> TSDF_SKIP_SHIFT) + 3;
+        }
+        a.blocks.mask = (unsigned long long)slots - 1ull;
+        MI_HIP(hipMemsetAsync(b.block_held.p, 0xff, sizeof(unsigned long long) * slots, c->stream));
+        MI_HIP(tsdf_blocks(b.in_coord.p, b.in_weight.p, nv, p.min_weight, a.blocks, b.block_held.p, b.cast_counts.p, c->stream));
+        MI_HIP(hipMemcpyAsync(h_count, b.cast_counts.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        MI_HIP(hipStreamSynchronize(c->stream));
+        const int held = *h_count;
+        if (held < 0 || held > nv) { set_error("internal: %s found %d blocks among %d voxels", who, held, nv); return MI_ERR_STATE; }
+        if (held == 0) return every_ray_misses();       // no voxel is observed at this min_weight
+        size_t marked = 2;
+        while (marked < 54 * (size_t)held) marked <<= 1;
+        MI_TRY(bufs.need(b.block_keys, marked));
+        if (!bufs.fits()) { set_error("internal: %s block table shorter than the launch", who); return MI_ERR_STATE; }
+        MI_HIP(hipMemsetAsync(b.block_keys.p, 0xff, sizeof(unsigned long long) * marked, c->stream));
+        MI_HIP(tsdf_blocks_dilate(b.block_held.p, (unsigned long long)slots, held, b.block_keys.p, (unsigned long long)marked - 1ull, c->stream));
+        a.blocks.keys = b.block_keys.p; a.blocks.vals = nullptr; a.blocks.mask = (unsigned long long)marked - 1ull;
+        a.skip = 1;
+    }
+    MI_TRY(clock.mark(4));
+    {
+        // with profiling on, the cast launch's time is booked to MI_KERNEL_NN (mi_profile_get)
+        ProfScope prof(c, MI_KERNEL_NN);
+        MI_HIP(tsdf_cast_rays(a, c->stream));
+    }
+    MI_TRY(clock.mark(5));
+    MI_HIP(hipMemcpyAsync(h_count, b.cast_counts.p + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MI_TRY(bufs.download(c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    MI_TRY(clock.mark(6));
+    if (*h_count < 0 || *h_count > n) { set_error("internal: %s counted %d hits of %d rays", who, *h_count, n); return MI_ERR_STATE; }
+    if (out_hits) *out_hits = *h_count;
     clock.finish();
     return MI_OK;
 }

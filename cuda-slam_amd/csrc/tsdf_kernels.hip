@@ -1,12 +1,13 @@
-// K68-K72: the kernels of mi_tsdf_integrate and mi_tsdf_extract (kernels.h has the plan; tsdf_ray.hpp the arithmetic, which host and device
-// share word for word).  Every kernel is one lane per ray, row or voxel, in workgroups of TSDF_BLOCK; none uses LDS or scratch, none has a
-// floating-point atomic: the only atomics are integer minima and maxima (the same answer in any order) and the table's compare-and-swap on
-// keys that are all different.
+// K68-K75: the kernels of mi_tsdf_integrate, mi_tsdf_extract and mi_tsdf_raycast (kernels.h has the plan; tsdf_ray.hpp and tsdf_cast.hpp the
+// arithmetic, which host and device share word for word).  Every kernel is one lane per ray, row, voxel or slot, in workgroups of TSDF_BLOCK;
+// none uses LDS or scratch, none has a floating-point atomic: the only atomics are integer minima, maxima and counts (the same answer in any
+// order) and the tables' compare-and-swap on keys (a key met again is left where it is).
 #include <hip/hip_runtime.h>
 
 #include <climits>
 
 #include "kernels.h"
+#include "tsdf_cast.hpp"
 #include "tsdf_ray.hpp"
 
 namespace mislam {
@@ -259,6 +260,111 @@ hipError_t tsdf_crossings(const TsdfCrossArgs& a, bool fill, hipStream_t s)
     const dim3 grid((a.nv - 1) / TSDF_BLOCK + 1), block(TSDF_BLOCK);
     if (fill) hipLaunchKernelGGL(tsdf_crossings_kernel<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(tsdf_crossings_kernel<false>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- K73, K74: the coarse table of mi_tsdf_raycast's empty-space skipping.  A block is 8^3 voxels, its coordinate the voxel's >> 3; the
+// tables have K71's packing and hash and no values.  Every key of a lane is in [0, ext) of its table (the driver sizes ext from the map's
+// range plus one block on either side), every slot index is masked, and at most half the slots are ever taken.
+__device__ __forceinline__ bool tsdf_key_insert(unsigned long long* __restrict__ keys, unsigned long long mask, unsigned long long key)      // true: the key is new
+{
+    unsigned long long slot = tsdf_hash(key) & mask;
+    for (unsigned long long probe = 0; probe <= mask; probe++) {
+        const unsigned long long old = atomicCAS(&keys[slot], TSDF_KEY_EMPTY, key);
+        if (old == TSDF_KEY_EMPTY) return true;
+        if (old == key) return false;
+        slot = (slot + 1) & mask;
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_blocks_kernel(const int* __restrict__ coord, const float* __restrict__ weight, int nv, float min_weight,
+                                                                 TsdfTableView t, unsigned long long* __restrict__ keys, int* __restrict__ count)
+{
+    const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
+    if (i >= nv || !(weight[i] >= min_weight)) return;
+    const unsigned long long key = (unsigned long long)((coord[3 * (size_t)i] >> TSDF_SKIP_SHIFT) - t.cmin[0]) |
+                                   (unsigned long long)((coord[3 * (size_t)i + 1] >> TSDF_SKIP_SHIFT) - t.cmin[1]) << 20 |
+                                   (unsigned long long)((coord[3 * (size_t)i + 2] >> TSDF_SKIP_SHIFT) - t.cmin[2]) << 40;
+    if (tsdf_key_insert(keys, t.mask, key)) atomicAdd(count, 1);
+}
+
+hipError_t tsdf_blocks(const int* coord, const float* weight, int nv, float min_weight, const TsdfTableView& t, unsigned long long* keys, int* count, hipStream_t s)
+{
+    if (nv < 1 || t.mask + 1 < 2 * (unsigned long long)nv || (t.mask & (t.mask + 1)) != 0 || !coord || !weight || !keys || !count) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tsdf_blocks_kernel, dim3((nv - 1) / TSDF_BLOCK + 1), dim3(TSDF_BLOCK), 0, s, coord, weight, nv, min_weight, t, keys, count);
+    return hipGetLastError();
+}
+
+// one lane per slot of K73's table: a block that holds an observed voxel marks itself and its 26 neighbours (they share the table's frame, and
+// the frame has a block to spare on every side)
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_blocks_dilate_kernel(const unsigned long long* __restrict__ held, unsigned long long slots,
+                                                                        unsigned long long* __restrict__ keys, unsigned long long mask)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * TSDF_BLOCK + threadIdx.x;
+    if (i >= slots) return;
+    const unsigned long long key = held[i];
+    if (key == TSDF_KEY_EMPTY) return;
+    const long long bx = (long long)(key & 0xfffffull), by = (long long)(key >> 20 & 0xfffffull), bz = (long long)(key >> 40 & 0xfffffull);
+    for (int dz = -1; dz <= 1; dz++)
+        for (int dy = -1; dy <= 1; dy++)
+            for (int dx = -1; dx <= 1; dx++)
+                tsdf_key_insert(keys, mask, (unsigned long long)(bx + dx) | (unsigned long long)(by + dy) << 20 | (unsigned long long)(bz + dz) << 40);
+}
+
+hipError_t tsdf_blocks_dilate(const unsigned long long* held, unsigned long long slots, int blocks, unsigned long long* keys, unsigned long long mask, hipStream_t s)
+{
+    if (slots < 1 || slots > (1ull << 32) || blocks < 1 || mask + 1 < 54ull * (unsigned long long)blocks || (mask & (mask + 1)) != 0 || !held || !keys) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tsdf_blocks_dilate_kernel, dim3((unsigned int)((slots - 1) / TSDF_BLOCK + 1)), dim3(TSDF_BLOCK), 0, s, held, slots, keys, mask);
+    return hipGetLastError();
+}
+
+// is the block (bx, by, bz) in K74's table?
+__device__ __forceinline__ bool tsdf_block_marked(const TsdfTableView& t, int bx, int by, int bz)
+{
+    const long long rx = (long long)bx - t.cmin[0], ry = (long long)by - t.cmin[1], rz = (long long)bz - t.cmin[2];
+    if (rx < 0 || rx >= t.ext[0] || ry < 0 || ry >= t.ext[1] || rz < 0 || rz >= t.ext[2]) return false;
+    const unsigned long long key = (unsigned long long)rx | (unsigned long long)ry << 20 | (unsigned long long)rz << 40;
+    unsigned long long slot = tsdf_hash(key) & t.mask;
+    for (unsigned long long probe = 0; probe <= t.mask; probe++) {
+        const unsigned long long k = t.keys[slot];
+        if (k == key) return true;
+        if (k == TSDF_KEY_EMPTY) return false;
+        slot = (slot + 1) & t.mask;
+    }
+    return false;
+}
+
+// ---- K75: one lane per ray, tsdf_cast.hpp's march over K71's table.  Row i of every output is ray i's; a miss writes zeros.
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cast_kernel(TsdfCastArgs a)
+{
+    const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
+    bool hit = false;
+    if (i < a.n) {
+        TsdfCastRay ray;
+        TsdfCastHit h;
+        h.depth = 0.f;
+        h.xyz[0] = h.xyz[1] = h.xyz[2] = h.normal[0] = h.normal[1] = h.normal[2] = 0.f;
+        if (tsdf_cast_dir(a.has_pose ? a.pose : nullptr, a.dirs[3 * (size_t)i], a.dirs[3 * (size_t)i + 1], a.dirs[3 * (size_t)i + 2], &ray)) {
+            TsdfCastGeom g;
+            g.origin[0] = a.origin[0]; g.origin[1] = a.origin[1]; g.origin[2] = a.origin[2];
+            g.voxel = a.voxel; g.min_range = a.min_range; g.steps = a.steps;
+            hit = tsdf_cast(ray, g, a.tsdf, [&](int cx, int cy, int cz) { return tsdf_lookup(a.table, cx, cy, cz); }, a.skip != 0,
+                            [&](int bx, int by, int bz) { return tsdf_block_marked(a.blocks, bx, by, bz); }, &h);
+        }
+        a.out_depth[i] = h.depth;
+        if (a.out_xyz) { a.out_xyz[3 * (size_t)i] = h.xyz[0]; a.out_xyz[3 * (size_t)i + 1] = h.xyz[1]; a.out_xyz[3 * (size_t)i + 2] = h.xyz[2]; }
+        if (a.out_normals) { a.out_normals[3 * (size_t)i] = h.normal[0]; a.out_normals[3 * (size_t)i + 1] = h.normal[1]; a.out_normals[3 * (size_t)i + 2] = h.normal[2]; }
+    }
+    const unsigned long long hits = __ballot(hit);       // an integer count: the same in any order
+    if ((threadIdx.x & 63) == 0 && hits != 0) atomicAdd(a.hits, __popcll(hits));
+}
+
+hipError_t tsdf_cast_rays(const TsdfCastArgs& a, hipStream_t s)
+{
+    if (a.n < 1 || a.steps < 1 || a.steps > TSDF_RAYCAST_MAX_STEPS || !a.dirs || !a.tsdf || !a.table.keys || !a.table.vals || !a.out_depth || !a.hits) return hipErrorInvalidValue;
+    if (a.skip && !a.blocks.keys) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tsdf_cast_kernel, dim3((a.n - 1) / TSDF_BLOCK + 1), dim3(TSDF_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

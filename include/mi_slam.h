@@ -2129,12 +2129,70 @@ int mi_tsdf_integrate(mi_ctx* ctx,
 int mi_tsdf_extract(mi_ctx* ctx, const int* coord, const float* tsdf, const float* weight, int nv,
                     const float origin3[3], float voxel_size, float min_weight /* > 0 */,
                     float* out_xyz, float* out_normals /* may be NULL */, long long capacity, long long* out_n);
-/* Where the last mi_tsdf_integrate or mi_tsdf_extract of this context spent its host wall time, in ms:
+/* mi_tsdf_raycast -- the map's surface as seen from a pose: one depth, one point and one normal per sensor ray, interpolated inside the
+ * voxels; the frame-to-model read-out of a TSDF tracker, a depth image, a synthetic LiDAR sweep or an occlusion test, according to the
+ * directions the caller gives.  The map is held to the checks of mi_tsdf_integrate's input map and to mi_tsdf_extract's extent (at most
+ * 2^20 voxels along an axis); nv == 0 is the empty map: every ray misses.  Every rule, so that it can be retraced in numpy
+ * (tests/tsdf_raycast_reference.py does).  Everything behind the fp32 rotation is fp64 on promoted operands, every operation rounded once,
+ * none fused; only +, -, *, /, sqrt, floor and comparisons occur.
+ *   1 Ray.  The sensor position o is T's translation column (T: 16 floats, column-major, sensor to world; NULL: the identity, through the
+ *     same arithmetic).  Ray i's direction in the world is u = (R0 d_x + R1 d_y) + R2 d_z per row of R in fp32, every operation rounded:
+ *     mi_tsdf_integrate's move without the translation.  len = sqrt((u_x^2 + u_y^2) + u_z^2), d = u / len.  A ray with len == 0 or len not
+ *     finite is a miss.  The directions may have any length; all depths are along the unit direction d.
+ *   2 Samples.  h = voxel_size / 2; K = floor((max_range - min_range) / h) + 1, refused above MI_TSDF_RAYCAST_MAX_STEPS.  For k = 0 .. K - 1
+ *     the depth is s_k = min_range + k h (one product, one sum), the position x_k = o + s_k d per coordinate (one product, one sum), rounded
+ *     once to fp32, and its voxel mi_voxel_index(x_k, origin3, voxel_size), exactly as mi_tsdf_integrate places a sample.  Sample k is
+ *     OBSERVED when that voxel is in the map with weight >= min_weight; g_k is then the voxel's value.  A voxel coordinate outside
+ *     [-2^30, 2^30), or outside the map's box, is unobserved, not an error.
+ *   3 March, over k ascending.  An unobserved sample, or an observed one with g_k > 0, goes on.  At the first observed sample with g_k <= 0
+ *     the march ends: as a HIT when k >= 1, sample k - 1 is observed and g_(k-1) > 0; otherwise as a MISS (the surface was met from behind
+ *     or out of unobserved space).  A march that runs out of samples is a miss.
+ *   4 Refinement, between a = s_(k-1) and b = s_k, by the trilinear field F(s): p = o + s d in fp64 (not rounded to fp32);
+ *     q = (p - origin) / voxel_size - 0.5 per axis (three operations); i = floor(q), w = q - i; the eight corner voxels i + {0, 1}^3 have the
+ *     values f_xyz.  F is AVAILABLE when every q is in [-2^30, 2^30) and all eight corners are observed; then
+ *     c_yz = f_0yz + w_x (f_1yz - f_0yz), c_z = c_0z + w_y (c_1z - c_0z), F = c_0 + w_z (c_1 - c_0).  If F(a) and F(b) are both available and
+ *     F(a) > 0 >= F(b), r = F(a) / (F(a) - F(b)); otherwise r = g_(k-1) / (g_(k-1) - g_k), which is always defined and in (0, 1].  The depth
+ *     is t = a + r h and the point o + t d per coordinate (one product, one sum), each rounded once to fp32.  (A depth that rounds to 0 in
+ *     fp32 makes the ray a miss: the depth is the hit flag.)
+ *   5 Normal.  With i the voxel of sample k - 1 and j the voxel of sample k (they differ: their values differ in sign) and the gradient g of
+ *     mi_tsdf_extract at each, over the observed neighbours, the normal is mi_tsdf_extract's: v = (1 - r) g(i) + r g(j) with the r of rule
+ *     4, divided by its norm, rounded once to fp32.  It points to the observed side, towards the sensor; a zero vector stays (0, 0, 0).
+ *   Output.  Row i of out_depth, out_xyz (world) and out_normals (world) belongs to ray i; out_xyz, out_normals and out_hits may each be
+ *     NULL.  A miss gets depth 0, point (0, 0, 0) and normal (0, 0, 0); a hit has depth > 0; *out_hits is the number of hits.  No
+ *     floating-point atomic occurs: the same input gives the same bits on every call, whatever ran on the context before.
+ *   Empty-space skipping.  Rule 3 says an unobserved sample does nothing, so the march leaves out samples it can prove unobserved: where a
+ *     sample's voxel lies in a block of 8^3 voxels that holds no observed voxel and has no neighbour block that does, the 14 samples behind
+ *     it are stepped over.  The proof needs (3 max|o| + 2 max|origin3| + 3 max_range) / voxel_size <= 2^21; where that fails the
+ *     call marches plainly.  visit_every_sample = 1 marches plainly always.  Neither moves a bit of the result.
+ *   MI_ERR_INVALID_ARG -- mi_last_error starts with "mi_tsdf_raycast" and names the cause and, for a bad element, the array and the lowest
+ *     index; NOTHING has been written -- for: a NULL required argument (ctx, origin3, params, dirs_xyz, out_depth; the map's arrays with
+ *     nv > 0); n < 1 or nv < 0; params outside what the struct states; K above MI_TSDF_RAYCAST_MAX_STEPS; a non-finite entry of T or
+ *     origin3; a component of dirs_xyz that is not finite or above 1e18 in magnitude; every map refusal of mi_tsdf_extract (the arrays are
+ *     called coord, tsdf and weight).  MI_ERR_STATE on a distributed context.  A device allocation that fails is MI_ERR_HIP; the context
+ *     stays usable.  A problem loaded by mi_icp_load and everything the searches keep survive the call. */
+#define MI_TSDF_RAYCAST_MAX_STEPS 65536
+typedef struct mi_tsdf_raycast_params {
+    float voxel_size;   /* > 0, finite: the map's */
+    float min_weight;   /* > 0: a voxel is OBSERVED when weight >= min_weight; default 1 */
+    float min_range;    /* >= 0, finite; default 0 */
+    float max_range;    /* > min_range, finite; no default: the caller must set it */
+    int   visit_every_sample;  /* 0: default; 1: no empty-space skipping (measurement, tests); moves no bit */
+    int   reserved[11];
+} mi_tsdf_raycast_params;      /* 64 bytes */
+void mi_tsdf_raycast_params_default(mi_tsdf_raycast_params* p);
+int mi_tsdf_raycast(mi_ctx* ctx, const int* coord, const float* tsdf, const float* weight, int nv,
+                    const float origin3[3], const mi_tsdf_raycast_params* params,
+                    const float T[16] /* sensor to world; NULL: identity, same arithmetic */,
+                    const float* dirs_xyz /* n x 3, sensor frame, any length */, int n,
+                    float* out_depth /* n */, float* out_xyz /* n x 3, world; may be NULL */,
+                    float* out_normals /* n x 3, world; may be NULL */, long long* out_hits /* may be NULL */);
+/* Where the last mi_tsdf_integrate, mi_tsdf_extract or mi_tsdf_raycast of this context spent its host wall time, in ms:
  *   out[0] workspace (device allocations)   out[1] upload   out[2] checks and read-backs
- *   out[3] sampling (extraction: the table)   out[4] sort and runs (extraction: count + scan)   out[5] fusion (extraction: fill)
+ *   out[3] sampling (extraction and ray cast: the table)   out[4] sort and runs (extraction: count + scan; ray cast: the block table)
+ *   out[5] fusion (extraction: fill; ray cast: the cast)
  *   out[6] download   out[7] the whole call
  * While profiling is enabled the stream is drained after every stage, so the parts are attributable (mi_profile_get then also holds the
- * sampling and crossing launches' own HIP-event time under MI_KERNEL_NN and the fusion kernel's under MI_KERNEL_MOMENTS). */
+ * sampling, crossing and cast launches' own HIP-event time under MI_KERNEL_NN and the fusion kernel's under MI_KERNEL_MOMENTS). */
 #define MI_TSDF_STAGES 8
 int mi_tsdf_times(mi_ctx* ctx, double out_ms[MI_TSDF_STAGES]);
 
