@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "pose_block.hpp"
+#include "voxel_table.hpp"
 
 namespace mislam {
 
@@ -603,7 +604,7 @@ hipError_t fgr_weights(const FgrStepArgs& a, hipStream_t s);            // K47: 
 // K27 - K31 NDT registration (ndt_kernels.hip; driver: ndt_api.hip, then pose_loop.hip for the iterations; the term of a pair: ndt_term.hpp).  mi_ndt_voxels: the voxel filter's
 // own front end (VoxArgs above: coordinates, counts and means are mi_voxel_downsample's by construction), then a second segmented pass
 // over the sorted order for the scatter about the fp32 mean and one lane per voxel for the eigenvalue floor and the inverse.
-// mi_ndt_register: the listed voxels in an open-addressing hash table, the step kernel writing K16's rows from a direct lookup per point,
+// mi_ndt_register: the listed voxels in the hash table of voxel_table.hpp, the step kernel writing K16's rows from a direct lookup per point,
 // and K16's own reduce and solve behind the rows.
 // ---------------------------------------------------------------------------------------------------------------
 struct NdtScatterArgs {
@@ -619,7 +620,6 @@ hipError_t ndt_voxel_finish(const double* q6, const int* count, const VoxState* 
                             float* cov6, hipStream_t s);
 
 constexpr int NDT_NO_ROW = 0x7fffffff;       // NdtMapState's bad_* while no row has been refused
-constexpr unsigned long long NDT_KEY_EMPTY = 0xffffffffffffffffull;   // a free slot of the table (a key has 60 bits)
 // Device-resident facts of the listed voxels; the host sets the starts, the check kernel folds every row in with integer atomics (minima
 // and maxima: the same answer in any order), and the host reads it back once, before anything is written.
 struct NdtMapState {
@@ -643,16 +643,13 @@ __host__ __device__ __forceinline__ float ndt_key_float(unsigned int k)
 }
 
 struct NdtMapView {
-    const unsigned long long* keys;  // capacity slots: the packed coordinate of the voxel stored there, or NDT_KEY_EMPTY
-    const int* vals;                 // its row in the caller's list
-    unsigned long long mask;         // capacity - 1, capacity a power of two >= 2 nv
-    int cmin[3], ext[3];             // the key of (cx, cy, cz) is (cx - cmin_x) | (cy - cmin_y) << 20 | (cz - cmin_z) << 40, each in [0, ext) <= 2^20
+    VoxelTableView table;            // voxel_table.hpp: the listed voxels' rows, 2 slots per voxel
     const float4* mean;              // nv: (x, y, z, 0)
     const float4* icov;              // 2 nv: (xx, xy, xz, 0), (yy, yz, zz, 0)
 };
 // the listed voxels as uploaded -> packed means and matrices, and the facts of NdtMapState
 hipError_t ndt_check_voxels(const int* coord, const float* mean, const float* icov6, int nv, float4* mean4, float4* icov4, NdtMapState* st, hipStream_t s);
-// the rows with a distribution into the table (keys all NDT_KEY_EMPTY before the launch)
+// the rows with a distribution into the table (every slot free before the launch)
 hipError_t ndt_hash_build(const int* coord, const float4* icov4, int nv, const NdtMapView& map, unsigned long long* keys, int* vals, hipStream_t s);
 
 struct NdtStepArgs {
@@ -963,8 +960,7 @@ hipError_t sc_finish(const unsigned long long* keys, const unsigned long long* k
 //       The voxel filter's stable radix sort (one per axis) and head-flag scan (vox_rows) order the entries and find the voxels' runs: a
 //       voxel's input row, then its samples in ascending (scan, point, k).
 //   K70 tsdf_fuse:     one lane per voxel: the fp64 sum of its run in that order, the count, the fused row.
-//   K71 tsdf_table:    one lane per row of a map: the observed voxels into an open-addressing table of packed coordinates (the layout of
-//                      the NDT map's table, NdtMapView).
+//   K71 tsdf_table:    one lane per row of a map: the observed voxels into the table of voxel_table.hpp.
 //   K72 tsdf_crossings: one lane per row, twice: the count of its crossings, and behind K51's scan the fill of points and normals.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int TSDF_BLOCK = 256;              // rays, rows or voxels per workgroup of K68-K72: one per lane
@@ -1009,18 +1005,12 @@ struct TsdfFuseArgs {
     float *out_tsdf, *out_weight;    // rows
 };
 hipError_t tsdf_fuse(const TsdfFuseArgs& a, hipStream_t s);
-struct TsdfTableView {
-    const unsigned long long* keys;  // capacity slots: the packed coordinate stored there, or all ones
-    const int* vals;                 // its row
-    unsigned long long mask;         // capacity - 1, capacity a power of two >= 2 nv
-    int cmin[3], ext[3];             // the key of (cx, cy, cz) is (cx - cmin_x) | (cy - cmin_y) << 20 | (cz - cmin_z) << 40, each in [0, ext) <= 2^20
-};
-// the rows with weight >= min_weight into the table (keys all ones before the launch)
-hipError_t tsdf_table(const int* coord, const float* weight, int nv, float min_weight, const TsdfTableView& t, unsigned long long* keys, int* vals, hipStream_t s);
+// the rows with weight >= min_weight into the table (2 slots per row, every slot free before the launch)
+hipError_t tsdf_table(const int* coord, const float* weight, int nv, float min_weight, const VoxelTableView& t, unsigned long long* keys, int* vals, hipStream_t s);
 struct TsdfCrossArgs {
     const int* coord; const float* tsdf; const float* weight; int nv;
     float origin[3], voxel, min_weight;
-    TsdfTableView table;
+    VoxelTableView table;
     int* count;                      // nv: the count pass writes
     const long long* offsets;        // nv + 1 (the fill)
     float *out_xyz, *out_normals;    // 3 per crossing; out_normals may be null
@@ -1040,7 +1030,7 @@ hipError_t tsdf_crossings(const TsdfCrossArgs& a, bool fill, hipStream_t s);
 //                           the wave and added once per wave.  No LDS, no scratch, no floating-point atomic.
 // ---------------------------------------------------------------------------------------------------------------
 // the blocks of the observed rows into the table t (keys all ones and *count 0 before the launch); t.cmin / t.ext are in blocks
-hipError_t tsdf_blocks(const int* coord, const float* weight, int nv, float min_weight, const TsdfTableView& t, unsigned long long* keys, int* count, hipStream_t s);
+hipError_t tsdf_blocks(const int* coord, const float* weight, int nv, float min_weight, const VoxelTableView& t, unsigned long long* keys, int* count, hipStream_t s);
 // held: K73's table of `slots` slots with `blocks` keys; keys: mask + 1 >= 54 blocks slots, all ones before the launch, in the same frame
 hipError_t tsdf_blocks_dilate(const unsigned long long* held, unsigned long long slots, int blocks, unsigned long long* keys, unsigned long long mask, hipStream_t s);
 struct TsdfCastArgs {
@@ -1049,8 +1039,8 @@ struct TsdfCastArgs {
     float origin[3], voxel, min_range;
     int steps;                       // K
     const float* tsdf;               // the map's values by row
-    TsdfTableView table;             // K71's
-    TsdfTableView blocks;            // K74's (vals null; cmin / ext in blocks); read while skip != 0
+    VoxelTableView table;             // K71's
+    VoxelTableView blocks;            // K74's (vals null; cmin / ext in blocks); read while skip != 0
     int skip;
     float* out_depth;                // n
     float *out_xyz, *out_normals;    // n x 3 each; either may be null

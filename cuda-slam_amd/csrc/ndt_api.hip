@@ -17,8 +17,6 @@ using namespace mislam;
 
 namespace {
 
-constexpr long long NDT_MAX_EXTENT = 1ll << 20;      // listed voxels per axis between the lowest and the highest one: 20 bits of the key each
-
 bool finite_f(float v) { return std::fabs(v) < INFINITY; }      // (false for NaN)
 
 }  // namespace
@@ -129,8 +127,7 @@ int ndt_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* befo
 {
     mi_ctx::NdtBuffers& b = c->ndt;
     const size_t np = (size_t)n, vp = (size_t)nv;
-    unsigned long long capacity = 2;
-    while (capacity < 2 * (unsigned long long)nv) capacity <<= 1;
+    const unsigned long long capacity = voxel_table_slots((unsigned long long)nv, 2);
     double constants[4];
     ndt_constants((double)voxel_size, (double)outlier_ratio, constants);
     for (int i = 0; i < 4; i++)
@@ -181,21 +178,18 @@ int ndt_prepare(mi_ctx* c, const char* who, StageClock& clock, const float* befo
         return MI_ERR_INVALID_ARG;
     }
     NdtMapView map{};
-    for (int k = 0; k < 3; k++) {
-        const long long extent = (long long)hs->cmax[k] - (long long)hs->cmin[k] + 1;
-        if (extent < 1 || extent > NDT_MAX_EXTENT) {
-            set_error("%s: the listed voxels span %lld along axis %d (limit 2^20 = %lld)", who, extent, k, NDT_MAX_EXTENT);
-            return MI_ERR_INVALID_ARG;
-        }
-        map.cmin[k] = hs->cmin[k]; map.ext[k] = (int)extent;
+    const int wide = voxel_table_frame(&map.table, hs->cmin, hs->cmax);
+    if (wide >= 0) {
+        set_error("%s: the listed voxels span %lld along axis %d (limit 2^20 = %lld)", who, voxel_extent(hs->cmin, hs->cmax, wide), wide, VOXEL_MAX_EXTENT);
+        return MI_ERR_INVALID_ARG;
     }
-    map.keys = b.hkeys.p; map.vals = b.hvals.p; map.mask = capacity - 1;
+    voxel_table_bind(&map.table, b.hkeys.p, b.hvals.p, capacity);
     map.mean = b.mean4.p; map.icov = b.icov4.p;
     const bool any = hs->with_distribution > 0;
     float centre[3] = {0.f, 0.f, 0.f};       // (no row with a distribution: no term can arise, and the centre is never used)
     for (int k = 0; k < 3 && any; k++) centre[k] = 0.5f * (ndt_key_float(hs->lo[k]) + ndt_key_float(hs->hi[k]));
 
-    MI_HIP(hipMemsetAsync(b.hkeys.p, 0xff, sizeof(unsigned long long) * (size_t)capacity, c->stream));      // every slot NDT_KEY_EMPTY
+    MI_HIP(voxel_table_clear(b.hkeys.p, capacity, c->stream));
     if (!bufs.fits()) {
         set_error("internal: %s buffers shorter than the launch", who);
         return MI_ERR_STATE;

@@ -8,9 +8,8 @@
 //   K29 check     one lane per LISTED voxel of a registration: finiteness of its mean and matrix, the coordinates' range and strict order
 //                 against the row before, every lowest bad row by an integer atomicMin; the coordinates' range and the bounding box of the
 //                 means of the rows with a distribution by integer atomicMin / atomicMax (floats as ordered keys); the repack into float4.
-//   K30 table     open addressing, linear probing, capacity a power of two >= 2 nv: one lane per listed voxel with a distribution claims
-//                 the first free slot from its hash by a 64-bit compare-and-swap.  Keys are unique (the list is strictly ascending), so
-//                 a lookup finds the same row whatever order the lanes arrived in.
+//   K30 table     one lane per listed voxel with a distribution claims its slot in the table of voxel_table.hpp, 2 slots per listed voxel.
+//                 Keys are unique (the list is strictly ascending), so a lookup finds the same row whatever order the lanes arrived in.
 //   K31 step      the lane's move and row are pose_step.hpp's.  The voxel of q by voxel_axis (mi_voxel_index's arithmetic), then per offset of the neighbourhood a
 //                 box test on the voxel index, the key, the probe and -- on a hit -- ndt_term.hpp's term, folded into ten running fp64
 //                 numbers: A = sum w M (6), b = sum w Md (3), E = sum e.  With P = q - c0 the row's entries are K17's 21 + 6 from A and
@@ -212,13 +211,6 @@ __global__ __launch_bounds__(256) void ndt_check_voxels_kernel(const int* __rest
 }
 
 // ---- K30.  (the driver has checked the range: every coordinate minus its axis minimum is in [0, ext) with ext <= 2^20)
-__device__ __forceinline__ unsigned long long ndt_hash(unsigned long long key)      // splitmix64's finaliser
-{
-    key ^= key >> 30; key *= 0xbf58476d1ce4e5b9ull;
-    key ^= key >> 27; key *= 0x94d049bb133111ebull;
-    return key ^ (key >> 31);
-}
-
 __global__ __launch_bounds__(256) void ndt_hash_build_kernel(const int* __restrict__ coord, const float4* __restrict__ icov4, int nv, NdtMapView map,
                                                              unsigned long long* __restrict__ keys, int* __restrict__ vals)
 {
@@ -226,30 +218,9 @@ __global__ __launch_bounds__(256) void ndt_hash_build_kernel(const int* __restri
     if (i >= nv) return;
     const float4 m0 = icov4[2 * (size_t)i], m1 = icov4[2 * (size_t)i + 1];
     if (m0.x == 0.f && m0.y == 0.f && m0.z == 0.f && m1.x == 0.f && m1.y == 0.f && m1.z == 0.f) return;      // no distribution: never found
-    const unsigned long long key = (unsigned long long)(coord[3 * (size_t)i] - map.cmin[0]) | (unsigned long long)(coord[3 * (size_t)i + 1] - map.cmin[1]) << 20 |
-                                   (unsigned long long)(coord[3 * (size_t)i + 2] - map.cmin[2]) << 40;
-    unsigned long long slot = ndt_hash(key) & map.mask;
-    for (unsigned long long probe = 0; probe <= map.mask; probe++) {             // (at most nv of the >= 2 nv slots are ever taken)
-        const unsigned long long old = atomicCAS(&keys[slot], NDT_KEY_EMPTY, key);
-        if (old == NDT_KEY_EMPTY || old == key) { vals[slot] = i; return; }
-        slot = (slot + 1) & map.mask;
-    }
-}
-
-// the row of voxel (cx, cy, cz) in the caller's list, or -1: not listed, or listed without a distribution
-__device__ __forceinline__ int ndt_lookup(const NdtMapView& map, int cx, int cy, int cz)
-{
-    const long long rx = (long long)cx - map.cmin[0], ry = (long long)cy - map.cmin[1], rz = (long long)cz - map.cmin[2];
-    if (rx < 0 || rx >= map.ext[0] || ry < 0 || ry >= map.ext[1] || rz < 0 || rz >= map.ext[2]) return -1;      // outside the listed box: no key is formed
-    const unsigned long long key = (unsigned long long)rx | (unsigned long long)ry << 20 | (unsigned long long)rz << 40;
-    unsigned long long slot = ndt_hash(key) & map.mask;
-    for (unsigned long long probe = 0; probe <= map.mask; probe++) {
-        const unsigned long long k = map.keys[slot];
-        if (k == key) return map.vals[slot];
-        if (k == NDT_KEY_EMPTY) return -1;
-        slot = (slot + 1) & map.mask;
-    }
-    return -1;
+    const VoxelTableView& t = map.table;
+    const long long slot = voxel_claim(keys, t.mask, voxel_key(coord[3 * (size_t)i] - t.cmin[0], coord[3 * (size_t)i + 1] - t.cmin[1], coord[3 * (size_t)i + 2] - t.cmin[2]));
+    if (slot >= 0) vals[slot] = i;           // (at most nv of the >= 2 nv slots are ever taken)
 }
 
 // ---- K31
@@ -283,7 +254,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void ndt_step_kernel(NdtStepArgs a)
                     dx = axis == 0 ? step : 0; dy = axis == 1 ? step : 0; dz = axis == 2 ? step : 0;
                 }
                 if (NB == 27) { dz = o / 9 - 1; dy = (o / 3) % 3 - 1; dx = o % 3 - 1; }      // (dz, dy, dx) ascending
-                const int row = ndt_lookup(a.map, c[0] + dx, c[1] + dy, c[2] + dz);
+                const int row = voxel_row(a.map.table, c[0] + dx, c[1] + dy, c[2] + dz);      // -1: not listed, or listed without a distribution
                 if (dx == 0 && dy == 0 && dz == 0) own = row;
                 if (row < 0) continue;
                 const float4 mu4 = a.map.mean[row], m0 = a.map.icov[2 * (size_t)row], m1 = a.map.icov[2 * (size_t)row + 1];
@@ -332,7 +303,7 @@ hipError_t ndt_check_voxels(const int* coord, const float* mean, const float* ic
 
 hipError_t ndt_hash_build(const int* coord, const float4* icov4, int nv, const NdtMapView& map, unsigned long long* keys, int* vals, hipStream_t s)
 {
-    if (nv < 1 || map.mask + 1 < 2 * (unsigned long long)nv || (map.mask & (map.mask + 1)) != 0) return hipErrorInvalidValue;
+    if (nv < 1 || !voxel_table_holds(map.table.mask, (unsigned long long)nv, 2)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ndt_hash_build_kernel, dim3((nv - 1) / 256 + 1), dim3(256), 0, s, coord, icov4, nv, map, keys, vals);
     return hipGetLastError();
 }

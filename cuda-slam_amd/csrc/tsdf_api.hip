@@ -40,14 +40,13 @@ static int tsdf_refuse_map(const char* who, const char* coord_name, const char* 
     }
 }
 
-static int tsdf_refuse_extent(const char* who, const int cmin[3], const int cmax[3])
+// the frame of a table of the occupied range (nv > 0: every extent is 1 at least)
+static int tsdf_refuse_extent(const char* who, const int cmin[3], const int cmax[3], VoxelTableView* t)
 {
-    for (int a = 0; a < 3; a++)
-        if ((long long)cmax[a] - (long long)cmin[a] + 1 > (1LL << 20)) {
-            set_error("%s: the occupied extent along axis %d is %lld voxels, above 2^20", who, a, (long long)cmax[a] - (long long)cmin[a] + 1);
-            return MI_ERR_INVALID_ARG;
-        }
-    return MI_OK;
+    const int a = voxel_table_frame(t, cmin, cmax);
+    if (a < 0) return MI_OK;
+    set_error("%s: the occupied extent along axis %d is %lld voxels, above 2^20", who, a, voxel_extent(cmin, cmax, a));
+    return MI_ERR_INVALID_ARG;
 }
 
 static bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
@@ -163,7 +162,8 @@ extern "C" int mi_tsdf_integrate(mi_ctx* c, const float* scans_xyz, const long l
         clock.finish();
         return MI_OK;
     }
-    MI_TRY(tsdf_refuse_extent(who, cmin, cmax));
+    VoxelTableView frame{};                  // (the sort's keys are per axis: only the extent rule is the table's)
+    MI_TRY(tsdf_refuse_extent(who, cmin, cmax, &frame));
 
     const int n = (int)entries_ll;           // (< 2^31: checked above)
     const size_t ne = (size_t)n;
@@ -246,8 +246,9 @@ extern "C" int mi_tsdf_extract(mi_ctx* c, const int* coord, const float* tsdf, c
     StageClock clock(c, b.ms);         // mi_tsdf_times
 
     int cmin[3] = {0, 0, 0}, cmax[3] = {0, 0, 0};
+    TsdfCrossArgs a{};
     MI_TRY(tsdf_refuse_map(who, "coord", "tsdf", "weight", coord, tsdf, weight, nv, cmin, cmax));
-    if (nv > 0) MI_TRY(tsdf_refuse_extent(who, cmin, cmax));
+    if (nv > 0) MI_TRY(tsdf_refuse_extent(who, cmin, cmax, &a.table));
     MI_TRY(clock.mark(2));
     if (nv == 0) {                           // the empty map has no surface
         *out_n = 0;
@@ -255,9 +256,7 @@ extern "C" int mi_tsdf_extract(mi_ctx* c, const int* coord, const float* tsdf, c
         return MI_OK;
     }
 
-    const size_t nm = (size_t)nv;
-    size_t slots = 2;
-    while (slots < 2 * nm) slots <<= 1;
+    const size_t nm = (size_t)nv, slots = (size_t)voxel_table_slots(nm, 2);
     CallBuffers bufs;
     MI_TRY(bufs.need(b.in_coord, 3 * nm)); MI_TRY(bufs.need(b.in_tsdf, nm)); MI_TRY(bufs.need(b.in_weight, nm));
     MI_TRY(bufs.need(b.hkeys, slots)); MI_TRY(bufs.need(b.hvals, slots));
@@ -269,13 +268,12 @@ extern "C" int mi_tsdf_extract(mi_ctx* c, const int* coord, const float* tsdf, c
     MI_TRY(clock.mark(1));
 
     if (!bufs.fits()) { set_error("internal: %s buffers shorter than the launch", who); return MI_ERR_STATE; }
-    TsdfCrossArgs a{};
     a.coord = b.in_coord.p; a.tsdf = b.in_tsdf.p; a.weight = b.in_weight.p; a.nv = nv;
-    for (int k = 0; k < 3; k++) { a.origin[k] = origin3[k]; a.table.cmin[k] = cmin[k]; a.table.ext[k] = cmax[k] - cmin[k] + 1; }
+    for (int k = 0; k < 3; k++) a.origin[k] = origin3[k];
     a.voxel = voxel_size; a.min_weight = min_weight;
-    a.table.keys = b.hkeys.p; a.table.vals = b.hvals.p; a.table.mask = (unsigned long long)slots - 1ull;
+    voxel_table_bind(&a.table, b.hkeys.p, b.hvals.p, slots);
     a.count = b.count.p;
-    MI_HIP(hipMemsetAsync(b.hkeys.p, 0xff, sizeof(unsigned long long) * slots, c->stream));       // every slot free
+    MI_HIP(voxel_table_clear(b.hkeys.p, slots, c->stream));
     MI_HIP(tsdf_table(b.in_coord.p, b.in_weight.p, nv, min_weight, a.table, b.hkeys.p, b.hvals.p, c->stream));
     MI_TRY(clock.mark(3));
     {
@@ -354,8 +352,9 @@ extern "C" int mi_tsdf_raycast(mi_ctx* c, const int* coord, const float* tsdf, c
     StageClock clock(c, b.ms);         // mi_tsdf_times
 
     int cmin[3] = {0, 0, 0}, cmax[3] = {0, 0, 0};
+    TsdfCastArgs a{};
     MI_TRY(tsdf_refuse_map(who, "coord", "tsdf", "weight", coord, tsdf, weight, nv, cmin, cmax));
-    if (nv > 0) MI_TRY(tsdf_refuse_extent(who, cmin, cmax));
+    if (nv > 0) MI_TRY(tsdf_refuse_extent(who, cmin, cmax, &a.table));
     MI_TRY(clock.mark(2));
     const size_t nr = (size_t)n, nm = (size_t)nv;
     auto every_ray_misses = [&]() {
@@ -367,8 +366,7 @@ extern "C" int mi_tsdf_raycast(mi_ctx* c, const int* coord, const float* tsdf, c
     };
     if (nv == 0) return every_ray_misses();  // the empty map
 
-    size_t slots = 2;
-    while (slots < 2 * nm) slots <<= 1;
+    const size_t slots = (size_t)voxel_table_slots(nm, 2);
     const bool skip = p.visit_every_sample == 0 && tsdf_cast_skip_sound(T, origin3, p.voxel_size, p.max_range);
     CallBuffers bufs;
     MI_TRY(bufs.need(b.in_coord, 3 * nm)); MI_TRY(bufs.need(b.in_tsdf, nm)); MI_TRY(bufs.need(b.in_weight, nm));
@@ -384,15 +382,14 @@ extern "C" int mi_tsdf_raycast(mi_ctx* c, const int* coord, const float* tsdf, c
     MI_TRY(clock.mark(1));
 
     if (!bufs.fits()) { set_error("internal: %s buffers shorter than the launch", who); return MI_ERR_STATE; }
-    TsdfCastArgs a{};
     a.dirs = b.xyz.p; a.n = n; a.has_pose = T ? 1 : 0;
     for (int k = 0; k < 16; k++) a.pose[k] = T ? T[k] : 0.f;
-    for (int k = 0; k < 3; k++) { a.origin[k] = origin3[k]; a.table.cmin[k] = cmin[k]; a.table.ext[k] = cmax[k] - cmin[k] + 1; }
+    for (int k = 0; k < 3; k++) a.origin[k] = origin3[k];
     a.voxel = p.voxel_size; a.min_range = p.min_range; a.steps = (int)steps; a.tsdf = b.in_tsdf.p;
-    a.table.keys = b.hkeys.p; a.table.vals = b.hvals.p; a.table.mask = (unsigned long long)slots - 1ull;
+    voxel_table_bind(&a.table, b.hkeys.p, b.hvals.p, slots);
     a.out_depth = b.out_depth.p; a.out_xyz = out_xyz ? b.out_xyz.p : nullptr; a.out_normals = out_normals ? b.out_normals.p : nullptr;
     a.hits = b.cast_counts.p + 1;
-    MI_HIP(hipMemsetAsync(b.hkeys.p, 0xff, sizeof(unsigned long long) * slots, c->stream));       // every slot free
+    MI_HIP(voxel_table_clear(b.hkeys.p, slots, c->stream));
     MI_HIP(hipMemsetAsync(b.cast_counts.p, 0, 2 * sizeof(int), c->stream));
     MI_HIP(tsdf_table(b.in_coord.p, b.in_weight.p, nv, p.min_weight, a.table, b.hkeys.p, b.hvals.p, c->stream));
     MI_TRY(clock.mark(3));
@@ -404,21 +401,20 @@ extern "C" int mi_tsdf_raycast(mi_ctx* c, const int* coord, const float* tsdf, c
             a.blocks.cmin[k] = (cmin[k] >> TSDF_SKIP_SHIFT) - 1;
             a.blocks.ext[k] = (cmax[k] >> TSDF_SKIP_SHIFT) - (cmin[k] >> TSDF_SKIP_SHIFT) + 3;
         }
-        a.blocks.mask = (unsigned long long)slots - 1ull;
-        MI_HIP(hipMemsetAsync(b.block_held.p, 0xff, sizeof(unsigned long long) * slots, c->stream));
+        voxel_table_bind(&a.blocks, b.block_held.p, nullptr, slots);
+        MI_HIP(voxel_table_clear(b.block_held.p, slots, c->stream));
         MI_HIP(tsdf_blocks(b.in_coord.p, b.in_weight.p, nv, p.min_weight, a.blocks, b.block_held.p, b.cast_counts.p, c->stream));
         MI_HIP(hipMemcpyAsync(h_count, b.cast_counts.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         MI_HIP(hipStreamSynchronize(c->stream));
         const int held = *h_count;
         if (held < 0 || held > nv) { set_error("internal: %s found %d blocks among %d voxels", who, held, nv); return MI_ERR_STATE; }
         if (held == 0) return every_ray_misses();       // no voxel is observed at this min_weight
-        size_t marked = 2;
-        while (marked < 54 * (size_t)held) marked <<= 1;
+        const size_t marked = (size_t)voxel_table_slots((unsigned long long)held, 54);
         MI_TRY(bufs.need(b.block_keys, marked));
         if (!bufs.fits()) { set_error("internal: %s block table shorter than the launch", who); return MI_ERR_STATE; }
-        MI_HIP(hipMemsetAsync(b.block_keys.p, 0xff, sizeof(unsigned long long) * marked, c->stream));
+        MI_HIP(voxel_table_clear(b.block_keys.p, marked, c->stream));
         MI_HIP(tsdf_blocks_dilate(b.block_held.p, (unsigned long long)slots, held, b.block_keys.p, (unsigned long long)marked - 1ull, c->stream));
-        a.blocks.keys = b.block_keys.p; a.blocks.vals = nullptr; a.blocks.mask = (unsigned long long)marked - 1ull;
+        voxel_table_bind(&a.blocks, b.block_keys.p, nullptr, marked);
         a.skip = 1;
     }
     MI_TRY(clock.mark(4));

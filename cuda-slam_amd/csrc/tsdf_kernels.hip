@@ -156,49 +156,20 @@ hipError_t tsdf_fuse(const TsdfFuseArgs& a, hipStream_t s)
     return hipGetLastError();
 }
 
-// ---- K71, K72.  (the driver has checked the range: every coordinate minus its axis minimum is in [0, ext) with ext <= 2^20)
-constexpr unsigned long long TSDF_KEY_EMPTY = 0xffffffffffffffffull;
-__device__ __forceinline__ unsigned long long tsdf_hash(unsigned long long key)      // splitmix64's finaliser, as the NDT map's table
-{
-    key ^= key >> 30; key *= 0xbf58476d1ce4e5b9ull;
-    key ^= key >> 27; key *= 0x94d049bb133111ebull;
-    return key ^ (key >> 31);
-}
-
+// ---- K71, K72: the observed voxels in voxel_table.hpp's table, voxel_row the row of one or -1.  (the driver has checked the range: every
+// coordinate minus its axis minimum is in [0, ext) with ext <= 2^20)
 __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_table_kernel(const int* __restrict__ coord, const float* __restrict__ weight, int nv, float min_weight,
-                                                                TsdfTableView t, unsigned long long* __restrict__ keys, int* __restrict__ vals)
+                                                                VoxelTableView t, unsigned long long* __restrict__ keys, int* __restrict__ vals)
 {
     const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
     if (i >= nv || !(weight[i] >= min_weight)) return;
-    const unsigned long long key = (unsigned long long)(coord[3 * (size_t)i] - t.cmin[0]) | (unsigned long long)(coord[3 * (size_t)i + 1] - t.cmin[1]) << 20 |
-                                   (unsigned long long)(coord[3 * (size_t)i + 2] - t.cmin[2]) << 40;
-    unsigned long long slot = tsdf_hash(key) & t.mask;
-    for (unsigned long long probe = 0; probe <= t.mask; probe++) {               // (at most nv of the >= 2 nv slots are ever taken)
-        const unsigned long long old = atomicCAS(&keys[slot], TSDF_KEY_EMPTY, key);
-        if (old == TSDF_KEY_EMPTY || old == key) { vals[slot] = i; return; }
-        slot = (slot + 1) & t.mask;
-    }
+    const long long slot = voxel_claim(keys, t.mask, voxel_key(coord[3 * (size_t)i] - t.cmin[0], coord[3 * (size_t)i + 1] - t.cmin[1], coord[3 * (size_t)i + 2] - t.cmin[2]));
+    if (slot >= 0) vals[slot] = i;           // (at most nv of the >= 2 nv slots are ever taken)
 }
 
-// the row of the observed voxel (cx, cy, cz), or -1
-__device__ __forceinline__ int tsdf_lookup(const TsdfTableView& t, int cx, int cy, int cz)
+hipError_t tsdf_table(const int* coord, const float* weight, int nv, float min_weight, const VoxelTableView& t, unsigned long long* keys, int* vals, hipStream_t s)
 {
-    const long long rx = (long long)cx - t.cmin[0], ry = (long long)cy - t.cmin[1], rz = (long long)cz - t.cmin[2];
-    if (rx < 0 || rx >= t.ext[0] || ry < 0 || ry >= t.ext[1] || rz < 0 || rz >= t.ext[2]) return -1;      // outside the listed box: no key is formed
-    const unsigned long long key = (unsigned long long)rx | (unsigned long long)ry << 20 | (unsigned long long)rz << 40;
-    unsigned long long slot = tsdf_hash(key) & t.mask;
-    for (unsigned long long probe = 0; probe <= t.mask; probe++) {
-        const unsigned long long k = t.keys[slot];
-        if (k == key) return t.vals[slot];
-        if (k == TSDF_KEY_EMPTY) return -1;
-        slot = (slot + 1) & t.mask;
-    }
-    return -1;
-}
-
-hipError_t tsdf_table(const int* coord, const float* weight, int nv, float min_weight, const TsdfTableView& t, unsigned long long* keys, int* vals, hipStream_t s)
-{
-    if (nv < 1 || t.mask + 1 < 2 * (unsigned long long)nv || (t.mask & (t.mask + 1)) != 0 || !coord || !weight || !keys || !vals) return hipErrorInvalidValue;
+    if (nv < 1 || !voxel_table_holds(t.mask, (unsigned long long)nv, 2) || !coord || !weight || !keys || !vals) return hipErrorInvalidValue;
     hipLaunchKernelGGL(tsdf_table_kernel, dim3((nv - 1) / TSDF_BLOCK + 1), dim3(TSDF_BLOCK), 0, s, coord, weight, nv, min_weight, t, keys, vals);
     return hipGetLastError();
 }
@@ -209,7 +180,7 @@ __device__ __forceinline__ void tsdf_gradient_at(const TsdfCrossArgs& a, int cx,
 #pragma unroll
     for (int ax = 0; ax < 3; ax++) {
         const int dx = ax == 0, dy = ax == 1, dz = ax == 2;
-        const int m = tsdf_lookup(a.table, cx - dx, cy - dy, cz - dz), p = tsdf_lookup(a.table, cx + dx, cy + dy, cz + dz);
+        const int m = voxel_row(a.table, cx - dx, cy - dy, cz - dz), p = voxel_row(a.table, cx + dx, cy + dy, cz + dz);
         g[ax] = tsdf_gradient(m >= 0, m >= 0 ? (double)a.tsdf[m] : 0.0, f, p >= 0, p >= 0 ? (double)a.tsdf[p] : 0.0);
     }
 }
@@ -228,7 +199,7 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_crossings_kernel(TsdfCrossArg
 #pragma unroll
         for (int ax = 0; ax < 3; ax++) {
             const int dx = ax == 0, dy = ax == 1, dz = ax == 2;
-            const int j = tsdf_lookup(a.table, cx + dx, cy + dy, cz + dz);
+            const int j = voxel_row(a.table, cx + dx, cy + dy, cz + dz);
             if (j < 0) continue;
             const double f1 = (double)a.tsdf[j];
             double r;
@@ -264,34 +235,22 @@ hipError_t tsdf_crossings(const TsdfCrossArgs& a, bool fill, hipStream_t s)
 }
 
 // ---- K73, K74: the coarse table of mi_tsdf_raycast's empty-space skipping.  A block is 8^3 voxels, its coordinate the voxel's >> 3; the
-// tables have K71's packing and hash and no values.  Every key of a lane is in [0, ext) of its table (the driver sizes ext from the map's
+// tables are voxel_table.hpp's without values.  Every key of a lane is in [0, ext) of its table (the driver sizes ext from the map's
 // range plus one block on either side), every slot index is masked, and at most half the slots are ever taken.
-__device__ __forceinline__ bool tsdf_key_insert(unsigned long long* __restrict__ keys, unsigned long long mask, unsigned long long key)      // true: the key is new
-{
-    unsigned long long slot = tsdf_hash(key) & mask;
-    for (unsigned long long probe = 0; probe <= mask; probe++) {
-        const unsigned long long old = atomicCAS(&keys[slot], TSDF_KEY_EMPTY, key);
-        if (old == TSDF_KEY_EMPTY) return true;
-        if (old == key) return false;
-        slot = (slot + 1) & mask;
-    }
-    return false;
-}
-
 __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_blocks_kernel(const int* __restrict__ coord, const float* __restrict__ weight, int nv, float min_weight,
-                                                                 TsdfTableView t, unsigned long long* __restrict__ keys, int* __restrict__ count)
+                                                                 VoxelTableView t, unsigned long long* __restrict__ keys, int* __restrict__ count)
 {
     const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
     if (i >= nv || !(weight[i] >= min_weight)) return;
-    const unsigned long long key = (unsigned long long)((coord[3 * (size_t)i] >> TSDF_SKIP_SHIFT) - t.cmin[0]) |
-                                   (unsigned long long)((coord[3 * (size_t)i + 1] >> TSDF_SKIP_SHIFT) - t.cmin[1]) << 20 |
-                                   (unsigned long long)((coord[3 * (size_t)i + 2] >> TSDF_SKIP_SHIFT) - t.cmin[2]) << 40;
-    if (tsdf_key_insert(keys, t.mask, key)) atomicAdd(count, 1);
+    bool fresh;
+    voxel_claim(keys, t.mask, voxel_key((coord[3 * (size_t)i] >> TSDF_SKIP_SHIFT) - t.cmin[0], (coord[3 * (size_t)i + 1] >> TSDF_SKIP_SHIFT) - t.cmin[1],
+                                        (coord[3 * (size_t)i + 2] >> TSDF_SKIP_SHIFT) - t.cmin[2]), &fresh);
+    if (fresh) atomicAdd(count, 1);
 }
 
-hipError_t tsdf_blocks(const int* coord, const float* weight, int nv, float min_weight, const TsdfTableView& t, unsigned long long* keys, int* count, hipStream_t s)
+hipError_t tsdf_blocks(const int* coord, const float* weight, int nv, float min_weight, const VoxelTableView& t, unsigned long long* keys, int* count, hipStream_t s)
 {
-    if (nv < 1 || t.mask + 1 < 2 * (unsigned long long)nv || (t.mask & (t.mask + 1)) != 0 || !coord || !weight || !keys || !count) return hipErrorInvalidValue;
+    if (nv < 1 || !voxel_table_holds(t.mask, (unsigned long long)nv, 2) || !coord || !weight || !keys || !count) return hipErrorInvalidValue;
     hipLaunchKernelGGL(tsdf_blocks_kernel, dim3((nv - 1) / TSDF_BLOCK + 1), dim3(TSDF_BLOCK), 0, s, coord, weight, nv, min_weight, t, keys, count);
     return hipGetLastError();
 }
@@ -304,38 +263,21 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_blocks_dilate_kernel(const un
     const unsigned long long i = (unsigned long long)blockIdx.x * TSDF_BLOCK + threadIdx.x;
     if (i >= slots) return;
     const unsigned long long key = held[i];
-    if (key == TSDF_KEY_EMPTY) return;
-    const long long bx = (long long)(key & 0xfffffull), by = (long long)(key >> 20 & 0xfffffull), bz = (long long)(key >> 40 & 0xfffffull);
+    if (key == VOXEL_KEY_EMPTY) return;
+    const int bx = voxel_key_axis(key, 0), by = voxel_key_axis(key, 1), bz = voxel_key_axis(key, 2);
     for (int dz = -1; dz <= 1; dz++)
         for (int dy = -1; dy <= 1; dy++)
-            for (int dx = -1; dx <= 1; dx++)
-                tsdf_key_insert(keys, mask, (unsigned long long)(bx + dx) | (unsigned long long)(by + dy) << 20 | (unsigned long long)(bz + dz) << 40);
+            for (int dx = -1; dx <= 1; dx++) voxel_claim(keys, mask, voxel_key(bx + dx, by + dy, bz + dz));
 }
 
 hipError_t tsdf_blocks_dilate(const unsigned long long* held, unsigned long long slots, int blocks, unsigned long long* keys, unsigned long long mask, hipStream_t s)
 {
-    if (slots < 1 || slots > (1ull << 32) || blocks < 1 || mask + 1 < 54ull * (unsigned long long)blocks || (mask & (mask + 1)) != 0 || !held || !keys) return hipErrorInvalidValue;
+    if (slots < 1 || slots > (1ull << 32) || blocks < 1 || !voxel_table_holds(mask, (unsigned long long)blocks, 54) || !held || !keys) return hipErrorInvalidValue;
     hipLaunchKernelGGL(tsdf_blocks_dilate_kernel, dim3((unsigned int)((slots - 1) / TSDF_BLOCK + 1)), dim3(TSDF_BLOCK), 0, s, held, slots, keys, mask);
     return hipGetLastError();
 }
 
-// is the block (bx, by, bz) in K74's table?
-__device__ __forceinline__ bool tsdf_block_marked(const TsdfTableView& t, int bx, int by, int bz)
-{
-    const long long rx = (long long)bx - t.cmin[0], ry = (long long)by - t.cmin[1], rz = (long long)bz - t.cmin[2];
-    if (rx < 0 || rx >= t.ext[0] || ry < 0 || ry >= t.ext[1] || rz < 0 || rz >= t.ext[2]) return false;
-    const unsigned long long key = (unsigned long long)rx | (unsigned long long)ry << 20 | (unsigned long long)rz << 40;
-    unsigned long long slot = tsdf_hash(key) & t.mask;
-    for (unsigned long long probe = 0; probe <= t.mask; probe++) {
-        const unsigned long long k = t.keys[slot];
-        if (k == key) return true;
-        if (k == TSDF_KEY_EMPTY) return false;
-        slot = (slot + 1) & t.mask;
-    }
-    return false;
-}
-
-// ---- K75: one lane per ray, tsdf_cast.hpp's march over K71's table.  Row i of every output is ray i's; a miss writes zeros.
+// ---- K75: one lane per ray, tsdf_cast.hpp's march over K71's table, the blocks asked of K74's.  Row i of every output is ray i's; a miss writes zeros.
 __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cast_kernel(TsdfCastArgs a)
 {
     const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
@@ -349,8 +291,8 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_cast_kernel(TsdfCastArgs a)
             TsdfCastGeom g;
             g.origin[0] = a.origin[0]; g.origin[1] = a.origin[1]; g.origin[2] = a.origin[2];
             g.voxel = a.voxel; g.min_range = a.min_range; g.steps = a.steps;
-            hit = tsdf_cast(ray, g, a.tsdf, [&](int cx, int cy, int cz) { return tsdf_lookup(a.table, cx, cy, cz); }, a.skip != 0,
-                            [&](int bx, int by, int bz) { return tsdf_block_marked(a.blocks, bx, by, bz); }, &h);
+            hit = tsdf_cast(ray, g, a.tsdf, [&](int cx, int cy, int cz) { return voxel_row(a.table, cx, cy, cz); }, a.skip != 0,
+                            [&](int bx, int by, int bz) { return voxel_present(a.blocks, bx, by, bz); }, &h);
         }
         a.out_depth[i] = h.depth;
         if (a.out_xyz) { a.out_xyz[3 * (size_t)i] = h.xyz[0]; a.out_xyz[3 * (size_t)i + 1] = h.xyz[1]; a.out_xyz[3 * (size_t)i + 2] = h.xyz[2]; }

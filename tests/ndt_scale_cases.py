@@ -1,9 +1,9 @@
 """The cases of tests/test_gpu_ndt_scale.py and what they share: clouds whose SORTED order is known run by run (K27's scan and fix-up at
 the tile and wave edges), clouds at the sizes and extents where the voxel front takes its other paths, voxel maps made by hand (K30's
-table and ndt_lookup at its limits) with their queries, the pose that sends a third of a cloud where voxel_axis refuses it -- and the numpy
+table and its look-up, voxel_table.hpp, at their limits) with their queries, the pose that sends a third of a cloud where voxel_axis refuses it -- and the numpy
 restatements that tests/test_ndt_scale_regimes.py holds every case against, so that a case is shown to be what it is named for without a
 device: the runs' starts and counts (ndt_reference.voxels), and, for the wrap map alone, the key, the hash and the capacity of
-csrc/ndt_kernels.hip and csrc/ndt_api.hip.
+csrc/voxel_table.hpp.
 
 No tolerance is introduced here: the matrices go through check_voxels and the sums through assert_sums / check_system of
 tests/test_gpu_ndt.py with their bounds."""
@@ -17,7 +17,7 @@ import plane_reference as P
 TILE, WAVE = 256, 64                 # VOX_SUM_TILE (csrc/kernels.h): sorted positions per workgroup of K27's scan, one per lane; lanes per wave
 FIXUP_LANES = 64                     # ndt_scatter_fixup_kernel: a lane adds the fronts of tiles first + 1 + lane, + 64, ...
 SORT_ONE_PASS = 4096 * 64            # keys up to which the radix sort takes its small path (tests/test_gpu_sort.py)
-MAX_EXTENT = 1 << 20                 # NDT_MAX_EXTENT, VOX_MAX_EXTENT: listed / occupied voxels per axis
+MAX_EXTENT = 1 << 20                 # VOXEL_MAX_EXTENT, VOX_MAX_EXTENT: listed / occupied voxels per axis
 PACKED_EXTENT = 1 << 10              # VOX_PACKED_EXTENT: up to here on every axis the voxel front sorts one packed key
 
 
@@ -219,7 +219,8 @@ def far_map(axis):
     return vox, map_queries(vox, 271 + axis, turned(extra))
 
 
-# the table, restated for the wrap map alone: ndt_hash_build_kernel's key, ndt_hash, and ndt_prepare's capacity
+# the table, restated for the wrap map alone: voxel_table.hpp's voxel_key, voxel_hash and voxel_table_slots(nv, 2)
+# (tests/test_voxel_table.py holds the header itself against these, on the host)
 def table_keys(coord, shifts=(0, 20, 40), cmin=None):
     """the keys of voxel coordinates inside the listed box; cmin None: the coordinates are the list itself"""
     rel = np.asarray(coord, np.int64) - (np.asarray(coord, np.int64).min(axis=0) if cmin is None else np.asarray(cmin, np.int64))

@@ -1,6 +1,6 @@
 """mi_ndt_voxels and mi_ndt_system beyond the one small scene of tests/test_gpu_ndt.py: K27's scan and fix-up at the tile and wave edges
 and over more tiles than the fix-up's wave has lanes, the voxel front's other sort paths and sizes, a cloud far from the origin, K28's
-further workgroups, K30's table and ndt_lookup on maps made by hand (a load of exactly one half, a probe chain past the last slot, an
+further workgroups, K30's table and its look-up (voxel_table.hpp: voxel_claim, voxel_row) on maps made by hand (a load of exactly one half, a probe chain past the last slot, an
 extent of exactly 2^20 on every axis, coordinates down to -2^30 + 8, neighbours beyond either face of the listed box), K31's fold of up to
 27 terms into all 28 sums, and positions voxel_axis refuses.  The cases and the proof that each is what it is named for:
 tests/ndt_scale_cases.py, tests/test_ndt_scale_regimes.py.

@@ -2,16 +2,17 @@
 without a tolerance anywhere, with empty-space skipping and with every sample visited: ray counts around a wave and a workgroup; rays
 along the axes, in lattice planes, from inside the band, from behind and out of unobserved space on hand-made slabs; pinhole and spherical
 views of the corner room, also with the scene far from zero, where fp32 positions are as coarse as the voxels; the empty map, the optional
-outputs, refusals, hygiene, and the loop closed through mi_icp_plane_register."""
+outputs, refusals, hygiene, the loop closed through mi_icp_plane_register, and K71's table with a probe chain past its last slot."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
+import ndt_scale_cases as S
 import tsdf_raycast_reference as RC
 import tsdf_reference as R
-from test_gpu_tsdf import CORNER_ORIGIN, CORNER_POSES, corner_scan, pose, same, shell
+from test_gpu_tsdf import CORNER_ORIGIN, CORNER_POSES, check_extract, corner_scan, pose, same, shell
 from test_tsdf_reference import ORIGIN
 
 pytestmark = pytest.mark.gpu
@@ -290,3 +291,27 @@ def test_the_next_scan_registers_onto_the_raycast_surface(ctx, capi):
     found[:3, :3], found[:3, 3] = Rg, tg
     grown = ctx.tsdf_integrate([fifth], np.array([found]), origin, capi.tsdf_params(voxel_size=0.1, truncation=0.3), map=m)
     assert len(grown[0]) >= len(m[0]) and grown[2].max() > m[2].max()
+
+
+# ---- 9. the table at its limit: tests/ndt_scale_cases.py's wrap map as a TSDF map, every row observed, so that K71's keys, capacity and
+# home slots are the NDT case's and a probe chain goes past the last slot and on from slot 0
+def test_a_map_whose_probe_chain_passes_the_last_slot(ctx, capi):
+    vox = S.wrap_map()[0]
+    coord = vox["coord"]
+    coord = np.ascontiguousarray(coord[np.lexsort((coord[:, 0], coord[:, 1], coord[:, 2]))], np.int32)      # ascending by (cz, cy, cx)
+    nv = len(coord)
+    assert np.array_equal(coord, vox["coord"])                   # (so table_build's rows are this map's rows)
+    assert S.table_build(vox, np.arange(nv))[1] >= 1 and S.table_build(vox, np.arange(nv)[::-1])[1] >= 1
+    # values of either sign by the parity of the cell, so that every pair of listed neighbours has a crossing; every weight >= min_weight = 1
+    rng = np.random.default_rng(293)
+    tsdf = (rng.uniform(0.05, 1, nv) * np.where(coord.sum(axis=1) % 2 == 0, 1, -1)).astype(np.float32)
+    m = (coord, tsdf, rng.uniform(1, 3, nv).astype(np.float32))
+    origin, voxel = vox["origin"], float(vox["voxel"])
+    xyz, _ = check_extract(ctx, m, origin, voxel)
+    assert len(xyz) >= 30
+    # 350 rays from inside the box: five towards every crossing, a little apart, and 100 anywhere
+    T = np.eye(4, dtype=np.float32)
+    T[:3, 3] = (origin.astype(np.float64) + (coord.min(axis=0) + 20.3) * voxel).astype(np.float32)
+    aim = np.repeat(xyz.astype(np.float64) - T[:3, 3], 5, axis=0)
+    dirs = np.concatenate([aim * (1 + 0.01 * rng.normal(size=aim.shape)), rng.normal(size=(100, 3))]).astype(np.float32)
+    assert 20 <= check(ctx, capi, m, origin, voxel, 30.0, T, dirs)[3] < len(dirs)
