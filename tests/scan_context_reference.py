@@ -158,6 +158,103 @@ def shift_distances_twin(q, db):
     return out
 
 
+# ---- the same search at pair counts where emulating every fmaf of every pair is not affordable
+def e_bound(rings):
+    """An upper bound of |d - t| for any one (query, row, shift): d the contract's fp32 distance (shift_distances), t the plain-float64
+    twin's (shift_distances_twin, row_minima_twin).  Derived, with u = 2^-24 the unit roundoff of fp32; nothing here is measured.
+
+    1. The components.  A unit component is x = v / norm formed in fp64 (relative error below 3 * 2^-53) and rounded to fp32 once: x(1 + a),
+       |a| <= u.  (Below fp32's normal range the error is absolute, at most 2^-150, and never counts.)  The product of two rounded
+       components is exact inside the fmaf and equals x y (1 + a)(1 + b); the columns have unit length, so by Cauchy-Schwarz the absolute
+       exact products of one G(j, k) sum to at most 1, the rounded ones to at most (1 + u)^2, and the two sums differ by at most 2u + u^2.
+    2. The chain.  G is `rings` fmafs, c <- fl(c + p), the first of them onto 0: `rings` roundings, each a relative error of at most u
+       on a partial sum.  The standard bound is gamma |p|_1 with gamma = rings u / (1 - rings u), at most rings u (1 + u)^2 / (1 - rings u)
+       here.  With rings <= 32 everything of second order in 1. and 2. together is below 2^-38 < 0.0001 u.
+    3. The mean.  1 - G, the sum of at most 64 such terms and the division are fp64 on both sides: below 70 * 2^-53 < 2^-46 each; the twin's
+       own matrix product, whatever the order of its sums, is within rings * 2^-53 of the exact one.  A mean of terms moves by no more than
+       its terms do.
+    4. The distance.  |G| <= 1 + 2^-19, so the mean lies in [-2^-19, 2 + 2^-19], and its one rounding to fp32 is at most half a unit in the
+       last place of a number below 2 (2 itself is representable): 2^-24 = u.
+
+    Together: 2u + rings u + u + less than 0.001 u = (rings + 3.001) u.  (rings + 5) u, the estimate this bound was first stated with,
+    holds with 2u to spare and is what is returned: it is used as a margin, where more is safe.  The minimum over the shifts of a row obeys
+    the same bound as each shift does."""
+    return (rings + 5) * 2.0 ** -24
+
+
+def row_minima_twin(query, db, block=1 << 16):
+    """float64 [nq, nd]: every row's smallest twin distance over the shifts.  The arithmetic of shift_distances_twin, but G of a block of
+    queries against a block of rows is one matrix product ([queries x sectors, rings] by [rings, rows x sectors]: BLAS does the
+    nq * nd * sectors^2 * rings work), and shift s reads its wrapped diagonal G(j, (j + s) mod sectors) through a strided view of G laid
+    beside itself.  The number of pairs under a shift is a matrix product of the masks, exact in float64.  block: elements of G per product:
+    small enough for the block's temporaries to stay in the cache."""
+    from numpy.lib.stride_tricks import as_strided
+
+    def unit(d):
+        d = np.asarray(d, np.float64)
+        n = np.sqrt((d * d).sum(axis=-2, keepdims=True))
+        return np.where(n > 0, d / np.where(n > 0, n, 1.0), 0.0), n[..., 0, :] > 0
+    uq, mq = unit(query)
+    uc, mc = unit(db)
+    (nq, rings, sectors), nd = uq.shape, uc.shape[0]
+    rb = min(nd, max(1, block // sectors ** 2))
+    qb = min(nq, max(1, block // (rb * sectors ** 2)))
+    out = np.empty((nq, nd))
+    for r0 in range(0, nd, rb):
+        n = min(rb, nd - r0)
+        B = np.ascontiguousarray(uc[r0:r0 + n].transpose(1, 0, 2)).reshape(rings, n * sectors)
+        mc2 = np.concatenate([mc[r0:r0 + n]] * 2, axis=1)
+        # rot[j, row, s] = the row's mask at column (j + s) mod sectors
+        rot = as_strided(mc2, (sectors, n, sectors), (mc2.strides[1], mc2.strides[0], mc2.strides[1]), writeable=False)
+        rot_count = rot.astype(np.float64).reshape(sectors, n * sectors)
+        for q0 in range(0, nq, qb):
+            b = min(qb, nq - q0)
+            A = np.ascontiguousarray(uq[q0:q0 + b].transpose(0, 2, 1)).reshape(b * sectors, rings)
+            G = np.matmul(A, B).reshape(b, sectors, n, sectors)         # [query, j, row, k]
+            G2 = np.concatenate([G, G], axis=3)
+            st = G2.strides
+            diag = as_strided(G2, G.shape, (st[0], st[1] + st[3], st[2], st[3]), writeable=False)      # [query, j, row, s]
+            valid = mq[q0:q0 + b][:, :, None, None] & rot[None]
+            tot = np.where(valid, 1.0 - diag, 0.0).sum(axis=1)          # [query, row, s]
+            cnt = np.matmul(mq[q0:q0 + b].astype(np.float64), rot_count).reshape(b, n, sectors)
+            out[q0:q0 + b, r0:r0 + n] = np.where(cnt > 0, tot / np.maximum(cnt, 1), 1.0).min(axis=2)
+    return out
+
+
+def search_pruned(query, db, limit=None, stats=None):
+    """search(), bit for bit, at a cost that many pairs allow.  Every row's smallest distance is known from row_minima_twin to within
+    e = e_bound(rings).  Let T2 be the second smallest twin minimum among a query's admitted rows: two rows have an fp32 minimum of at most
+    T2 + e, so the winner and the runner-up of the contract, and every row that ties with either, have a twin minimum of at most T2 + 2e.
+    The rows within 4e of T2 are kept -- twice what the argument needs -- and shift_distances, every fmaf of it, runs over them alone, in
+    ascending row order; fewer than two admitted rows are all kept.  The ties fall as in search(): the lowest row, then the lowest shift.
+    stats: a dict that receives `kept` (rows kept, per query with a row) and `worst` (the largest |fp32 minimum - twin minimum| seen on a
+    kept row), for the tests of the bound."""
+    uq, mq = unit_columns(query)
+    uc, mc = unit_columns(db)
+    nq, nd, rings = len(uq), len(uc), uq.shape[1]
+    twin = row_minima_twin(query, db)
+    margin = 4 * e_bound(rings)
+    idx, dist, shift, second = np.full(nq, -1, np.int32), np.full(nq, np.inf, np.float32), np.zeros(nq, np.int32), np.full(nq, np.inf, np.float32)
+    kept_counts, worst = [], 0.0
+    for i in range(nq):
+        lim = nd if limit is None else min(int(limit[i]), nd)
+        if lim <= 0:
+            continue
+        t = twin[i, :lim]
+        kept = np.arange(lim) if lim < 2 else np.nonzero(t <= np.partition(t, 1)[1] + margin)[0]
+        d = shift_distances(uq[i], mq[i], uc[kept], mc[kept])
+        per_row, per_shift = d.min(axis=1), d.argmin(axis=1)
+        w = per_row.argmin()
+        idx[i], dist[i], shift[i] = kept[w], per_row[w], per_shift[w]
+        if lim > 1:
+            second[i] = np.delete(per_row, w).min()
+        kept_counts.append(len(kept))
+        worst = max(worst, float(np.abs(per_row.astype(np.float64) - t[kept]).max()))
+    if stats is not None:
+        stats["kept"], stats["worst"] = np.array(kept_counts, np.int64), worst
+    return idx, dist, shift, second
+
+
 # ---- the planted places of the tests: a ground plane with boxes and pillars on it, and the same place seen again
 def place(rng, n_points=2000, extent=60.0):
     """[n, 3] float32: about n_points points of a ground plane at z = -2 (a sensor two units above it) and a few dozen boxes and pillars."""

@@ -1,7 +1,9 @@
 """GPU suite: mi_scan_context and mi_scan_context_search against tests/scan_context_reference.py, bit for bit and without a tolerance
-anywhere: descriptors at every size, batch and shape, on the rule's own boundaries; the search at every size around the chunk of rows a
-workgroup takes, at shapes that pad the matrix instruction's tile and K, with empty columns, duplicates, limits and the runner-up; the
-planted places end to end; refusals and context hygiene."""
+anywhere: descriptors at every size, batch and shape, on the rule's own boundaries; the search at database sizes around one and a few
+64-row units, at shapes that pad the matrix instruction's tile and K, with empty columns, duplicates, limits and the runner-up; the
+planted places end to end; refusals and context hygiene.  Every database here (1 to 300 rows under 1 to 70 queries) plans one 64-row unit
+per chunk on any device from 32 CUs on, so a wave walks at most 32 rows of one unit: chunks of several units, limits inside and across
+them, winners in different chunks and rows beyond 2^16 are tests/test_gpu_scan_context_scale.py's."""
 import ctypes as C
 import functools
 
