@@ -540,6 +540,7 @@ def tsdf_params(**kw):
 
 tsdf_integrate_raw = _raw("mi_tsdf_integrate")
 tsdf_extract_raw = _raw("mi_tsdf_extract")
+tsdf_mesh_raw = _raw("mi_tsdf_mesh")
 
 
 def _tsdf_map(m):
@@ -1476,6 +1477,27 @@ class Context:
                 raise MiSlamError("mi_tsdf_extract: %d points counted, then %d" % (n, found.value))
         return xyz, normals
 
+    def tsdf_mesh(self, map, origin, voxel_size, min_weight=1.0, normals=True):
+        """The surface of a TSDF map as an indexed triangle mesh (mi_tsdf_mesh): (xyz [nv, 3] float32, normals [nv, 3] float32 or None,
+        tri [nt, 3] int32).  The vertices are tsdf_extract's crossings that a triangle uses, in its order and with its bits, each stored
+        once; the triangles come by cube in row order, wound so that (v1 - v0) x (v2 - v0) points to the observed side, as the normals do.
+        A cube with an unobserved corner gives no triangle.  Two calls inside: one for the two counts, one to fill arrays of exactly that
+        size."""
+        coord, tsdf, weight = _tsdf_map(map)
+        origin = np.ascontiguousarray(origin, np.float32).reshape(3)
+        nv, nvert, ntri = len(coord), C.c_longlong(0), C.c_longlong(0)
+        args = (self._h, coord.ctypes.data if nv else None, tsdf.ctypes.data if nv else None, weight.ctypes.data if nv else None, nv,
+                origin.ctypes.data, float(voxel_size), float(min_weight))
+        _check(tsdf_mesh_raw(*args, None, None, 0, C.addressof(nvert), None, 0, C.addressof(ntri)))
+        n, t = nvert.value, ntri.value
+        xyz, tri = np.empty((n, 3), np.float32), np.empty((t, 3), np.int32)
+        nrm = np.empty((n, 3), np.float32) if normals else None
+        if n and t:
+            _check(tsdf_mesh_raw(*args, xyz.ctypes.data, _ptr(nrm), n, C.addressof(nvert), tri.ctypes.data, t, C.addressof(ntri)))
+            if (nvert.value, ntri.value) != (n, t):
+                raise MiSlamError("mi_tsdf_mesh: %d vertices and %d triangles counted, then %d and %d" % (n, t, nvert.value, ntri.value))
+        return xyz, nrm, tri
+
     def tsdf_raycast(self, map, origin, params, pose, dirs, compact=False):
         """The map's surface as seen from a pose (mi_tsdf_raycast): (depth [n] float32, xyz [n, 3] float32, normals [n, 3] float32), row i for
         ray i, zeros where a ray misses (depth > 0 marks a hit).  map: a (coord, tsdf, weight) triple or None; origin [3]; params:
@@ -1504,9 +1526,9 @@ class Context:
         return depth[index], xyz[index], normals[index], index
 
     def tsdf_times(self):
-        """ms per stage of the last tsdf_integrate, tsdf_extract or tsdf_raycast: workspace, upload, check, sampling (extraction and ray cast:
-        table), sort (extraction: count + scan; ray cast: block table), fusion (extraction: fill; ray cast: cast), download, total
-        (mi_tsdf_times)."""
+        """ms per stage of the last tsdf_integrate, tsdf_extract, tsdf_mesh or tsdf_raycast: workspace, upload, check, sampling (extraction,
+        mesh and ray cast: table), sort (extraction: count + scan; mesh: cases, used crossings, two scans; ray cast: block table), fusion
+        (extraction: fill; mesh: vertex and triangle fill; ray cast: cast), download, total (mi_tsdf_times)."""
         return self._times("tsdf")
 
     # ---- generalized ICP

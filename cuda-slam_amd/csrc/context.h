@@ -365,7 +365,8 @@ struct mi_ctx {
     // ---- mi_tsdf_integrate: the scans, offsets and poses as uploaded, the input map, the rays' counts and K51's scan of them, the entries'
     // keys, values and the sort's ping and pong, the voxel filter's head-flag scan, and the fused rows; mi_tsdf_extract: the map as uploaded,
     // the table of its observed voxels, the rows' counts and their scan, the points and normals; mi_tsdf_raycast: the map and that table again,
-    // the directions in xyz, the two block tables of the skip, the counts, and a depth, a point and a normal per ray
+    // the directions in xyz, the two block tables of the skip, the counts, and a depth, a point and a normal per ray; mi_tsdf_mesh: the
+    // extraction's, with the cubes' cases and triangle counts, the rows' masks, a second scan and the triangles
     struct TsdfBuffers {
         mislam::DevBuf<float> xyz, poses, in_tsdf, in_weight;
         mislam::DevBuf<long long> offsets, tile_sums, sample_off;
@@ -384,6 +385,9 @@ struct mi_ctx {
         mislam::DevBuf<unsigned long long> block_held, block_keys;       // mi_tsdf_raycast: K73's and K74's tables
         mislam::DevBuf<int> cast_counts;                 // [0] the blocks K73 found, [1] the hits
         mislam::DevBuf<float> out_depth;
+        mislam::DevBuf<unsigned char> mesh_case, mesh_use;               // mi_tsdf_mesh: K76's case bytes, K77's used-crossing masks
+        mislam::DevBuf<int> mesh_tris, out_tri;          // the rows' triangle counts; the triangles
+        mislam::DevBuf<long long> tri_off;               // K51's scan of mesh_tris (the vertices' scan is sample_off)
         double ms[MI_TSDF_STAGES] = {0};                 // mi_tsdf_times
     } tsdf;
 

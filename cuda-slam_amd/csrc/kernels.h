@@ -1014,6 +1014,7 @@ struct TsdfCrossArgs {
     int* count;                      // nv: the count pass writes
     const long long* offsets;        // nv + 1 (the fill)
     float *out_xyz, *out_normals;    // 3 per crossing; out_normals may be null
+    const unsigned char* use;        // null: every crossing.  K77's masks (the fill of mi_tsdf_mesh): bit a of use[i] keeps the crossing (i, a)
 };
 hipError_t tsdf_crossings(const TsdfCrossArgs& a, bool fill, hipStream_t s);
 
@@ -1047,6 +1048,37 @@ struct TsdfCastArgs {
     int* hits;                       // 0 before the launch
 };
 hipError_t tsdf_cast_rays(const TsdfCastArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------------------------
+// K76-K78 TSDF mesh: the map's surface as an indexed triangle mesh by marching cubes (tsdf_kernels.hip; driver: tsdf_api.hip; the table:
+// tsdf_mesh_table.hpp, generated by tools/gen_mc_table.py; the contract: mi_tsdf_mesh in mi_slam.h).  The observed voxels are in K71's table;
+// the vertices are K72's crossings, filled by K72's own fill behind K77's masks.
+//   K76 tsdf_mesh_classify:  one lane per row: the seven other corners of its cube looked up, the case byte, and -- where all eight corners
+//                            are observed and no crossed edge is saturated at both ends -- the row's number of triangles, from the table.
+//   K77 tsdf_mesh_edges:     one lane per row: for each of its up to three crossings, whether one of the four cubes round that edge has a
+//                            triangle: a gather over K76's counts (no atomic, no racing store).  A 3-bit mask and its population per row.
+//       K51's scan, twice: the rows' vertices and the rows' triangles into 64-bit offsets.
+//   K78 tsdf_mesh_triangles: one lane per row with triangles: every table edge becomes offset[owner row] + the rank of the edge's axis in
+//                            the owner's mask.
+// K76 and K78 stage the table (256 packed 64-bit rows, 2 KB) in LDS: every lane indexes it by its own case, which a scalar or constant read
+// would serialise.  K78 also keeps each lane's eight corner rows in LDS ([corner][lane]: a lane's column is its own bank), because the table
+// picks the corner at run time and a register array indexed so would go to scratch.  No scratch, no floating-point atomic, no atomic at all.
+// ---------------------------------------------------------------------------------------------------------------
+struct TsdfMeshArgs {
+    const int* coord; const float* tsdf; const float* weight; int nv;
+    float min_weight;
+    VoxelTableView table;            // K71's
+    unsigned char* cube_case;        // nv: K76 writes
+    int* tri_count;                  // nv: K76 writes; > 0 exactly where the row's cube is meshed and has a triangle
+    unsigned char* use;              // nv: K77 writes
+    int* vert_count;                 // nv: K77 writes
+    const long long* vert_off;       // nv + 1: K51's scan of vert_count (K78)
+    const long long* tri_off;        // nv + 1: K51's scan of tri_count (K78)
+    int* out_tri;                    // 3 per triangle (K78)
+};
+hipError_t tsdf_mesh_classify(const TsdfMeshArgs& a, hipStream_t s);
+hipError_t tsdf_mesh_edges(const TsdfMeshArgs& a, hipStream_t s);
+hipError_t tsdf_mesh_triangles(const TsdfMeshArgs& a, hipStream_t s);
 
 // One per translation unit with kernels: loads that unit's code object (see the definitions).
 hipError_t preload_nn_kernel();

@@ -1,6 +1,6 @@
-// mi_tsdf_integrate, mi_tsdf_extract, mi_tsdf_raycast and mi_tsdf_times behind the C ABI: argument checks, the host check of a listed map
+// mi_tsdf_integrate, mi_tsdf_extract, mi_tsdf_mesh, mi_tsdf_raycast and mi_tsdf_times behind the C ABI: argument checks, the host check of a listed map
 // (tsdf_ray.hpp), the reserves of the calls' own buffers in the context, the uploads, the launches with their read-backs (the count pass's facts
-// and total; the number of voxels; the blocks and the hits of a ray cast) and the download.  The kernels: tsdf_kernels.hip.  Nothing is written to a caller's array before the last refusal.
+// and total; the number of voxels; a mesh's vertices and triangles; the blocks and the hits of a ray cast) and the download.  The kernels: tsdf_kernels.hip.  Nothing is written to a caller's array before the last refusal.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -8,6 +8,7 @@
 
 #include "context.h"
 #include "tsdf_cast.hpp"
+#include "tsdf_mesh_table.hpp"
 #include "tsdf_ray.hpp"
 
 using namespace mislam;
@@ -305,6 +306,111 @@ extern "C" int mi_tsdf_extract(mi_ctx* c, const int* coord, const float* tsdf, c
         MI_TRY(clock.mark(6));
     }
     *out_n = found;
+    clock.finish();
+    return MI_OK;
+}
+
+extern "C" int mi_tsdf_mesh(mi_ctx* c, const int* coord, const float* tsdf, const float* weight, int nv, const float origin3[3], float voxel_size,
+                            float min_weight, float* out_xyz, float* out_normals, long long vertex_capacity, long long* out_nvert, int* out_tri,
+                            long long tri_capacity, long long* out_ntri)
+{
+    const char* who = "mi_tsdf_mesh";
+    if (!c) { set_error("%s: null context", who); return MI_ERR_INVALID_ARG; }
+    if (!origin3 || !out_nvert || !out_ntri) { set_error("%s: null origin3, out_nvert or out_ntri", who); return MI_ERR_INVALID_ARG; }
+    if (nv < 0) { set_error("%s: nv = %d", who, nv); return MI_ERR_INVALID_ARG; }
+    if (nv > 0 && (!coord || !tsdf || !weight)) { set_error("%s: null coord, tsdf or weight with nv = %d", who, nv); return MI_ERR_INVALID_ARG; }
+    if (!std::isfinite(voxel_size) || !(voxel_size > 0.f)) { set_error("%s: voxel_size not finite or not positive", who); return MI_ERR_INVALID_ARG; }
+    if (!(min_weight > 0.f)) { set_error("%s: min_weight not positive", who); return MI_ERR_INVALID_ARG; }
+    if (!finite3(origin3)) { set_error("%s: origin3 not finite", who); return MI_ERR_INVALID_ARG; }
+    if (vertex_capacity < 0) { set_error("%s: vertex_capacity = %lld", who, vertex_capacity); return MI_ERR_INVALID_ARG; }
+    if (tri_capacity < 0) { set_error("%s: tri_capacity = %lld", who, tri_capacity); return MI_ERR_INVALID_ARG; }
+    if (vertex_capacity > 0 && !out_xyz) { set_error("%s: null out_xyz with vertex_capacity = %lld", who, vertex_capacity); return MI_ERR_INVALID_ARG; }
+    if (tri_capacity > 0 && !out_tri) { set_error("%s: null out_tri with tri_capacity = %lld", who, tri_capacity); return MI_ERR_INVALID_ARG; }
+    if (c->distributed()) { set_error("%s: single-GPU contexts only", who); return MI_ERR_STATE; }
+    MI_ENTER(c);
+    mi_ctx::TsdfBuffers& b = c->tsdf;
+    StageClock clock(c, b.ms);         // mi_tsdf_times
+
+    int cmin[3] = {0, 0, 0}, cmax[3] = {0, 0, 0};
+    TsdfMeshArgs m{};
+    MI_TRY(tsdf_refuse_map(who, "coord", "tsdf", "weight", coord, tsdf, weight, nv, cmin, cmax));
+    if (nv > 0) MI_TRY(tsdf_refuse_extent(who, cmin, cmax, &m.table));
+    MI_TRY(clock.mark(2));
+    if (nv == 0) {                           // the empty map has no surface
+        *out_nvert = 0; *out_ntri = 0;
+        clock.finish();
+        return MI_OK;
+    }
+
+    const size_t nm = (size_t)nv, slots = (size_t)voxel_table_slots(nm, 2);
+    CallBuffers bufs;
+    MI_TRY(bufs.need(b.in_coord, 3 * nm)); MI_TRY(bufs.need(b.in_tsdf, nm)); MI_TRY(bufs.need(b.in_weight, nm));
+    MI_TRY(bufs.need(b.hkeys, slots)); MI_TRY(bufs.need(b.hvals, slots));
+    MI_TRY(bufs.need(b.count, nm)); MI_TRY(bufs.need(b.tile_sums, (size_t)radius_scan_tiles(nv))); MI_TRY(bufs.need(b.sample_off, nm + 1));
+    MI_TRY(bufs.need(b.mesh_case, nm)); MI_TRY(bufs.need(b.mesh_use, nm)); MI_TRY(bufs.need(b.mesh_tris, nm)); MI_TRY(bufs.need(b.tri_off, nm + 1));
+    MI_TRY(clock.mark(0));
+    MI_TRY(host_to_device(c, b.in_coord.p, coord, sizeof(int) * 3 * nm));
+    MI_TRY(host_to_device(c, b.in_tsdf.p, tsdf, sizeof(float) * nm));
+    MI_TRY(host_to_device(c, b.in_weight.p, weight, sizeof(float) * nm));
+    MI_TRY(clock.mark(1));
+
+    if (!bufs.fits()) { set_error("internal: %s buffers shorter than the launch", who); return MI_ERR_STATE; }
+    m.coord = b.in_coord.p; m.tsdf = b.in_tsdf.p; m.weight = b.in_weight.p; m.nv = nv; m.min_weight = min_weight;
+    voxel_table_bind(&m.table, b.hkeys.p, b.hvals.p, slots);
+    m.cube_case = b.mesh_case.p; m.tri_count = b.mesh_tris.p; m.use = b.mesh_use.p; m.vert_count = b.count.p;
+    MI_HIP(voxel_table_clear(b.hkeys.p, slots, c->stream));
+    MI_HIP(tsdf_table(b.in_coord.p, b.in_weight.p, nv, min_weight, m.table, b.hkeys.p, b.hvals.p, c->stream));
+    MI_TRY(clock.mark(3));
+    {
+        // with profiling on, the mesh's own launches (K76, K77, K78) are booked to MI_KERNEL_MOMENTS, the shared vertex fill to MI_KERNEL_NN
+        ProfScope prof(c, MI_KERNEL_MOMENTS);
+        MI_HIP(tsdf_mesh_classify(m, c->stream));
+        MI_HIP(tsdf_mesh_edges(m, c->stream));
+    }
+    // (the two scans share tile_sums: they run one after the other on the stream)
+    MI_HIP(radius_scan_offsets(b.count.p, nv, b.tile_sums.p, b.sample_off.p, c->stream));
+    MI_HIP(radius_scan_offsets(b.mesh_tris.p, nv, b.tile_sums.p, b.tri_off.p, c->stream));
+    long long* h_total = reinterpret_cast<long long*>(c->h_scratch);
+    MI_HIP(hipMemcpyAsync(h_total, b.sample_off.p + nm, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipMemcpyAsync(h_total + 1, b.tri_off.p + nm, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    MI_TRY(clock.mark(4));
+    const long long nvert = h_total[0], ntri = h_total[1];
+    if (nvert < 0 || nvert > 3LL * nv || ntri < 0 || ntri > (long long)TSDF_MESH_MAX_TRIANGLES * nv || (nvert == 0) != (ntri == 0)) {
+        set_error("internal: %s counted %lld vertices and %lld triangles of %d voxels", who, nvert, ntri, nv);
+        return MI_ERR_STATE;
+    }
+    if (nvert >= (1LL << 31) || 3 * ntri >= (1LL << 31)) {
+        set_error("%s: %lld vertices and %lld triangles: 2^31 vertices or triangle indices, or more", who, nvert, ntri);
+        return MI_ERR_INVALID_ARG;
+    }
+
+    if (nvert > 0 && nvert <= vertex_capacity && ntri <= tri_capacity) {
+        const size_t np = (size_t)nvert, nt = (size_t)ntri;
+        MI_TRY(bufs.need(b.out_xyz, 3 * np, out_xyz)); MI_TRY(bufs.result(b.out_normals, 3 * np, out_normals)); MI_TRY(bufs.need(b.out_tri, 3 * nt, out_tri));
+        MI_TRY(clock.mark(0));
+        if (!bufs.fits()) { set_error("internal: %s lists shorter than the launch", who); return MI_ERR_STATE; }
+        TsdfCrossArgs a{};                   // K72's fill, behind K77's masks and their scan
+        a.coord = m.coord; a.tsdf = m.tsdf; a.weight = m.weight; a.nv = nv;
+        for (int k = 0; k < 3; k++) a.origin[k] = origin3[k];
+        a.voxel = voxel_size; a.min_weight = min_weight; a.table = m.table;
+        a.count = b.count.p; a.offsets = b.sample_off.p; a.use = b.mesh_use.p;
+        a.out_xyz = b.out_xyz.p; a.out_normals = out_normals ? b.out_normals.p : nullptr;
+        {
+            ProfScope prof(c, MI_KERNEL_NN);
+            MI_HIP(tsdf_crossings(a, true, c->stream));
+        }
+        m.vert_off = b.sample_off.p; m.tri_off = b.tri_off.p; m.out_tri = b.out_tri.p;
+        {
+            ProfScope prof(c, MI_KERNEL_MOMENTS);
+            MI_HIP(tsdf_mesh_triangles(m, c->stream));
+        }
+        MI_TRY(clock.mark(5));
+        MI_TRY(bufs.download(c->stream));
+        MI_HIP(hipStreamSynchronize(c->stream));
+        MI_TRY(clock.mark(6));
+    }
+    *out_nvert = nvert; *out_ntri = ntri;
     clock.finish();
     return MI_OK;
 }

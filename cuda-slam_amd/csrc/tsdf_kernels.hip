@@ -1,13 +1,15 @@
-// K68-K75: the kernels of mi_tsdf_integrate, mi_tsdf_extract and mi_tsdf_raycast (kernels.h has the plan; tsdf_ray.hpp and tsdf_cast.hpp the
-// arithmetic, which host and device share word for word).  Every kernel is one lane per ray, row, voxel or slot, in workgroups of TSDF_BLOCK;
-// none uses LDS or scratch, none has a floating-point atomic: the only atomics are integer minima, maxima and counts (the same answer in any
-// order) and the tables' compare-and-swap on keys (a key met again is left where it is).
+// K68-K78: the kernels of mi_tsdf_integrate, mi_tsdf_extract, mi_tsdf_raycast and mi_tsdf_mesh (kernels.h has the plan; tsdf_ray.hpp and
+// tsdf_cast.hpp the arithmetic, which host and device share word for word).  Every kernel is one lane per ray, row, voxel or slot, in
+// workgroups of TSDF_BLOCK; none uses scratch, only the mesh's K76 and K78 use LDS (the triangle table), none has a floating-point atomic: the
+// only atomics are integer minima, maxima and counts (the same answer in any order) and the tables' compare-and-swap on keys (a key met again
+// is left where it is).
 #include <hip/hip_runtime.h>
 
 #include <climits>
 
 #include "kernels.h"
 #include "tsdf_cast.hpp"
+#include "tsdf_mesh_table.hpp"
 #include "tsdf_ray.hpp"
 
 namespace mislam {
@@ -204,6 +206,7 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_crossings_kernel(TsdfCrossArg
             const double f1 = (double)a.tsdf[j];
             double r;
             if (!tsdf_crossing(f0, f1, &r)) continue;
+            if (a.use && !(a.use[i] >> ax & 1)) continue;                       // (mi_tsdf_mesh: a crossing no triangle uses)
             if (FILL && (long long)n < a.offsets[i + 1] - a.offsets[i]) {       // (the count's own code again; never past the row's share)
                 const size_t at = 3 *((size_t)a.offsets[i] + (size_t)n);
                 a.out_xyz[at] = ax == 0 ? tsdf_crossing_coord(cx, a.origin[0], a.voxel, r) : (float)tsdf_centre(cx, a.origin[0], a.voxel);
@@ -307,6 +310,135 @@ hipError_t tsdf_cast_rays(const TsdfCastArgs& a, hipStream_t s)
     if (a.n < 1 || a.steps < 1 || a.steps > TSDF_RAYCAST_MAX_STEPS || !a.dirs || !a.tsdf || !a.table.keys || !a.table.vals || !a.out_depth || !a.hits) return hipErrorInvalidValue;
     if (a.skip && !a.blocks.keys) return hipErrorInvalidValue;
     hipLaunchKernelGGL(tsdf_cast_kernel, dim3((a.n - 1) / TSDF_BLOCK + 1), dim3(TSDF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- K76-K78: marching cubes over K71's table (kernels.h has the plan, mi_slam.h the rules).  Corner c of the cube at a voxel is the voxel
+// + (c & 1, (c >> 1) & 1, (c >> 2) & 1); edge e = 4 axis + 2 hi + lo runs along `axis` from its owner corner, whose offset has lo on the
+// lower and hi on the higher of the two other axes.
+static_assert(TSDF_BLOCK == TSDF_MESH_CASES, "a workgroup stages one row of the table per lane");
+__host__ __device__ constexpr int tsdf_mesh_edge_corner(int e)
+{
+    return (e >> 2) == 0 ? ((e & 1) << 1 | (e & 2) << 1) : ((e >> 2) == 1 ? ((e & 1) | (e & 2) << 1) : ((e & 1) | (e & 2)));
+}
+static_assert(tsdf_mesh_edge_corner(1) == 2 && tsdf_mesh_edge_corner(3) == 6 && tsdf_mesh_edge_corner(5) == 1 && tsdf_mesh_edge_corner(6) == 4 &&
+              tsdf_mesh_edge_corner(7) == 5 && tsdf_mesh_edge_corner(9) == 1 && tsdf_mesh_edge_corner(10) == 2 && tsdf_mesh_edge_corner(11) == 3,
+              "the owner corners of mi_slam.h");
+
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_mesh_classify_kernel(TsdfMeshArgs a)
+{
+    __shared__ unsigned long long table[TSDF_MESH_CASES];
+    table[threadIdx.x] = TSDF_MESH_TABLE[threadIdx.x];
+    __syncthreads();
+    const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
+    if (i >= a.nv) return;
+    unsigned int cube = 0;
+    int triangles = 0;
+    if (a.weight[i] >= a.min_weight) {
+        const int cx = a.coord[3 * (size_t)i], cy = a.coord[3 * (size_t)i + 1], cz = a.coord[3 * (size_t)i + 2];
+        double f[8];
+        bool all = true;
+        f[0] = (double)a.tsdf[i];
+#pragma unroll
+        for (int c = 1; c < 8; c++) {
+            const int r = voxel_row(a.table, cx + (c & 1), cy + ((c >> 1) & 1), cz + ((c >> 2) & 1));
+            all = all && r >= 0;
+            f[c] = r >= 0 ? (double)a.tsdf[r] : 0.0;
+        }
+        if (all) {
+#pragma unroll
+            for (int c = 0; c < 8; c++) cube |= (unsigned int)(f[c] > 0.0) << c;
+            bool meshed = true;              // every edge whose ends differ in sign is a crossing of K72
+#pragma unroll
+            for (int e = 0; e < 12; e++) {
+                const int c0 = tsdf_mesh_edge_corner(e), c1 = c0 | 1 << (e >> 2);
+                double r;
+                if ((f[c0] > 0.0) != (f[c1] > 0.0) && !tsdf_crossing(f[c0], f[c1], &r)) meshed = false;
+            }
+            if (meshed) triangles = (int)(table[cube] >> 60);
+        }
+    }
+    a.cube_case[i] = (unsigned char)cube;
+    a.tri_count[i] = triangles;
+}
+
+hipError_t tsdf_mesh_classify(const TsdfMeshArgs& a, hipStream_t s)
+{
+    if (a.nv < 1 || !a.coord || !a.tsdf || !a.weight || !a.table.keys || !a.table.vals || !a.cube_case || !a.tri_count) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tsdf_mesh_classify_kernel, dim3((a.nv - 1) / TSDF_BLOCK + 1), dim3(TSDF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_mesh_edges_kernel(TsdfMeshArgs a)
+{
+    const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
+    if (i >= a.nv) return;
+    unsigned int mask = 0;
+    if (a.weight[i] >= a.min_weight) {
+        const int c[3] = {a.coord[3 * (size_t)i], a.coord[3 * (size_t)i + 1], a.coord[3 * (size_t)i + 2]};
+        const double f0 = (double)a.tsdf[i];
+#pragma unroll
+        for (int ax = 0; ax < 3; ax++) {
+            const int j = voxel_row(a.table, c[0] + (ax == 0), c[1] + (ax == 1), c[2] + (ax == 2));
+            if (j < 0) continue;
+            double r;
+            if (!tsdf_crossing(f0, (double)a.tsdf[j], &r)) continue;
+            // the four cubes round the edge: this voxel's and the three a step back along the other axes
+            const int u = ax == 0 ? 1 : 0, v = ax == 2 ? 1 : 2;
+            bool used = a.tri_count[i] > 0;
+#pragma unroll
+            for (int k = 1; k < 4 && !used; k++) {
+                int d[3] = {0, 0, 0};
+                d[u] = k & 1; d[v] = k >> 1;
+                const int row = voxel_row(a.table, c[0] - d[0], c[1] - d[1], c[2] - d[2]);
+                used = row >= 0 && a.tri_count[row] > 0;
+            }
+            mask |= (unsigned int)used << ax;
+        }
+    }
+    a.use[i] = (unsigned char)mask;
+    a.vert_count[i] = __popc(mask);
+}
+
+hipError_t tsdf_mesh_edges(const TsdfMeshArgs& a, hipStream_t s)
+{
+    if (a.nv < 1 || !a.coord || !a.tsdf || !a.weight || !a.table.keys || !a.table.vals || !a.tri_count || !a.use || !a.vert_count) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tsdf_mesh_edges_kernel, dim3((a.nv - 1) / TSDF_BLOCK + 1), dim3(TSDF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(TSDF_BLOCK) void tsdf_mesh_triangles_kernel(TsdfMeshArgs a)
+{
+    __shared__ unsigned long long table[TSDF_MESH_CASES];
+    __shared__ int corner_row[8][TSDF_BLOCK];            // [corner][lane]: a lane reads and writes its own column alone
+    table[threadIdx.x] = TSDF_MESH_TABLE[threadIdx.x];
+    __syncthreads();
+    const int i = blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
+    if (i >= a.nv) return;
+    const long long first = a.tri_off[i];
+    const unsigned long long word = table[a.cube_case[i]];
+    long long triangles = a.tri_off[i + 1] - first;      // (the count's own words; never past the row's share or the table's row)
+    if (triangles > (long long)(word >> 60)) triangles = (long long)(word >> 60);
+    if (triangles < 1) return;
+    const int cx = a.coord[3 * (size_t)i], cy = a.coord[3 * (size_t)i + 1], cz = a.coord[3 * (size_t)i + 2];
+    corner_row[0][threadIdx.x] = i;
+#pragma unroll
+    for (int c = 1; c < 8; c++) corner_row[c][threadIdx.x] = voxel_row(a.table, cx + (c & 1), cy + ((c >> 1) & 1), cz + ((c >> 2) & 1));
+    for (int t = 0; t < (int)triangles; t++) {
+#pragma unroll
+        for (int v = 0; v < 3; v++) {
+            const int e = (int)(word >> 4 * (3 * t + v)) & 15, axis = e >> 2;
+            const int owner = e < 12 ? corner_row[tsdf_mesh_edge_corner(e)][threadIdx.x] : -1;
+            // the vertex of the crossing (owner, axis): the owner's first vertex plus the used crossings of its lower axes
+            a.out_tri[3 * ((size_t)first + (size_t)t) + v] = owner < 0 ? -1 : (int)(a.vert_off[owner] + (long long)__popc(a.use[owner] & ((1u << axis) - 1u)));
+        }
+    }
+}
+
+hipError_t tsdf_mesh_triangles(const TsdfMeshArgs& a, hipStream_t s)
+{
+    if (a.nv < 1 || !a.coord || !a.table.keys || !a.table.vals || !a.cube_case || !a.use || !a.vert_off || !a.tri_off || !a.out_tri) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tsdf_mesh_triangles_kernel, dim3((a.nv - 1) / TSDF_BLOCK + 1), dim3(TSDF_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

@@ -2129,6 +2129,41 @@ int mi_tsdf_integrate(mi_ctx* ctx,
 int mi_tsdf_extract(mi_ctx* ctx, const int* coord, const float* tsdf, const float* weight, int nv,
                     const float origin3[3], float voxel_size, float min_weight /* > 0 */,
                     float* out_xyz, float* out_normals /* may be NULL */, long long capacity, long long* out_n);
+/* mi_tsdf_mesh -- the surface of a map as an indexed triangle mesh, by marching cubes over the observed voxels: what a viewer, a mesh file or
+ * a collision check takes.  The map is held to every check of mi_tsdf_extract (nv == 0 is the empty map: both counts 0), a voxel is OBSERVED as
+ * there, and the vertices are mi_tsdf_extract's crossings with its bits.  Every rule, so that it can be retraced in numpy
+ * (tests/tsdf_mesh_reference.py does):
+ *   Cube.  The cube at an observed voxel i has the corners c = 0 .. 7 at i + (c & 1, (c >> 1) & 1, (c >> 2) & 1).  Its case is the OR of
+ *     1 << c over the corners whose value is > 0: mi_tsdf_extract's sign test.  Edge e = 4 axis + 2 hi + lo runs along `axis` from its owner
+ *     corner, whose offset has lo on the lower and hi on the higher of the two other axes: along x (e = 0 .. 3) the owners are (0,0,0),
+ *     (0,1,0), (0,0,1), (0,1,1); along y (e = 4 .. 7) (0,0,0), (1,0,0), (0,0,1), (1,0,1); along z (e = 8 .. 11) (0,0,0), (1,0,0), (0,1,0),
+ *     (1,1,0).  The vertex on edge e of the cube at i is mi_tsdf_extract's crossing of the voxel i + owner offset along `axis`.
+ *   Meshed.  The cube is MESHED when all eight corners are observed and every edge whose ends differ in sign is a crossing by
+ *     mi_tsdf_extract's rule (not both |f| >= 1).  Every other cube gives no triangle: the mesh has a hole where the map has one, and at a
+ *     saturated step (+1 beside -1), which is the back of the band and no surface.
+ *   Table.  256 rows of at most 5 triangles, each three edge numbers (csrc/tsdf_mesh_table.hpp), generated by tools/gen_mc_table.py from
+ *     these rules.  Segments: on each of the six faces the edges whose ends differ in sign are two or four; two are joined by one segment,
+ *     four by two, each cutting off one positive corner and joining the two face edges that meet at it -- a rule of the face's four signs
+ *     alone, so the two cubes on a face agree.  Direction: with n the face's outward normal, m_a and m_b the edge midpoints and p a positive
+ *     corner of the face (the one cut off, on a face of four), the segment runs a -> b when n . ((m_b - m_a) x (p - m_a)) > 0: seen from
+ *     outside, the positive corner lies to the left.  Every crossed edge then has one successor.  Loops: follow the successors from the
+ *     lowest unvisited edge; loops come by their lowest edge.  Fan: rotate the loop to the first start, counted from its lowest edge, for
+ *     which no diagonal (r0, rk), 2 <= k <= len - 2, joins two edges of one cube face (the neighbour cube could make the same diagonal
+ *     again); the triangles are (r0, rk, rk+1) for k = 1 .. len - 2.  Row 0x01 is (0,8,4); row 0x03 is (4,5,9), (4,9,8).  The geometric
+ *     normal (v1 - v0) x (v2 - v0) points to the positive side, towards the sensor, as the vertex normals do.
+ *   Output.  Triangles by cube in row order, then in table order, three vertex indices each.  The vertices are the crossings (row, axis) of
+ *     mi_tsdf_extract that at least one triangle uses, in its order (by row, then axis), with its bits for coordinates and normals: the
+ *     vertex arrays are a subsequence of mi_tsdf_extract's output, each vertex stored once and shared by every triangle round its edge.
+ *   Capacity.  *out_nvert and *out_ntri are always written; the three arrays are written if and only if 0 < *out_nvert <= vertex_capacity
+ *     and 0 < *out_ntri <= tri_capacity; a short capacity still returns MI_OK; both capacities 0 (the arrays may be NULL) is a counts-only
+ *     call.  No floating-point atomic occurs: the same input gives the same bits on every call, whatever ran on the context before.
+ *   Refusals.  Every refusal of mi_tsdf_extract, the message starting with "mi_tsdf_mesh"; also a negative capacity, a positive capacity
+ *     with a NULL out_xyz (vertex_capacity) or out_tri (tri_capacity), a NULL out_nvert or out_ntri, and 2^31 or more vertices or triangle
+ *     indices (3 per triangle).  NOTHING has been written then, the counts included.  MI_ERR_STATE on a distributed context. */
+int mi_tsdf_mesh(mi_ctx* ctx, const int* coord, const float* tsdf, const float* weight, int nv,
+                 const float origin3[3], float voxel_size, float min_weight /* > 0 */,
+                 float* out_xyz, float* out_normals /* may be NULL */, long long vertex_capacity, long long* out_nvert,
+                 int* out_tri /* 3 per triangle */, long long tri_capacity, long long* out_ntri);
 /* mi_tsdf_raycast -- the map's surface as seen from a pose: one depth, one point and one normal per sensor ray, interpolated inside the
  * voxels; the frame-to-model read-out of a TSDF tracker, a depth image, a synthetic LiDAR sweep or an occlusion test, according to the
  * directions the caller gives.  The map is held to the checks of mi_tsdf_integrate's input map and to mi_tsdf_extract's extent (at most
@@ -2186,13 +2221,15 @@ int mi_tsdf_raycast(mi_ctx* ctx, const int* coord, const float* tsdf, const floa
                     const float* dirs_xyz /* n x 3, sensor frame, any length */, int n,
                     float* out_depth /* n */, float* out_xyz /* n x 3, world; may be NULL */,
                     float* out_normals /* n x 3, world; may be NULL */, long long* out_hits /* may be NULL */);
-/* Where the last mi_tsdf_integrate, mi_tsdf_extract or mi_tsdf_raycast of this context spent its host wall time, in ms:
+/* Where the last mi_tsdf_integrate, mi_tsdf_extract, mi_tsdf_mesh or mi_tsdf_raycast of this context spent its host wall time, in ms:
  *   out[0] workspace (device allocations)   out[1] upload   out[2] checks and read-backs
- *   out[3] sampling (extraction and ray cast: the table)   out[4] sort and runs (extraction: count + scan; ray cast: the block table)
- *   out[5] fusion (extraction: fill; ray cast: the cast)
+ *   out[3] sampling (extraction, mesh and ray cast: the table)
+ *   out[4] sort and runs (extraction: count + scan; mesh: the cubes' cases, the used crossings and the two scans; ray cast: the block table)
+ *   out[5] fusion (extraction: fill; mesh: the vertex fill and the triangle fill; ray cast: the cast)
  *   out[6] download   out[7] the whole call
  * While profiling is enabled the stream is drained after every stage, so the parts are attributable (mi_profile_get then also holds the
- * sampling, crossing and cast launches' own HIP-event time under MI_KERNEL_NN and the fusion kernel's under MI_KERNEL_MOMENTS). */
+ * sampling, crossing and cast launches' own HIP-event time under MI_KERNEL_NN and the fusion kernel's under MI_KERNEL_MOMENTS; of a mesh,
+ * the vertex fill under MI_KERNEL_NN and the three launches of its own -- cases, used crossings, triangles -- under MI_KERNEL_MOMENTS). */
 #define MI_TSDF_STAGES 8
 int mi_tsdf_times(mi_ctx* ctx, double out_ms[MI_TSDF_STAGES]);
 
