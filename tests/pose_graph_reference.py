@@ -115,16 +115,35 @@ def edge_terms(R, t, src, tgt, Rz, tz, info, uncertain=None, mu=0.0):
     return dict(r=r, chi2=chi2, w=w, share=share, A=A, M=M, h=h, cost=float(share.sum()))
 
 
-def node_blocks(V, src, tgt, M, h):
+def used_nodes(src, tgt):
+    """The nodes that some edge touches, ascending."""
+    return np.unique(np.concatenate([np.asarray(src), np.asarray(tgt)]))
+
+
+def node_blocks(V, src, tgt, M, h, nodes=None):
+    """-> D [V, 6, 6], g [V, 6]; with nodes (used_nodes: ascending, every edge's ends among them) the rows of those nodes alone, in their
+    order -- every other node's block and gradient are 0, and a node's sum depends on the edges' order only, not on the labels."""
+    if nodes is not None:
+        src, tgt, V = np.searchsorted(nodes, src), np.searchsorted(nodes, tgt), len(nodes)
     D, g = np.zeros((V, 6, 6)), np.zeros((V, 6))
     np.add.at(D, src, M); np.add.at(D, tgt, M)
     np.add.at(g, src, h); np.add.at(g, tgt, -h)
     return D, g
 
 
-def apply_system(src, tgt, M, D, lam, p, ref):
-    """(H + lam diag H) p in the Laplacian form, p_ref taken as 0 and the reference's row left 0."""
+def apply_system(src, tgt, M, D, lam, p, ref, nodes=None):
+    """(H + lam diag H) p in the Laplacian form, p_ref taken as 0 and the reference's row left 0.  With nodes (used_nodes) D holds the rows
+    of those nodes alone (node_blocks with nodes); p and the result stay [V, 6], the rows of every other node 0."""
+    if nodes is not None:
+        at = np.searchsorted(nodes, ref)
+        inner = apply_system(np.searchsorted(nodes, src), np.searchsorted(nodes, tgt), M, D, lam, p[nodes],
+                             int(at) if at < len(nodes) and nodes[at] == ref else None)
+        q = np.zeros_like(p)
+        q[nodes] = inner
+        return q
     p = p.copy()
+    if ref is None:
+        ref = []
     p[ref] = 0.0
     y = (M @ (p[src] - p[tgt])[..., None])[..., 0]
     q = np.zeros_like(p)
@@ -175,8 +194,9 @@ def precondition(D, lam, r):
     return np.where(ok[:, None], x, r)
 
 
-def pcg(src, tgt, M, D, g, lam, ref, tolerance, max_iterations):
-    """The stated inner solve: zero start, block-Jacobi preconditioner, stop at |r| <= tolerance |g| or at the cap.  -> x, iterations, |r| / |g|"""
+def pcg(src, tgt, M, D, g, lam, ref, tolerance, max_iterations, trace=None):
+    """The stated inner solve: zero start, block-Jacobi preconditioner, stop at |r| <= tolerance |g| or at the cap.  -> x, iterations, |r| / |g|
+    trace: a list that receives |r| / |g| behind every iteration."""
     r = -g.copy()
     r[ref] = 0.0
     x = np.zeros_like(r)
@@ -184,8 +204,8 @@ def pcg(src, tgt, M, D, g, lam, ref, tolerance, max_iterations):
     p = z.copy()
     rz, gg = float((r * z).sum()), float((r * r).sum())
     rr, it = gg, 0
-    if not gg > 0 or max_iterations <= 0:
-        return x, 0, 0.0
+    if not gg > 0 or max_iterations <= 0 or not np.sqrt(gg) > tolerance * np.sqrt(gg):         # (r_0 = -g: a tolerance >= 1 is met at the start)
+        return x, 0, 1.0 if gg > 0 else 0.0
     while True:
         q = apply_system(src, tgt, M, D, lam, p, ref)
         pq = float((p * q).sum())
@@ -197,6 +217,8 @@ def pcg(src, tgt, M, D, g, lam, ref, tolerance, max_iterations):
         z = precondition(D, lam, r)
         rz_new, rr = float((r * z).sum()), float((r * r).sum())
         it += 1
+        if trace is not None:
+            trace.append(float(np.sqrt(rr) / np.sqrt(gg)))
         if not np.sqrt(rr) > tolerance * np.sqrt(gg) or it >= max_iterations or not rz_new > 0:
             break
         p = z + (rz_new / rz) * p
@@ -216,9 +238,11 @@ def solve_dense(V, src, tgt, M, g, lam, ref):
     return x.reshape(V, 6)
 
 
-def optimize(R, t, src, tgt, Rz, tz, info, uncertain=None, solver="dense", **kw):
+def optimize(R, t, src, tgt, Rz, tz, info, uncertain=None, solver="dense", trace=None, **kw):
     """The outer loop as mi_slam.h states it.  -> dict(R, t, w, chi2, report) with report = (initial cost, final cost, linearisations,
-    accepted steps, inner iterations in total, final lambda, stop reason, the last solve's relative residual)."""
+    accepted steps, inner iterations in total, final lambda, stop reason, the last solve's relative residual).  trace: a list that receives
+    one record per trial step: dict(lam, F, F_new, accepted, inner) -- the lambda it was solved at, the cost before it, the candidate's
+    cost, whether it was taken, and the inner solve's iterations."""
     p = dict(DEFAULTS, **kw)
     V, ref, mu = len(R), p["reference_node"], p["line_process_mu"]
     src, tgt = np.asarray(src), np.asarray(tgt)
@@ -234,7 +258,7 @@ def optimize(R, t, src, tgt, Rz, tz, info, uncertain=None, solver="dense", **kw)
     while not stop:
         D, g = node_blocks(V, src, tgt, lin["M"], lin["h"])
         if solver == "dense":
-            x = solve_dense(V, src, tgt, lin["M"], g, lam, ref)
+            x, it = solve_dense(V, src, tgt, lin["M"], g, lam, ref), 0
         else:
             x, it, rel = pcg(src, tgt, lin["M"], D, g, lam, ref, p["pcg_tolerance"], p["max_pcg_iterations"])
             inner += it
@@ -244,6 +268,8 @@ def optimize(R, t, src, tgt, Rz, tz, info, uncertain=None, solver="dense", **kw)
         still = ~x.any(axis=1)
         Rn[still], tn[still] = R[still], t[still]
         cand = edge_terms(Rn, tn, src, tgt, Rz, tz, info, uncertain, mu)
+        if trace is not None:
+            trace.append(dict(lam=lam, F=F, F_new=cand["cost"], accepted=bool(cand["cost"] < F), inner=it))
         if cand["cost"] < F:
             decrease = (F - cand["cost"]) / F
             R, t, F, lin = Rn, tn, cand["cost"], cand
